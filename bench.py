@@ -84,7 +84,16 @@ def parse_args():
                          "(a bracket is two extra stream commands)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-events", type=int, default=0, help="0 = one event per host core (max 16)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, or "
+                         "float64 for 64-bit values): train: the loss and every parameter and buffer the step left "
+                         "(<state_dict key>.npy); infer: the per-event MET.  The training state is reset before the timed "
+                         "region to the state after the run's first step, so that the files depend on the arguments "
+                         "alone and not on how many run-in steps the time-based prewarm and the hipGraph probe took")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class _StdoutToStderr:
@@ -208,6 +217,29 @@ def parity_sample(args, model, dev, seed: int):
             "met_mse_vs_ref": float((d * d).sum(1).mean() / 2.0),
             "met_max_abs_diff": float(d.abs().max()), "met_sum_abs_wp_per_event": scale,
             "knn_index_mismatches": int((nbr.cpu() != nbr_ref).sum())}
+
+
+def training_state(model, opt):
+    """Every tensor a training step updates in place: the model's parameters and buffers and the optimizer's state.
+    Restored with copy_, so that captured hipGraphs keep reading the same storage."""
+    import torch
+
+    ts = list(model.state_dict().values())
+    for st in opt.state.values():
+        ts += [v for v in st.values() if torch.is_tensor(v)]
+    return ts
+
+
+def dump_outputs(dirname, arrays):
+    """arrays: name -> tensor, written as dirname/<name>.npy in float64 when the values are 64-bit, else float32."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        wide = t.dtype in (torch.float64, torch.int64)
+        a = t.detach().cpu().to(torch.float64 if wide else torch.float32).numpy()
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 def workload_label(args, B, n, k) -> str:
@@ -484,9 +516,6 @@ def main():
                     return None
 
             step = eager_train_step
-            if args.hip_graph:
-                step = graphed_train_step() or eager_train_step
-                args.hip_graph = step is not eager_train_step
     else:
         model.eval()
 
@@ -500,6 +529,16 @@ def main():
         if use_group:
             dist.barrier()
         torch.cuda.synchronize(dev)
+
+    first_state = None
+    if args.dump_outputs and args.mode == "train":
+        # the optimizer creates its state on the first step: snapshot after it, restore before the timed region
+        step()
+        torch.cuda.synchronize(dev)
+        first_state = [t.clone() for t in training_state(model, opt)]
+    if args.hip_graph and graph_capable:       # after the snapshot: the capture's own warm-up steps are not in it
+        step = graphed_train_step() or eager_train_step
+        args.hip_graph = step is not eager_train_step
 
     prewarm_steps = 0
     if args.prewarm_ms > 0:
@@ -540,6 +579,10 @@ def main():
                 torch.cuda.synchronize(dev)
     for _ in range(args.warmup):
         step()
+    if first_state is not None:
+        with torch.no_grad():
+            for t, saved in zip(training_state(model, opt), first_state, strict=True):
+                t.copy_(saved)
     ev_overhead_ms = _native.timer.calibrate(dev)
     # inside the timed region only the graded kernel is bracketed (a bracket is two extra stream commands, ~5-10 us
     # of GPU idle each); the other native calls are bracketed in a few extra, untimed steps afterwards
@@ -555,11 +598,17 @@ def main():
     dbg = [] if os.environ.get("DMET_BENCH_STEP_TIMES") == "1" else None
     for it in range(args.steps):
         _native.timer.enabled = it % args.bracket_every == 0
-        step()
+        result = step()
         if dbg is not None:
             dbg.append(time.perf_counter() - t0)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # before the untimed steps below overwrite it (a replayed hipGraph returns the same loss buffer every step)
+        if args.mode == "train":
+            dump_outputs(args.dump_outputs, {"loss": result, **model.state_dict()})
+        else:
+            dump_outputs(args.dump_outputs, {"met": result})
     if dbg is not None:
         print("host enqueue time per step (ms):", [round(1e3 * (b - a), 3) for a, b in zip([0.0] + dbg[:-1], dbg)][:25],
               "total", round(1e3 * elapsed, 3), file=sys.stderr)

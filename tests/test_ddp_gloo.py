@@ -111,7 +111,7 @@ def test_shard_helpers():
 
 
 @pytest.mark.timeout(600)
-def test_two_rank_gloo_training_step(tmp_path):
+def test_two_rank_gloo_training_step(tmp_path, monkeypatch):
     world = 2
     port = _free_port()
     mp.start_processes(_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True, start_method="spawn")
@@ -125,7 +125,7 @@ def test_two_rank_gloo_training_step(tmp_path):
     # the all-reduced gradient is the mean of the two single-process shard gradients (per-rank BatchNorm statistics)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import fake_native
-    fake_native.install()
+    fake_native.install(monkeypatch)
     from deepmetv2_amd.model import Net, loss_fn, split_features
     from deepmetv2_amd.parallel import FlatModule
     grads = []
@@ -144,7 +144,7 @@ def test_two_rank_gloo_training_step(tmp_path):
 
 
 @pytest.mark.timeout(600)
-def test_two_rank_gloo_unequal_shares(tmp_path):
+def test_two_rank_gloo_unequal_shares(tmp_path, monkeypatch):
     """1 + 3 events (shards balanced by cost): the all-reduced gradient must be the gradient of the GLOBAL batch mean
     (model/net.py:60: mean over the 4 events), not the mean of the two rank means -- checked against a single process that
     forwards each shard on its own (per-rank BatchNorm statistics, as the ranks do) and differentiates the global mean."""
@@ -157,7 +157,7 @@ def test_two_rank_gloo_unequal_shares(tmp_path):
 
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import fake_native
-    fake_native.install()
+    fake_native.install(monkeypatch)
     from deepmetv2_amd import data
     from deepmetv2_amd.model import Net, loss_fn, split_features
     from deepmetv2_amd.parallel import FlatModule
