@@ -6,6 +6,8 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import EdgeConv, DynamicEdgeConv      # torch_geometric.nn
     from deepmetv2_amd import knn_graph, radius_graph, knn   # torch_cluster
     from deepmetv2_amd import scatter_add, scatter_max       # torch_scatter
+    from deepmetv2_amd import graclus                        # torch_cluster
+    from deepmetv2_amd import normalized_cut, max_pool, max_pool_x, global_max_pool   # torch_geometric
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -18,10 +20,15 @@ from .graph import GraphFuture, NeighborTable, build_async, raise_deferred_error
 from .metrics import metrics, resolution, u_perp_par_loss
 from .scatter import met_reduce, scatter_add, scatter_max
 from .nn import accelerate
+from .pool import (avg_pool, avg_pool_x, global_add_pool, global_max_pool, global_mean_pool, graclus, max_pool,
+                   max_pool_x, normalized_cut, normalized_cut_2d)
+from .drn import DynamicReductionNetwork
 
 __all__ = [
     "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "radius_graph", "radius_table",
     "scatter_add", "scatter_max", "met_reduce", "NeighborTable", "register_batch", "metrics", "resolution",
     "u_perp_par_loss", "to_undirected", "raise_deferred_errors", "accelerate", "build_async", "GraphFuture", "Batch", "EventLoader", "DeviceLoader", "collate", "events_from_padded",
+    "graclus", "normalized_cut", "normalized_cut_2d", "max_pool", "max_pool_x", "avg_pool", "avg_pool_x",
+    "global_max_pool", "global_mean_pool", "global_add_pool", "DynamicReductionNetwork",
 ]
 __version__ = "0.1.0"

@@ -113,6 +113,15 @@ SIGNATURES = {
     "dmet_encode_fwd_f32": (_i, [_vp, _i64, _vp, _i64] + [_vp] * 9 + [_vp, _vp]),
     "dmet_encode_bwd_workspace_bytes": (_sz, [_i64]),
     "dmet_encode_bwd_f32": (_i, [_vp, _i64, _vp, _i64] + [_vp] * 9 + [_vp, _vp] + [_vp] * 9 + [_vp, _sz, _vp]),
+    "dmet_graclus_workspace_bytes": (_sz, [_i64]),
+    "dmet_graclus_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i64, C.c_uint64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dmet_normalized_cut_workspace_bytes": (_sz, [_i64]),
+    "dmet_normalized_cut_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dmet_normalized_cut_2d_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
+    "dmet_pool_pairs_workspace_bytes": (_sz, [_i64, _i]),
+    "dmet_pool_pairs_index": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dmet_pool_pairs_f32": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "dmet_pool_pairs_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i64, _vp, _vp]),
 }
 
 

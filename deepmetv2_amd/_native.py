@@ -1363,3 +1363,116 @@ def table_edges(nbr: torch.Tensor, cnt: Optional[torch.Tensor], rowptr: torch.Te
                                           s32.data_ptr() if s32 is not None else None,
                                           t32.data_ptr() if t32 is not None else None, _stream(dev)), "dmet_table_edges")
     return ei, s32, t32
+
+
+# ---- graph coarsening (csrc/pool.hip): graclus, normalized cut, pair pooling ------------------------------------------
+def graclus(rowptr: torch.Tensor, col: torch.Tensor, weight: Optional[torch.Tensor], ptr: torch.Tensor, seed: int,
+            max_rounds: int = 0, want_rounds: bool = False):
+    """(cluster[N] int64, partner[N] int32, rounds[B] int32 or None) of dmet_graclus_f32."""
+    dev = _require_device(rowptr, col, weight, ptr)
+    L = _lib.load()
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or ptr.dtype != torch.int64:
+        raise TypeError("graclus: rowptr / ptr must be int64 and col int32")
+    N = rowptr.numel() - 1
+    B = ptr.numel() - 1
+    if weight is not None:
+        weight = _f32c(weight, "weight")
+    cluster = torch.empty((N,), dtype=torch.int64, device=dev)
+    partner = torch.empty((N,), dtype=torch.int32, device=dev)
+    rounds = torch.empty((max(B, 1),), dtype=torch.int32, device=dev) if want_rounds else None
+    _t = timer.record('graclus', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_graclus_workspace_bytes(N), dev)
+        _lib.check(L.dmet_graclus_f32(rowptr.data_ptr(), col.data_ptr(), weight.data_ptr() if weight is not None else None,
+                                      ptr.data_ptr(), B, N, int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_rounds),
+                                      cluster.data_ptr(), partner.data_ptr(),
+                                      rounds.data_ptr() if rounds is not None else None, ws.data_ptr(), ws.numel(),
+                                      _stream(dev)), "dmet_graclus_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return cluster, partner, (rounds[:B] if rounds is not None else None)
+
+
+def normalized_cut(edge_index: torch.Tensor, N: int, attr: Optional[torch.Tensor] = None,
+                   x: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """w[E] of dmet_normalized_cut_f32 (attr[E]) or dmet_normalized_cut_2d_f32 (x[N,D])."""
+    dev = _require_device(edge_index, attr, x)
+    L = _lib.load()
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise TypeError("edge_index must be an int64 [2, E] tensor")
+    ei = edge_index.contiguous()
+    E = ei.shape[1]
+    w = torch.empty((E,), dtype=torch.float32, device=dev)
+    row, col = ei[0], ei[1]
+    _t = timer.record('normalized_cut', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_normalized_cut_workspace_bytes(N), dev)
+        if x is not None:
+            x = _f32c(x, "x")
+            _lib.check(L.dmet_normalized_cut_2d_f32(row.data_ptr(), col.data_ptr(), E, N, x.data_ptr(), x.shape[1],
+                                                    w.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+                       "dmet_normalized_cut_2d_f32")
+        else:
+            attr = _f32c(attr.reshape(-1), "edge_attr")
+            if attr.numel() != E:
+                raise ValueError(f"edge_attr must hold one value per edge ({E}), got {attr.numel()}")
+            _lib.check(L.dmet_normalized_cut_f32(row.data_ptr(), col.data_ptr(), E, N, attr.data_ptr(), w.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_normalized_cut_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return w
+
+
+def pool_pairs_index(partner: torch.Tensor, ptr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(cid[N] int64, pooled_ptr[B+1] int64) of dmet_pool_pairs_index."""
+    dev = _require_device(partner, ptr)
+    L = _lib.load()
+    N = partner.numel()
+    B = ptr.numel() - 1
+    cid = torch.empty((N,), dtype=torch.int64, device=dev)
+    pooled_ptr = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+    _t = timer.record('pool_pairs_index', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_pool_pairs_workspace_bytes(N, B), dev)
+        _lib.check(L.dmet_pool_pairs_index(partner.data_ptr(), ptr.data_ptr(), B, N, cid.data_ptr(), pooled_ptr.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_pool_pairs_index")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return cid, pooled_ptr
+
+
+def pool_pairs(x: torch.Tensor, partner: torch.Tensor, cid: torch.Tensor, ptr: Optional[torch.Tensor], C: int,
+               want_max: bool, want_mean: bool, want_batch: bool):
+    """(out_max, arg, out_mean, pooled_batch) of dmet_pool_pairs_f32; the ones not asked for are None."""
+    dev = _require_device(x, partner, cid, ptr)
+    L = _lib.load()
+    x = _f32c(x, "x")
+    N, F = x.shape
+    B = ptr.numel() - 1 if ptr is not None else 0
+    out_max = torch.empty((C, F), dtype=torch.float32, device=dev) if want_max else None
+    arg = torch.empty((C, F), dtype=torch.int32, device=dev) if want_max else None
+    out_mean = torch.empty((C, F), dtype=torch.float32, device=dev) if want_mean else None
+    pb = torch.empty((C,), dtype=torch.int64, device=dev) if want_batch else None
+    _p = lambda t: t.data_ptr() if t is not None else None
+    _t = timer.record('pool_pairs', dev)
+    with _on(dev):
+        _lib.check(L.dmet_pool_pairs_f32(x.data_ptr(), N, F, partner.data_ptr(), cid.data_ptr(), _p(ptr), B, C,
+                                         _p(out_max), _p(arg), _p(out_mean), _p(pb), _stream(dev)), "dmet_pool_pairs_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out_max, arg, out_mean, pb
+
+
+def pool_pairs_bwd(g_max: Optional[torch.Tensor], arg: Optional[torch.Tensor], g_mean: Optional[torch.Tensor],
+                   partner: torch.Tensor, cid: torch.Tensor, F: int, C: int) -> torch.Tensor:
+    dev = _require_device(g_max, arg, g_mean, partner, cid)
+    L = _lib.load()
+    N = partner.numel()
+    g_max = _f32c(g_max, "g_max") if g_max is not None else None
+    g_mean = _f32c(g_mean, "g_mean") if g_mean is not None else None
+    gx = torch.empty((N, F), dtype=torch.float32, device=dev)
+    _p = lambda t: t.data_ptr() if t is not None else None
+    with _on(dev):
+        _lib.check(L.dmet_pool_pairs_bwd_f32(_p(g_max), _p(arg), _p(g_mean), partner.data_ptr(), cid.data_ptr(), N, F, C,
+                                             gx.data_ptr(), _stream(dev)), "dmet_pool_pairs_bwd_f32")
+    return gx

@@ -398,4 +398,17 @@ def to_undirected(edge_index: torch.Tensor, num_nodes: Optional[int] = None) -> 
     row = torch.cat([edge_index[0], edge_index[1]])
     col = torch.cat([edge_index[1], edge_index[0]])
     key = torch.unique(row * n + col)            # sorted ascending = (row, col) lexicographic
-    return torch.stack([key // n, key % n], 0)
+    out = torch.stack([key // n, key % n], 0)
+    src = lookup_graph(edge_index)
+    _registry_put(_coalesced_registry, out, (src[0].ptr if src is not None else None,))
+    return out
+
+
+# edge_index -> (ptr or None,): the tensor is coalesced (sorted by (row, col), no duplicates; to_undirected's output),
+# with the events of the graph it was made from when that one came from knn_graph / radius_graph (graclus reads both)
+_coalesced_registry: Dict[int, Tuple[weakref.ref, int, object]] = {}
+
+
+def coalesced_tag(edge_index: torch.Tensor):
+    """(ptr or None,) if this exact edge_index tensor came from to_undirected, else None."""
+    return _registry_get(_coalesced_registry, edge_index)

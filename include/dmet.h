@@ -533,6 +533,69 @@ int dmet_finalize_defer_begin(void);
 int dmet_finalize_pending(void);
 int dmet_finalize_flush(dmet_stream_t stream);
 
+/* ---- Graph coarsening: graclus matching, normalized-cut weights, pair pooling (csrc/pool.hip) -----------------------
+ * replaces torch_cluster.graclus, torch_geometric.utils.normalized_cut and the cluster pooling of
+ * torch_geometric.nn.max_pool / max_pool_x / avg_pool_x
+ *   call sites: model/dynamic_reduction_network.py:89-92 (normalized_cut_2d, graclus, max_pool) and :97-99
+ *   (normalized_cut_2d, graclus, max_pool_x).
+ *
+ * dmet_graclus_f32: greedy matching of torch_cluster's GPU algorithm (colour, propose, respond), deterministic.
+ *   Graph: CSR rowptr[N+1] int64, col[E] int32 (row u lists its neighbours in ascending (row, col) order), optional
+ *   weight[E] (NULL = unweighted).  Blocks: ptr[B+1] (events); one workgroup per block.  Edges whose endpoints lie in
+ *   different blocks, or outside 0..N-1, are ignored; self loops (col == u) are ignored.
+ *   All nodes start unmatched.  Round r = 0, 1, ... of a block, for every node u unmatched at the round's start:
+ *     colour: s = (uint32)seed ^ (uint32)(seed >> 32), key_r = lowbias32(s + 0x9E3779B9u * r),
+ *             red(u) = lowbias32((uint32)u ^ key_r) >> 31   (1 = red, 0 = blue), where
+ *             lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *     "best" of a candidate set in row u: scan the row in CSR order, take the first candidate and replace it only by a
+ *             candidate of strictly greater weight (IEEE >); unweighted: the first candidate.
+ *     a node with no unmatched neighbour (other than itself) becomes a singleton;
+ *     propose: a blue node proposes to its best unmatched red neighbour (if any);
+ *     respond: a red node accepts its best neighbour among the blue nodes that proposed to it: the two are matched.
+ *   Rounds end when the block has no unmatched node at the start of a round.  After max_rounds rounds (0 = the default
+ *   DMET_GRACLUS_DEFAULT_ROUNDS) the unmatched nodes are finished sequentially in ascending index: each is matched to
+ *   its best unmatched neighbour, or made a singleton.  The kernel loops over a bounded number of rounds only.
+ *   Outputs: cluster[N] int64 = min(u, v) for a matched pair (u, v), u for a singleton (torch_cluster's convention: u
+ *   leads its cluster iff cluster[u] == u); partner[N] int32 = v, -1 for a singleton; rounds[B] int32 (may be NULL) =
+ *   colour rounds the block ran (max_rounds when the finisher ran).  The result depends on (graph, weights, seed) only:
+ *   colours are keyed by the global node id and the block's own round count, so one block per event and one block for
+ *   a whole graph without edges across events give the same bits.  Block state is kept in LDS for blocks of up to
+ *   DMET_GRACLUS_LDS_NODES nodes and in the workspace above that.
+ *
+ * dmet_normalized_cut_f32: w[e] = attr[e] * (1/deg(row[e]) + 1/deg(col[e])) in fp32, deg = in-degree counted over col
+ *   (torch_geometric.utils.normalized_cut).  dmet_normalized_cut_2d_f32: the same with attr[e] = ||x[row[e]] -
+ *   x[col[e]]||_2 for x[N,D], D <= DMET_MAX_CUT_DIM (the DRN's normalized_cut_2d, :89,97); squares summed in double,
+ *   one rounding to fp32.  row / col: the two rows of an int64 edge_index; an out-of-range endpoint gives NaN.
+ *
+ * Pair pooling of a graclus result (partner[N] as written by dmet_graclus_f32; a node leads its cluster unless its
+ *   partner is a lower index).  dmet_pool_pairs_index: cid[N] int64 = pooled row of every node, pooled_ptr[B+1] int64 =
+ *   exclusive prefix sum over events b of the leaders in ptr[b] .. ptr[b+1]-1 (clusters are numbered in ascending leader
+ *   index, so pooled rows stay grouped by event; a cluster belongs to its leader's event).  dmet_pool_pairs_f32 with
+ *   C = pooled_ptr[B]: out_max[C,F] = the larger member row channel-wise, arg[C,F] int32 = its node (the leader on
+ *   ties), out_mean[C,F] = (x_u + x_v) * 0.5 (x_u for a singleton), pooled_batch[C] int64 = event of the leader; any of
+ *   the outputs may be NULL (out_max and arg together).  dmet_pool_pairs_bwd_f32: gx[u,f] = (arg[cid[u],f] == u ?
+ *   g_max[cid[u],f] : 0) + g_mean[cid[u],f] * (1/2 for a pair, 1 for a singleton); g_max / g_mean may be NULL. */
+#define DMET_GRACLUS_LDS_NODES 16384    /* blocks up to this size keep their matching state in LDS (128 KiB) */
+#define DMET_GRACLUS_DEFAULT_ROUNDS 64
+#define DMET_MAX_CUT_DIM 64
+size_t dmet_graclus_workspace_bytes(int64_t N);
+int dmet_graclus_f32(const int64_t *rowptr, const int32_t *col, const float *weight, const int64_t *ptr, int B,
+                     int64_t N, uint64_t seed, int max_rounds, int64_t *cluster, int32_t *partner, int32_t *rounds,
+                     void *ws, size_t ws_bytes, dmet_stream_t stream);
+size_t dmet_normalized_cut_workspace_bytes(int64_t N);
+int dmet_normalized_cut_f32(const int64_t *row, const int64_t *col, int64_t E, int64_t N, const float *attr, float *w,
+                            void *ws, size_t ws_bytes, dmet_stream_t stream);
+int dmet_normalized_cut_2d_f32(const int64_t *row, const int64_t *col, int64_t E, int64_t N, const float *x, int D,
+                               float *w, void *ws, size_t ws_bytes, dmet_stream_t stream);
+size_t dmet_pool_pairs_workspace_bytes(int64_t N, int B);
+int dmet_pool_pairs_index(const int32_t *partner, const int64_t *ptr, int B, int64_t N, int64_t *cid,
+                          int64_t *pooled_ptr, void *ws, size_t ws_bytes, dmet_stream_t stream);
+int dmet_pool_pairs_f32(const float *x, int64_t N, int F, const int32_t *partner, const int64_t *cid, const int64_t *ptr,
+                        int B, int64_t C, float *out_max, int32_t *arg, float *out_mean, int64_t *pooled_batch,
+                        dmet_stream_t stream);
+int dmet_pool_pairs_bwd_f32(const float *g_max, const int32_t *arg, const float *g_mean, const int32_t *partner,
+                            const int64_t *cid, int64_t N, int F, int64_t C, float *gx, dmet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
