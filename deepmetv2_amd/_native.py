@@ -646,6 +646,131 @@ def edge_mlp2_bn_bf16(x: torch.Tensor, nbr: torch.Tensor, W1: torch.Tensor, b1: 
     return out
 
 
+def edge_mlp_f32_supported(Hin: int, H1: int, H2: int) -> bool:
+    return bool(_lib.load().dmet_edge_mlp_f32_supported(int(Hin), int(H1), int(H2)))
+
+
+_EMLP_AGGR = {"max": 0, "add": 1, "sum": 1, "mean": 2}
+
+
+def _edge_arrays(rowptr, src, tgt, N):
+    for name, t in (("rowptr", rowptr), ("src", src), ("tgt", tgt)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise TypeError(f"edge_mlp_f32: {name} must be a contiguous int32 tensor")
+    if rowptr.numel() != N + 1:
+        raise ValueError(f"edge_mlp_f32: rowptr must hold N + 1 = {N + 1} entries, got {rowptr.numel()}")
+    if src.numel() != tgt.numel():
+        raise ValueError("edge_mlp_f32: src and tgt differ in length")
+    return src.numel()
+
+
+def edge_mlp_fwd_f32(x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, W1: torch.Tensor,
+                     b1: Optional[torch.Tensor], W2: torch.Tensor, b2: Optional[torch.Tensor], act2: bool, aggr: str,
+                     bn: int = 0, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+                     eps: float = 1e-5, momentum: float = 0.1, running_mean: Optional[torch.Tensor] = None,
+                     running_var: Optional[torch.Tensor] = None, num_batches_tracked: Optional[torch.Tensor] = None):
+    """out[N, H2] = aggr_e nn([x_tgt || x_src - x_tgt]) over a grouped edge list, nn = Linear - ELU - Linear [- ELU]
+    [- BatchNorm1d] in fp32 (include/dmet.h: dmet_edge_mlp_fwd_f32).  Returns (out, state); `state` is what
+    edge_mlp_bwd_f32 needs (pq, agg, win, bnstat).  bn: 0 none, 1 training (statistics moved in place), 2 eval."""
+    dev = _require_device(x, rowptr, src, tgt, W1, W2, b1, b2, gamma, beta)
+    L = _lib.load()
+    x = _f32c(x, "x"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2")
+    N, Hin = x.shape
+    H1, H2 = W1.shape[0], W2.shape[0]
+    if W1.shape[1] != 2 * Hin or W2.shape[1] != H1:
+        raise ValueError(f"edge_mlp_f32: W1 must be [H1, {2 * Hin}] and W2 [H2, H1], got {tuple(W1.shape)}, {tuple(W2.shape)}")
+    if aggr not in _EMLP_AGGR:
+        raise ValueError(f"edge_mlp_f32: unsupported aggr {aggr!r}")
+    E = _edge_arrays(rowptr, src, tgt, N)
+    out = torch.empty((N, H2), dtype=torch.float32, device=dev)
+    pq = torch.empty((N, 2 * H1), dtype=torch.float32, device=dev)
+    agg = torch.empty((2 if aggr == "max" and bn else 1, N, H2), dtype=torch.float32, device=dev)
+    win = torch.empty((2 if bn else 1, N, H2), dtype=torch.int32, device=dev) if aggr == "max" else None
+    bnstat = torch.empty((4, H2), dtype=torch.float32, device=dev)
+    p = lambda t: _f32c(t, "param").data_ptr() if t is not None else None
+    _t = timer.record('edge_mlp_f32', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_edge_mlp_f32_workspace_bytes(N, E, Hin, H1, H2), dev)
+        _lib.check(L.dmet_edge_mlp_fwd_f32(x.data_ptr(), N, Hin, rowptr.data_ptr(), src.data_ptr(), tgt.data_ptr(), E,
+                                           W1.data_ptr(), p(b1), H1, W2.data_ptr(), p(b2), H2, 1 if act2 else 0,
+                                           _EMLP_AGGR[aggr], int(bn), p(gamma), p(beta), float(eps), float(momentum),
+                                           p(running_mean), p(running_var),
+                                           num_batches_tracked.data_ptr() if num_batches_tracked is not None else None,
+                                           out.data_ptr(), pq.data_ptr(), agg.data_ptr(),
+                                           win.data_ptr() if win is not None else None, bnstat.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), _stream(dev)), "dmet_edge_mlp_fwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, (pq, agg, win, bnstat)
+
+
+def _xty_wide(A: torch.Tensor, Bm: torch.Tensor) -> torch.Tensor:
+    """A^T B for widths above dmet_xty_f32's 64 columns: 64 x 64 tiles, each one deterministic call."""
+    Ha, Hb = A.shape[1], Bm.shape[1]
+    if Ha <= 64 and Hb <= 64:
+        return xty(A, Bm)
+    rows = []
+    for a0 in range(0, Ha, 64):
+        Ac = A[:, a0:a0 + 64].contiguous()
+        rows.append(torch.cat([xty(Ac, Bm[:, b0:b0 + 64].contiguous()) for b0 in range(0, Hb, 64)], dim=1))
+    return torch.cat(rows, dim=0)
+
+
+def edge_mlp_bwd_f32(g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor,
+                     srcptr: torch.Tensor, srcperm: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                     b2: Optional[torch.Tensor], act2: bool, aggr: str, bn: int, state, want_x: bool = True,
+                     want_w1: bool = True, want_b1: bool = True):
+    """Gradients of edge_mlp_fwd_f32 (include/dmet.h: dmet_edge_mlp_bwd_f32): (gx, gW1, gb1, gW2, gb2, ggamma, gbeta);
+    gx / gW1 / gb1 are None when not wanted, ggamma / gbeta when bn == 0."""
+    dev = _require_device(g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2)
+    L = _lib.load()
+    x = _f32c(x, "x"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2"); g_out = _f32c(g_out, "g_out")
+    N, Hin = x.shape
+    H1, H2 = W1.shape[0], W2.shape[0]
+    E = _edge_arrays(rowptr, src, tgt, N)
+    if srcptr.dtype != torch.int32 or srcperm.dtype != torch.int32 or srcptr.numel() != N + 1:
+        raise TypeError("edge_mlp_f32: srcptr [N + 1] and srcperm must be int32 (EdgeList.by_source())")
+    if tuple(g_out.shape) != (N, H2):
+        raise ValueError(f"edge_mlp_f32: g_out must be [{N}, {H2}], got {tuple(g_out.shape)}")
+    pq, agg, win, bnstat = state
+    gx = torch.empty((N, Hin), dtype=torch.float32, device=dev) if want_x else None
+    gpq = torch.empty((N, 2 * H1), dtype=torch.float32, device=dev)
+    gW2 = torch.empty((H2, H1), dtype=torch.float32, device=dev)
+    gb2 = torch.empty((H2,), dtype=torch.float32, device=dev)
+    ggamma = torch.empty((H2,), dtype=torch.float32, device=dev) if bn else None
+    gbeta = torch.empty((H2,), dtype=torch.float32, device=dev) if bn else None
+    p = lambda t: t.data_ptr() if t is not None else None
+    _t = timer.record('edge_mlp_f32_bwd', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_edge_mlp_f32_workspace_bytes(N, E, Hin, H1, H2), dev)
+        _lib.check(L.dmet_edge_mlp_bwd_f32(x.data_ptr(), N, Hin, rowptr.data_ptr(), src.data_ptr(), tgt.data_ptr(), E,
+                                           srcptr.data_ptr(), srcperm.data_ptr(), W1.data_ptr(), H1, W2.data_ptr(),
+                                           p(_f32c(b2, "b2") if b2 is not None else None), H2, 1 if act2 else 0,
+                                           _EMLP_AGGR[aggr], int(bn), pq.data_ptr(), agg.data_ptr(), p(win),
+                                           bnstat.data_ptr(), g_out.data_ptr(), p(gx), gpq.data_ptr(), gW2.data_ptr(),
+                                           gb2.data_ptr(), p(ggamma), p(gbeta), ws.data_ptr(), ws.numel(), _stream(dev)),
+                   "dmet_edge_mlp_bwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    gW1 = gb1 = None
+    gP = gpq[:, :H1]
+    if want_w1:
+        if N == 0:
+            gW1 = torch.zeros_like(W1)
+        else:
+            C = _xty_wide(gpq, x)              # [2 H1, Hin] = [gP^T x ; gQ^T x]
+            gW1 = torch.cat([C[:H1], C[H1:] - C[:H1]], dim=1)
+    if want_b1:
+        gb1 = xty_wide_ones(gP) if N else torch.zeros((H1,), dtype=torch.float32, device=dev)
+    return gx, gW1, gb1, gW2, gb2, ggamma, gbeta
+
+
+def xty_wide_ones(A: torch.Tensor) -> torch.Tensor:
+    """Column sums of A[N, H] through dmet_xty_f32 (fixed order, deterministic)."""
+    ones = torch.ones((A.shape[0], 1), dtype=torch.float32, device=A.device)
+    return _xty_wide(ones, A).reshape(-1)
+
+
 def node_linear_split_bf16(x: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     """bf16-MFMA variant: P fp32 [N,H], Q as bf16 [N,H] (gathered table)."""
     dev = _require_device(x, W, b)

@@ -19,6 +19,7 @@ from . import _native
 from .cluster import knn_table
 from .graph import EdgeList, GraphFuture, NeighborTable, batch_info, edge_list_from_edge_index, lookup_graph
 from .scatter import _SegmentMaxRows, _SegmentSumRows
+from torch.autograd.function import once_differentiable
 
 _FUSED_WIDTHS = (32, 64)
 
@@ -275,6 +276,44 @@ class _EdgeMLP2Bf16(torch.autograd.Function):
         return tuple(res)
 
 
+class _EdgeMLP2F32(torch.autograd.Function):
+    """aggr_e nn([x_tgt || x_src - x_tgt]) for nn = Linear - ELU - Linear [- ELU] [- BatchNorm1d] in fp32 over a grouped
+    edge list (csrc/edgemlp_f32.hip): the first Linear split per node, the second one per edge, fused with the
+    aggregation and the BatchNorm.  Nothing per edge is kept between the passes: the backward re-computes the messages
+    from the node-level state.  The backward is `once_differentiable`: double backward raises (DMET_EDGE_MLP_F32=0 gives
+    the generic route, which supports it)."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
+        mode, track = 0, False
+        if bn is not None:
+            track = bn.track_running_stats and bn.running_mean is not None
+            mode = 1 if (bn.training or not track) else 2
+        update = mode == 1 and track
+        out, state = _native.edge_mlp_fwd_f32(
+            x, edges.rowptr, edges.src, edges.tgt, W1, b1, W2, b2, act2, aggr, mode, gamma, beta,
+            bn.eps if bn is not None else 1e-5, bn.momentum if bn is not None else 0.1,
+            bn.running_mean if track else None, bn.running_var if track else None,
+            bn.num_batches_tracked if update else None)
+        ctx.save_for_backward(x, W1, W2, b2, *state[:2], state[2], state[3])
+        ctx.edges, ctx.act2, ctx.aggr, ctx.mode = edges, act2, aggr, mode
+        ctx.has_b1, ctx.has_b2 = b1 is not None, b2 is not None
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        x, W1, W2, b2, pq, agg, win, bnstat = ctx.saved_tensors
+        edges: EdgeList = ctx.edges
+        srcptr, srcperm = edges.by_source()
+        need = ctx.needs_input_grad
+        gx, gW1, gb1, gW2, gb2, gg, gbeta = _native.edge_mlp_bwd_f32(
+            g_out, x, edges.rowptr, edges.src, edges.tgt, srcptr, srcperm, W1, W2, b2, ctx.act2, ctx.aggr, ctx.mode,
+            (pq, agg, win, bnstat), want_x=need[0], want_w1=need[1], want_b1=ctx.has_b1 and need[2])
+        return (gx, gW1 if need[1] else None, gb1, gW2 if need[3] else None, gb2 if (ctx.has_b2 and need[4]) else None,
+                gg if need[5] else None, gbeta if need[6] else None, None, None, None, None)
+
+
 class _EdgeFeatures(torch.autograd.Function):
     """feat[e] = [x[tgt] || x[src] - x[tgt]] for a by-target grouped edge list."""
 
@@ -298,6 +337,14 @@ class EdgeConv(torch.nn.Module):
     Args mirror PyG: ``nn`` (any callable mapping [*, 2F_in] -> [*, F_out]), ``aggr`` in {'max','add','sum','mean'},
     ``flow`` keyword.  ``forward(x, edge_index)`` takes a [N,F] tensor (or a pair of identical tensors) and an int64
     [2,E] edge index.
+
+    Fused routes by ``nn``: a single ``Linear(2F, F')`` with max aggregation (F, F' in {32, 64}) runs through the
+    per-node split (csrc/edgeconv.hip); ``Sequential(Linear(2F, H1), ELU, Linear(H1, H2)[, ELU][, BatchNorm1d(H2)])``
+    (ELU alpha 1, fp32, BatchNorm momentum not None) runs fused in fp32 over any graph, forward and backward, for
+    H2 in {16, 32, 64, 128}, H1 <= min(192, 2 H2), F <= 128 (csrc/edgemlp_f32.hip; ``DMET_EDGE_MLP_F32=0`` restores
+    the generic route, e.g. for double backward), or on the bf16 matrix cores when bf16 is requested over a kNN
+    table (csrc/edgemlp.hip).  Every other ``nn`` runs the generic route: edge features, ``nn`` over E rows, segment
+    reduction.
     """
 
     def __init__(self, nn: Callable, aggr: str = "max", **kwargs):
@@ -347,7 +394,10 @@ class EdgeConv(torch.nn.Module):
                                       lambda xx: self._forward_edges(xx, table.edge_list()), bn,
                                       bn.weight if bn is not None else None, bn.bias if bn is not None else None)
             return (out, x) if passthrough else out
-        out = self._forward_edges(x, table.edge_list())
+        edges = table.edge_list()
+        out = self._forward_edge_mlp_f32(x, edges)
+        if out is None:
+            out = self._forward_edges(x, edges)
         return (out, x) if passthrough else out
 
     def _wants_bf16(self) -> bool:
@@ -362,6 +412,28 @@ class EdgeConv(torch.nn.Module):
             dt = torch.get_autocast_gpu_dtype()
         return (dt == torch.bfloat16 and lin.in_features == 64 and lin.out_features == 32
                 and table.k in (8, 16, 32))
+
+    def _forward_edge_mlp_f32(self, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
+        """The fused fp32 route (_EdgeMLP2F32) for a two-layer edge MLP, or None when this call keeps the generic route:
+        another `nn`, widths outside dmet_edge_mlp_f32_supported, bf16 or autocast requested, DMET_EDGE_MLP_F32=0, or a
+        training-mode BatchNorm over E <= 1 edges (torch's own error for one value per channel stays)."""
+        if os.environ.get("DMET_EDGE_MLP_F32", "1") == "0" or not x.is_cuda or x.dtype != torch.float32:
+            return None
+        if self.compute_dtype not in (None, torch.float32) or torch.is_autocast_enabled():
+            return None
+        mlp = _as_mlp2(self.nn)
+        if mlp is None:
+            return None
+        l1, l2, act2, bn = mlp
+        params = [l1.weight, l1.bias, l2.weight, l2.bias] + ([bn.weight, bn.bias] if bn is not None else [])
+        if any(p is not None and p.dtype != torch.float32 for p in params) or l1.in_features != 2 * x.shape[1]:
+            return None
+        if not _native.edge_mlp_f32_supported(x.shape[1], l1.out_features, l2.out_features):
+            return None
+        if bn is not None and (bn.training or not bn.track_running_stats) and edges.num_edges <= 1:
+            return None
+        return _EdgeMLP2F32.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, bn.weight if bn is not None else None,
+                                  bn.bias if bn is not None else None, edges, act2, self.aggr, bn)
 
     def _forward_edges(self, x: torch.Tensor, edges: EdgeList) -> torch.Tensor:
         N = x.shape[0]
@@ -401,7 +473,9 @@ class EdgeConv(torch.nn.Module):
         hit = lookup_graph(edge_index)
         if hit is not None and hit[1] == self.flow and hit[0].num_nodes == x.shape[0]:
             return self._forward_table(x, hit[0])
-        return self._forward_edges(x, edge_list_from_edge_index(edge_index, x.shape[0], self.flow))
+        edges = edge_list_from_edge_index(edge_index, x.shape[0], self.flow)
+        out = self._forward_edge_mlp_f32(x, edges)
+        return out if out is not None else self._forward_edges(x, edges)
 
     # -- BatchNorm transform of the PREVIOUS block fused into this layer's node-level dense layer (static graphs) --------
     def prebuild_hook(self, batch=None, graph=None):
