@@ -672,15 +672,37 @@ def edge_mlp_fwd_f32(x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, t
     """out[N, H2] = aggr_e nn([x_tgt || x_src - x_tgt]) over a grouped edge list, nn = Linear - ELU - Linear [- ELU]
     [- BatchNorm1d] in fp32 (include/dmet.h: dmet_edge_mlp_fwd_f32).  Returns (out, state); `state` is what
     edge_mlp_bwd_f32 needs (pq, agg, win, bnstat).  bn: 0 none, 1 training (statistics moved in place), 2 eval."""
+    return _edge_mlp_fwd("f32", x, rowptr, src, tgt, W1, b1, W2, b2, act2, aggr, bn, gamma, beta, eps, momentum,
+                         running_mean, running_var, num_batches_tracked)
+
+
+def edge_mlp_bf16_supported(Hin: int, H1: int, H2: int) -> bool:
+    return bool(_lib.load().dmet_edge_mlp_bf16_supported(int(Hin), int(H1), int(H2)))
+
+
+def edge_mlp_fwd_bf16(x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, W1: torch.Tensor,
+                      b1: Optional[torch.Tensor], W2: torch.Tensor, b2: Optional[torch.Tensor], act2: bool, aggr: str,
+                      bn: int = 0, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+                      eps: float = 1e-5, momentum: float = 0.1, running_mean: Optional[torch.Tensor] = None,
+                      running_var: Optional[torch.Tensor] = None, num_batches_tracked: Optional[torch.Tensor] = None):
+    """edge_mlp_fwd_f32 with the per-edge product on the bf16 matrix cores (include/dmet.h: dmet_edge_mlp_fwd_bf16):
+    fp32 inputs, parameters and output; h1 and W2 rounded to bf16 inside the kernel.  Returns (out, state) for
+    edge_mlp_bwd_bf16."""
+    return _edge_mlp_fwd("bf16", x, rowptr, src, tgt, W1, b1, W2, b2, act2, aggr, bn, gamma, beta, eps, momentum,
+                         running_mean, running_var, num_batches_tracked)
+
+
+def _edge_mlp_fwd(route, x, rowptr, src, tgt, W1, b1, W2, b2, act2, aggr, bn, gamma, beta, eps, momentum, running_mean,
+                  running_var, num_batches_tracked):
     dev = _require_device(x, rowptr, src, tgt, W1, W2, b1, b2, gamma, beta)
     L = _lib.load()
     x = _f32c(x, "x"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2")
     N, Hin = x.shape
     H1, H2 = W1.shape[0], W2.shape[0]
     if W1.shape[1] != 2 * Hin or W2.shape[1] != H1:
-        raise ValueError(f"edge_mlp_f32: W1 must be [H1, {2 * Hin}] and W2 [H2, H1], got {tuple(W1.shape)}, {tuple(W2.shape)}")
+        raise ValueError(f"edge_mlp_{route}: W1 must be [H1, {2 * Hin}] and W2 [H2, H1], got {tuple(W1.shape)}, {tuple(W2.shape)}")
     if aggr not in _EMLP_AGGR:
-        raise ValueError(f"edge_mlp_f32: unsupported aggr {aggr!r}")
+        raise ValueError(f"edge_mlp_{route}: unsupported aggr {aggr!r}")
     E = _edge_arrays(rowptr, src, tgt, N)
     out = torch.empty((N, H2), dtype=torch.float32, device=dev)
     pq = torch.empty((N, 2 * H1), dtype=torch.float32, device=dev)
@@ -688,17 +710,18 @@ def edge_mlp_fwd_f32(x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, t
     win = torch.empty((2 if bn else 1, N, H2), dtype=torch.int32, device=dev) if aggr == "max" else None
     bnstat = torch.empty((4, H2), dtype=torch.float32, device=dev)
     p = lambda t: _f32c(t, "param").data_ptr() if t is not None else None
-    _t = timer.record('edge_mlp_f32', dev)
+    _t = timer.record(f'edge_mlp_{route}', dev)
     with _on(dev):
-        ws = _ws(L.dmet_edge_mlp_f32_workspace_bytes(N, E, Hin, H1, H2), dev)
-        _lib.check(L.dmet_edge_mlp_fwd_f32(x.data_ptr(), N, Hin, rowptr.data_ptr(), src.data_ptr(), tgt.data_ptr(), E,
-                                           W1.data_ptr(), p(b1), H1, W2.data_ptr(), p(b2), H2, 1 if act2 else 0,
-                                           _EMLP_AGGR[aggr], int(bn), p(gamma), p(beta), float(eps), float(momentum),
-                                           p(running_mean), p(running_var),
-                                           num_batches_tracked.data_ptr() if num_batches_tracked is not None else None,
-                                           out.data_ptr(), pq.data_ptr(), agg.data_ptr(),
-                                           win.data_ptr() if win is not None else None, bnstat.data_ptr(), ws.data_ptr(),
-                                           ws.numel(), _stream(dev)), "dmet_edge_mlp_fwd_f32")
+        ws = _ws(getattr(L, f"dmet_edge_mlp_{route}_workspace_bytes")(N, E, Hin, H1, H2), dev)
+        call = getattr(L, f"dmet_edge_mlp_fwd_{route}")
+        _lib.check(call(x.data_ptr(), N, Hin, rowptr.data_ptr(), src.data_ptr(), tgt.data_ptr(), E,
+                        W1.data_ptr(), p(b1), H1, W2.data_ptr(), p(b2), H2, 1 if act2 else 0,
+                        _EMLP_AGGR[aggr], int(bn), p(gamma), p(beta), float(eps), float(momentum),
+                        p(running_mean), p(running_var),
+                        num_batches_tracked.data_ptr() if num_batches_tracked is not None else None,
+                        out.data_ptr(), pq.data_ptr(), agg.data_ptr(),
+                        win.data_ptr() if win is not None else None, bnstat.data_ptr(), ws.data_ptr(),
+                        ws.numel(), _stream(dev)), f"dmet_edge_mlp_fwd_{route}")
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
     return out, (pq, agg, win, bnstat)
@@ -722,6 +745,22 @@ def edge_mlp_bwd_f32(g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor,
                      want_w1: bool = True, want_b1: bool = True):
     """Gradients of edge_mlp_fwd_f32 (include/dmet.h: dmet_edge_mlp_bwd_f32): (gx, gW1, gb1, gW2, gb2, ggamma, gbeta);
     gx / gW1 / gb1 are None when not wanted, ggamma / gbeta when bn == 0."""
+    return _edge_mlp_bwd("f32", g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2, act2, aggr, bn, state, want_x,
+                         want_w1, want_b1)
+
+
+def edge_mlp_bwd_bf16(g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor,
+                      srcptr: torch.Tensor, srcperm: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                      b2: Optional[torch.Tensor], act2: bool, aggr: str, bn: int, state, want_x: bool = True,
+                      want_w1: bool = True, want_b1: bool = True):
+    """Gradients of edge_mlp_fwd_bf16 (include/dmet.h: dmet_edge_mlp_bwd_bf16), as edge_mlp_bwd_f32 returns them: the
+    per-edge products g_h1 and gW2 on the bf16 matrix cores, everything else fp32."""
+    return _edge_mlp_bwd("bf16", g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2, act2, aggr, bn, state, want_x,
+                         want_w1, want_b1)
+
+
+def _edge_mlp_bwd(route, g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2, act2, aggr, bn, state, want_x, want_w1,
+                  want_b1):
     dev = _require_device(g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2)
     L = _lib.load()
     x = _f32c(x, "x"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2"); g_out = _f32c(g_out, "g_out")
@@ -729,9 +768,9 @@ def edge_mlp_bwd_f32(g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor,
     H1, H2 = W1.shape[0], W2.shape[0]
     E = _edge_arrays(rowptr, src, tgt, N)
     if srcptr.dtype != torch.int32 or srcperm.dtype != torch.int32 or srcptr.numel() != N + 1:
-        raise TypeError("edge_mlp_f32: srcptr [N + 1] and srcperm must be int32 (EdgeList.by_source())")
+        raise TypeError(f"edge_mlp_{route}: srcptr [N + 1] and srcperm must be int32 (EdgeList.by_source())")
     if tuple(g_out.shape) != (N, H2):
-        raise ValueError(f"edge_mlp_f32: g_out must be [{N}, {H2}], got {tuple(g_out.shape)}")
+        raise ValueError(f"edge_mlp_{route}: g_out must be [{N}, {H2}], got {tuple(g_out.shape)}")
     pq, agg, win, bnstat = state
     gx = torch.empty((N, Hin), dtype=torch.float32, device=dev) if want_x else None
     gpq = torch.empty((N, 2 * H1), dtype=torch.float32, device=dev)
@@ -740,16 +779,17 @@ def edge_mlp_bwd_f32(g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor,
     ggamma = torch.empty((H2,), dtype=torch.float32, device=dev) if bn else None
     gbeta = torch.empty((H2,), dtype=torch.float32, device=dev) if bn else None
     p = lambda t: t.data_ptr() if t is not None else None
-    _t = timer.record('edge_mlp_f32_bwd', dev)
+    _t = timer.record(f'edge_mlp_{route}_bwd', dev)
     with _on(dev):
-        ws = _ws(L.dmet_edge_mlp_f32_workspace_bytes(N, E, Hin, H1, H2), dev)
-        _lib.check(L.dmet_edge_mlp_bwd_f32(x.data_ptr(), N, Hin, rowptr.data_ptr(), src.data_ptr(), tgt.data_ptr(), E,
-                                           srcptr.data_ptr(), srcperm.data_ptr(), W1.data_ptr(), H1, W2.data_ptr(),
-                                           p(_f32c(b2, "b2") if b2 is not None else None), H2, 1 if act2 else 0,
-                                           _EMLP_AGGR[aggr], int(bn), pq.data_ptr(), agg.data_ptr(), p(win),
-                                           bnstat.data_ptr(), g_out.data_ptr(), p(gx), gpq.data_ptr(), gW2.data_ptr(),
-                                           gb2.data_ptr(), p(ggamma), p(gbeta), ws.data_ptr(), ws.numel(), _stream(dev)),
-                   "dmet_edge_mlp_bwd_f32")
+        ws = _ws(getattr(L, f"dmet_edge_mlp_{route}_workspace_bytes")(N, E, Hin, H1, H2), dev)
+        call = getattr(L, f"dmet_edge_mlp_bwd_{route}")
+        _lib.check(call(x.data_ptr(), N, Hin, rowptr.data_ptr(), src.data_ptr(), tgt.data_ptr(), E,
+                        srcptr.data_ptr(), srcperm.data_ptr(), W1.data_ptr(), H1, W2.data_ptr(),
+                        p(_f32c(b2, "b2") if b2 is not None else None), H2, 1 if act2 else 0,
+                        _EMLP_AGGR[aggr], int(bn), pq.data_ptr(), agg.data_ptr(), p(win),
+                        bnstat.data_ptr(), g_out.data_ptr(), p(gx), gpq.data_ptr(), gW2.data_ptr(),
+                        gb2.data_ptr(), p(ggamma), p(gbeta), ws.data_ptr(), ws.numel(), _stream(dev)),
+                   f"dmet_edge_mlp_bwd_{route}")
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
     gW1 = gb1 = None

@@ -31,7 +31,10 @@ def knn_table(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loo
               num_events: Optional[int] = None, dense=None) -> NeighborTable:
     """Fixed-width neighbour table for `x` (row i = the message sources of node i).  loop=False searches k+1
     and blanks j == i, exactly like upstream's `row != col` mask (a node whose k+1 nearest do not include itself,
-    possible only with >= k+1 duplicates at lower index, keeps all k+1)."""
+    possible only with >= k+1 duplicates at lower index, keeps all k+1).  A bf16 `x` (bf16 autocast upstream) is
+    upcast first, an exact conversion: the result is the kNN of x.float()."""
+    if torch.is_tensor(x) and x.dtype == torch.bfloat16:
+        x = x.float()
     x = _check_x(x)
     if not isinstance(k, int) or k < 1:
         raise ValueError(f"k must be a positive int, got {k!r}")

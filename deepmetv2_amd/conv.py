@@ -276,6 +276,36 @@ class _EdgeMLP2Bf16(torch.autograd.Function):
         return tuple(res)
 
 
+def _edge_mlp2_forward(route, ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
+    """Forward of the fused edge-list routes (route "f32" or "bf16": _native.edge_mlp_fwd_<route>)."""
+    mode, track = 0, False
+    if bn is not None:
+        track = bn.track_running_stats and bn.running_mean is not None
+        mode = 1 if (bn.training or not track) else 2
+    update = mode == 1 and track
+    out, state = getattr(_native, f"edge_mlp_fwd_{route}")(
+        x, edges.rowptr, edges.src, edges.tgt, W1, b1, W2, b2, act2, aggr, mode, gamma, beta,
+        bn.eps if bn is not None else 1e-5, bn.momentum if bn is not None else 0.1,
+        bn.running_mean if track else None, bn.running_var if track else None,
+        bn.num_batches_tracked if update else None)
+    ctx.save_for_backward(x, W1, W2, b2, *state[:2], state[2], state[3])
+    ctx.edges, ctx.act2, ctx.aggr, ctx.mode = edges, act2, aggr, mode
+    ctx.has_b1, ctx.has_b2 = b1 is not None, b2 is not None
+    return out
+
+
+def _edge_mlp2_backward(route, ctx, g_out):
+    x, W1, W2, b2, pq, agg, win, bnstat = ctx.saved_tensors
+    edges: EdgeList = ctx.edges
+    srcptr, srcperm = edges.by_source()
+    need = ctx.needs_input_grad
+    gx, gW1, gb1, gW2, gb2, gg, gbeta = getattr(_native, f"edge_mlp_bwd_{route}")(
+        g_out, x, edges.rowptr, edges.src, edges.tgt, srcptr, srcperm, W1, W2, b2, ctx.act2, ctx.aggr, ctx.mode,
+        (pq, agg, win, bnstat), want_x=need[0], want_w1=need[1], want_b1=ctx.has_b1 and need[2])
+    return (gx, gW1 if need[1] else None, gb1, gW2 if need[3] else None, gb2 if (ctx.has_b2 and need[4]) else None,
+            gg if need[5] else None, gbeta if need[6] else None, None, None, None, None)
+
+
 class _EdgeMLP2F32(torch.autograd.Function):
     """aggr_e nn([x_tgt || x_src - x_tgt]) for nn = Linear - ELU - Linear [- ELU] [- BatchNorm1d] in fp32 over a grouped
     edge list (csrc/edgemlp_f32.hip): the first Linear split per node, the second one per edge, fused with the
@@ -285,33 +315,28 @@ class _EdgeMLP2F32(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
-        mode, track = 0, False
-        if bn is not None:
-            track = bn.track_running_stats and bn.running_mean is not None
-            mode = 1 if (bn.training or not track) else 2
-        update = mode == 1 and track
-        out, state = _native.edge_mlp_fwd_f32(
-            x, edges.rowptr, edges.src, edges.tgt, W1, b1, W2, b2, act2, aggr, mode, gamma, beta,
-            bn.eps if bn is not None else 1e-5, bn.momentum if bn is not None else 0.1,
-            bn.running_mean if track else None, bn.running_var if track else None,
-            bn.num_batches_tracked if update else None)
-        ctx.save_for_backward(x, W1, W2, b2, *state[:2], state[2], state[3])
-        ctx.edges, ctx.act2, ctx.aggr, ctx.mode = edges, act2, aggr, mode
-        ctx.has_b1, ctx.has_b2 = b1 is not None, b2 is not None
-        return out
+        return _edge_mlp2_forward("f32", ctx, x, W1, b1, W2, b2, gamma, beta, edges, act2, aggr, bn)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_out):
-        x, W1, W2, b2, pq, agg, win, bnstat = ctx.saved_tensors
-        edges: EdgeList = ctx.edges
-        srcptr, srcperm = edges.by_source()
-        need = ctx.needs_input_grad
-        gx, gW1, gb1, gW2, gb2, gg, gbeta = _native.edge_mlp_bwd_f32(
-            g_out, x, edges.rowptr, edges.src, edges.tgt, srcptr, srcperm, W1, W2, b2, ctx.act2, ctx.aggr, ctx.mode,
-            (pq, agg, win, bnstat), want_x=need[0], want_w1=need[1], want_b1=ctx.has_b1 and need[2])
-        return (gx, gW1 if need[1] else None, gb1, gW2 if need[3] else None, gb2 if (ctx.has_b2 and need[4]) else None,
-                gg if need[5] else None, gbeta if need[6] else None, None, None, None, None)
+        return _edge_mlp2_backward("f32", ctx, g_out)
+
+
+class _EdgeMLP2Bf16Edges(torch.autograd.Function):
+    """The layer of _EdgeMLP2F32 with its per-edge products on the bf16 matrix cores (csrc/edgemlp_bf16.hip), forward
+    and backward: the route taken when bf16 is requested (autocast or compute_dtype) over a grouped edge list.  fp32 in
+    and out; h1, W2 and g_z2 are rounded to bf16 inside the kernels only.  `once_differentiable`: DMET_EDGE_MLP_BF16=0
+    gives the generic route, e.g. for double backward."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
+        return _edge_mlp2_forward("bf16", ctx, x, W1, b1, W2, b2, gamma, beta, edges, act2, aggr, bn)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        return _edge_mlp2_backward("bf16", ctx, g_out)
 
 
 class _EdgeFeatures(torch.autograd.Function):
@@ -342,9 +367,11 @@ class EdgeConv(torch.nn.Module):
     per-node split (csrc/edgeconv.hip); ``Sequential(Linear(2F, H1), ELU, Linear(H1, H2)[, ELU][, BatchNorm1d(H2)])``
     (ELU alpha 1, fp32, BatchNorm momentum not None) runs fused in fp32 over any graph, forward and backward, for
     H2 in {16, 32, 64, 128}, H1 <= min(192, 2 H2), F <= 128 (csrc/edgemlp_f32.hip; ``DMET_EDGE_MLP_F32=0`` restores
-    the generic route, e.g. for double backward), or on the bf16 matrix cores when bf16 is requested over a kNN
-    table (csrc/edgemlp.hip).  Every other ``nn`` runs the generic route: edge features, ``nn`` over E rows, segment
-    reduction.
+    the generic route, e.g. for double backward), or on the bf16 matrix cores when bf16 is requested (autocast or
+    ``compute_dtype``): over a fixed-width kNN table that csrc/edgemlp.hip takes, and otherwise over any graph, forward
+    and backward, for H2 in {32, 64, 128}, H1 a multiple of 16 <= min(192, 2 H2), F <= 128 (csrc/edgemlp_bf16.hip,
+    fp32 output; ``DMET_EDGE_MLP_BF16=0`` restores the generic route).  Every other ``nn`` runs the generic route: edge
+    features, ``nn`` over E rows, segment reduction.  A bf16 ``x`` is upcast to fp32 on entry (exact).
     """
 
     def __init__(self, nn: Callable, aggr: str = "max", **kwargs):
@@ -395,7 +422,9 @@ class EdgeConv(torch.nn.Module):
                                       bn.weight if bn is not None else None, bn.bias if bn is not None else None)
             return (out, x) if passthrough else out
         edges = table.edge_list()
-        out = self._forward_edge_mlp_f32(x, edges)
+        out = self._forward_edge_mlp_bf16(x, edges)
+        if out is None:
+            out = self._forward_edge_mlp_f32(x, edges)
         if out is None:
             out = self._forward_edges(x, edges)
         return (out, x) if passthrough else out
@@ -412,6 +441,28 @@ class EdgeConv(torch.nn.Module):
             dt = torch.get_autocast_gpu_dtype()
         return (dt == torch.bfloat16 and lin.in_features == 64 and lin.out_features == 32
                 and table.k in (8, 16, 32))
+
+    def _forward_edge_mlp_bf16(self, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
+        """The bf16 matrix-core route over a grouped edge list (_EdgeMLP2Bf16Edges), or None when this call does not take
+        it: bf16 not requested (autocast or compute_dtype), another `nn`, non-fp32 parameters, widths outside
+        dmet_edge_mlp_bf16_supported, DMET_EDGE_MLP_BF16=0, or a training-mode BatchNorm over E <= 1 edges.  fp32 out."""
+        if os.environ.get("DMET_EDGE_MLP_BF16", "1") == "0" or not x.is_cuda or x.dtype != torch.float32:
+            return None
+        if not self._wants_bf16():
+            return None
+        mlp = _as_mlp2(self.nn)
+        if mlp is None:
+            return None
+        l1, l2, act2, bn = mlp
+        params = [l1.weight, l1.bias, l2.weight, l2.bias] + ([bn.weight, bn.bias] if bn is not None else [])
+        if any(p is not None and p.dtype != torch.float32 for p in params) or l1.in_features != 2 * x.shape[1]:
+            return None
+        if not _native.edge_mlp_bf16_supported(x.shape[1], l1.out_features, l2.out_features):
+            return None
+        if bn is not None and (bn.training or not bn.track_running_stats) and edges.num_edges <= 1:
+            return None
+        return _EdgeMLP2Bf16Edges.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, bn.weight if bn is not None else None,
+                                        bn.bias if bn is not None else None, edges, act2, self.aggr, bn)
 
     def _forward_edge_mlp_f32(self, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
         """The fused fp32 route (_EdgeMLP2F32) for a two-layer edge MLP, or None when this call keeps the generic route:
@@ -444,6 +495,8 @@ class EdgeConv(torch.nn.Module):
         msg = self.nn(feat)
         if msg.dim() != 2 or msg.shape[0] != edges.num_edges:
             raise ValueError("nn must map [E, 2F] -> [E, F_out]")
+        if msg.dtype == torch.bfloat16:
+            msg = msg.float()       # nn under bf16 autocast: exact upcast, the segment reductions are fp32
         msg = msg.contiguous()
         if self.aggr == "max":
             out, _arg = _SegmentMaxRows.apply(msg, edges.rowptr, N)
@@ -461,6 +514,8 @@ class EdgeConv(torch.nn.Module):
             x = x[0]
         if x.dim() != 2:
             raise ValueError(f"x must be [N, F], got {tuple(x.shape)}")
+        if x.dtype == torch.bfloat16:
+            x = x.float()       # bf16 autocast upstream: exact upcast, gradients flow back through it
         if x.dtype != torch.float32:
             raise TypeError(f"x must be float32, got {x.dtype}")
         if isinstance(edge_index, GraphFuture):
@@ -474,7 +529,9 @@ class EdgeConv(torch.nn.Module):
         if hit is not None and hit[1] == self.flow and hit[0].num_nodes == x.shape[0]:
             return self._forward_table(x, hit[0])
         edges = edge_list_from_edge_index(edge_index, x.shape[0], self.flow)
-        out = self._forward_edge_mlp_f32(x, edges)
+        out = self._forward_edge_mlp_bf16(x, edges)
+        if out is None:
+            out = self._forward_edge_mlp_f32(x, edges)
         return out if out is not None else self._forward_edges(x, edges)
 
     # -- BatchNorm transform of the PREVIOUS block fused into this layer's node-level dense layer (static graphs) --------
@@ -554,6 +611,8 @@ class DynamicEdgeConv(EdgeConv):
             batch = batch[0]
         if x.dim() != 2:
             raise ValueError("Static graphs not supported in DynamicEdgeConv")  # upstream's message
+        if x.dtype == torch.bfloat16:
+            x = x.float()       # bf16 autocast upstream: exact upcast, gradients flow back through it
         if x.dtype != torch.float32:
             raise TypeError(f"x must be float32, got {x.dtype}")
         table = self._take_prebuilt(x)

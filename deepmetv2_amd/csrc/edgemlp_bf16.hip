@@ -1,0 +1,474 @@
+// edgemlp_bf16.hip -- EdgeConv for a two-layer edge MLP over ANY grouped edge list with the per-edge products on the
+// bf16 matrix cores (gfx950), forward and backward.
+//
+// Replaces, for  nn = Sequential(Linear(2 Hin, H1), ELU, Linear(H1, H2)[, ELU][, BatchNorm1d(H2)])  and aggr in
+// {max, add, mean}, the generic route under bf16 autocast (edge_features -> nn over E rows -> segment max / sum) and its
+// autograd graph: the call shape of model/dynamic_reduction_network.py:59-73,86-87,94-95 (EdgeConv over
+// to_undirected(knn_graph(...))) when the model runs under torch.autocast(dtype=torch.bfloat16).
+//
+// Only the two edge passes live here.  Everything at node level is the fp32 route's (edgemlp_f32.hip, which also owns
+// the host orchestration): the split of the first Linear PQ = [x (W1a - W1b)^T + b1 | x W1b^T], the BatchNorm finalize
+// and apply kernels, the BatchNorm backward reduction, the gW2 partial sums and gx.  The plan is that route's plan:
+//   forward edge pass: workgroup b owns the node range whose edges start at b E / nblk; it walks its edges in tiles of
+//     T = 32 consecutive edges that may span targets: h1 = ELU(P_tgt + Q_src) in fp32 -> bf16 tile in LDS,
+//     z2 = h1 W2^T + b2 on v_mfma_f32_16x16x32_bf16 (fp32 accumulation; W2 bf16 in LDS), m = ELU?(z2) in fp32, then
+//     one thread per channel folds the tile in edge order into the current target's aggregate (max winners as int32
+//     edge positions, lowest on ties) and keeps the BatchNorm partials sum m, sum m^2.
+//   backward edge pass by target: per tile re-computes z2 as above, g_z2 in fp32 (fp32 route's formula), then on the
+//     matrix cores g_h1 = g_z2 W2 and the gW2 accumulation gW2 += g_z2^T h1 (both operands bf16, fp32 accumulators that
+//     live in registers across the workgroup's tiles); g_pre1 = g_h1 ELU'(h1) in fp32 is summed per target into gP in
+//     edge order; gb2 is an fp32 sum of g_z2.  The same pass by source (EdgeList.by_source order) sums gQ.
+// No [E, *] tensor in HBM, no atomics: every sum runs in a fixed order inside one workgroup; run to run bit-identical.
+//
+// MFMA operand maps (16x16x32 bf16): lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15],
+// j = 0..7; C/D: col = l & 15, row = 4 (l >> 4) + reg.
+//   z2    : A = h1 [t][c]  (edge-major bf16 tile, row pitch SH),  B[c][o] = W2[o][c] (W2 bf16 [H2][SH]); K = H1 padded to 32
+//   g_h1  : A = g_z2 [t][o] (edge-major bf16 tile, pitch H2 + 8), B[o][c] = W2[o][c] (the same W2 image, read by column)
+//   gW2   : A[o][t] = g_z2 (channel-major fp32 tile, rounded on the read), B[t][c] = h1 (channel-major fp32 tile); K = T
+// The channel-major fp32 tiles also serve the fp32 parts: ELU'(h1), gb2, and (in place of h1) g_pre1 for the fold.
+//
+// Numerics: P, Q, ELU, the aggregation and the BatchNorm are fp32.  Forward: h1 and W2 rounded to bf16 (RNE), products
+// exact, fp32 accumulation.  Backward: g_z2, h1 and W2 rounded to bf16 for g_h1 and gW2, fp32 accumulation; node-level
+// products fp32.  Compared with the fp32 result at the R6 bar (rtol 2e-2 of the output scale).
+//
+// Widths (dmet_edge_mlp_bf16_supported): H2 in {32, 64, 128}, H1 a multiple of 16 with H1 <= min(192, 2 H2),
+// 1 <= Hin <= 128.  LDS per workgroup (T = 32): forward 2 SH (H2 + T) + 4 H2 (TS + 1) + 8 T bytes, backward
+// 2 SH (H2 + T) + 4 TS (H1 + H2) + 2 T (H2 + 8) + 4 H2 + 12 T bytes, SH = roundup(H1, 32) + 8, TS = T + 4.
+#include "edgemlp_fused.h"
+
+namespace dmet {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef short bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kT = 32;          // edges per tile (the K of the gW2 product)
+constexpr int kTS = kT + 4;     // row pitch of the channel-major fp32 tiles
+constexpr int kWaves = kBlk / 64;
+
+__device__ __forceinline__ unsigned short bf16_bits(float f)
+{
+    const __bf16 b = (__bf16)f;     // RNE (v_cvt_pk_bf16_f32)
+    return __builtin_bit_cast(unsigned short, b);
+}
+
+__host__ __device__ __forceinline__ int h1_pad(int H1) { return (H1 + 31) & ~31; }
+__host__ __device__ __forceinline__ int h1_pitch(int H1) { return h1_pad(H1) + 8; }
+
+// 8 consecutive bf16 from LDS (16-B aligned)
+__device__ __forceinline__ bf16x8 ld8(const unsigned short *p) { return *reinterpret_cast<const bf16x8 *>(p); }
+
+// 8 consecutive fp32 from LDS (16-B aligned), rounded to bf16
+__device__ __forceinline__ bf16x8 ld8_f32(const float *p)
+{
+    const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
+    bf16x8 r;
+    r[0] = (short)bf16_bits(a.x); r[1] = (short)bf16_bits(a.y); r[2] = (short)bf16_bits(a.z); r[3] = (short)bf16_bits(a.w);
+    r[4] = (short)bf16_bits(b.x); r[5] = (short)bf16_bits(b.y); r[6] = (short)bf16_bits(b.z); r[7] = (short)bf16_bits(b.w);
+    return r;
+}
+
+// W2 as bf16 [H2][SH] (columns H1 .. SH - 1 zero) and b2 fp32 [H2]
+__device__ __forceinline__ void stage_w2(const float *__restrict__ W2, const float *__restrict__ b2, int H1, int H2,
+                                         unsigned short *w2s, float *b2s)
+{
+    const int SH = h1_pitch(H1);
+    for (int idx = threadIdx.x; idx < H2 * SH; idx += blockDim.x) {
+        const int o = idx / SH, c = idx - o * SH;
+        w2s[idx] = c < H1 ? bf16_bits(W2[(int64_t)o * H1 + c]) : (unsigned short)0;
+    }
+    for (int o = threadIdx.x; o < H2; o += blockDim.x) b2s[o] = b2 ? b2[o] : 0.0f;
+}
+
+// h1 = ELU(P_tgt + Q_src) of the tile's cnt edges (beyond: 0): bf16 edge-major [T][SH] (padding columns 0) and, when
+// h1c is given, fp32 channel-major [H1][TS]
+__device__ __forceinline__ void fill_h1_bf16(const float *__restrict__ PQ, int H1, const int32_t *tg, const int32_t *sr,
+                                             int cnt, unsigned short *h1e, float *h1c)
+{
+    const int H1p = h1_pad(H1), SH = h1_pitch(H1);
+    for (int idx = threadIdx.x; idx < kT * H1p; idx += blockDim.x) {
+        const int t = idx / H1p, c = idx - t * H1p;
+        float h = 0.0f;
+        if (t < cnt && c < H1) h = elu1f(PQ[(int64_t)tg[t] * 2 * H1 + c] + PQ[(int64_t)sr[t] * 2 * H1 + H1 + c]);
+        h1e[t * SH + c] = bf16_bits(h);
+        if (h1c && c < H1) h1c[c * kTS + t] = h;
+    }
+}
+
+// z2 block (edge block eb, channel block ob) of the tile, before the bias: C[t][o], t = 16 eb + 4 (l >> 4) + r
+__device__ __forceinline__ f32x4 z2_block(const unsigned short *h1e, const unsigned short *w2s, int H1, int eb, int ob, int lane)
+{
+    const int SH = h1_pitch(H1), ksteps = h1_pad(H1) / 32;
+    const unsigned short *pa = h1e + (16 * eb + (lane & 15)) * SH + 8 * (lane >> 4);
+    const unsigned short *pb = w2s + (16 * ob + (lane & 15)) * SH + 8 * (lane >> 4);
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int ks = 0; ks < ksteps; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(pa + 32 * ks), ld8(pb + 32 * ks), acc, 0, 0, 0);
+    return acc;
+}
+
+// aggr: 0 max, 1 add, 2 mean.  bn: 0 none, 1 training (keep the statistics partials), 2 eval.
+template <int H2>
+__global__ __launch_bounds__(kBlk) void edge_mlp_fwd_bf16_kernel(const float *__restrict__ PQ, const int32_t *__restrict__ rowptr,
+                                                                 const int32_t *__restrict__ src, const int32_t *__restrict__ tgt,
+                                                                 int64_t N, int64_t E, int H1, const float *__restrict__ W2,
+                                                                 const float *__restrict__ b2, int act2, int aggr, int bn,
+                                                                 float *__restrict__ agg, int32_t *__restrict__ win,
+                                                                 float *__restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const int SH = h1_pitch(H1);
+    unsigned short *w2s = reinterpret_cast<unsigned short *>(lds_raw);   // [H2][SH]
+    unsigned short *h1e = w2s + H2 * SH;                                 // [T][SH]
+    float *b2s = reinterpret_cast<float *>(h1e + kT * SH);               // [H2]
+    float *ms = b2s + H2;                                                // [H2][TS]
+    int32_t *tg = reinterpret_cast<int32_t *>(ms + H2 * kTS);            // [T]
+    int32_t *sr = tg + kT;                                               // [T]
+    stage_w2(W2, b2, H1, H2, w2s, b2s);
+
+    const int nblk = gridDim.x;
+    const int64_t n0 = range_start(rowptr, N, E, blockIdx.x, nblk), n1 = range_start(rowptr, N, E, blockIdx.x + 1, nblk);
+    const int64_t p0 = rowptr[n0], p1 = rowptr[n1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool maxa = aggr == 0, mins = maxa && bn != 0;
+    // running aggregate of channel threadIdx.x (threads < H2)
+    int64_t cur = -1;
+    float s = 0.0f, mx = 0.0f, mn = 0.0f, st1 = 0.0f, st2 = 0.0f;
+    int32_t amx = -1, amn = -1;
+    auto flush = [&]() {
+        if (cur < 0) return;
+        const int64_t q = cur * H2 + threadIdx.x;
+        if (maxa) {
+            agg[q] = mx;
+            win[q] = amx;
+            if (mins) {
+                agg[N * H2 + q] = mn;
+                win[N * H2 + q] = amn;
+            }
+        } else {
+            agg[q] = s;
+        }
+    };
+    for (int64_t pt = p0; pt < p1; pt += kT) {
+        const int cnt = (int)(p1 - pt < kT ? p1 - pt : kT);
+        __syncthreads();       // the previous tile's readers of tg / sr / ms are done
+        for (int t = threadIdx.x; t < kT; t += blockDim.x) {
+            tg[t] = t < cnt ? tgt[pt + t] : 0;
+            sr[t] = t < cnt ? src[pt + t] : 0;
+        }
+        __syncthreads();
+        fill_h1_bf16(PQ, H1, tg, sr, cnt, h1e, nullptr);
+        __syncthreads();
+        for (int blk = wave; blk < 2 * (H2 / 16); blk += kWaves) {
+            const int eb = blk & 1, ob = blk >> 1;
+            const f32x4 acc = z2_block(h1e, w2s, H1, eb, ob, lane);
+            const int o = 16 * ob + (lane & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float z = acc[r] + b2s[o];
+                ms[o * kTS + 16 * eb + 4 * (lane >> 4) + r] = act2 ? elu1f(z) : z;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < H2) {
+            const int c = threadIdx.x;
+            for (int t = 0; t < cnt; ++t) {
+                const int64_t own = tg[t];
+                const float m = ms[c * kTS + t];
+                const int32_t e = (int32_t)(pt + t);
+                if (own != cur) {
+                    flush();
+                    cur = own;
+                    s = m; mx = m; mn = m; amx = e; amn = e;
+                } else {
+                    s += m;
+                    if (m > mx) { mx = m; amx = e; }
+                    if (m < mn) { mn = m; amn = e; }
+                }
+                if (bn == 1) {
+                    st1 += m;
+                    st2 = __builtin_fmaf(m, m, st2);
+                }
+            }
+        }
+    }
+    if (threadIdx.x < H2) {
+        flush();
+        if (bn == 1) {
+            partial[(int64_t)blockIdx.x * 2 * H2 + threadIdx.x] = st1;
+            partial[(int64_t)blockIdx.x * 2 * H2 + H2 + threadIdx.x] = st2;
+        }
+    }
+}
+
+// Backward edge pass.  BY_SRC = false: positions are grouped edges (owner = tgt), sums g_pre1 per target into
+// gpq[:, 0:H1] and keeps gW2 / gb2 partials; BY_SRC = true: positions walk srcperm (owner = src), sums into gpq[:, H1:2H1].
+template <int H2, bool BY_SRC>
+__global__ __launch_bounds__(kBlk) void edge_mlp_bwd_bf16_kernel(const float *__restrict__ PQ, const int32_t *__restrict__ rowptr,
+                                                                 const int32_t *__restrict__ optr, const int32_t *__restrict__ perm,
+                                                                 const int32_t *__restrict__ src, const int32_t *__restrict__ tgt,
+                                                                 int64_t N, int64_t E, int H1, const float *__restrict__ W2,
+                                                                 const float *__restrict__ b2, int act2, int aggr, int bn,
+                                                                 const float *__restrict__ g_out, const int32_t *__restrict__ win,
+                                                                 const float *__restrict__ bnstat, const float *__restrict__ coef,
+                                                                 float *__restrict__ gpq, float *__restrict__ partial)
+{
+    constexpr int H1MAX = 2 * H2 < 192 ? 2 * H2 : 192;
+    constexpr int NGW = (H2 / 16) * (H1MAX / 16) / kWaves;     // gW2 blocks per wave at the widest H1
+    constexpr int NGH = (2 * (H1MAX / 16) + kWaves - 1) / kWaves;  // g_h1 blocks per wave at the widest H1
+    constexpr int SZ = H2 + 8;                                   // row pitch of the edge-major g_z2 tile
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const int SH = h1_pitch(H1);
+    unsigned short *w2s = reinterpret_cast<unsigned short *>(lds_raw);   // [H2][SH]
+    unsigned short *h1e = w2s + H2 * SH;                                 // [T][SH]
+    unsigned short *gze = h1e + kT * SH;                                 // [T][SZ]   g_z2, bf16
+    float *b2s = reinterpret_cast<float *>(gze + kT * SZ);               // [H2]
+    float *h1c = b2s + H2;                                               // [H1][TS]  h1, then g_pre1
+    float *gzc = h1c + H1 * kTS;                                         // [H2][TS]  g_z2, fp32
+    int32_t *tg = reinterpret_cast<int32_t *>(gzc + H2 * kTS);           // [T]
+    int32_t *sr = tg + kT;                                               // [T]
+    int32_t *ep = sr + kT;                                               // [T] grouped edge position
+    stage_w2(W2, b2, H1, H2, w2s, b2s);
+
+    const int nblk = gridDim.x;
+    const int64_t n0 = range_start(optr, N, E, blockIdx.x, nblk), n1 = range_start(optr, N, E, blockIdx.x + 1, nblk);
+    const int64_t p0 = optr[n0], p1 = optr[n1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ngw = (H2 / 16) * (H1 / 16), ngh = 2 * (H1 / 16);
+    f32x4 gw[BY_SRC ? 1 : NGW];
+    if (!BY_SRC) {
+#pragma unroll
+        for (int j = 0; j < NGW; ++j) gw[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    float gb = 0.0f;
+    int64_t cur = -1;
+    float run = 0.0f;
+    const int coff = BY_SRC ? H1 : 0;
+    for (int64_t pt = p0; pt < p1; pt += kT) {
+        const int cnt = (int)(p1 - pt < kT ? p1 - pt : kT);
+        __syncthreads();
+        for (int t = threadIdx.x; t < kT; t += blockDim.x) {
+            const int32_t e = t < cnt ? (BY_SRC ? perm[pt + t] : (int32_t)(pt + t)) : 0;
+            ep[t] = e;
+            tg[t] = t < cnt ? tgt[e] : 0;
+            sr[t] = t < cnt ? src[e] : 0;
+        }
+        __syncthreads();
+        fill_h1_bf16(PQ, H1, tg, sr, cnt, h1e, h1c);
+        __syncthreads();
+        // g_z2 per (edge, channel) from the re-computed z2 (fp32), into both g_z2 tiles
+        for (int blk = wave; blk < 2 * (H2 / 16); blk += kWaves) {
+            const int eb = blk & 1, ob = blk >> 1;
+            const f32x4 acc = z2_block(h1e, w2s, H1, eb, ob, lane);
+            const int o = 16 * ob + (lane & 15);
+            const float ka = coef[o], k1 = coef[H2 + o], k2 = coef[2 * H2 + o];
+            const float bmean = bnstat[2 * H2 + o], binv = bnstat[3 * H2 + o];
+            const int32_t *winsel = win + ((aggr == 0 && bn != 0 && ka < 0.0f) ? N * H2 : 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int t = 16 * eb + 4 * (lane >> 4) + r;
+                float gzv = 0.0f;
+                if (t < cnt) {
+                    const float z = acc[r] + b2s[o];
+                    const float m = act2 ? elu1f(z) : z;
+                    const float gy = gy_of(g_out, rowptr, winsel, aggr, tg[t], H2, o, ep[t]);
+                    float gm = gy;
+                    if (bn == 1) gm = ka * (gy - k1 - (m - bmean) * binv * k2);
+                    else if (bn == 2) gm = ka * gy;
+                    gzv = act2 ? gm * (z > 0.0f ? 1.0f : m + 1.0f) : gm;
+                }
+                gzc[o * kTS + t] = gzv;
+                gze[t * SZ + o] = bf16_bits(gzv);
+            }
+        }
+        __syncthreads();
+        if (!BY_SRC) {
+            // gW2[o][c] += sum_t g_z2[t][o] h1[t][c]: blocks (ob, cb) of this wave, K = the tile's T edges
+#pragma unroll
+            for (int j = 0; j < NGW; ++j) {
+                const int blk = wave + kWaves * j;
+                if (blk < ngw) {
+                    const int ob = blk % (H2 / 16), cb = blk / (H2 / 16);
+                    const bf16x8 a = ld8_f32(gzc + (16 * ob + (lane & 15)) * kTS + 8 * (lane >> 4));
+                    const bf16x8 b = ld8_f32(h1c + (16 * cb + (lane & 15)) * kTS + 8 * (lane >> 4));
+                    gw[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, gw[j], 0, 0, 0);
+                }
+            }
+            if (threadIdx.x < H2) {
+                float a = 0.0f;
+                for (int t = 0; t < cnt; ++t) a += gzc[threadIdx.x * kTS + t];
+                gb += a;
+            }
+        }
+        // g_h1[t][c] = sum_o g_z2[t][o] W2[o][c]: blocks (eb, cb), kept in registers until every h1c reader is done
+        f32x4 gh[NGH];
+#pragma unroll
+        for (int j = 0; j < NGH; ++j) {
+            gh[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            const int blk = wave + kWaves * j;
+            if (blk < ngh) {
+                const int eb = blk & 1, cb = blk >> 1;
+                const unsigned short *pa = gze + (16 * eb + (lane & 15)) * SZ + 8 * (lane >> 4);
+                const unsigned short *pb = w2s + 8 * (lane >> 4) * SH + 16 * cb + (lane & 15);
+                for (int ks = 0; ks < H2 / 32; ++ks) {
+                    bf16x8 b;
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) b[q] = (short)pb[(32 * ks + q) * SH];
+                    gh[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(pa + 32 * ks), b, gh[j], 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();
+        // g_pre1 = g_h1 ELU'(h1) in place of h1 (each element read and written by its own lane)
+#pragma unroll
+        for (int j = 0; j < NGH; ++j) {
+            const int blk = wave + kWaves * j;
+            if (blk < ngh) {
+                const int eb = blk & 1, c = 16 * (blk >> 1) + (lane & 15);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float *p = h1c + c * kTS + 16 * eb + 4 * (lane >> 4) + r;
+                    const float h = *p;
+                    *p = gh[j][r] * (h > 0.0f ? 1.0f : h + 1.0f);
+                }
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < H1) {
+            const int c = threadIdx.x;
+            for (int t = 0; t < cnt; ++t) {
+                const int64_t own = BY_SRC ? sr[t] : tg[t];
+                const float v = h1c[c * kTS + t];
+                if (own != cur) {
+                    if (cur >= 0) gpq[cur * 2 * H1 + coff + c] = run;
+                    cur = own;
+                    run = v;
+                } else {
+                    run += v;
+                }
+            }
+        }
+    }
+    if (threadIdx.x < H1 && cur >= 0) gpq[cur * 2 * H1 + coff + threadIdx.x] = run;
+    if (!BY_SRC) {
+        // partial[blk] = gW2 [H2][H1] | gb2 [H2]
+        float *pb = partial + (int64_t)blockIdx.x * (H2 * H1 + H2);
+#pragma unroll
+        for (int j = 0; j < NGW; ++j) {
+            const int blk = wave + kWaves * j;
+            if (blk < ngw) {
+                const int ob = blk % (H2 / 16), cb = blk / (H2 / 16);
+                const int c = 16 * cb + (lane & 15);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pb[(16 * ob + 4 * (lane >> 4) + r) * H1 + c] = gw[j][r];
+            }
+        }
+        if (threadIdx.x < H2) pb[H2 * H1 + threadIdx.x] = gb;
+    }
+}
+
+inline size_t fwd_lds_bytes_bf16(int H1, int H2)
+{
+    const size_t SH = h1_pitch(H1);
+    return 2 * SH * (H2 + kT) + sizeof(float) * (size_t)H2 * (kTS + 1) + 2 * sizeof(int32_t) * kT;
+}
+
+inline size_t bwd_lds_bytes_bf16(int H1, int H2)
+{
+    const size_t SH = h1_pitch(H1);
+    return 2 * SH * (H2 + kT) + 2 * (size_t)kT * (H2 + 8) + sizeof(float) * ((size_t)H2 + (size_t)kTS * (H1 + H2)) +
+           3 * sizeof(int32_t) * kT;
+}
+
+}  // namespace
+
+int edge_mlp_fwd_pass_bf16(const EdgePassArgs &a, int nblk, float *partial, hipStream_t st)
+{
+    const size_t lds = fwd_lds_bytes_bf16(a.H1, a.H2);
+    int rc = 0;
+#define EMLP_FWD_BF16(kH2)                                                                                                  \
+    {                                                                                                                       \
+        static size_t granted = 0;                                                                                          \
+        rc = grant_lds(edge_mlp_fwd_bf16_kernel<kH2>, lds, granted, "hipFuncSetAttribute(edge_mlp_fwd_bf16_kernel)");       \
+        if (rc == 0)                                                                                                        \
+            hipLaunchKernelGGL((edge_mlp_fwd_bf16_kernel<kH2>), dim3(nblk), dim3(kBlk), lds, st, a.pq, a.rowptr, a.src,     \
+                               a.tgt, a.N, a.E, a.H1, a.W2, a.b2, a.act2, a.aggr, a.bn, a.agg, a.win, partial);             \
+    }
+    switch (a.H2) {
+    case 32: EMLP_FWD_BF16(32) break;
+    case 64: EMLP_FWD_BF16(64) break;
+    default: EMLP_FWD_BF16(128) break;
+    }
+#undef EMLP_FWD_BF16
+    if (rc) return rc;
+    DMET_LAUNCH_CHECK("edge_mlp_fwd_bf16_kernel");
+    return 0;
+}
+
+int edge_mlp_bwd_pass_bf16(const EdgePassArgs &a, bool by_src, int nblk, float *partial, hipStream_t st)
+{
+    const size_t lds = bwd_lds_bytes_bf16(a.H1, a.H2);
+    const int32_t *optr = by_src ? a.srcptr : a.rowptr, *perm = by_src ? a.srcperm : nullptr;
+    int rc = 0;
+#define EMLP_BWD_BF16(kH2, kBS)                                                                                             \
+    {                                                                                                                       \
+        static size_t granted = 0;                                                                                          \
+        rc = grant_lds(edge_mlp_bwd_bf16_kernel<kH2, kBS>, lds, granted, "hipFuncSetAttribute(edge_mlp_bwd_bf16_kernel)");  \
+        if (rc == 0)                                                                                                        \
+            hipLaunchKernelGGL((edge_mlp_bwd_bf16_kernel<kH2, kBS>), dim3(nblk), dim3(kBlk), lds, st, a.pq, a.rowptr, optr, \
+                               perm, a.src, a.tgt, a.N, a.E, a.H1, a.W2, a.b2, a.act2, a.aggr, a.bn, a.g_out, a.cwin,       \
+                               a.bnstat, a.coef, a.gpq, partial);                                                           \
+    }
+    switch (a.H2 * 2 + (by_src ? 1 : 0)) {
+    case 64: EMLP_BWD_BF16(32, false) break;
+    case 65: EMLP_BWD_BF16(32, true) break;
+    case 128: EMLP_BWD_BF16(64, false) break;
+    case 129: EMLP_BWD_BF16(64, true) break;
+    case 256: EMLP_BWD_BF16(128, false) break;
+    default: EMLP_BWD_BF16(128, true) break;
+    }
+#undef EMLP_BWD_BF16
+    if (rc) return rc;
+    DMET_LAUNCH_CHECK(by_src ? "edge_mlp_bwd_bf16_kernel (by source)" : "edge_mlp_bwd_bf16_kernel (by target)");
+    return 0;
+}
+
+}  // namespace dmet
+
+using namespace dmet;
+
+extern "C" int dmet_edge_mlp_bf16_supported(int Hin, int H1, int H2)
+{
+    if (!(H2 == 32 || H2 == 64 || H2 == 128)) return 0;
+    if (Hin < 1 || Hin > 128 || H1 < 16 || H1 % 16 != 0 || H1 > 192 || H1 > 2 * H2) return 0;
+    return 1;
+}
+
+extern "C" size_t dmet_edge_mlp_bf16_workspace_bytes(int64_t N, int64_t E, int Hin, int H1, int H2)
+{
+    // the node-level state and the partials are the fp32 route's
+    if (!dmet_edge_mlp_bf16_supported(Hin, H1, H2)) return 0;
+    return dmet_edge_mlp_f32_workspace_bytes(N, E, Hin, H1, H2);
+}
+
+extern "C" int dmet_edge_mlp_fwd_bf16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+                                      const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1, const float *W2,
+                                      const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
+                                      const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                                      int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
+                                      float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    return edge_mlp_fwd("dmet_edge_mlp_fwd_bf16", true, x, N, Hin, rowptr, src, tgt, E, W1, b1, H1, W2, b2, H2, act2, aggr,
+                        bn, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq, agg, win,
+                        bnstat, ws, ws_bytes, stream);
+}
+
+extern "C" int dmet_edge_mlp_bwd_bf16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+                                      const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
+                                      const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr,
+                                      int bn, const float *pq, const float *agg, const int32_t *win, const float *bnstat,
+                                      const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
+                                      float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    return edge_mlp_bwd("dmet_edge_mlp_bwd_bf16", true, x, N, Hin, rowptr, src, tgt, E, srcptr, srcperm, W1, H1, W2, b2, H2,
+                        act2, aggr, bn, pq, agg, win, bnstat, g_out, gx, gpq, gW2, gb2, ggamma, gbeta, ws, ws_bytes, stream);
+}

@@ -29,29 +29,12 @@
 //      gb1 follow from [gP | gQ]^T x on the caller's side (dmet_xty_f32).
 // Numerics: fp32 throughout (fmaf chains), sums in edge order; BatchNorm statistics reduced in double.  Not bit-equal to
 // the generic route (the split of the first Linear and the fused sums round differently); run to run bit-identical.
-#include "common.h"
+#include "edgemlp_fused.h"
 
 namespace dmet {
 namespace {
 
-constexpr int kBlk = 256;     // threads per workgroup of the edge passes
 constexpr int kTpt = 8;       // edges per thread in the z2 / g_h1 products
-constexpr int kMaxBlocks = 512;
-
-__device__ __forceinline__ float elu1f(float z) { return z > 0.0f ? z : expm1f(z); }
-
-// first node of workgroup b's range: the first i with rowptr[i] >= b E / nblk (rowptr non-decreasing, rowptr[N] = E)
-__device__ __forceinline__ int64_t range_start(const int32_t *__restrict__ rowptr, int64_t N, int64_t E, int b, int nblk)
-{
-    if (b >= nblk) return N;
-    const int64_t target = (int64_t)b * E / nblk;
-    int64_t lo = 0, hi = N;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)rowptr[mid] >= target) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
 
 // Y[n][m] = b[m] + sum_k X[n][k] Wt[k][m], 16 rows per workgroup; fixed summation order (ascending k)
 __global__ __launch_bounds__(256) void rows_linear_kernel(const float *__restrict__ X, int64_t N, int K,
@@ -317,17 +300,6 @@ __global__ __launch_bounds__(256) void edge_mlp_apply_kernel(const float *__rest
     out[t] = v;
 }
 
-// per-node g_y weight of an edge (sum 1, mean 1 / deg) and, for max, the winner array in use
-__device__ __forceinline__ float gy_of(const float *__restrict__ g_out, const int32_t *__restrict__ rowptr,
-                                       const int32_t *__restrict__ winsel, int aggr, int64_t tnode, int H2, int o, int32_t e)
-{
-    const int64_t q = tnode * H2 + o;
-    const float go = g_out[q];
-    if (aggr == 0) return winsel[q] == e ? go : 0.0f;
-    if (aggr == 2) return go / (float)(rowptr[tnode + 1] - rowptr[tnode]);
-    return go;
-}
-
 // stage 1 of the BatchNorm backward sums: R1 = sum_i g_out w_i, R2 = sum_i g_out v_i (see the file comment); one partial
 // per workgroup, threads (channel, row lane) reduced through LDS in a fixed order
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float *__restrict__ g_out, const float *__restrict__ agg,
@@ -552,13 +524,6 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float *__restri
     else if (outB) outB[t - nA] = (float)a;
 }
 
-inline int edge_blocks(int64_t E)
-{
-    int64_t nb = (E + 2047) / 2048;
-    if (nb < 1) nb = 1;
-    return (int)(nb > kMaxBlocks ? kMaxBlocks : nb);
-}
-
 inline size_t fwd_lds_bytes(int H1, int H2)
 {
     const int T = 2048 / H2, TS = T + 4;
@@ -574,17 +539,6 @@ inline size_t bwd_lds_bytes(int H1, int H2)
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 constexpr int kBnReduceBlocks = 256;
-
-// dynamic LDS above 64 KB must be granted per kernel (hidden 128: up to 141 KB); remembered per instantiation
-template <typename K>
-int grant_lds(K kernel, size_t lds, size_t &granted, const char *what)
-{
-    if (lds <= 65536 || lds <= granted) return 0;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_fail(e, what);
-    granted = lds;
-    return 0;
-}
 
 }  // namespace
 }  // namespace dmet
@@ -616,13 +570,15 @@ extern "C" size_t dmet_edge_mlp_f32_workspace_bytes(int64_t N, int64_t E, int Hi
     default: { constexpr int kH2 = 128; __VA_ARGS__; } break;           \
     }
 
-static int check_common(const char *fn, const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
-                        const int32_t *tgt, int64_t E, const float *W1, int H1, const float *W2, int H2, int aggr, int bn,
-                        const float *running_mean, const float *running_var, size_t ws_bytes, const void *ws, bool fwd)
+static int check_common(const char *fn, bool bf16, const float *x, int64_t N, int Hin, const int32_t *rowptr,
+                        const int32_t *src, const int32_t *tgt, int64_t E, const float *W1, int H1, const float *W2, int H2,
+                        int aggr, int bn, const float *running_mean, const float *running_var, size_t ws_bytes,
+                        const void *ws, bool fwd)
 {
+    const int supported = bf16 ? dmet_edge_mlp_bf16_supported(Hin, H1, H2) : dmet_edge_mlp_f32_supported(Hin, H1, H2);
     DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647 / 384, "%s: N out of range", fn);
     DMET_REQUIRE(E >= 0 && E < (int64_t)2147483647, "%s: E out of range", fn);
-    DMET_REQUIRE(dmet_edge_mlp_f32_supported(Hin, H1, H2), "%s: unsupported widths Hin=%d H1=%d H2=%d", fn, Hin, H1, H2);
+    DMET_REQUIRE(supported, "%s: unsupported widths Hin=%d H1=%d H2=%d", fn, Hin, H1, H2);
     DMET_REQUIRE(aggr >= 0 && aggr <= 2, "%s: aggr must be 0 (max), 1 (add) or 2 (mean)", fn);
     DMET_REQUIRE(bn >= 0 && bn <= 2, "%s: bn must be 0 (none), 1 (training) or 2 (eval)", fn);
     DMET_REQUIRE(!fwd || bn != 2 || (running_mean && running_var), "%s: eval mode needs running statistics", fn);
@@ -635,15 +591,14 @@ static int check_common(const char *fn, const float *x, int64_t N, int Hin, cons
     return 0;
 }
 
-extern "C" int dmet_edge_mlp_fwd_f32(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
-                                     const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1, const float *W2,
-                                     const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
-                                     const float *beta, float eps, float momentum, float *running_mean, float *running_var,
-                                     int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
-                                     float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
+int dmet::edge_mlp_fwd(const char *fn, bool bf16, const float *x, int64_t N, int Hin, const int32_t *rowptr,
+                       const int32_t *src, const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1,
+                       const float *W2, const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
+                       const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                       int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win, float *bnstat,
+                       void *ws, size_t ws_bytes, dmet_stream_t stream)
 {
-    const char *fn = "dmet_edge_mlp_fwd_f32";
-    if (int rc = check_common(fn, x, N, Hin, rowptr, src, tgt, E, W1, H1, W2, H2, aggr, bn, running_mean, running_var,
+    if (int rc = check_common(fn, bf16, x, N, Hin, rowptr, src, tgt, E, W1, H1, W2, H2, aggr, bn, running_mean, running_var,
                               ws_bytes, ws, true))
         return rc;
     DMET_REQUIRE(bn != 1 || E > 0, "%s: batch statistics need at least one edge", fn);
@@ -662,7 +617,12 @@ extern "C" int dmet_edge_mlp_fwd_f32(const float *x, int64_t N, int Hin, const i
                        (const float *)bias, 2 * H1, pq);
     DMET_LAUNCH_CHECK("rows_linear_kernel (P | Q)");
     const int nblk = edge_blocks(E);
-    if (E > 0) {
+    if (E > 0 && bf16) {
+        EdgePassArgs a{};
+        a.pq = pq; a.rowptr = rowptr; a.src = src; a.tgt = tgt; a.N = N; a.E = E; a.H1 = H1; a.H2 = H2;
+        a.W2 = W2; a.b2 = b2; a.act2 = act2; a.aggr = aggr; a.bn = bn; a.agg = agg; a.win = win;
+        if (int rc = edge_mlp_fwd_pass_bf16(a, nblk, partial, st)) return rc;
+    } else if (E > 0) {
         const size_t lds = fwd_lds_bytes(H1, H2);
         int rc = 0;
         EMLP_DISPATCH(H2, static size_t granted = 0;
@@ -683,15 +643,14 @@ extern "C" int dmet_edge_mlp_fwd_f32(const float *x, int64_t N, int Hin, const i
     return 0;
 }
 
-extern "C" int dmet_edge_mlp_bwd_f32(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
-                                     const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
-                                     const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr,
-                                     int bn, const float *pq, const float *agg, const int32_t *win, const float *bnstat,
-                                     const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
-                                     float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
+int dmet::edge_mlp_bwd(const char *fn, bool bf16, const float *x, int64_t N, int Hin, const int32_t *rowptr,
+                       const int32_t *src, const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
+                       const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr, int bn,
+                       const float *pq, const float *agg, const int32_t *win, const float *bnstat, const float *g_out,
+                       float *gx, float *gpq, float *gW2, float *gb2, float *ggamma, float *gbeta, void *ws,
+                       size_t ws_bytes, dmet_stream_t stream)
 {
-    const char *fn = "dmet_edge_mlp_bwd_f32";
-    if (int rc = check_common(fn, x, N, Hin, rowptr, src, tgt, E, W1, H1, W2, H2, aggr, bn, nullptr, nullptr, ws_bytes, ws, false))
+    if (int rc = check_common(fn, bf16, x, N, Hin, rowptr, src, tgt, E, W1, H1, W2, H2, aggr, bn, nullptr, nullptr, ws_bytes, ws, false))
         return rc;
     hipStream_t st = as_stream(stream);
     if (N == 0) {
@@ -729,7 +688,14 @@ extern "C" int dmet_edge_mlp_bwd_f32(const float *x, int64_t N, int Hin, const i
     hipLaunchKernelGGL(zero_kernel, dim3((unsigned)((npq + 255) / 256)), dim3(256), 0, st, gpq, npq);
     DMET_LAUNCH_CHECK("zero_kernel");
     const int nblk = edge_blocks(E);
-    if (E > 0) {
+    if (E > 0 && bf16) {
+        EdgePassArgs a{};
+        a.pq = pq; a.rowptr = rowptr; a.src = src; a.tgt = tgt; a.N = N; a.E = E; a.H1 = H1; a.H2 = H2;
+        a.W2 = W2; a.b2 = b2; a.act2 = act2; a.aggr = aggr; a.bn = bn; a.srcptr = srcptr; a.srcperm = srcperm;
+        a.g_out = g_out; a.bnstat = bnstat; a.coef = coef; a.cwin = win; a.gpq = gpq;
+        if (int rc = edge_mlp_bwd_pass_bf16(a, false, nblk, partial, st)) return rc;
+        if (int rc = edge_mlp_bwd_pass_bf16(a, true, nblk, nullptr, st)) return rc;
+    } else if (E > 0) {
         const size_t lds = bwd_lds_bytes(H1, H2);
         int rc = 0;
         EMLP_DISPATCH(H2, static size_t granted = 0;
@@ -746,6 +712,8 @@ extern "C" int dmet_edge_mlp_bwd_f32(const float *x, int64_t N, int Hin, const i
                                                       g_out, win, bnstat, (const float *)coef, gpq, (float *)nullptr));
         if (rc) return rc;
         DMET_LAUNCH_CHECK("edge_mlp_bwd_kernel (by source)");
+    }
+    if (E > 0) {
         const int n = H2 * H1 + H2;
         hipLaunchKernelGGL(sum_partials_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const float *)partial, nblk,
                            (int64_t)n, n, gW2, H2 * H1, gb2);
@@ -761,4 +729,27 @@ extern "C" int dmet_edge_mlp_bwd_f32(const float *x, int64_t N, int Hin, const i
         DMET_LAUNCH_CHECK("rows_linear_kernel (gx)");
     }
     return 0;
+}
+
+extern "C" int dmet_edge_mlp_fwd_f32(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+                                     const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1, const float *W2,
+                                     const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
+                                     const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                                     int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
+                                     float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    return edge_mlp_fwd("dmet_edge_mlp_fwd_f32", false, x, N, Hin, rowptr, src, tgt, E, W1, b1, H1, W2, b2, H2, act2, aggr,
+                        bn, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq, agg, win,
+                        bnstat, ws, ws_bytes, stream);
+}
+
+extern "C" int dmet_edge_mlp_bwd_f32(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+                                     const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
+                                     const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr,
+                                     int bn, const float *pq, const float *agg, const int32_t *win, const float *bnstat,
+                                     const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
+                                     float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    return edge_mlp_bwd("dmet_edge_mlp_bwd_f32", false, x, N, Hin, rowptr, src, tgt, E, srcptr, srcperm, W1, H1, W2, b2, H2,
+                        act2, aggr, bn, pq, agg, win, bnstat, g_out, gx, gpq, gW2, gb2, ggamma, gbeta, ws, ws_bytes, stream);
 }

@@ -305,6 +305,30 @@ int dmet_edge_mlp_bwd_f32(const float *x, int64_t N, int Hin, const int32_t *row
                           const float *b2, int H2, int act2, int aggr, int bn, const float *pq, const float *agg,
                           const int32_t *win, const float *bnstat, const float *g_out, float *gx, float *gpq, float *gW2,
                           float *gb2, float *ggamma, float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream);
+/* --- bf16 matrix-core edge MLP over any grouped edge list (csrc/edgemlp_bf16.hip) ---------------------------------------
+ * The same layer, arguments, state and outputs as dmet_edge_mlp_fwd_f32 / dmet_edge_mlp_bwd_f32 above (it replaces the
+ * same reference lines, model/dynamic_reduction_network.py:59-73,86-87,94-95, as the DRN runs them under bf16
+ * autocast), with the per-edge products on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16):
+ *   forward: P, Q, ELU, aggregation and BatchNorm fp32; h1 and W2 rounded to bf16 (RNE), fp32 accumulation.
+ *   backward: g_z2, h1 and W2 rounded to bf16 for g_h1 = g_z2 W2 and gW2 = g_z2^T h1, fp32 accumulation; node-level
+ *   products (gx, and gW1 / gb1 on the caller's side) fp32.
+ * Within rtol 2e-2 of the output and gradient scales of the fp32 layer (R6); bit-identical from run to run, no atomics,
+ * no per-edge tensor in memory.  The state (pq, agg, win, bnstat) is interchangeable with the fp32 route's.
+ * Widths: H2 in {32, 64, 128}, H1 a multiple of 16 with 16 <= H1 <= min(192, 2 H2), 1 <= Hin <= 128
+ *   (dmet_edge_mlp_bf16_supported): the DRN at hidden 32, 64, 128 (Hin = H2 = h, H1 = 3h/2).
+ * ws: dmet_edge_mlp_bf16_workspace_bytes(N, E, Hin, H1, H2), for either call (0 for unsupported widths). */
+int dmet_edge_mlp_bf16_supported(int Hin, int H1, int H2);
+size_t dmet_edge_mlp_bf16_workspace_bytes(int64_t N, int64_t E, int Hin, int H1, int H2);
+int dmet_edge_mlp_fwd_bf16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src, const int32_t *tgt,
+                           int64_t E, const float *W1, const float *b1, int H1, const float *W2, const float *b2, int H2,
+                           int act2, int aggr, int bn, const float *gamma, const float *beta, float eps, float momentum,
+                           float *running_mean, float *running_var, int64_t *num_batches_tracked, float *out, float *pq,
+                           float *agg, int32_t *win, float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream);
+int dmet_edge_mlp_bwd_bf16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src, const int32_t *tgt,
+                           int64_t E, const int32_t *srcptr, const int32_t *srcperm, const float *W1, int H1, const float *W2,
+                           const float *b2, int H2, int act2, int aggr, int bn, const float *pq, const float *agg,
+                           const int32_t *win, const float *bnstat, const float *g_out, float *gx, float *gpq, float *gW2,
+                           float *gb2, float *ggamma, float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream);
 /* bf16 variant (BASELINE configs[2]): x and the split weights rounded to bf16 (RNE), multiplied on the bf16 matrix
  * cores with fp32 accumulation; P stays fp32, Q is stored as bf16 (raw bits) and gathered as 64-B rows.
  * Built for Hin = Hout = 32, k in {8,16,32}.  Backward is shared with the fp32 path (arg-based, fp32). */

@@ -1,11 +1,13 @@
 """DynamicReductionNetwork forward + backward rate, with a per-operator breakdown and the graclus round statistics.
 
-    python tools/drn_step.py [--shapes 64x4500 128x1000] [--hidden 64] [--k 16] [--steps 10] [--warmup 3] [--json OUT]
+    python tools/drn_step.py [--shapes 64x4500 128x1000] [--hidden 64] [--k 16] [--steps 10] [--warmup 3] [--autocast]
+                             [--json OUT]
 
 Measurement only (bench.py measures the flagship model).  The rate is taken over `--steps` back-to-back forward +
 backward passes (no optimizer).  The breakdown is a separate pass that synchronises after every stage, so its stages are
 device time plus the host time the stage itself spends (one host sync each in to_undirected, knn_graph with loop=False,
-and max_pool_x)."""
+and max_pool_x).  --autocast runs every pass under torch.autocast("cuda", dtype=torch.bfloat16): the EdgeConvs then take
+the bf16 matrix-core route (csrc/edgemlp_bf16.hip)."""
 import argparse
 import json
 import os
@@ -61,25 +63,26 @@ def breakdown(m, data):
         rounds.append(r.cpu())
         x, batch = stage(f"max_pool_x{i}", lambda: dm.max_pool_x(cl, x, batch))
     out = stage("global_pool+output", lambda: m.output(dm.global_max_pool(x, batch)).squeeze(-1))
-    stage("backward", lambda: out.sum().backward())
+    stage("backward", lambda: out.float().sum().backward())
     return t, rounds
 
 
-def run(B, n, hidden, k, steps, warmup, dev):
+def run(B, n, hidden, k, steps, warmup, dev, autocast=False):
     torch.manual_seed(0)
     m = dm.DynamicReductionNetwork(input_dim=5, hidden_dim=hidden, k=k).to(dev).train()
     data = make_batch(B, n, dev)
-    for _ in range(warmup):
-        m(data).sum().backward()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        m(data).sum().backward()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / steps
-    t, rounds = breakdown(m, data)
-    res = {"shape": f"{B}x{n}", "hidden": hidden, "k": k, "ms_per_step": dt * 1e3, "events_per_s": B / dt,
-           "breakdown_ms": {kk: v * 1e3 for kk, v in t.items()}}
+    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+        for _ in range(warmup):
+            m(data).float().sum().backward()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            m(data).float().sum().backward()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / steps
+        t, rounds = breakdown(m, data)
+    res = {"shape": f"{B}x{n}", "hidden": hidden, "k": k, "autocast": autocast, "ms_per_step": dt * 1e3,
+           "events_per_s": B / dt, "breakdown_ms": {kk: v * 1e3 for kk, v in t.items()}}
     for i, r in enumerate(rounds, 1):
         res[f"graclus{i}_rounds_mean"] = float(r.float().mean())
         res[f"graclus{i}_rounds_max"] = int(r.max())
@@ -93,13 +96,14 @@ def main():
     ap.add_argument("--k", type=int, default=16)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--autocast", action="store_true", help="bf16 autocast (the EdgeConvs' bf16 matrix-core route)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     out = []
     for s in a.shapes:
         B, n = (int(v) for v in s.split("x"))
-        r = run(B, n, a.hidden, a.k, a.steps, a.warmup, dev)
+        r = run(B, n, a.hidden, a.k, a.steps, a.warmup, dev, a.autocast)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.json:
