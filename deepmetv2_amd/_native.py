@@ -798,7 +798,10 @@ def _edge_mlp_bwd(route, g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2
         if N == 0:
             gW1 = torch.zeros_like(W1)
         else:
-            C = _xty_wide(gpq, x)              # [2 H1, Hin] = [gP^T x ; gQ^T x]
+            # a node without in- or out-edges has gP = gQ = 0: its x row is dropped from the product, so that a node no
+            # edge reads (a non-finite kNN query) adds nothing instead of 0 * NaN (exact for finite x)
+            isolated = (rowptr[1:] == rowptr[:-1]) & (srcptr[1:] == srcptr[:-1])
+            C = _xty_wide(gpq, x.masked_fill(isolated.view(-1, 1), 0.0))   # [2 H1, Hin] = [gP^T x ; gQ^T x]
             gW1 = torch.cat([C[:H1], C[H1:] - C[:H1]], dim=1)
     if want_b1:
         gb1 = xty_wide_ones(gP) if N else torch.zeros((H1,), dtype=torch.float32, device=dev)

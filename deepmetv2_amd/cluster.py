@@ -55,12 +55,14 @@ def knn_table(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loo
         nbr, dist, loc = _native.knn_local(x, info.ptr, kk)
     else:
         nbr, dist = _native.knn(x, info.ptr, kk)
-    # dense <=> no -1 entry anywhere.  Sizes alone cannot promise that (a NaN query, or candidates beyond the 1e10
-    # sentinel distance, leave a row short), so no table claims it.  What sizes DO give is the expectation `full_rows`:
-    # self loops kept and every event >= kk nodes (batch_info / register_batch(min_nodes=...)).  The [2,E] view of such a
-    # table is sized E = N kk on the host, so the reference's call shape `conv(emb, knn_graph(emb, k, batch, loop=True))`
-    # (graph_met_network.py:63) enqueues without a device->host sync; the expectation is verified by a deferred check
-    # (a short row would appear as -1 in the edge list, and the next operator call raises).
+    # dense <=> no -1 entry anywhere.  Sizes alone cannot promise that (a NaN / inf query, or a node farther than the 1e10
+    # squared-distance sentinel from every other node of its event, leaves a row short), so no table claims it.  What
+    # sizes DO give is the expectation `full_rows`: self loops kept and every event >= kk nodes (batch_info, which counts
+    # batch=None as one event, or register_batch(min_nodes=...)).  Only the [2,E] view of such a table is sized E = N kk
+    # on the host, so the reference's call shape `conv(emb, knn_graph(emb, k, batch, loop=True))`
+    # (graph_met_network.py:63) enqueues without a device->host sync; knn_graph / knn verify the expectation by a deferred
+    # check (a short row appears as -1 in that view, and the next operator call raises).  The edge list the operators
+    # consume (NeighborTable.edge_list) counts the valid slots: a short row is fewer edges there, never a -1 source.
     dense = False
     full_rows = bool(loop and info.min_nodes is not None and info.min_nodes >= kk and x.shape[0] > 0)
     if not loop:
@@ -83,13 +85,19 @@ def knn_graph(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loo
         raise ValueError(f"flow must be 'source_to_target' or 'target_to_source', got {flow!r}")
     _deferred.poll()
     table = knn_table(x, k, batch, loop=loop, num_events=batch_size)
+    _check_full_rows(table, x, "knn_graph")
+    return table.edge_index(flow)
+
+
+def _check_full_rows(table: NeighborTable, x: torch.Tensor, who: str) -> None:
+    """The [2,E] view of a `full_rows` table is sized N k without asking the device: post the deferred check that every
+    row did come out full."""
     if table.full_rows and x.is_cuda and not torch.cuda.is_current_stream_capturing():
         # rows are sorted by (d, j) with the empty slots last: the last column tells whether any row is short
         _deferred.post((table.nbr[:, -1].min() < 0).to(torch.int32),
-                       "knn_graph: a neighbour row came out short although every event holds at least k nodes (non-finite "
+                       f"{who}: a neighbour row came out short although every event holds at least k nodes (non-finite "
                        "coordinates, or candidates beyond the 1e10 sentinel distance): the [2,E] edge index handed out "
                        "for it carries -1 entries")
-    return table.edge_index(flow)
 
 
 def knn(x: torch.Tensor, y: torch.Tensor, k: int, batch_x: Optional[torch.Tensor] = None,
@@ -100,7 +108,9 @@ def knn(x: torch.Tensor, y: torch.Tensor, k: int, batch_x: Optional[torch.Tensor
         raise NotImplementedError("cosine=True is not on the DeepMETv2 hot path")
     if y is not x or (batch_y is not batch_x):
         raise NotImplementedError("knn(x, y): only the self-query form y is x is implemented (DynamicEdgeConv)")
-    return knn_table(x, k, batch_x, loop=True).edge_index("target_to_source")
+    table = knn_table(x, k, batch_x, loop=True)
+    _check_full_rows(table, x, "knn")
+    return table.edge_index("target_to_source")
 
 
 def radius_table(x: torch.Tensor, r: float, batch: Optional[torch.Tensor] = None, loop: bool = False,

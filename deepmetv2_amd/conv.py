@@ -193,8 +193,11 @@ class _EdgeConvLinearMax(torch.autograd.Function):
             if g_pass is not None:
                 gx = gx + g_pass
         if ctx.needs_input_grad[1]:
-            gWd = _native.xty(gP.contiguous(), x)
-            gW2 = _native.xty(gQ, x)
+            # as the fused kernel: a node whose gP and gQ rows are zero (no edge reads it) adds nothing, not 0 * NaN
+            idle = ((gP != 0).any(1) | (gQ != 0).any(1)).logical_not()
+            xw = x.masked_fill(idle.view(-1, 1), 0.0)
+            gWd = _native.xty(gP.contiguous(), xw)
+            gW2 = _native.xty(gQ, xw)
             gW = torch.cat([gWd, gW2 - gWd], dim=1)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = gP.sum(0)

@@ -111,6 +111,12 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, 2) void edgeconv_linear_bwd
                 if (((na[g].x >> 16) & 0xFFu) == 0xFFu) np[g].z = 0.f;
                 if ((na[g].x >> 24) == 0xFFu) np[g].w = 0.f;
             }
+            // a node whose gP and gQ rows are all zero adds nothing to the weight gradient: its x row is dropped, so that
+            // a node no edge reads (a non-finite kNN query: empty row, nobody's neighbour) does not add 0 * NaN there.
+            // Exact for finite x; a NaN in gP / gQ compares != 0 and keeps the row.  The row's 8 lanes decide together.
+            const bool g_nz = np[g].x != 0.f || np[g].y != 0.f || np[g].z != 0.f || np[g].w != 0.f ||
+                              nq[g].x != 0.f || nq[g].y != 0.f || nq[g].z != 0.f || nq[g].w != 0.f;
+            if (((__ballot(g_nz) >> (lane & ~7)) & 0xffull) == 0ull) nx[g] = make_float4(0.f, 0.f, 0.f, 0.f);
             *reinterpret_cast<float4 *>(&P[r * kPad + 4 * lp]) = np[g];
             *reinterpret_cast<float4 *>(&Q[r * kPad + 4 * lp]) = nq[g];
             *reinterpret_cast<float4 *>(&X[r * kPad + 4 * lp]) = nx[g];

@@ -393,9 +393,12 @@ __global__ __launch_bounds__(256) void table_edges_kernel(const int32_t *__restr
     const int m = live ? (cnt ? min(k, cnt[ii]) : k) : 0;
     const int32_t *row = nbr + ii * k;
     int64_t e = rowptr[ii];
-    // a row the caller sized at the table's full width is copied slot for slot: a table ASSUMED to have no empty slot
-    // (kNN with self loops over events of at least k nodes: no edge count is fetched from the device) whose row is short
-    // after all (a non-finite query) hands out -1 there -- a defined, loudly invalid index, never uninitialised memory
+    // a row the caller sized at the table's full width is copied slot for slot.  With rowptr from dmet_table_degree
+    // that only happens to full rows.  The sync-free [2,E] view of a table ASSUMED to have no empty slot (kNN with self
+    // loops over events of at least k nodes, rowptr = i k: no edge count fetched from the device) may meet a short row
+    // after all (a non-finite query, or a node beyond the 1e10 sentinel distance from the rest of its event): it hands
+    // out -1 there -- a defined, loudly invalid index for the caller's deferred check, never uninitialised memory.  That
+    // view is never an input of the edge-list operators, which need 0 <= src < N (include/dmet.h).
     const bool verbatim = live && (rowptr[ii + 1] - e) == k;
     for (int s0 = 0; __any(s0 < m); s0 += 8) {
         const int s = s0 + l;

@@ -225,9 +225,11 @@ class NeighborTable:
         if nbr is None and (shape is None or rows16 is None or cnt is None or ptr is None):
             raise ValueError("NeighborTable without an int32 table needs shape, rows16, cnt and ptr")
         self._nbr = nbr
-        # True: every row is EXPECTED to hold k entries (kNN with self loops, every event >= k nodes): the [2,E] view is
-        # sized E = N k without asking the device; the expectation is verified by a deferred check (knn_table).  Unlike
-        # `dense` it is not relied upon for masking: a short row (non-finite query) still yields 0 and no gradient.
+        # True: every row is EXPECTED to hold k entries (kNN with self loops, every event >= k nodes).  Only the [2,E] view
+        # handed to the caller (edge_index) trusts it: sized E = N k without asking the device, a short row there carries
+        # -1 and a deferred check reports it (knn_graph, knn).  The edge list the operators consume (edge_list) counts
+        # the valid slots instead: a row comes out short for a non-finite query, or a node farther than the 1e10 squared
+        # distance sentinel from every other node of its event, and a short row is fewer edges, never a -1 source.
         self.full_rows = full_rows
         self._pending = None        # a GraphFuture whose side-stream build has not been joined on the consumer's stream
         self.pq = None              # (P, Q, sliced) of the consuming EdgeConv's dense layer when the kNN build carried it
@@ -242,7 +244,8 @@ class NeighborTable:
         self.dense = dense          # True: no -1 entries anywhere (every row has exactly k neighbours)
         self.dist = dist
         self._rev = None
-        self._rp = None
+        self._rp = None             # (rowptr, E) counted from the device
+        self._rp_full = None        # (rowptr, E) sized N k on the host (dense / full_rows)
         self._edges = None
         self._edge_index = {}
 
@@ -292,21 +295,26 @@ class NeighborTable:
                 self._rev = (rev_ptr, pos[rev_e[: keys.numel()].long()].contiguous())
         return self._rev
 
-    def _rowptr(self):
-        """(rowptr[N+1] int32, E): one host sync to learn the edge count (upstream returns exact-size tensors too)."""
+    def _rowptr(self, exact: bool = False):
+        """(rowptr[N+1] int32, E).  A `dense` table, or (exact=False) a `full_rows` one, is sized N k on the host; else one
+        host sync learns the edge count of the valid slots (upstream returns exact-size tensors too)."""
         self.join()
-        if self._rp is None:
-            if self.dense or self.full_rows:
+        if self.dense or (self.full_rows and not exact):
+            if self._rp_full is None:
                 N, k = self.num_nodes, self.k
-                self._rp = (torch.arange(0, (N + 1) * k, k, dtype=torch.int32, device=self.ptr.device if self._nbr is None else self._nbr.device), N * k)
-            else:
-                rp = _native.table_rowptr(self.nbr, self.cnt)
-                self._rp = (rp, int(rp[-1].item()) if self.num_nodes else 0)
+                dev = self.ptr.device if self._nbr is None else self._nbr.device
+                self._rp_full = (torch.arange(0, (N + 1) * k, k, dtype=torch.int32, device=dev), N * k)
+            return self._rp_full
+        if self._rp is None:
+            rp = _native.table_rowptr(self.nbr, self.cnt)
+            self._rp = (rp, int(rp[-1].item()) if self.num_nodes else 0)
         return self._rp
 
     def edge_list(self) -> EdgeList:
+        """The valid entries as a by-target edge list, for the operators: 0 <= src < N always (a short row of a `full_rows`
+        table is fewer edges, not -1 sources; this costs the one host sync of the edge count)."""
         if self._edges is None:
-            rowptr, E = self._rowptr()
+            rowptr, E = self._rowptr(exact=True)
             _ei, src, tgt = _native.table_edges(self.nbr, self.cnt, rowptr, E, False, False, True)
             self._edges = EdgeList(src, tgt, rowptr, self.num_nodes)
         return self._edges

@@ -388,7 +388,9 @@ int dmet_reverse_index(const int32_t *keys, int64_t M, int64_t num_keys, int32_t
  * replaces the PyG MessagePassing.propagate pieces around a user `nn`
  *   (model/dynamic_reduction_network.py:59-73,86-87: Linear-ELU-Linear-ELU-BN, aggr in {'add','max'}).
  * Edges are (src[e] -> tgt[e]) int32, grouped by target: rowptr[N+1] int32 with tgt[e]==i for
- * rowptr[i] <= e < rowptr[i+1].
+ * rowptr[i] <= e < rowptr[i+1], and 0 <= src[e] < N for every e: these entry points, and the edge-MLP ones above that
+ * take the same list, index x / P / Q with src unchecked.  A table's -1 slots must not reach them (build the list with
+ * the rowptr of dmet_table_degree, which drops them).
  *   edge_features: feat[e] = [ x[tgt[e]] || x[src[e]] - x[tgt[e]] ]                      ([E, 2H])
  *   segment_max  : out[i,c] = max_e msg[e,c] (empty -> 0), arg[i,c] = winning e (lowest on ties), -1 if empty
  *   segment_sum  : out[i,c] = sum_e msg[e,c] in ascending e (deterministic)
@@ -446,7 +448,8 @@ int dmet_segment_sum_1d_f32(const float *src, const int64_t *ptr, int B, float *
 /* Neighbour table -> edge list (what knn_graph / radius_graph return): deg[i] = valid entries of row i (among the
  * first cnt[i] slots when cnt is given); with rowptr = exclusive prefix sum of deg, dmet_table_edges writes the edges
  * grouped by target i in slot order: first/second [E] int64 = (source, target), or (target, source) when swap != 0,
- * and/or src32/tgt32 [E] int32. */
+ * and/or src32/tgt32 [E] int32.  A row given exactly k edges by rowptr is copied slot for slot, -1 slots included (the
+ * sync-free rowptr = i k of a table expected to be full); such a list is no input of the edge-list entry points. */
 int dmet_table_degree(const int32_t *nbr, const int32_t *cnt, int64_t N, int k, int32_t *deg, dmet_stream_t stream);
 int dmet_table_edges(const int32_t *nbr, const int32_t *cnt, const int32_t *rowptr, int64_t N, int k, int swap,
                      int64_t *first, int64_t *second, int32_t *src32, int32_t *tgt32, dmet_stream_t stream);

@@ -305,6 +305,10 @@ def head_bwd(emb, params, out, g_out):
     return list(torch.autograd.grad(o, [e] + ps, g_out))
 
 
+def knn_size_hint(min_nodes, max_nodes):
+    """A performance hint of the kNN build (which kernel forms it runs): nothing to do for the oracle."""
+
+
 def table_rowptr(nbr, cnt):
     N, k = nbr.shape
     valid = nbr >= 0
@@ -317,9 +321,12 @@ def table_rowptr(nbr, cnt):
 
 def table_edges(nbr, cnt, rowptr, num_edges, swap, want_index64, want_int32):
     N, k = nbr.shape
-    valid = nbr >= 0
-    if cnt is not None:
-        valid = valid & (torch.arange(k).view(1, -1) < cnt.view(-1, 1))
+    slot = torch.arange(k).view(1, -1)
+    inrow = slot < cnt.view(-1, 1) if cnt is not None else torch.ones((N, k), dtype=torch.bool)
+    # as the kernel: a row that rowptr sizes at the full width k is copied slot for slot, -1 slots included
+    verbatim = ((rowptr[1:] - rowptr[:-1]) == k).view(-1, 1)
+    valid = inrow & ((nbr >= 0) | verbatim)
+    assert int(valid.sum()) == num_edges == int(rowptr[-1]), "rowptr does not match the table"
     tgt = torch.arange(N, dtype=torch.int32).view(-1, 1).expand(N, k)[valid]
     src = nbr[valid]
     ei = None
@@ -377,7 +384,7 @@ def gather_max_bwd_j16(g_out, argj, ptr, max_nodes=None, sliced=False):
     return _to_sliced(gQ) if (sliced and H == 32) else gQ
 
 
-_NAMES = ["table_order_by_count", "gather_max_local_j16", "gather_max_counted_j16", "gather_max_bwd_j16", "table_rowptr", "table_edges", "head_fwd", "head_bwd", "met_loss", "gather_max_bwd_lds", "edgeconv_linear_bwd", "bn_fwd", "bn_bwd", "encode_fwd", "encode_bwd", "knn", "knn_local", "radius", "node_linear_split", "gather_max", "gather_max_bwd", "reverse_index", "edge_features",
+_NAMES = ["knn_size_hint", "table_order_by_count", "gather_max_local_j16", "gather_max_counted_j16", "gather_max_bwd_j16", "table_rowptr", "table_edges", "head_fwd", "head_bwd", "met_loss", "gather_max_bwd_lds", "edgeconv_linear_bwd", "bn_fwd", "bn_bwd", "encode_fwd", "encode_bwd", "knn", "knn_local", "radius", "node_linear_split", "gather_max", "gather_max_bwd", "reverse_index", "edge_features",
           "edge_features_bwd", "segment_max", "segment_sum", "segment_max_bwd", "segment_sum_bwd", "met_reduce",
           "met_reduce_bwd", "segment_sum_1d", "batch_to_ptr", "xty", "onehot_xty", "edgeconv_fused_lds"]
 
