@@ -692,6 +692,22 @@ def edge_mlp_fwd_bf16(x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, 
                          running_mean, running_var, num_batches_tracked)
 
 
+def edge_mlp_f16_supported(Hin: int, H1: int, H2: int) -> bool:
+    return bool(_lib.load().dmet_edge_mlp_f16_supported(int(Hin), int(H1), int(H2)))
+
+
+def edge_mlp_fwd_f16(x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, W1: torch.Tensor,
+                     b1: Optional[torch.Tensor], W2: torch.Tensor, b2: Optional[torch.Tensor], act2: bool, aggr: str,
+                     bn: int = 0, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+                     eps: float = 1e-5, momentum: float = 0.1, running_mean: Optional[torch.Tensor] = None,
+                     running_var: Optional[torch.Tensor] = None, num_batches_tracked: Optional[torch.Tensor] = None):
+    """edge_mlp_fwd_bf16 with fp16 operands on the fp16 matrix cores (include/dmet.h: dmet_edge_mlp_fwd_f16): fp32
+    inputs, parameters and output; h1 and W2 rounded to fp16 (RNE, overflow to inf) inside the kernel.  Returns (out,
+    state) for edge_mlp_bwd_f16."""
+    return _edge_mlp_fwd("f16", x, rowptr, src, tgt, W1, b1, W2, b2, act2, aggr, bn, gamma, beta, eps, momentum,
+                         running_mean, running_var, num_batches_tracked)
+
+
 def _edge_mlp_fwd(route, x, rowptr, src, tgt, W1, b1, W2, b2, act2, aggr, bn, gamma, beta, eps, momentum, running_mean,
                   running_var, num_batches_tracked):
     dev = _require_device(x, rowptr, src, tgt, W1, W2, b1, b2, gamma, beta)
@@ -756,6 +772,16 @@ def edge_mlp_bwd_bf16(g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor
     """Gradients of edge_mlp_fwd_bf16 (include/dmet.h: dmet_edge_mlp_bwd_bf16), as edge_mlp_bwd_f32 returns them: the
     per-edge products g_h1 and gW2 on the bf16 matrix cores, everything else fp32."""
     return _edge_mlp_bwd("bf16", g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2, act2, aggr, bn, state, want_x,
+                         want_w1, want_b1)
+
+
+def edge_mlp_bwd_f16(g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor,
+                     srcptr: torch.Tensor, srcperm: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                     b2: Optional[torch.Tensor], act2: bool, aggr: str, bn: int, state, want_x: bool = True,
+                     want_w1: bool = True, want_b1: bool = True):
+    """Gradients of edge_mlp_fwd_f16 (include/dmet.h: dmet_edge_mlp_bwd_f16), as edge_mlp_bwd_f32 returns them: the
+    per-edge products g_h1 and gW2 on the fp16 matrix cores, everything else fp32."""
+    return _edge_mlp_bwd("f16", g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2, act2, aggr, bn, state, want_x,
                          want_w1, want_b1)
 
 

@@ -17,7 +17,16 @@ from .graph import NeighborTable, _deferred, batch_info
 MAX_K = 64  # DMET_MAX_K
 
 
+def fp16_autocast() -> bool:
+    """torch.autocast is on for the GPU with float16 (what torch.autocast("cuda") without a dtype gives)."""
+    return torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() == torch.float16
+
+
 def _check_x(x: torch.Tensor) -> torch.Tensor:
+    # 16-bit features from autocast upstream: exact upcast, the graph is the one of x.float().  bf16 always; fp16 while
+    # fp16 autocast is on (outside it an fp16 x stays an error, as it always was)
+    if x.dtype == torch.bfloat16 or (x.dtype == torch.float16 and fp16_autocast()):
+        x = x.float()
     if x.dim() == 1:
         x = x.view(-1, 1)
     if x.dim() != 2:
@@ -31,10 +40,8 @@ def knn_table(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loo
               num_events: Optional[int] = None, dense=None) -> NeighborTable:
     """Fixed-width neighbour table for `x` (row i = the message sources of node i).  loop=False searches k+1
     and blanks j == i, exactly like upstream's `row != col` mask (a node whose k+1 nearest do not include itself,
-    possible only with >= k+1 duplicates at lower index, keeps all k+1).  A bf16 `x` (bf16 autocast upstream) is
-    upcast first, an exact conversion: the result is the kNN of x.float()."""
-    if torch.is_tensor(x) and x.dtype == torch.bfloat16:
-        x = x.float()
+    possible only with >= k+1 duplicates at lower index, keeps all k+1).  A bf16 `x`, or an fp16 one under fp16
+    autocast, is upcast first, an exact conversion: the result is the kNN of x.float()."""
     x = _check_x(x)
     if not isinstance(k, int) or k < 1:
         raise ValueError(f"k must be a positive int, got {k!r}")

@@ -16,7 +16,7 @@ from typing import Callable, Optional, Tuple, Union
 import torch
 
 from . import _native
-from .cluster import knn_table
+from .cluster import fp16_autocast, knn_table
 from .graph import EdgeList, GraphFuture, NeighborTable, batch_info, edge_list_from_edge_index, lookup_graph
 from .scatter import _SegmentMaxRows, _SegmentSumRows
 from torch.autograd.function import once_differentiable
@@ -280,7 +280,7 @@ class _EdgeMLP2Bf16(torch.autograd.Function):
 
 
 def _edge_mlp2_forward(route, ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
-    """Forward of the fused edge-list routes (route "f32" or "bf16": _native.edge_mlp_fwd_<route>)."""
+    """Forward of the fused edge-list routes (route "f32", "bf16" or "f16": _native.edge_mlp_fwd_<route>)."""
     mode, track = 0, False
     if bn is not None:
         track = bn.track_running_stats and bn.running_mean is not None
@@ -342,6 +342,22 @@ class _EdgeMLP2Bf16Edges(torch.autograd.Function):
         return _edge_mlp2_backward("bf16", ctx, g_out)
 
 
+class _EdgeMLP2F16Edges(torch.autograd.Function):
+    """_EdgeMLP2Bf16Edges with fp16 operands on the fp16 matrix cores (csrc/edgemlp_bf16.hip, the same kernels): the
+    route taken when fp16 is requested (torch.autocast("cuda") without a dtype, or compute_dtype) over a grouped edge
+    list.  fp32 in and out; h1, W2 and g_z2 are rounded to fp16 (RNE, overflow to inf) inside the kernels only.
+    `once_differentiable`: DMET_EDGE_MLP_F16=0 gives the generic route, e.g. for double backward."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
+        return _edge_mlp2_forward("f16", ctx, x, W1, b1, W2, b2, gamma, beta, edges, act2, aggr, bn)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        return _edge_mlp2_backward("f16", ctx, g_out)
+
+
 class _EdgeFeatures(torch.autograd.Function):
     """feat[e] = [x[tgt] || x[src] - x[tgt]] for a by-target grouped edge list."""
 
@@ -373,8 +389,12 @@ class EdgeConv(torch.nn.Module):
     the generic route, e.g. for double backward), or on the bf16 matrix cores when bf16 is requested (autocast or
     ``compute_dtype``): over a fixed-width kNN table that csrc/edgemlp.hip takes, and otherwise over any graph, forward
     and backward, for H2 in {32, 64, 128}, H1 a multiple of 16 <= min(192, 2 H2), F <= 128 (csrc/edgemlp_bf16.hip,
-    fp32 output; ``DMET_EDGE_MLP_BF16=0`` restores the generic route).  Every other ``nn`` runs the generic route: edge
-    features, ``nn`` over E rows, segment reduction.  A bf16 ``x`` is upcast to fp32 on entry (exact).
+    fp32 output; ``DMET_EDGE_MLP_BF16=0`` restores the generic route).  When fp16 is requested (``torch.autocast("cuda")``
+    without a dtype, or ``compute_dtype=torch.float16``) the same two-layer ``nn`` runs over any graph on the fp16 matrix
+    cores, with the bf16 route's widths (csrc/edgemlp_bf16.hip, fp32 output; ``DMET_EDGE_MLP_F16=0`` restores the
+    generic route); a fixed-width kNN table is then read through its edge list.  Every other ``nn`` runs the generic
+    route: edge features, ``nn`` over E rows, segment reduction.  A bf16 ``x``, or an fp16 one when fp16 is requested
+    (fp16 autocast or ``compute_dtype``), is upcast to fp32 on entry (exact).
     """
 
     def __init__(self, nn: Callable, aggr: str = "max", **kwargs):
@@ -391,7 +411,8 @@ class EdgeConv(torch.nn.Module):
         self.aggr = aggr
         self.flow = flow
         self.node_dim = 0
-        # None: follow torch.autocast (bf16 autocast -> bf16 MFMA dense layer); or torch.float32 / torch.bfloat16
+        # None: follow torch.autocast (bf16 autocast -> bf16 MFMA dense layer, fp16 autocast -> fp16 MFMA edge MLP); or
+        # torch.float32 / torch.bfloat16 / torch.float16
         self.compute_dtype = None
         self.reset_parameters()
 
@@ -424,19 +445,34 @@ class EdgeConv(torch.nn.Module):
                                       lambda xx: self._forward_edges(xx, table.edge_list()), bn,
                                       bn.weight if bn is not None else None, bn.bias if bn is not None else None)
             return (out, x) if passthrough else out
-        edges = table.edge_list()
-        out = self._forward_edge_mlp_bf16(x, edges)
-        if out is None:
-            out = self._forward_edge_mlp_f32(x, edges)
-        if out is None:
-            out = self._forward_edges(x, edges)
+        out = self._forward_edge_list(x, table.edge_list())
         return (out, x) if passthrough else out
 
-    def _wants_bf16(self) -> bool:
+    def _wants_16bit(self) -> Optional[torch.dtype]:
+        """The 16-bit compute dtype requested (torch.bfloat16 or torch.float16), from compute_dtype or else from
+        torch.autocast's GPU dtype; None when neither asks for one."""
         dt = self.compute_dtype
         if dt is None and torch.is_autocast_enabled():
             dt = torch.get_autocast_gpu_dtype()
-        return dt == torch.bfloat16
+        return dt if dt in (torch.bfloat16, torch.float16) else None
+
+    def _wants_bf16(self) -> bool:
+        return self._wants_16bit() == torch.bfloat16
+
+    def _takes_fp16(self) -> bool:
+        """An fp16 x is upcast on entry when fp16 is in play: compute_dtype torch.float16 or fp16 autocast.  Otherwise it
+        stays the TypeError it always was."""
+        return self.compute_dtype == torch.float16 or fp16_autocast()
+
+    def _forward_edge_list(self, x: torch.Tensor, edges: EdgeList) -> torch.Tensor:
+        """The layer over a grouped edge list: the first fused route that takes the call (bf16, fp16, fp32), else the
+        generic one."""
+        out = self._forward_edge_mlp_bf16(x, edges)
+        if out is None:
+            out = self._forward_edge_mlp_f16(x, edges)
+        if out is None:
+            out = self._forward_edge_mlp_f32(x, edges)
+        return out if out is not None else self._forward_edges(x, edges)
 
     def _use_bf16(self, lin: torch.nn.Linear, table: NeighborTable) -> bool:
         dt = self.compute_dtype
@@ -449,9 +485,19 @@ class EdgeConv(torch.nn.Module):
         """The bf16 matrix-core route over a grouped edge list (_EdgeMLP2Bf16Edges), or None when this call does not take
         it: bf16 not requested (autocast or compute_dtype), another `nn`, non-fp32 parameters, widths outside
         dmet_edge_mlp_bf16_supported, DMET_EDGE_MLP_BF16=0, or a training-mode BatchNorm over E <= 1 edges.  fp32 out."""
-        if os.environ.get("DMET_EDGE_MLP_BF16", "1") == "0" or not x.is_cuda or x.dtype != torch.float32:
+        return self._forward_edge_mlp_16bit("bf16", x, edges)
+
+    def _forward_edge_mlp_f16(self, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
+        """The fp16 matrix-core route over a grouped edge list (_EdgeMLP2F16Edges), or None when this call does not take
+        it, by the bf16 route's rules: fp16 not requested (autocast or compute_dtype), another `nn`, non-fp32
+        parameters, widths outside dmet_edge_mlp_f16_supported, DMET_EDGE_MLP_F16=0, or a training-mode BatchNorm over
+        E <= 1 edges.  fp32 out."""
+        return self._forward_edge_mlp_16bit("f16", x, edges)
+
+    def _forward_edge_mlp_16bit(self, route: str, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
+        if os.environ.get(f"DMET_EDGE_MLP_{route.upper()}", "1") == "0" or not x.is_cuda or x.dtype != torch.float32:
             return None
-        if not self._wants_bf16():
+        if self._wants_16bit() != (torch.bfloat16 if route == "bf16" else torch.float16):
             return None
         mlp = _as_mlp2(self.nn)
         if mlp is None:
@@ -460,16 +506,17 @@ class EdgeConv(torch.nn.Module):
         params = [l1.weight, l1.bias, l2.weight, l2.bias] + ([bn.weight, bn.bias] if bn is not None else [])
         if any(p is not None and p.dtype != torch.float32 for p in params) or l1.in_features != 2 * x.shape[1]:
             return None
-        if not _native.edge_mlp_bf16_supported(x.shape[1], l1.out_features, l2.out_features):
+        if not getattr(_native, f"edge_mlp_{route}_supported")(x.shape[1], l1.out_features, l2.out_features):
             return None
         if bn is not None and (bn.training or not bn.track_running_stats) and edges.num_edges <= 1:
             return None
-        return _EdgeMLP2Bf16Edges.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, bn.weight if bn is not None else None,
-                                        bn.bias if bn is not None else None, edges, act2, self.aggr, bn)
+        fn = _EdgeMLP2Bf16Edges if route == "bf16" else _EdgeMLP2F16Edges
+        return fn.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, bn.weight if bn is not None else None,
+                        bn.bias if bn is not None else None, edges, act2, self.aggr, bn)
 
     def _forward_edge_mlp_f32(self, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
         """The fused fp32 route (_EdgeMLP2F32) for a two-layer edge MLP, or None when this call keeps the generic route:
-        another `nn`, widths outside dmet_edge_mlp_f32_supported, bf16 or autocast requested, DMET_EDGE_MLP_F32=0, or a
+        another `nn`, widths outside dmet_edge_mlp_f32_supported, 16 bits or autocast requested, DMET_EDGE_MLP_F32=0, or a
         training-mode BatchNorm over E <= 1 edges (torch's own error for one value per channel stays)."""
         if os.environ.get("DMET_EDGE_MLP_F32", "1") == "0" or not x.is_cuda or x.dtype != torch.float32:
             return None
@@ -498,8 +545,8 @@ class EdgeConv(torch.nn.Module):
         msg = self.nn(feat)
         if msg.dim() != 2 or msg.shape[0] != edges.num_edges:
             raise ValueError("nn must map [E, 2F] -> [E, F_out]")
-        if msg.dtype == torch.bfloat16:
-            msg = msg.float()       # nn under bf16 autocast: exact upcast, the segment reductions are fp32
+        if msg.dtype in (torch.bfloat16, torch.float16):
+            msg = msg.float()       # nn under autocast: exact upcast, the segment reductions are fp32
         msg = msg.contiguous()
         if self.aggr == "max":
             out, _arg = _SegmentMaxRows.apply(msg, edges.rowptr, N)
@@ -517,8 +564,8 @@ class EdgeConv(torch.nn.Module):
             x = x[0]
         if x.dim() != 2:
             raise ValueError(f"x must be [N, F], got {tuple(x.shape)}")
-        if x.dtype == torch.bfloat16:
-            x = x.float()       # bf16 autocast upstream: exact upcast, gradients flow back through it
+        if x.dtype == torch.bfloat16 or (x.dtype == torch.float16 and self._takes_fp16()):
+            x = x.float()       # autocast upstream: exact upcast, gradients flow back through it in x's dtype
         if x.dtype != torch.float32:
             raise TypeError(f"x must be float32, got {x.dtype}")
         if isinstance(edge_index, GraphFuture):
@@ -531,11 +578,7 @@ class EdgeConv(torch.nn.Module):
         hit = lookup_graph(edge_index)
         if hit is not None and hit[1] == self.flow and hit[0].num_nodes == x.shape[0]:
             return self._forward_table(x, hit[0])
-        edges = edge_list_from_edge_index(edge_index, x.shape[0], self.flow)
-        out = self._forward_edge_mlp_bf16(x, edges)
-        if out is None:
-            out = self._forward_edge_mlp_f32(x, edges)
-        return out if out is not None else self._forward_edges(x, edges)
+        return self._forward_edge_list(x, edge_list_from_edge_index(edge_index, x.shape[0], self.flow))
 
     # -- BatchNorm transform of the PREVIOUS block fused into this layer's node-level dense layer (static graphs) --------
     def prebuild_hook(self, batch=None, graph=None):
@@ -614,8 +657,8 @@ class DynamicEdgeConv(EdgeConv):
             batch = batch[0]
         if x.dim() != 2:
             raise ValueError("Static graphs not supported in DynamicEdgeConv")  # upstream's message
-        if x.dtype == torch.bfloat16:
-            x = x.float()       # bf16 autocast upstream: exact upcast, gradients flow back through it
+        if x.dtype == torch.bfloat16 or (x.dtype == torch.float16 and self._takes_fp16()):
+            x = x.float()       # autocast upstream: exact upcast, gradients flow back through it in x's dtype
         if x.dtype != torch.float32:
             raise TypeError(f"x must be float32, got {x.dtype}")
         table = self._take_prebuilt(x)

@@ -1,5 +1,8 @@
 // edgemlp_bf16.hip -- EdgeConv for a two-layer edge MLP over ANY grouped edge list with the per-edge products on the
-// bf16 matrix cores (gfx950), forward and backward.
+// bf16 or fp16 matrix cores (gfx950), forward and backward.  Both operand types run the same two kernels, templates over
+// the operand type (OpBf16, OpF16): the fp16 instances differ only in the rounding to 16 bits (v_cvt_f16_f32 /
+// v_cvt_pk_f16_f32 instead of v_cvt_pk_bf16_f32) and the MFMA (v_mfma_f32_16x16x32_f16); what follows says bf16 for
+// either.
 //
 // Replaces, for  nn = Sequential(Linear(2 Hin, H1), ELU, Linear(H1, H2)[, ELU][, BatchNorm1d(H2)])  and aggr in
 // {max, add, mean}, the generic route under bf16 autocast (edge_features -> nn over E rows -> segment max / sum) and its
@@ -29,7 +32,9 @@
 //
 // Numerics: P, Q, ELU, the aggregation and the BatchNorm are fp32.  Forward: h1 and W2 rounded to bf16 (RNE), products
 // exact, fp32 accumulation.  Backward: g_z2, h1 and W2 rounded to bf16 for g_h1 and gW2, fp32 accumulation; node-level
-// products fp32.  Compared with the fp32 result at the R6 bar (rtol 2e-2 of the output scale).
+// products fp32.  Compared with the fp32 result at the R6 bar (rtol 2e-2 of the output scale).  fp16: the same, rounded
+// to nearest even, overflow to +-inf (a GradScaler scale too large for g_z2 gives a non-finite gradient, never a
+// saturated finite one), subnormals kept (the kernel's default fp16 denorm mode).
 //
 // Widths (dmet_edge_mlp_bf16_supported): H2 in {32, 64, 128}, H1 a multiple of 16 with H1 <= min(192, 2 H2),
 // 1 <= Hin <= 128.  LDS per workgroup (T = 32): forward 2 SH (H2 + T) + 4 H2 (TS + 1) + 8 T bytes, backward
@@ -41,74 +46,106 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kT = 32;          // edges per tile (the K of the gW2 product)
 constexpr int kTS = kT + 4;     // row pitch of the channel-major fp32 tiles
 constexpr int kWaves = kBlk / 64;
 
-__device__ __forceinline__ unsigned short bf16_bits(float f)
-{
-    const __bf16 b = (__bf16)f;     // RNE (v_cvt_pk_bf16_f32)
-    return __builtin_bit_cast(unsigned short, b);
-}
+// The 16-bit operand type of the per-edge products: how an fp32 value is rounded to its 16 bits (kept as such in LDS),
+// how 16 bits enter an MFMA operand, and the MFMA.  The kernels below are written once over it.
+struct OpBf16 {
+    typedef bf16x8 vec;
+    static __device__ __forceinline__ unsigned short bits(float f)
+    {
+        const __bf16 b = (__bf16)f;     // RNE (v_cvt_pk_bf16_f32)
+        return __builtin_bit_cast(unsigned short, b);
+    }
+    static __device__ __forceinline__ short elem(unsigned short u) { return (short)u; }
+    static __device__ __forceinline__ f32x4 mfma(vec a, vec b, f32x4 c)
+    {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+};
+
+struct OpF16 {
+    typedef f16x8 vec;
+    static __device__ __forceinline__ unsigned short bits(float f)
+    {
+        // v_cvt_f16_f32 in the kernel's default mode: RNE, beyond 65504 (after rounding) +-inf, subnormals kept -- not
+        // the packed round-toward-zero v_cvt_pkrtz_f16_f32
+        const _Float16 h = (_Float16)f;
+        return __builtin_bit_cast(unsigned short, h);
+    }
+    static __device__ __forceinline__ _Float16 elem(unsigned short u) { return __builtin_bit_cast(_Float16, u); }
+    static __device__ __forceinline__ f32x4 mfma(vec a, vec b, f32x4 c)
+    {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+};
 
 __host__ __device__ __forceinline__ int h1_pad(int H1) { return (H1 + 31) & ~31; }
 __host__ __device__ __forceinline__ int h1_pitch(int H1) { return h1_pad(H1) + 8; }
 
-// 8 consecutive bf16 from LDS (16-B aligned)
-__device__ __forceinline__ bf16x8 ld8(const unsigned short *p) { return *reinterpret_cast<const bf16x8 *>(p); }
+// 8 consecutive 16-bit operands from LDS (16-B aligned)
+template <typename Op>
+__device__ __forceinline__ typename Op::vec ld8(const unsigned short *p) { return *reinterpret_cast<const typename Op::vec *>(p); }
 
-// 8 consecutive fp32 from LDS (16-B aligned), rounded to bf16
-__device__ __forceinline__ bf16x8 ld8_f32(const float *p)
+// 8 consecutive fp32 from LDS (16-B aligned), rounded to the operand type
+template <typename Op>
+__device__ __forceinline__ typename Op::vec ld8_f32(const float *p)
 {
     const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
-    bf16x8 r;
-    r[0] = (short)bf16_bits(a.x); r[1] = (short)bf16_bits(a.y); r[2] = (short)bf16_bits(a.z); r[3] = (short)bf16_bits(a.w);
-    r[4] = (short)bf16_bits(b.x); r[5] = (short)bf16_bits(b.y); r[6] = (short)bf16_bits(b.z); r[7] = (short)bf16_bits(b.w);
+    typename Op::vec r;
+    r[0] = Op::elem(Op::bits(a.x)); r[1] = Op::elem(Op::bits(a.y)); r[2] = Op::elem(Op::bits(a.z)); r[3] = Op::elem(Op::bits(a.w));
+    r[4] = Op::elem(Op::bits(b.x)); r[5] = Op::elem(Op::bits(b.y)); r[6] = Op::elem(Op::bits(b.z)); r[7] = Op::elem(Op::bits(b.w));
     return r;
 }
 
-// W2 as bf16 [H2][SH] (columns H1 .. SH - 1 zero) and b2 fp32 [H2]
+// W2 as 16-bit [H2][SH] (columns H1 .. SH - 1 zero) and b2 fp32 [H2]
+template <typename Op>
 __device__ __forceinline__ void stage_w2(const float *__restrict__ W2, const float *__restrict__ b2, int H1, int H2,
                                          unsigned short *w2s, float *b2s)
 {
     const int SH = h1_pitch(H1);
     for (int idx = threadIdx.x; idx < H2 * SH; idx += blockDim.x) {
         const int o = idx / SH, c = idx - o * SH;
-        w2s[idx] = c < H1 ? bf16_bits(W2[(int64_t)o * H1 + c]) : (unsigned short)0;
+        w2s[idx] = c < H1 ? Op::bits(W2[(int64_t)o * H1 + c]) : (unsigned short)0;
     }
     for (int o = threadIdx.x; o < H2; o += blockDim.x) b2s[o] = b2 ? b2[o] : 0.0f;
 }
 
-// h1 = ELU(P_tgt + Q_src) of the tile's cnt edges (beyond: 0): bf16 edge-major [T][SH] (padding columns 0) and, when
+// h1 = ELU(P_tgt + Q_src) of the tile's cnt edges (beyond: 0): 16-bit edge-major [T][SH] (padding columns 0) and, when
 // h1c is given, fp32 channel-major [H1][TS]
-__device__ __forceinline__ void fill_h1_bf16(const float *__restrict__ PQ, int H1, const int32_t *tg, const int32_t *sr,
-                                             int cnt, unsigned short *h1e, float *h1c)
+template <typename Op>
+__device__ __forceinline__ void fill_h1(const float *__restrict__ PQ, int H1, const int32_t *tg, const int32_t *sr, int cnt,
+                                        unsigned short *h1e, float *h1c)
 {
     const int H1p = h1_pad(H1), SH = h1_pitch(H1);
     for (int idx = threadIdx.x; idx < kT * H1p; idx += blockDim.x) {
         const int t = idx / H1p, c = idx - t * H1p;
         float h = 0.0f;
         if (t < cnt && c < H1) h = elu1f(PQ[(int64_t)tg[t] * 2 * H1 + c] + PQ[(int64_t)sr[t] * 2 * H1 + H1 + c]);
-        h1e[t * SH + c] = bf16_bits(h);
+        h1e[t * SH + c] = Op::bits(h);
         if (h1c && c < H1) h1c[c * kTS + t] = h;
     }
 }
 
 // z2 block (edge block eb, channel block ob) of the tile, before the bias: C[t][o], t = 16 eb + 4 (l >> 4) + r
+template <typename Op>
 __device__ __forceinline__ f32x4 z2_block(const unsigned short *h1e, const unsigned short *w2s, int H1, int eb, int ob, int lane)
 {
     const int SH = h1_pitch(H1), ksteps = h1_pad(H1) / 32;
     const unsigned short *pa = h1e + (16 * eb + (lane & 15)) * SH + 8 * (lane >> 4);
     const unsigned short *pb = w2s + (16 * ob + (lane & 15)) * SH + 8 * (lane >> 4);
     f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int ks = 0; ks < ksteps; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(pa + 32 * ks), ld8(pb + 32 * ks), acc, 0, 0, 0);
+    for (int ks = 0; ks < ksteps; ++ks) acc = Op::mfma(ld8<Op>(pa + 32 * ks), ld8<Op>(pb + 32 * ks), acc);
     return acc;
 }
 
 // aggr: 0 max, 1 add, 2 mean.  bn: 0 none, 1 training (keep the statistics partials), 2 eval.
-template <int H2>
-__global__ __launch_bounds__(kBlk) void edge_mlp_fwd_bf16_kernel(const float *__restrict__ PQ, const int32_t *__restrict__ rowptr,
+template <typename Op, int H2>
+__global__ __launch_bounds__(kBlk) void edge_mlp_fwd_mma_kernel(const float *__restrict__ PQ, const int32_t *__restrict__ rowptr,
                                                                  const int32_t *__restrict__ src, const int32_t *__restrict__ tgt,
                                                                  int64_t N, int64_t E, int H1, const float *__restrict__ W2,
                                                                  const float *__restrict__ b2, int act2, int aggr, int bn,
@@ -123,7 +160,7 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_fwd_bf16_kernel(const float *__
     float *ms = b2s + H2;                                                // [H2][TS]
     int32_t *tg = reinterpret_cast<int32_t *>(ms + H2 * kTS);            // [T]
     int32_t *sr = tg + kT;                                               // [T]
-    stage_w2(W2, b2, H1, H2, w2s, b2s);
+    stage_w2<Op>(W2, b2, H1, H2, w2s, b2s);
 
     const int nblk = gridDim.x;
     const int64_t n0 = range_start(rowptr, N, E, blockIdx.x, nblk), n1 = range_start(rowptr, N, E, blockIdx.x + 1, nblk);
@@ -156,11 +193,11 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_fwd_bf16_kernel(const float *__
             sr[t] = t < cnt ? src[pt + t] : 0;
         }
         __syncthreads();
-        fill_h1_bf16(PQ, H1, tg, sr, cnt, h1e, nullptr);
+        fill_h1<Op>(PQ, H1, tg, sr, cnt, h1e, nullptr);
         __syncthreads();
         for (int blk = wave; blk < 2 * (H2 / 16); blk += kWaves) {
             const int eb = blk & 1, ob = blk >> 1;
-            const f32x4 acc = z2_block(h1e, w2s, H1, eb, ob, lane);
+            const f32x4 acc = z2_block<Op>(h1e, w2s, H1, eb, ob, lane);
             const int o = 16 * ob + (lane & 15);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -202,8 +239,8 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_fwd_bf16_kernel(const float *__
 
 // Backward edge pass.  BY_SRC = false: positions are grouped edges (owner = tgt), sums g_pre1 per target into
 // gpq[:, 0:H1] and keeps gW2 / gb2 partials; BY_SRC = true: positions walk srcperm (owner = src), sums into gpq[:, H1:2H1].
-template <int H2, bool BY_SRC>
-__global__ __launch_bounds__(kBlk) void edge_mlp_bwd_bf16_kernel(const float *__restrict__ PQ, const int32_t *__restrict__ rowptr,
+template <typename Op, int H2, bool BY_SRC>
+__global__ __launch_bounds__(kBlk) void edge_mlp_bwd_mma_kernel(const float *__restrict__ PQ, const int32_t *__restrict__ rowptr,
                                                                  const int32_t *__restrict__ optr, const int32_t *__restrict__ perm,
                                                                  const int32_t *__restrict__ src, const int32_t *__restrict__ tgt,
                                                                  int64_t N, int64_t E, int H1, const float *__restrict__ W2,
@@ -220,14 +257,14 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_bf16_kernel(const float *__
     const int SH = h1_pitch(H1);
     unsigned short *w2s = reinterpret_cast<unsigned short *>(lds_raw);   // [H2][SH]
     unsigned short *h1e = w2s + H2 * SH;                                 // [T][SH]
-    unsigned short *gze = h1e + kT * SH;                                 // [T][SZ]   g_z2, bf16
+    unsigned short *gze = h1e + kT * SH;                                 // [T][SZ]   g_z2, 16-bit
     float *b2s = reinterpret_cast<float *>(gze + kT * SZ);               // [H2]
     float *h1c = b2s + H2;                                               // [H1][TS]  h1, then g_pre1
     float *gzc = h1c + H1 * kTS;                                         // [H2][TS]  g_z2, fp32
     int32_t *tg = reinterpret_cast<int32_t *>(gzc + H2 * kTS);           // [T]
     int32_t *sr = tg + kT;                                               // [T]
     int32_t *ep = sr + kT;                                               // [T] grouped edge position
-    stage_w2(W2, b2, H1, H2, w2s, b2s);
+    stage_w2<Op>(W2, b2, H1, H2, w2s, b2s);
 
     const int nblk = gridDim.x;
     const int64_t n0 = range_start(optr, N, E, blockIdx.x, nblk), n1 = range_start(optr, N, E, blockIdx.x + 1, nblk);
@@ -253,12 +290,12 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_bf16_kernel(const float *__
             sr[t] = t < cnt ? src[e] : 0;
         }
         __syncthreads();
-        fill_h1_bf16(PQ, H1, tg, sr, cnt, h1e, h1c);
+        fill_h1<Op>(PQ, H1, tg, sr, cnt, h1e, h1c);
         __syncthreads();
         // g_z2 per (edge, channel) from the re-computed z2 (fp32), into both g_z2 tiles
         for (int blk = wave; blk < 2 * (H2 / 16); blk += kWaves) {
             const int eb = blk & 1, ob = blk >> 1;
-            const f32x4 acc = z2_block(h1e, w2s, H1, eb, ob, lane);
+            const f32x4 acc = z2_block<Op>(h1e, w2s, H1, eb, ob, lane);
             const int o = 16 * ob + (lane & 15);
             const float ka = coef[o], k1 = coef[H2 + o], k2 = coef[2 * H2 + o];
             const float bmean = bnstat[2 * H2 + o], binv = bnstat[3 * H2 + o];
@@ -277,7 +314,7 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_bf16_kernel(const float *__
                     gzv = act2 ? gm * (z > 0.0f ? 1.0f : m + 1.0f) : gm;
                 }
                 gzc[o * kTS + t] = gzv;
-                gze[t * SZ + o] = bf16_bits(gzv);
+                gze[t * SZ + o] = Op::bits(gzv);
             }
         }
         __syncthreads();
@@ -288,9 +325,9 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_bf16_kernel(const float *__
                 const int blk = wave + kWaves * j;
                 if (blk < ngw) {
                     const int ob = blk % (H2 / 16), cb = blk / (H2 / 16);
-                    const bf16x8 a = ld8_f32(gzc + (16 * ob + (lane & 15)) * kTS + 8 * (lane >> 4));
-                    const bf16x8 b = ld8_f32(h1c + (16 * cb + (lane & 15)) * kTS + 8 * (lane >> 4));
-                    gw[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, gw[j], 0, 0, 0);
+                    const typename Op::vec a = ld8_f32<Op>(gzc + (16 * ob + (lane & 15)) * kTS + 8 * (lane >> 4));
+                    const typename Op::vec b = ld8_f32<Op>(h1c + (16 * cb + (lane & 15)) * kTS + 8 * (lane >> 4));
+                    gw[j] = Op::mfma(a, b, gw[j]);
                 }
             }
             if (threadIdx.x < H2) {
@@ -310,10 +347,10 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_bf16_kernel(const float *__
                 const unsigned short *pa = gze + (16 * eb + (lane & 15)) * SZ + 8 * (lane >> 4);
                 const unsigned short *pb = w2s + 8 * (lane >> 4) * SH + 16 * cb + (lane & 15);
                 for (int ks = 0; ks < H2 / 32; ++ks) {
-                    bf16x8 b;
+                    typename Op::vec b;
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) b[q] = (short)pb[(32 * ks + q) * SH];
-                    gh[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(pa + 32 * ks), b, gh[j], 0, 0, 0);
+                    for (int q = 0; q < 8; ++q) b[q] = Op::elem(pb[(32 * ks + q) * SH]);
+                    gh[j] = Op::mfma(ld8<Op>(pa + 32 * ks), b, gh[j]);
                 }
             }
         }
@@ -366,69 +403,84 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_bf16_kernel(const float *__
     }
 }
 
-inline size_t fwd_lds_bytes_bf16(int H1, int H2)
+inline size_t fwd_lds_bytes_mma(int H1, int H2)
 {
     const size_t SH = h1_pitch(H1);
     return 2 * SH * (H2 + kT) + sizeof(float) * (size_t)H2 * (kTS + 1) + 2 * sizeof(int32_t) * kT;
 }
 
-inline size_t bwd_lds_bytes_bf16(int H1, int H2)
+inline size_t bwd_lds_bytes_mma(int H1, int H2)
 {
     const size_t SH = h1_pitch(H1);
     return 2 * SH * (H2 + kT) + 2 * (size_t)kT * (H2 + 8) + sizeof(float) * ((size_t)H2 + (size_t)kTS * (H1 + H2)) +
            3 * sizeof(int32_t) * kT;
 }
 
-}  // namespace
-
-int edge_mlp_fwd_pass_bf16(const EdgePassArgs &a, int nblk, float *partial, hipStream_t st)
+template <typename Op>
+int fwd_pass(const EdgePassArgs &a, int nblk, float *partial, hipStream_t st)
 {
-    const size_t lds = fwd_lds_bytes_bf16(a.H1, a.H2);
+    const size_t lds = fwd_lds_bytes_mma(a.H1, a.H2);
     int rc = 0;
-#define EMLP_FWD_BF16(kH2)                                                                                                  \
+#define EMLP_FWD_MMA(kH2)                                                                                                   \
     {                                                                                                                       \
         static size_t granted = 0;                                                                                          \
-        rc = grant_lds(edge_mlp_fwd_bf16_kernel<kH2>, lds, granted, "hipFuncSetAttribute(edge_mlp_fwd_bf16_kernel)");       \
+        rc = grant_lds(edge_mlp_fwd_mma_kernel<Op, kH2>, lds, granted, "hipFuncSetAttribute(edge_mlp_fwd_mma_kernel)");     \
         if (rc == 0)                                                                                                        \
-            hipLaunchKernelGGL((edge_mlp_fwd_bf16_kernel<kH2>), dim3(nblk), dim3(kBlk), lds, st, a.pq, a.rowptr, a.src,     \
+            hipLaunchKernelGGL((edge_mlp_fwd_mma_kernel<Op, kH2>), dim3(nblk), dim3(kBlk), lds, st, a.pq, a.rowptr, a.src,  \
                                a.tgt, a.N, a.E, a.H1, a.W2, a.b2, a.act2, a.aggr, a.bn, a.agg, a.win, partial);             \
     }
     switch (a.H2) {
-    case 32: EMLP_FWD_BF16(32) break;
-    case 64: EMLP_FWD_BF16(64) break;
-    default: EMLP_FWD_BF16(128) break;
+    case 32: EMLP_FWD_MMA(32) break;
+    case 64: EMLP_FWD_MMA(64) break;
+    default: EMLP_FWD_MMA(128) break;
     }
-#undef EMLP_FWD_BF16
-    if (rc) return rc;
-    DMET_LAUNCH_CHECK("edge_mlp_fwd_bf16_kernel");
-    return 0;
+#undef EMLP_FWD_MMA
+    return rc;
 }
 
-int edge_mlp_bwd_pass_bf16(const EdgePassArgs &a, bool by_src, int nblk, float *partial, hipStream_t st)
+template <typename Op>
+int bwd_pass(const EdgePassArgs &a, bool by_src, int nblk, float *partial, hipStream_t st)
 {
-    const size_t lds = bwd_lds_bytes_bf16(a.H1, a.H2);
+    const size_t lds = bwd_lds_bytes_mma(a.H1, a.H2);
     const int32_t *optr = by_src ? a.srcptr : a.rowptr, *perm = by_src ? a.srcperm : nullptr;
     int rc = 0;
-#define EMLP_BWD_BF16(kH2, kBS)                                                                                             \
+#define EMLP_BWD_MMA(kH2, kBS)                                                                                              \
     {                                                                                                                       \
         static size_t granted = 0;                                                                                          \
-        rc = grant_lds(edge_mlp_bwd_bf16_kernel<kH2, kBS>, lds, granted, "hipFuncSetAttribute(edge_mlp_bwd_bf16_kernel)");  \
+        rc = grant_lds(edge_mlp_bwd_mma_kernel<Op, kH2, kBS>, lds, granted, "hipFuncSetAttribute(edge_mlp_bwd_mma_kernel)");\
         if (rc == 0)                                                                                                        \
-            hipLaunchKernelGGL((edge_mlp_bwd_bf16_kernel<kH2, kBS>), dim3(nblk), dim3(kBlk), lds, st, a.pq, a.rowptr, optr, \
-                               perm, a.src, a.tgt, a.N, a.E, a.H1, a.W2, a.b2, a.act2, a.aggr, a.bn, a.g_out, a.cwin,       \
+            hipLaunchKernelGGL((edge_mlp_bwd_mma_kernel<Op, kH2, kBS>), dim3(nblk), dim3(kBlk), lds, st, a.pq, a.rowptr,    \
+                               optr, perm, a.src, a.tgt, a.N, a.E, a.H1, a.W2, a.b2, a.act2, a.aggr, a.bn, a.g_out, a.cwin, \
                                a.bnstat, a.coef, a.gpq, partial);                                                           \
     }
     switch (a.H2 * 2 + (by_src ? 1 : 0)) {
-    case 64: EMLP_BWD_BF16(32, false) break;
-    case 65: EMLP_BWD_BF16(32, true) break;
-    case 128: EMLP_BWD_BF16(64, false) break;
-    case 129: EMLP_BWD_BF16(64, true) break;
-    case 256: EMLP_BWD_BF16(128, false) break;
-    default: EMLP_BWD_BF16(128, true) break;
+    case 64: EMLP_BWD_MMA(32, false) break;
+    case 65: EMLP_BWD_MMA(32, true) break;
+    case 128: EMLP_BWD_MMA(64, false) break;
+    case 129: EMLP_BWD_MMA(64, true) break;
+    case 256: EMLP_BWD_MMA(128, false) break;
+    default: EMLP_BWD_MMA(128, true) break;
     }
-#undef EMLP_BWD_BF16
-    if (rc) return rc;
-    DMET_LAUNCH_CHECK(by_src ? "edge_mlp_bwd_bf16_kernel (by source)" : "edge_mlp_bwd_bf16_kernel (by target)");
+#undef EMLP_BWD_MMA
+    return rc;
+}
+
+}  // namespace
+
+int edge_mlp_fwd_pass_mma(const EdgePassArgs &a, EdgePrec prec, int nblk, float *partial, hipStream_t st)
+{
+    if (int rc = prec == EdgePrec::f16 ? fwd_pass<OpF16>(a, nblk, partial, st) : fwd_pass<OpBf16>(a, nblk, partial, st))
+        return rc;
+    DMET_LAUNCH_CHECK(prec == EdgePrec::f16 ? "edge_mlp_fwd_mma_kernel (f16)" : "edge_mlp_fwd_mma_kernel (bf16)");
+    return 0;
+}
+
+int edge_mlp_bwd_pass_mma(const EdgePassArgs &a, EdgePrec prec, bool by_src, int nblk, float *partial, hipStream_t st)
+{
+    if (int rc = prec == EdgePrec::f16 ? bwd_pass<OpF16>(a, by_src, nblk, partial, st)
+                                       : bwd_pass<OpBf16>(a, by_src, nblk, partial, st))
+        return rc;
+    DMET_LAUNCH_CHECK(by_src ? "edge_mlp_bwd_mma_kernel (by source)" : "edge_mlp_bwd_mma_kernel (by target)");
     return 0;
 }
 
@@ -457,9 +509,9 @@ extern "C" int dmet_edge_mlp_fwd_bf16(const float *x, int64_t N, int Hin, const 
                                       int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
                                       float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
 {
-    return edge_mlp_fwd("dmet_edge_mlp_fwd_bf16", true, x, N, Hin, rowptr, src, tgt, E, W1, b1, H1, W2, b2, H2, act2, aggr,
-                        bn, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq, agg, win,
-                        bnstat, ws, ws_bytes, stream);
+    return edge_mlp_fwd("dmet_edge_mlp_fwd_bf16", EdgePrec::bf16, x, N, Hin, rowptr, src, tgt, E, W1, b1, H1, W2, b2, H2,
+                        act2, aggr, bn, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq,
+                        agg, win, bnstat, ws, ws_bytes, stream);
 }
 
 extern "C" int dmet_edge_mlp_bwd_bf16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
@@ -469,6 +521,39 @@ extern "C" int dmet_edge_mlp_bwd_bf16(const float *x, int64_t N, int Hin, const 
                                       const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
                                       float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
 {
-    return edge_mlp_bwd("dmet_edge_mlp_bwd_bf16", true, x, N, Hin, rowptr, src, tgt, E, srcptr, srcperm, W1, H1, W2, b2, H2,
-                        act2, aggr, bn, pq, agg, win, bnstat, g_out, gx, gpq, gW2, gb2, ggamma, gbeta, ws, ws_bytes, stream);
+    return edge_mlp_bwd("dmet_edge_mlp_bwd_bf16", EdgePrec::bf16, x, N, Hin, rowptr, src, tgt, E, srcptr, srcperm, W1, H1,
+                        W2, b2, H2, act2, aggr, bn, pq, agg, win, bnstat, g_out, gx, gpq, gW2, gb2, ggamma, gbeta, ws,
+                        ws_bytes, stream);
+}
+
+// fp16: the same widths, workspace and argument checks as bf16
+extern "C" int dmet_edge_mlp_f16_supported(int Hin, int H1, int H2) { return dmet_edge_mlp_bf16_supported(Hin, H1, H2); }
+
+extern "C" size_t dmet_edge_mlp_f16_workspace_bytes(int64_t N, int64_t E, int Hin, int H1, int H2)
+{
+    return dmet_edge_mlp_bf16_workspace_bytes(N, E, Hin, H1, H2);
+}
+
+extern "C" int dmet_edge_mlp_fwd_f16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+                                     const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1, const float *W2,
+                                     const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
+                                     const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                                     int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
+                                     float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    return edge_mlp_fwd("dmet_edge_mlp_fwd_f16", EdgePrec::f16, x, N, Hin, rowptr, src, tgt, E, W1, b1, H1, W2, b2, H2,
+                        act2, aggr, bn, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq,
+                        agg, win, bnstat, ws, ws_bytes, stream);
+}
+
+extern "C" int dmet_edge_mlp_bwd_f16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+                                     const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
+                                     const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr,
+                                     int bn, const float *pq, const float *agg, const int32_t *win, const float *bnstat,
+                                     const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
+                                     float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    return edge_mlp_bwd("dmet_edge_mlp_bwd_f16", EdgePrec::f16, x, N, Hin, rowptr, src, tgt, E, srcptr, srcperm, W1, H1,
+                        W2, b2, H2, act2, aggr, bn, pq, agg, win, bnstat, g_out, gx, gpq, gW2, gb2, ggamma, gbeta, ws,
+                        ws_bytes, stream);
 }

@@ -570,12 +570,14 @@ extern "C" size_t dmet_edge_mlp_f32_workspace_bytes(int64_t N, int64_t E, int Hi
     default: { constexpr int kH2 = 128; __VA_ARGS__; } break;           \
     }
 
-static int check_common(const char *fn, bool bf16, const float *x, int64_t N, int Hin, const int32_t *rowptr,
+static int check_common(const char *fn, EdgePrec prec, const float *x, int64_t N, int Hin, const int32_t *rowptr,
                         const int32_t *src, const int32_t *tgt, int64_t E, const float *W1, int H1, const float *W2, int H2,
                         int aggr, int bn, const float *running_mean, const float *running_var, size_t ws_bytes,
                         const void *ws, bool fwd)
 {
-    const int supported = bf16 ? dmet_edge_mlp_bf16_supported(Hin, H1, H2) : dmet_edge_mlp_f32_supported(Hin, H1, H2);
+    const int supported = prec == EdgePrec::bf16  ? dmet_edge_mlp_bf16_supported(Hin, H1, H2)
+                          : prec == EdgePrec::f16 ? dmet_edge_mlp_f16_supported(Hin, H1, H2)
+                                                  : dmet_edge_mlp_f32_supported(Hin, H1, H2);
     DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647 / 384, "%s: N out of range", fn);
     DMET_REQUIRE(E >= 0 && E < (int64_t)2147483647, "%s: E out of range", fn);
     DMET_REQUIRE(supported, "%s: unsupported widths Hin=%d H1=%d H2=%d", fn, Hin, H1, H2);
@@ -591,14 +593,14 @@ static int check_common(const char *fn, bool bf16, const float *x, int64_t N, in
     return 0;
 }
 
-int dmet::edge_mlp_fwd(const char *fn, bool bf16, const float *x, int64_t N, int Hin, const int32_t *rowptr,
+int dmet::edge_mlp_fwd(const char *fn, EdgePrec prec, const float *x, int64_t N, int Hin, const int32_t *rowptr,
                        const int32_t *src, const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1,
                        const float *W2, const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
                        const float *beta, float eps, float momentum, float *running_mean, float *running_var,
                        int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win, float *bnstat,
                        void *ws, size_t ws_bytes, dmet_stream_t stream)
 {
-    if (int rc = check_common(fn, bf16, x, N, Hin, rowptr, src, tgt, E, W1, H1, W2, H2, aggr, bn, running_mean, running_var,
+    if (int rc = check_common(fn, prec, x, N, Hin, rowptr, src, tgt, E, W1, H1, W2, H2, aggr, bn, running_mean, running_var,
                               ws_bytes, ws, true))
         return rc;
     DMET_REQUIRE(bn != 1 || E > 0, "%s: batch statistics need at least one edge", fn);
@@ -617,11 +619,11 @@ int dmet::edge_mlp_fwd(const char *fn, bool bf16, const float *x, int64_t N, int
                        (const float *)bias, 2 * H1, pq);
     DMET_LAUNCH_CHECK("rows_linear_kernel (P | Q)");
     const int nblk = edge_blocks(E);
-    if (E > 0 && bf16) {
+    if (E > 0 && prec != EdgePrec::f32) {
         EdgePassArgs a{};
         a.pq = pq; a.rowptr = rowptr; a.src = src; a.tgt = tgt; a.N = N; a.E = E; a.H1 = H1; a.H2 = H2;
         a.W2 = W2; a.b2 = b2; a.act2 = act2; a.aggr = aggr; a.bn = bn; a.agg = agg; a.win = win;
-        if (int rc = edge_mlp_fwd_pass_bf16(a, nblk, partial, st)) return rc;
+        if (int rc = edge_mlp_fwd_pass_mma(a, prec, nblk, partial, st)) return rc;
     } else if (E > 0) {
         const size_t lds = fwd_lds_bytes(H1, H2);
         int rc = 0;
@@ -643,14 +645,14 @@ int dmet::edge_mlp_fwd(const char *fn, bool bf16, const float *x, int64_t N, int
     return 0;
 }
 
-int dmet::edge_mlp_bwd(const char *fn, bool bf16, const float *x, int64_t N, int Hin, const int32_t *rowptr,
+int dmet::edge_mlp_bwd(const char *fn, EdgePrec prec, const float *x, int64_t N, int Hin, const int32_t *rowptr,
                        const int32_t *src, const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
                        const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr, int bn,
                        const float *pq, const float *agg, const int32_t *win, const float *bnstat, const float *g_out,
                        float *gx, float *gpq, float *gW2, float *gb2, float *ggamma, float *gbeta, void *ws,
                        size_t ws_bytes, dmet_stream_t stream)
 {
-    if (int rc = check_common(fn, bf16, x, N, Hin, rowptr, src, tgt, E, W1, H1, W2, H2, aggr, bn, nullptr, nullptr, ws_bytes, ws, false))
+    if (int rc = check_common(fn, prec, x, N, Hin, rowptr, src, tgt, E, W1, H1, W2, H2, aggr, bn, nullptr, nullptr, ws_bytes, ws, false))
         return rc;
     hipStream_t st = as_stream(stream);
     if (N == 0) {
@@ -688,13 +690,13 @@ int dmet::edge_mlp_bwd(const char *fn, bool bf16, const float *x, int64_t N, int
     hipLaunchKernelGGL(zero_kernel, dim3((unsigned)((npq + 255) / 256)), dim3(256), 0, st, gpq, npq);
     DMET_LAUNCH_CHECK("zero_kernel");
     const int nblk = edge_blocks(E);
-    if (E > 0 && bf16) {
+    if (E > 0 && prec != EdgePrec::f32) {
         EdgePassArgs a{};
         a.pq = pq; a.rowptr = rowptr; a.src = src; a.tgt = tgt; a.N = N; a.E = E; a.H1 = H1; a.H2 = H2;
         a.W2 = W2; a.b2 = b2; a.act2 = act2; a.aggr = aggr; a.bn = bn; a.srcptr = srcptr; a.srcperm = srcperm;
         a.g_out = g_out; a.bnstat = bnstat; a.coef = coef; a.cwin = win; a.gpq = gpq;
-        if (int rc = edge_mlp_bwd_pass_bf16(a, false, nblk, partial, st)) return rc;
-        if (int rc = edge_mlp_bwd_pass_bf16(a, true, nblk, nullptr, st)) return rc;
+        if (int rc = edge_mlp_bwd_pass_mma(a, prec, false, nblk, partial, st)) return rc;
+        if (int rc = edge_mlp_bwd_pass_mma(a, prec, true, nblk, nullptr, st)) return rc;
     } else if (E > 0) {
         const size_t lds = bwd_lds_bytes(H1, H2);
         int rc = 0;
@@ -738,7 +740,7 @@ extern "C" int dmet_edge_mlp_fwd_f32(const float *x, int64_t N, int Hin, const i
                                      int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
                                      float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
 {
-    return edge_mlp_fwd("dmet_edge_mlp_fwd_f32", false, x, N, Hin, rowptr, src, tgt, E, W1, b1, H1, W2, b2, H2, act2, aggr,
+    return edge_mlp_fwd("dmet_edge_mlp_fwd_f32", EdgePrec::f32, x, N, Hin, rowptr, src, tgt, E, W1, b1, H1, W2, b2, H2, act2, aggr,
                         bn, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq, agg, win,
                         bnstat, ws, ws_bytes, stream);
 }
@@ -750,6 +752,6 @@ extern "C" int dmet_edge_mlp_bwd_f32(const float *x, int64_t N, int Hin, const i
                                      const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
                                      float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
 {
-    return edge_mlp_bwd("dmet_edge_mlp_bwd_f32", false, x, N, Hin, rowptr, src, tgt, E, srcptr, srcperm, W1, H1, W2, b2, H2,
+    return edge_mlp_bwd("dmet_edge_mlp_bwd_f32", EdgePrec::f32, x, N, Hin, rowptr, src, tgt, E, srcptr, srcperm, W1, H1, W2, b2, H2,
                         act2, aggr, bn, pq, agg, win, bnstat, g_out, gx, gpq, gW2, gb2, ggamma, gbeta, ws, ws_bytes, stream);
 }

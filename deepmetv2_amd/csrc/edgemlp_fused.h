@@ -1,6 +1,6 @@
 // edgemlp_fused.h -- what the fused edge-MLP routes over a grouped edge list share: the fp32 route (edgemlp_f32.hip),
-// which owns the node-level kernels and the host orchestration, and the bf16 matrix-core route (edgemlp_bf16.hip),
-// which brings its own two edge passes.
+// which owns the node-level kernels and the host orchestration, and the bf16 / fp16 matrix-core routes
+// (edgemlp_bf16.hip), which bring their own two edge passes.
 #pragma once
 
 #include "common.h"
@@ -75,17 +75,20 @@ struct EdgePassArgs {
     float *gpq;
 };
 
-// bf16 edge passes (edgemlp_bf16.hip): launch on `st` over nblk workgroups; 0 or a dmet error code
-int edge_mlp_fwd_pass_bf16(const EdgePassArgs &a, int nblk, float *partial, hipStream_t st);
-int edge_mlp_bwd_pass_bf16(const EdgePassArgs &a, bool by_src, int nblk, float *partial, hipStream_t st);
+// operand type of the per-edge products: fp32 VALU (edgemlp_f32.hip), bf16 or fp16 matrix cores (edgemlp_bf16.hip)
+enum class EdgePrec { f32, bf16, f16 };
 
-// host orchestration of either route (edgemlp_f32.hip): the entry points of include/dmet.h with the route chosen by bf16
-int edge_mlp_fwd(const char *fn, bool bf16, const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+// matrix-core edge passes (edgemlp_bf16.hip, prec bf16 or f16): launch on `st` over nblk workgroups; 0 or a dmet error code
+int edge_mlp_fwd_pass_mma(const EdgePassArgs &a, EdgePrec prec, int nblk, float *partial, hipStream_t st);
+int edge_mlp_bwd_pass_mma(const EdgePassArgs &a, EdgePrec prec, bool by_src, int nblk, float *partial, hipStream_t st);
+
+// host orchestration of every route (edgemlp_f32.hip): the entry points of include/dmet.h with the route chosen by prec
+int edge_mlp_fwd(const char *fn, EdgePrec prec, const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
                  const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1, const float *W2, const float *b2,
                  int H2, int act2, int aggr, int bn, const float *gamma, const float *beta, float eps, float momentum,
                  float *running_mean, float *running_var, int64_t *num_batches_tracked, float *out, float *pq, float *agg,
                  int32_t *win, float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream);
-int edge_mlp_bwd(const char *fn, bool bf16, const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+int edge_mlp_bwd(const char *fn, EdgePrec prec, const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
                  const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm, const float *W1, int H1,
                  const float *W2, const float *b2, int H2, int act2, int aggr, int bn, const float *pq, const float *agg,
                  const int32_t *win, const float *bnstat, const float *g_out, float *gx, float *gpq, float *gW2,

@@ -132,7 +132,9 @@ class Net(nn.Module):
 def loss_fn(weights: torch.Tensor, prediction: torch.Tensor, truth: torch.Tensor, batch: torch.Tensor,
             ptr: Optional[torch.Tensor] = None) -> torch.Tensor:
     """net.py:49-62 with the two scatter_add calls fused into one MET reduction:
-    0.5 * mean_b((METx + true_px)^2 + (METy + true_py)^2)."""
+    0.5 * mean_b((METx + true_px)^2 + (METy + true_py)^2).  bf16 or fp16 weights (autocast) are upcast; the loss is fp32."""
+    if weights.dtype in (torch.float16, torch.bfloat16):
+        weights = weights.float()
     if weights.dtype == torch.float32 and prediction.dtype == torch.float32 and truth.dtype == torch.float32:
         return met_loss_from_weights(weights, prediction, truth, batch, ptr=ptr)
     met = met_reduce(weights, prediction, batch, ptr=ptr, num_events=truth.shape[0])

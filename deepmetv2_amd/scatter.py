@@ -54,6 +54,9 @@ class _SegmentMaxRows(torch.autograd.Function):
         return _native.segment_max_bwd(g_out, arg, rowptr, ctx.E), None, None
 
 
+_HALF = (torch.float16, torch.bfloat16)
+
+
 def _dim_size(index: torch.Tensor, dim_size: Optional[int]) -> int:
     if dim_size is not None:
         return int(dim_size)
@@ -64,9 +67,17 @@ def scatter_add(src: torch.Tensor, index: torch.Tensor, dim: int = -1, out: Opti
                 dim_size: Optional[int] = None) -> torch.Tensor:
     """torch_scatter.scatter_add for the shapes on the hot path:
     1-D `src` with a sorted `index` (the batch vector): one deterministic segmented sum per event;
-    2-D `src` [E,H] along dim 0 (aggr='add'): grouped by index with a stable sort, then per-row sums."""
+    2-D `src` [E,H] along dim 0 (aggr='add'): grouped by index with a stable sort, then per-row sums.
+    A bf16 or fp16 `src` is summed in fp32 by the same kernels and the result returned in src.dtype, as torch_scatter
+    returns it."""
     if index.dtype != torch.int64:
         raise TypeError(f"index must be int64, got {index.dtype}")
+    if src.dtype in _HALF:
+        res = scatter_add(src.float(), index, dim, None, dim_size).to(src.dtype)
+        if out is not None:
+            out.add_(res)
+            return out
+        return res
     if src.dim() == 1:
         if index.shape != src.shape:
             raise ValueError("index must have the same shape as a 1-D src")
@@ -96,9 +107,13 @@ def scatter_add(src: torch.Tensor, index: torch.Tensor, dim: int = -1, out: Opti
 def scatter_max(src: torch.Tensor, index: torch.Tensor, dim: int = 0, out=None,
                 dim_size: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """torch_scatter.scatter_max for [E,H] rows along dim 0: (out, arg); empty rows -> 0 (R3), arg = winning row
-    position in `src` (lowest on ties, R4); rows with no entry report arg = E like upstream."""
+    position in `src` (lowest on ties, R4); rows with no entry report arg = E like upstream.  A bf16 or fp16 `src` is
+    compared in fp32 (exact) and the maxima returned in src.dtype."""
     if src.dim() != 2 or dim not in (0, -2) or out is not None:
         raise NotImplementedError("scatter_max: only [E,H] along dim 0 without `out` is implemented")
+    if src.dtype in _HALF:
+        res, arg = scatter_max(src.float(), index, dim, None, dim_size)
+        return res.to(src.dtype), arg
     idx = index if index.dim() == 1 else index[:, 0]
     n = _dim_size(idx, dim_size)
     E = idx.numel()
@@ -132,7 +147,10 @@ class _MetReduce(torch.autograd.Function):
 def met_reduce(weights: torch.Tensor, x: torch.Tensor, batch: Optional[torch.Tensor] = None,
                ptr: Optional[torch.Tensor] = None, num_events: Optional[int] = None) -> torch.Tensor:
     """met[b] = (sum_i w_i * x[i,0], sum_i w_i * x[i,1]) over the nodes of event b: both scatter_add calls of
-    model/net.py:55-56 in one pass over w and the px/py columns.  Differentiable w.r.t. `weights`."""
+    model/net.py:55-56 in one pass over w and the px/py columns.  Differentiable w.r.t. `weights`.  bf16 or fp16
+    `weights` are upcast (exact); the result is fp32."""
+    if weights.dtype in _HALF:
+        weights = weights.float()
     if ptr is None:
         ptr = batch_info(batch, weights.numel(), weights.device, num_events).ptr
     return _MetReduce.apply(weights, x, ptr)
@@ -170,7 +188,9 @@ class _MetLossFromWeights(torch.autograd.Function):
 
 def met_loss_from_weights(weights: torch.Tensor, x: torch.Tensor, truth: torch.Tensor, batch: Optional[torch.Tensor] = None,
                           ptr: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """met_loss(met_reduce(weights, x), truth) with the same bits, as one autograd node."""
+    """met_loss(met_reduce(weights, x), truth) with the same bits, as one autograd node (bf16 or fp16 weights upcast)."""
+    if weights.dtype in _HALF:
+        weights = weights.float()
     if ptr is None:
         ptr = batch_info(batch, weights.numel(), weights.device, truth.shape[0]).ptr
     return _MetLossFromWeights.apply(weights, x, ptr, truth)

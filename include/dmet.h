@@ -329,6 +329,29 @@ int dmet_edge_mlp_bwd_bf16(const float *x, int64_t N, int Hin, const int32_t *ro
                            const float *b2, int H2, int act2, int aggr, int bn, const float *pq, const float *agg,
                            const int32_t *win, const float *bnstat, const float *g_out, float *gx, float *gpq, float *gW2,
                            float *gb2, float *ggamma, float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream);
+/* --- fp16 matrix-core edge MLP over any grouped edge list (csrc/edgemlp_bf16.hip) ---------------------------------------
+ * The bf16 entries above with fp16 in place of bf16 (v_mfma_f32_16x16x32_f16; the route of the DRN under fp16 autocast,
+ * torch.autocast("cuda") without a dtype, with torch.amp.GradScaler).  Same arguments, argument checks, widths,
+ * workspace and state; the same kernels, instantiated for the other operand type.
+ *   forward: P, Q, ELU, aggregation and BatchNorm fp32; h1 and W2 rounded to fp16, fp32 accumulation.
+ *   backward: g_z2, h1 and W2 rounded to fp16 for g_h1 = g_z2 W2 and gW2 = g_z2^T h1, fp32 accumulation; node-level
+ *   products fp32.
+ * Rounding is round-to-nearest-even (as torch's .half()), never the packed round-toward-zero conversion.  A value whose
+ * magnitude rounds beyond 65504 becomes +-inf (no saturation), so a gradient scaled past the fp16 range comes out
+ * non-finite and GradScaler skips the step; fp16 subnormals are kept, so a scaled-up tiny g_z2 keeps its bits.
+ * ws: dmet_edge_mlp_f16_workspace_bytes(N, E, Hin, H1, H2) (equal to the bf16 size). */
+int dmet_edge_mlp_f16_supported(int Hin, int H1, int H2);
+size_t dmet_edge_mlp_f16_workspace_bytes(int64_t N, int64_t E, int Hin, int H1, int H2);
+int dmet_edge_mlp_fwd_f16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src, const int32_t *tgt,
+                          int64_t E, const float *W1, const float *b1, int H1, const float *W2, const float *b2, int H2,
+                          int act2, int aggr, int bn, const float *gamma, const float *beta, float eps, float momentum,
+                          float *running_mean, float *running_var, int64_t *num_batches_tracked, float *out, float *pq,
+                          float *agg, int32_t *win, float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream);
+int dmet_edge_mlp_bwd_f16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src, const int32_t *tgt,
+                          int64_t E, const int32_t *srcptr, const int32_t *srcperm, const float *W1, int H1, const float *W2,
+                          const float *b2, int H2, int act2, int aggr, int bn, const float *pq, const float *agg,
+                          const int32_t *win, const float *bnstat, const float *g_out, float *gx, float *gpq, float *gW2,
+                          float *gb2, float *ggamma, float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream);
 /* bf16 variant (BASELINE configs[2]): x and the split weights rounded to bf16 (RNE), multiplied on the bf16 matrix
  * cores with fp32 accumulation; P stays fp32, Q is stored as bf16 (raw bits) and gathered as 64-B rows.
  * Built for Hin = Hout = 32, k in {8,16,32}.  Backward is shared with the fp32 path (arg-based, fp32). */

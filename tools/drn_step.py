@@ -1,13 +1,14 @@
 """DynamicReductionNetwork forward + backward rate, with a per-operator breakdown and the graclus round statistics.
 
     python tools/drn_step.py [--shapes 64x4500 128x1000] [--hidden 64] [--k 16] [--steps 10] [--warmup 3] [--autocast]
-                             [--json OUT]
+                             [--autocast-dtype {bfloat16,float16}] [--json OUT]
 
 Measurement only (bench.py measures the flagship model).  The rate is taken over `--steps` back-to-back forward +
 backward passes (no optimizer).  The breakdown is a separate pass that synchronises after every stage, so its stages are
 device time plus the host time the stage itself spends (one host sync each in to_undirected, knn_graph with loop=False,
 and max_pool_x).  --autocast runs every pass under torch.autocast("cuda", dtype=torch.bfloat16): the EdgeConvs then take
-the bf16 matrix-core route (csrc/edgemlp_bf16.hip)."""
+the bf16 matrix-core route (csrc/edgemlp_bf16.hip); with --autocast-dtype float16 under torch.autocast("cuda",
+dtype=torch.float16), the fp16 one (the same kernels on the fp16 matrix cores)."""
 import argparse
 import json
 import os
@@ -67,11 +68,11 @@ def breakdown(m, data):
     return t, rounds
 
 
-def run(B, n, hidden, k, steps, warmup, dev, autocast=False):
+def run(B, n, hidden, k, steps, warmup, dev, autocast=False, autocast_dtype=torch.bfloat16):
     torch.manual_seed(0)
     m = dm.DynamicReductionNetwork(input_dim=5, hidden_dim=hidden, k=k).to(dev).train()
     data = make_batch(B, n, dev)
-    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+    with torch.autocast("cuda", dtype=autocast_dtype, enabled=autocast):
         for _ in range(warmup):
             m(data).float().sum().backward()
         torch.cuda.synchronize()
@@ -96,14 +97,18 @@ def main():
     ap.add_argument("--k", type=int, default=16)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--autocast", action="store_true", help="bf16 autocast (the EdgeConvs' bf16 matrix-core route)")
+    ap.add_argument("--autocast", action="store_true", help="autocast (the EdgeConvs' 16-bit matrix-core route)")
+    ap.add_argument("--autocast-dtype", choices=("bfloat16", "float16"), default="bfloat16",
+                    help="autocast dtype with --autocast (default bfloat16)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     out = []
     for s in a.shapes:
         B, n = (int(v) for v in s.split("x"))
-        r = run(B, n, a.hidden, a.k, a.steps, a.warmup, dev, a.autocast)
+        r = run(B, n, a.hidden, a.k, a.steps, a.warmup, dev, a.autocast, getattr(torch, a.autocast_dtype))
+        if a.autocast:
+            r["autocast_dtype"] = a.autocast_dtype
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.json:
