@@ -928,14 +928,26 @@ __device__ __forceinline__ int64_t rec_base_tile(const int64_t *__restrict__ ptr
 
 // Second-form events (kF2MinNodes..kF2MaxNodes nodes, when the second form is enabled) get SINGLE-TERM fp16 records
 // instead of the bf16 split: frag[m][lane], m = 0..2 NH - 1, = the 8 fp16 values (round to nearest even) of features
-// 16 m + 8 hh + 0..7 of row col, then the 32 squared norms at byte kRec16FragBytes * NH (the record stride stays
-// rec_bytes(NH)).  Two MFMAs per 32 x 32 block instead of six; the certificate of the second form carries the fp16
-// rounding (see f2_slack).  A row with a feature outside the range whose doubled value fits fp16 (|v| >= 16384, or not
-// finite) is stored as zeros with norm -inf: its key is -inf for every query, so it is always a candidate of the exact
-// re-rank and never dropped on the strength of an overflowed product (as a QUERY such a row is refused by the
-// certificate through its true norm, kept in nrm[]).
+// 16 m + 8 hh + 0..7 of row col, then at byte kRec16FragBytes * NH one more fragment (1 KB) that carries the squared
+// norms and the scales of the threshold (the record stride stays rec_bytes(NH)).  2 NH + 1 MFMAs per 32 x 32 block
+// instead of six; the certificate of the second form carries the fp16 rounding (see f2_slack).  A row with a feature
+// outside the range whose doubled value fits fp16 (|v| >= 16384, or not finite) is stored as zeros with the norm term
+// -inf: its key is -inf for every query, so it is always a candidate of the exact re-rank and never dropped on the
+// strength of an overflowed product (as a QUERY such a row is refused by the certificate through its true norm, kept
+// in nrm[]).
 constexpr int kRec16FragBytes = 2 * kWave * 16;         // 2048: the two fp16 operand fragments of 32 features
 constexpr float kF16WideLimit = 16384.0f;
+static_assert(kRec16FragBytes + kWave * 16 <= rec_bytes(1) && 2 * kRec16FragBytes + kWave * 16 <= rec_bytes(2),
+              "the fold fragment fits the record");
+// Fold of the squared norms and of the threshold into the matrix product (f2_block): the key block comes out as
+// |x_j|^2 - 2 x_i.x_j - tau_rep(i).  Norm terms: N_i x kF2NormP[i], each scale chosen so that the residual of the term
+// before (<= 2^-11 of it) fits fp16: N1 <= 65504 for s < kF2NormMax, N2..N4 <= 2^15.  Threshold terms: y x kF2TauC[i]
+// with y the fp16 on the query side (f2_tau16).
+constexpr float kF2NormP[4] = {0x1p15f, 0x1p5f, 0x1p-6f, 0x1p-17f};
+constexpr float kF2NormInvP[4] = {0x1p-15f, 0x1p-5f, 0x1p6f, 0x1p17f};
+constexpr float kF2NormMax = 65504.0f * 0x1p15f;
+constexpr float kF2TauC[2] = {0x1p14f, 0x1p-15f};
+constexpr float kF2TauRepMax = 65504.0f * 0x1p14f;   // the largest threshold the fold represents (f2_cert_T)
 
 __device__ __forceinline__ bool f2_in_domain64(int64_t n) { return n >= kF2MinNodes && n <= kF2MaxNodes; }
 
@@ -1079,11 +1091,41 @@ __global__ __launch_bounds__(256) void knn_prep_kernel(const float *__restrict__
                 dst[kb * 64 + lane] = __builtin_bit_cast(uint4, hv);
             }
         }
-        if (hh == 0) {
-            reinterpret_cast<float *>(recp + kRec16FragBytes * NH)[col] =
-                !live ? __builtin_inff() : (wide ? -__builtin_inff() : s);
-            if (live) nrm[r] = s;
+        // the fold fragment (see f2_block): lane (col, 0) = {0, 0, 0, 0, N1, N2, N3, N4}, the squared norm as four fp16
+        // terms on the fixed scales kF2NormP (N1 = +inf for rows past the event's end, -inf for forced rows); lane
+        // (col, 1) = {2^14, 2^-15, 0, ...}, the scales of the two threshold terms.  Each residual is exact (the
+        // subtracted term is the rounded residual itself or a multiple of its ulp), so |s - sum N_i P_i| is the last
+        // rounding alone: <= 2^-44 s + 2^-40 (f2_slack).  A norm at or beyond 65504 x 2^15 makes the row a forced
+        // candidate (as a query it is refused by the certificate already: nx >= 2^28).
+        // 64 features (NH = 2) keep the 32 fp32 squared norms there instead: the accumulator seed of f2_block.
+        if constexpr (NH != 1) {
+            if (hh == 0) {
+                reinterpret_cast<float *>(recp + kRec16FragBytes * NH)[col] =
+                    !live ? __builtin_inff() : (wide ? -__builtin_inff() : s);
+                if (live) nrm[r] = s;
+            }
+            return;
         }
+        f16x8 fv = {};
+        if (hh == 0) {
+            const float sn = !live ? __builtin_inff() : ((wide || !(s < kF2NormMax)) ? -__builtin_inff() : s);
+            if (sn == sn && __builtin_fabsf(sn) < __builtin_inff()) {
+                float rr = sn;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const _Float16 h = (_Float16)(rr * kF2NormInvP[i]);   // v_cvt_f16_f32: RNE
+                    fv[4 + i] = h;
+                    rr -= (float)h * kF2NormP[i];
+                }
+            } else {
+                fv[4] = (_Float16)sn;
+            }
+            if (live) nrm[r] = s;
+        } else {
+            fv[0] = (_Float16)kF2TauC[0];
+            fv[1] = (_Float16)kF2TauC[1];
+        }
+        reinterpret_cast<uint4 *>(recp + kRec16FragBytes * NH)[lane] = __builtin_bit_cast(uint4, fv);
         return;
     }
 #pragma unroll
@@ -1578,6 +1620,8 @@ template <int M>
 struct F2Lane {
     float tk[M];     // the M smallest tile minima, sorted
     float tau;       // admission threshold (= tk[M-1]; -inf for idle lanes / after an overflow)
+    unsigned tq;     // tau as the query side of the fold (f2_tau16; 0 while no mask is recorded)
+    float rep;       // the threshold tq stands for (>= tau, or kF2TauRepMax)
     int cnt;         // entries in the lane's queue
     bool overflow;
 };
@@ -1611,27 +1655,51 @@ __device__ __forceinline__ void f2_compact(F2Lane<M> &L, F2Wave &S, int lane, in
     }
 }
 
-// Operands of one candidate tile (A fragments + accumulator seed): single-term fp16 records (see knn_prep_kernel).
+// Query side of the fold block for one 32-query block, the same in every lane: {y_0, y_1, 0, 0, P1, P2, P3, P4} with
+// tq = (y_0, y_1) packed (f2_tau16).  Lanes hh = 0 meet the zeros of the candidate side in slots 0, 1 and the norm
+// terms in 4..7; lanes hh = 1 meet the threshold scales in 0, 1 and zeros in 4..7.
+__device__ __forceinline__ f16x8 f2_fold(unsigned tq)
+{
+    const f16x8 pc = {(_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f, (_Float16)kF2NormP[0],
+                      (_Float16)kF2NormP[1], (_Float16)kF2NormP[2], (_Float16)kF2NormP[3]};
+    uint4 u = __builtin_bit_cast(uint4, pc);
+    u.x = tq;
+    return __builtin_bit_cast(f16x8, u);
+}
+
+// Operands of one candidate tile: single-term fp16 records (see knn_prep_kernel).  32 features: the A fragments + the
+// fold fragment.  64 features: the A fragments + the fp32 accumulator seed (the squared norms of the 16 candidate rows
+// the lane receives results for, rows (e & 3) + 8 (e >> 2) + 4 hh) -- the fold's registers and conversions pushed the
+// 64-feature kernels, which hold sixteen query fragments, into more scratch; their keys still need the subtract.
 template <int NH = 1>
 struct F2Ops {
     f16x8 a[2 * NH];
+    f16x8 f;
+};
+template <>
+struct F2Ops<2> {
+    f16x8 a[4];
     f32x16 c;
 };
 
-// One 32(candidates) x 32(queries) block: acc = cinit + sum over the 16-feature k-blocks of h.h' (fp16 operands, fp32
-// accumulate): 2 NH MFMAs.  Operand map of v_mfma_f32_32x32x16_f16: lane (r = lane & 31, hh = lane >> 5) holds
-// A[row r][k = 8 hh + 0..7].
+// One 32(candidates) x 32(queries) block: acc = fold (or seed) + sum over the 16-feature k-blocks of h.h' (fp16
+// operands, fp32 accumulate).  Operand map of v_mfma_f32_32x32x16_f16: lane (r = lane & 31, hh = lane >> 5) holds
+// A[row r][k = 8 hh + 0..7].  32 features: 3 MFMAs, the first one from the inline constant 0 -- the fold block (o.f from
+// the record, f2_fold(tq) on the query side) is  sum_k A[j][k] B[k][i] = N1 P1 + .. + N4 P4 + 2^14 y_0(i) +
+// 2^-15 y_1(i) = |x_j|^2 - tau_rep(i) up to the norm's rounding: every product is exact in fp32 and the ones of the zero
+// slots are 0 (every operand there is finite).  64 features: 4 MFMAs from the seed (keys, tq unused).
 template <int NH = 1>
-__device__ __forceinline__ f32x16 f2_block(const f16x8 (&av)[2 * NH], const f16x8 (&bv)[2 * NH], const f32x16 &cinit)
+__device__ __forceinline__ f32x16 f2_block(const F2Ops<NH> &o, const f16x8 (&bv)[2 * NH], unsigned tq)
 {
-    f32x16 acc = cinit;
+    f32x16 acc;
+    if constexpr (NH == 1) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(o.f, f2_fold(tq), f32x16{}, 0, 0, 0);
+    else acc = o.c;
 #pragma unroll
-    for (int m = 0; m < 2 * NH; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[m], bv[m], acc, 0, 0, 0);
+    for (int m = 0; m < 2 * NH; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(o.a[m], bv[m], acc, 0, 0, 0);
     return acc;
 }
 
-// one fp16 candidate tile record: the lane's 2 NH A operands and the squared norms of the 16 candidate rows it receives
-// results for (accumulator seed; rows (e & 3) + 8 (e >> 2) + 4 hh)
+// one fp16 candidate tile record: the lane's 2 NH A operands and its part of the fold fragment (or its 16 norms)
 template <int NH = 1>
 __device__ __forceinline__ void f2_load(F2Ops<NH> &o, const uint8_t *__restrict__ rec, int64_t tidx, int lane, int hh)
 {
@@ -1639,13 +1707,66 @@ __device__ __forceinline__ void f2_load(F2Ops<NH> &o, const uint8_t *__restrict_
     const f16x8 *g = reinterpret_cast<const f16x8 *>(base);
 #pragma unroll
     for (int m = 0; m < 2 * NH; ++m) o.a[m] = g[m * 64 + lane];
-    const float4 *nr = reinterpret_cast<const float4 *>(base + kRec16FragBytes * NH);
+    if constexpr (NH == 1) {
+        o.f = g[2 * NH * 64 + lane];
+    } else {
+        const float4 *nr = reinterpret_cast<const float4 *>(base + kRec16FragBytes * NH);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = nr[2 * q + hh];
-        o.c[4 * q] = v.x; o.c[4 * q + 1] = v.y; o.c[4 * q + 2] = v.z; o.c[4 * q + 3] = v.w;
+        for (int q = 0; q < 4; ++q) {
+            const float4 v = nr[2 * q + hh];
+            o.c[4 * q] = v.x; o.c[4 * q + 1] = v.y; o.c[4 * q + 2] = v.z; o.c[4 * q + 3] = v.w;
+        }
     }
 }
+
+// The threshold as the query side of the fold: returns (y_0, y_1) packed and sets rep = -(2^14 y_0 + 2^-15 y_1), a
+// value >= tau (or kF2TauRepMax, see f2_cert_T), so that a key below tau has a negative fold result.  down(v) moves v
+// down by 2^-9 |v| + 2^-24 (more than an fp16 ulp at |v|, normal or subnormal, and than the fp32 rounding of v) and
+// rounds toward zero, i.e. down for v > 0 and up by less than the move for v < 0: down(v) <= v, within 2^-8 |v| + 2^-23.
+// y_0 = x with x = -tau / 2^14 (clamped to +-65504: -inf, idle lanes, gives rep = -65376 x 2^14 and only forced
+// candidates, key -inf, are admitted there; a tau beyond kF2TauRepMax gives rep = kF2TauRepMax) moved down by 2^-9 |x|
+// and rounded toward zero: below x in the fp16 normal range, 0 for |x| < 2^-25 (|tau| < 2^-11), within one subnormal
+// step of x between.  The remainder (x - y_0) 2^29 (> -32, rounded once) goes to the second term: y_1 = down(min(it,
+// 65504)) <= it.  rep - tau stays within 2^-16 |tau| for 1 <= |tau| < 676; it reaches ~2^-11 |tau| for 676 <= |tau| <
+// 2^10 (the remainder is clipped at 65504), ~2^-15 |tau| for 0.1 <= |tau| < 1 (y_0 is an fp16 subnormal there), and is
+// never more than 2^-8 |tau| + 2^-38.  A looser tau_rep only admits more candidates.
+__device__ __forceinline__ unsigned f2_tau16(float tau, float &rep)
+{
+    const float x = __builtin_amdgcn_fmed3f(-tau * (1.0f / kF2TauC[0]), -65504.0f, 65504.0f);
+    float v = __builtin_amdgcn_fmed3f(__builtin_fmaf(__builtin_fabsf(x), -0x1p-9f, x), -65504.0f, 65504.0f);
+    const float y0 = (float)__builtin_amdgcn_cvt_pkrtz(v, v)[0];
+    const float w = __builtin_fmaf(-y0, kF2TauC[0] / kF2TauC[1], x * (kF2TauC[0] / kF2TauC[1]));
+    v = fminf(__builtin_fmaf(__builtin_fabsf(w), -0x1p-9f, w - 0x1p-24f), 65504.0f);
+    const auto y = __builtin_amdgcn_cvt_pkrtz(y0, v);   // y0 is an fp16 value already: converted exactly
+    rep = -__builtin_fmaf(y0, kF2TauC[0], (float)y[1] * kF2TauC[1]);   // rounded once: f2_key_lower covers it
+    return __builtin_bit_cast(unsigned, y);
+}
+
+// A key-space lower bound of the tile's keys from the minimum cmin of its fold results computed against rep: the fp32
+// sum is moved down by more than its rounding, and by 2^-17 |rep| for the share of the MFMA's accumulation error that
+// the threshold term brings (<= 79 x 2^-24 |rep| for the 80 products of a 64-feature block).  Entries store this
+// value (f2_compact drops an entry only when it is above tau) and the threshold list is built from it.
+__device__ __forceinline__ float f2_key_lower(float cmin, float rep)
+{
+    const float s = cmin + rep;
+    return __builtin_fmaf(__builtin_fabsf(s), -0x1p-22f, __builtin_fmaf(__builtin_fabsf(rep), -0x1p-17f, s));
+}
+
+// The threshold a certificate may use for a lane whose masks were taken against tau (or any larger one): the fold
+// applied rep >= min(tau, kF2TauRepMax), and a fold result >= 0 proves key >= rep - 2^-17 |rep| - (the share of the
+// other terms, in f2_slack); t - 2^-17 |t| is increasing in t, so the bound holds with T = min(tau, kF2TauRepMax) in
+// place of rep (2^-16 and the constant take the fp32 rounding of this expression).
+// (64 features keep the subtract: their masks are exact against tau, T = tau, and a tau still at the sentinel dropped
+// nothing -- kF2Full says whether such a lane needs the check at all)
+template <int NH = 1>
+__device__ __forceinline__ float f2_cert_T(float tau)
+{
+    if constexpr (NH != 1) return tau;
+    const float T = fminf(tau, kF2TauRepMax);
+    return __builtin_fmaf(__builtin_fabsf(T), -0x1p-16f, T) - 1e-16f;
+}
+template <int NH = 1>
+__device__ __forceinline__ bool f2_full(float tau) { return NH == 1 || tau < kKnnSentinel; }
 
 // Certificate slack of the second form (dropped candidates had key >= T; true d >= T + |x_i|^2 - slack).  an >= |x_i|,
 // rn >= |x_i| + sqrt(d_k): a candidate with a larger norm than rn is farther than d_k by the triangle inequality, so the
@@ -1656,11 +1777,14 @@ __device__ __forceinline__ void f2_load(F2Ops<NH> &o, const uint8_t *__restrict_
 //     writer), the products are exact in fp32, so |x.x' - h.h'| <= (2^-10 + 2^-22) sum_c |x_c||x'_c| <= 1.0003 x 2^-10
 //     |x||x'| (Cauchy-Schwarz), twice that on the key: 2^-9 an rn, taken as 1.96e-3 (> 1.0003 x 2^-9 = 1.9537e-3);
 //   * fp16 subnormals (|v| < 2^-14): absolute error <= 2^-25 per feature, on the key <= 2 x 2^-25 x sqrt(D) (|x|+|x'|)
-//     <= 4.8e-7 (an + rn) at D <= 64; taken as 6e-7.
+//     <= 4.8e-7 (an + rn) at D <= 64; taken as 6e-7;
+//   * the norm in the fold block (knn_prep_kernel): four fp16 terms, |s - sum| <= 2^-44 s + 2^-40 <= 6e-14 rn^2 + 1e-12.
+//     The fold's longer sum (2 NH x 16 + 16 products) is still covered by the accumulation term above, which carried
+//     the fp32 seed |x_j|^2 before; the threshold's own share of it is taken off tau itself (f2_cert_T).
 __device__ __forceinline__ float f2_slack(float an, float rn, float scale)
 {
     return 2.0f * scale * (4e-5f * an * rn + 1e-5f * rn * rn + 4e-6f * an * an) + 1.96e-3f * an * rn + 6e-7f * (an + rn) +
-           1e-30f;
+           6e-14f * rn * rn + 1e-12f;
 }
 
 // threshold list length of the second form: the fp16 slack needs the M-th smallest tile minimum two ranks further out
@@ -1681,11 +1805,11 @@ __device__ __forceinline__ int f2_mask_row(int p) { return (p & 3) + 8 * ((p & 1
 // M smallest minima of tile PAIRS -- still M groups that each contain a key <= tau); otherwise it only updates `carry`.
 // NH = 2 (64 features): `use` and `ld` are the SAME operand set (two sets of eight fragments next to the sixteen of
 // the queries do not fit the register file at two wavefronts per SIMD), reloaded right after its MFMAs were issued.
-template <int M, bool UPD, bool REC, bool INS, int NH = 1>
+template <int M, bool UPD, bool REC, bool INS, int NH = 1, bool CONV = true, int LEAD = 2>
 __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *__restrict__ rec, int64_t rbase, int t,
-                                        int t_hi, f32x16 &c0, f32x16 &c1, f32x16 &n0, f32x16 &n1, const F2Ops<NH> &use,
-                                        F2Ops<NH> &ld, const f16x8 (&bq)[2][2 * NH], int lane, int hh, bool alive,
-                                        float &carry)
+                                        int t_hi, f32x16 &c0, f32x16 &c1, f32x16 &n0, f32x16 &n1, float &rc, float &rn,
+                                        const F2Ops<NH> &use, F2Ops<NH> &ld, const f16x8 (&bq)[2][2 * NH], int lane,
+                                        int hh, bool alive, float &carry)
 {
 #if defined(DMET_F2_ABL) && DMET_F2_ABL >= 2
     constexpr bool kRec = false;     // cycle-budget experiment (tools/knn_budget2.sh)
@@ -1703,10 +1827,21 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
 #if defined(DMET_F2_SAMEREC)
     f2_load<NH>(ld, rec, rbase + (t & 1), lane, hh);   // experiment: operands always cache-resident
 #else
-    f2_load<NH>(ld, rec, rbase + min(t + 2, t_hi - 1), lane, hh);   // clamped: the last two calls re-read the last tile
+    f2_load<NH>(ld, rec, rbase + min(t + LEAD, t_hi - 1), lane, hh);   // clamped: the last calls re-read the last tile
 #endif
-    n0 = f2_block<NH>(use.a, bq[0], use.c);     // (s_setprio 1 around these was measured: 10 % slower)
-    n1 = f2_block<NH>(use.a, bq[1], use.c);
+    // the fold against the thresholds as they are now (tile t + 1's keys: stale by one update, i.e. larger -- a
+    // superset); v_permlane32_swap hands every lane the two thresholds of its lane pair (query (0, col), (1, col)).
+    // Sweeps that record no masks fold threshold 0: their results are the keys themselves.
+    {
+        unsigned q0 = 0u, q1 = 0u;
+        if (NH == 1 && kRec) {
+            const auto tt = __builtin_amdgcn_permlane32_swap(L.tq, L.tq, false, false);
+            q0 = tt[0]; q1 = tt[1];
+        }
+        n0 = f2_block<NH>(use, bq[0], q0);     // (s_setprio 1 around these was measured: 10 % slower)
+        n1 = f2_block<NH>(use, bq[1], q1);
+        rn = L.rep;
+    }
     // The accumulators stay where the MFMAs left them: lane (col, hh) holds, for candidate rows (e & 3) + 8 (e >> 2) + 4 hh,
     // the keys of query (0, col) in c0 and of query (1, col) in c1 -- 16 keys of each of the two queries the lane PAIR
     // (col, 0), (col, 1) owns.  Every lane reduces both halves it holds (hit mask against the owner's threshold, minimum)
@@ -1717,16 +1852,24 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
     // costs two issue slots and sat between the MFMA results and everything else).
     unsigned mask = 0u;
     if (kRec) {
-        const auto tt = __builtin_amdgcn_permlane32_swap(__float_as_uint(L.tau), __float_as_uint(L.tau), false, false);
-        const float t0 = __uint_as_float(tt[0]), t1 = __uint_as_float(tt[1]);   // thresholds of query (0, col) / (1, col)
-        // Two VALU ops per key: key - tau, then v_alignbit shifts its sign bit into the mask (a NaN key may set a bit:
-        // its exact distance is NaN and never enters the result).  Element e of a half ends up in bit 15 - e.
-        // (v_pk_add_f32 for two rows at once was measured: no gain -- packed fp32 issues at half rate here)
+        // One VALU op per key: the fold result is key - rep, v_alignbit shifts its sign bit into the mask (a -0 would
+        // set a bit: admitted, never dropped).  Element e of a half ends up in bit 15 - e.
+        // (64 features: the keys themselves, key - tau first, thresholds of query (0, col) / (1, col) from the swap)
         unsigned ma = 0u, mb = 0u;
+        if constexpr (NH == 1) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            ma = __builtin_amdgcn_alignbit(ma, __float_as_uint(c0[e] - t0), 31);
-            mb = __builtin_amdgcn_alignbit(mb, __float_as_uint(c1[e] - t1), 31);
+            for (int e = 0; e < 16; ++e) {
+                ma = __builtin_amdgcn_alignbit(ma, __float_as_uint(c0[e]), 31);
+                mb = __builtin_amdgcn_alignbit(mb, __float_as_uint(c1[e]), 31);
+            }
+        } else {
+            const auto tt = __builtin_amdgcn_permlane32_swap(__float_as_uint(L.tau), __float_as_uint(L.tau), false, false);
+            const float t0 = __uint_as_float(tt[0]), t1 = __uint_as_float(tt[1]);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                ma = __builtin_amdgcn_alignbit(ma, __float_as_uint(c0[e] - t0), 31);
+                mb = __builtin_amdgcn_alignbit(mb, __float_as_uint(c1[e] - t1), 31);
+            }
         }
         const auto mm = __builtin_amdgcn_permlane32_swap(ma, mb, false, false);
         // bit 31 - p: p < 16 -> element p of the hh = 0 rows, else element p - 16 of the hh = 1 rows (f2_mask_row)
@@ -1744,6 +1887,7 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
         const auto nn = __builtin_amdgcn_permlane32_swap(__float_as_uint(na), __float_as_uint(nb), false, false);
         tmin = __uint_as_float(nn[0]);
         asm("v_min_f32 %0, %0, %1" : "+v"(tmin) : "v"(__uint_as_float(nn[1])));
+        if (NH == 1 && kRec) tmin = f2_key_lower(tmin, rc);   // back to key space, rounded down (the -inf of a forced row stays)
     }
     if (kRec) {
         // one 8-byte entry per tile and lane, kept only when the mask is non-zero (branch-free append)
@@ -1762,6 +1906,7 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
             for (int p = M - 1; p >= 1; --p) L.tk[p] = __builtin_amdgcn_fmed3f(L.tk[p - 1], v, L.tk[p]);
             asm("v_min_f32 %0, %0, %1" : "+v"(L.tk[0]) : "v"(v));
             if (alive && !L.overflow) L.tau = L.tk[M - 1];
+            if (NH == 1 && kRec && CONV) L.tq = f2_tau16(L.tau, L.rep);   // (every second tile: see f2_sweep)
         } else {
             carry = tmin;
         }
@@ -1784,18 +1929,56 @@ __device__ __forceinline__ void f2_sweep(F2Lane<M> &L, F2Wave &S, const uint8_t 
     if (t_lo >= t_hi) return;
     F2Ops<NH> A, B;
     f2_load<NH>(A, rec, rbase + t_lo, lane, hh);
-    f32x16 c0 = f2_block<NH>(A.a, bq[0], A.c);      // prologue: the first tile's keys
-    f32x16 c1 = f2_block<NH>(A.a, bq[1], A.c);
+    unsigned q0 = 0u, q1 = 0u;
+    if (NH == 1 && REC) {
+        L.tq = f2_tau16(L.tau, L.rep);
+        const auto tt = __builtin_amdgcn_permlane32_swap(L.tq, L.tq, false, false);
+        q0 = tt[0]; q1 = tt[1];
+    }
+    float rc = L.rep, rn;
+    f32x16 c0 = f2_block<NH>(A, bq[0], q0);      // prologue: the first tile's keys
+    f32x16 c1 = f2_block<NH>(A, bq[1], q1);
     f32x16 n0, n1;
     f2_load<NH>(A, rec, rbase + min(t_lo + 1, t_hi - 1), lane, hh);
     float carry = kKnnSentinel;
+    if constexpr (NH == 1 && UPD && REC) {
+        // the main sweep keeps THREE tiles of operands in flight (the fold freed the seed registers): call t issues
+        // tile t + 1's MFMAs and loads tile t + 3.  Six calls per trip: the operand sets rotate with period 3, the key
+        // blocks (c, n) and the threshold conversions with period 2
+        F2Ops<NH> C;
+        f2_load<NH>(B, rec, rbase + min(t_lo + 2, t_hi - 1), lane, hh);
+        for (int t = t_lo; t < t_hi; t += 6) {
+            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t, t_hi, c0, c1, n0, n1, rc, rn, A, C, bq, lane, hh,
+                                                     alive, carry);
+            if (t + 1 >= t_hi) break;
+            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 1, t_hi, n0, n1, c0, c1, rn, rc, B, A, bq, lane,
+                                                    hh, alive, carry);
+            if (t + 2 >= t_hi) break;
+            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t + 2, t_hi, c0, c1, n0, n1, rc, rn, C, B, bq, lane,
+                                                     hh, alive, carry);
+            if (t + 3 >= t_hi) break;
+            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 3, t_hi, n0, n1, c0, c1, rn, rc, A, C, bq, lane,
+                                                    hh, alive, carry);
+            if (t + 4 >= t_hi) break;
+            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t + 4, t_hi, c0, c1, n0, n1, rc, rn, B, A, bq, lane,
+                                                     hh, alive, carry);
+            if (t + 5 >= t_hi) break;
+            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 5, t_hi, n0, n1, c0, c1, rn, rc, C, B, bq, lane,
+                                                    hh, alive, carry);
+        }
+        return;
+    }
     for (int t = t_lo; t < t_hi; t += 2) {
         // every tile inserts its own minimum (INS = true).  Inserting the minimum of tile PAIRS instead (half the
         // v_med3 chains) was tried: the threshold then admits up to 2M tiles, more than the 26 entries a lane can keep
         // -> 3 761 overflowed queries per launch and twice the kernel time
-        f2_tile<M, UPD, REC, true, NH>(L, S, rec, rbase, t, t_hi, c0, c1, n0, n1, A, B, bq, lane, hh, alive, carry);
+        // the fold's threshold is converted after every second tile only (f2_tau16 is ~15 VALU ops): the masks of
+        // the next two tiles are taken against a threshold older by one more update -- larger, a superset
+        f2_tile<M, UPD, REC, true, NH, false>(L, S, rec, rbase, t, t_hi, c0, c1, n0, n1, rc, rn, A, B, bq, lane, hh, alive,
+                                              carry);
         if (t + 1 < t_hi)
-            f2_tile<M, UPD, REC, true, NH>(L, S, rec, rbase, t + 1, t_hi, n0, n1, c0, c1, B, A, bq, lane, hh, alive, carry);
+            f2_tile<M, UPD, REC, true, NH, true>(L, S, rec, rbase, t + 1, t_hi, n0, n1, c0, c1, rn, rc, B, A, bq, lane, hh,
+                                                 alive, carry);
     }
 }
 
@@ -1876,6 +2059,8 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
 #pragma unroll
     for (int p = 0; p < M; ++p) L.tk[p] = kKnnSentinel;
     L.tau = attempt == 0 ? -__builtin_inff() : t_fix;     // first attempt: nothing is recorded before tk is full
+    L.tq = 0u;
+    L.rep = 0.0f;
     L.cnt = 0;
     L.overflow = false;
     {
@@ -2222,21 +2407,22 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
             const float an = __builtin_sqrtf(nx) * 1.000001f;
             const float rn = an + __builtin_sqrtf(fmaxf(kth, 0.0f)) * 1.00002f;
             const float slack = f2_slack(an, rn, NH == 1 ? 1.0f : 1.5f);
-            const bool full = tau < kKnnSentinel;
-            // a query whose own row is outside the fp16 range (or not finite) swept with zero operands: never certified
+            // a query whose own row is outside the fp16 range (or not finite) swept with zero operands: never certified.
+            // Every lane is checked, also one whose tau stayed at the sentinel: the fold drops keys above
+            // kF2TauRepMax whatever tau is (f2_cert_T)
             const bool wideq = !(nx < kF16WideLimit * kF16WideLimit);
-            const bool fail = L.overflow || wideq || (full && !(kth >= 0.0f && tau + nx - slack > kth));
+            const bool fail = L.overflow || wideq || (f2_full<NH>(tau) && !(kth >= 0.0f && f2_cert_T<NH>(tau) + nx - slack > kth));
             // slack-only failures get the second attempt: the smallest threshold that certifies this k-th distance,
-            // nudged up by a few ulps of the largest term so that the same fp32 expression holds for it
+            // nudged up by f2_cert_T's margin and a few ulps of the largest term so that the same fp32 expression holds
             float ts = kth - nx + slack;
-            ts += (__builtin_fabsf(ts) + nx + slack) * 4.8e-7f + 1e-30f;
-            retry = fail && attempt == 0 && !L.overflow && !wideq && kth >= 0.0f && ts + nx - slack > kth &&
+            ts += __builtin_fabsf(ts) * ((NH == 1 ? 0x1p-15f : 0.0f) + 4.8e-7f) + (nx + slack) * 4.8e-7f + (NH == 1 ? 2e-16f : 1e-30f);
+            retry = fail && attempt == 0 && !L.overflow && !wideq && kth >= 0.0f && f2_cert_T<NH>(ts) + nx - slack > kth &&
                     ts < kKnnSentinel;
             if (fail && !retry) {
                 flag_query(a, myq, a.xtile_ptr[pos] + (myq - ev_lo) / a.xtile_queries);
 #ifdef DMET_KNN_WHY
                 a.qflag[myq] = (uint8_t)(1 | (L.overflow ? 2 : 0) | (wideq ? 4 : 0) | (kth < 0.0f ? 8 : 0) | (attempt ? 16 : 0) |
-                                         (!(ts < kKnnSentinel) ? 32 : 0) | (!(ts + nx - slack > kth) ? 64 : 0));
+                                         (!(ts < kKnnSentinel) ? 32 : 0) | (!(f2_cert_T<NH>(ts) + nx - slack > kth) ? 64 : 0));
                 a.dist[(int64_t)myq * k + 0] = tau; a.dist[(int64_t)myq * k + 1] = kth; a.dist[(int64_t)myq * k + 2] = slack; a.dist[(int64_t)myq * k + 3] = (float)L.cnt;
 #endif
             }
@@ -2298,8 +2484,8 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         const float rn = an + __builtin_sqrtf(fmaxf(kth, 0.0f)) * 1.00002f;
         const float slack = f2_slack(an, rn, NH == 1 ? 1.0f : 1.5f);
         const bool wideq = !(nx < kF16WideLimit * kF16WideLimit);
-        const bool fail_a = tau < kKnnSentinel && !(kth >= 0.0f && tau + nx - slack > kth);
-        const bool fail_b = tau_o < kKnnSentinel && !(kth >= 0.0f && tau_o + nx - slack > kth);
+        const bool fail_a = f2_full<NH>(tau) && !(kth >= 0.0f && f2_cert_T<NH>(tau) + nx - slack > kth);
+        const bool fail_b = f2_full<NH>(tau_o) && !(kth >= 0.0f && f2_cert_T<NH>(tau_o) + nx - slack > kth);
         if (L.overflow || of_o != 0 || wideq || fail_a || fail_b)
             flag_query(a, myq, a.xtile_ptr[pos] + (myq - ev_lo) / a.xtile_queries);
     }
