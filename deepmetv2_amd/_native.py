@@ -893,6 +893,75 @@ def gather_max_bwd(g_out: torch.Tensor, arg: torch.Tensor, rev_ptr: torch.Tensor
     return gQ
 
 
+def _i32c(t: torch.Tensor, name: str) -> torch.Tensor:
+    if t.dtype != torch.int32:
+        raise TypeError(f"{name} must be int32, got {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def gather_sum_table(P: torch.Tensor, Q: torch.Tensor, nbr: torch.Tensor, cnt: Optional[torch.Tensor],
+                     mean: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(out[N,H], deg[N] int32): out = deg P + sum of the Q rows listed in nbr (mean: P + that sum / deg), 0 for a row
+    without neighbours.  cnt (radius tables): only the first cnt[i] slots of row i."""
+    dev = _require_device(P, Q, nbr, cnt)
+    L = _lib.load()
+    P = _f32c(P, "P"); Q = _f32c(Q, "Q"); nbr = _i32c(nbr, "nbr")
+    N, H = P.shape
+    k = nbr.shape[1]
+    out = torch.empty((N, H), dtype=torch.float32, device=dev)
+    deg = torch.empty((N,), dtype=torch.int32, device=dev)
+    cp = _i32c(cnt, "cnt").data_ptr() if cnt is not None else None
+    _t = timer.record('gather_sum', dev)
+    with _on(dev):
+        _lib.check(L.dmet_gather_sum_table_f32(P.data_ptr(), Q.data_ptr(), nbr.data_ptr(), cp, N, k, H, int(mean),
+                                               out.data_ptr(), deg.data_ptr(), _stream(dev)),
+                   "dmet_gather_sum_table_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, deg
+
+
+def gather_sum_csr(P: torch.Tensor, Q: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor,
+                   mean: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gather_sum_table over a by-target edge list (rowptr[N+1], src[E] int32)."""
+    dev = _require_device(P, Q, rowptr, src)
+    L = _lib.load()
+    P = _f32c(P, "P"); Q = _f32c(Q, "Q"); rowptr = _i32c(rowptr, "rowptr"); src = _i32c(src, "src")
+    N, H = P.shape
+    out = torch.empty((N, H), dtype=torch.float32, device=dev)
+    deg = torch.empty((N,), dtype=torch.int32, device=dev)
+    _t = timer.record('gather_sum', dev)
+    with _on(dev):
+        _lib.check(L.dmet_gather_sum_csr_f32(P.data_ptr(), Q.data_ptr(), rowptr.data_ptr(), src.data_ptr(), N, H,
+                                             int(mean), out.data_ptr(), deg.data_ptr(), _stream(dev)),
+                   "dmet_gather_sum_csr_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, deg
+
+
+def gather_sum_bwd(g_out: torch.Tensor, deg: torch.Tensor, rev_ptr: torch.Tensor, rev_idx: torch.Tensor,
+                   tgt: Optional[torch.Tensor], k: int, mean: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(gP, gQ) of gather_sum_table / gather_sum_csr.  Tables: tgt None, k the table width and (rev_ptr, rev_idx) =
+    NeighborTable.reverse(); edge lists: (rev_ptr, rev_idx) = EdgeList.by_source() and tgt = EdgeList.tgt (k ignored)."""
+    dev = _require_device(g_out, deg, rev_ptr, rev_idx, tgt)
+    L = _lib.load()
+    g_out = _f32c(g_out, "g_out"); deg = _i32c(deg, "deg")
+    rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_idx = _i32c(rev_idx, "rev_idx")
+    N, H = g_out.shape
+    gPQ = torch.empty((2, N, H), dtype=torch.float32, device=dev)
+    tp = _i32c(tgt, "tgt").data_ptr() if tgt is not None else None
+    _t = timer.record('gather_sum_bwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_gather_sum_bwd_f32(g_out.data_ptr(), deg.data_ptr(), rev_ptr.data_ptr(), rev_idx.data_ptr(),
+                                             tp, N, 0 if tgt is not None else k, H, int(mean), gPQ[0].data_ptr(),
+                                             gPQ[1].data_ptr(), _stream(dev)),
+                   "dmet_gather_sum_bwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return gPQ[0], gPQ[1]
+
+
 def reverse_index(keys: torch.Tensor, num_keys: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Stable sort of positions by int32 key: rev_ptr[num_keys+1] int32, rev_pos[M] int32 (see include/dmet.h)."""
     dev = _require_device(keys)

@@ -13,7 +13,7 @@ OBJ_DIR = os.path.join(CSRC, "_obj")
 LIB_PATH = os.path.join(PKG_DIR, "libdmet_hip.so")
 SOURCES = ["knn.hip", "edgeconv.hip", "edgemlp.hip", "misc.hip", "dense.hip", "encoder.hip", "norm.hip", "edgeconv_bwd.hip",
            "head.hip", "finalize.hip", "pool.hip",
-           "edgemlp_f32.hip", "edgemlp_bf16.hip"]
+           "edgemlp_f32.hip", "edgemlp_bf16.hip", "edgeconv_sum.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "nls_body.h"), os.path.join(CSRC, "edgemlp_fused.h"), os.path.join(PKG_DIR, "..", "include", "dmet.h")]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=off", "-Wall",

@@ -204,6 +204,72 @@ class _EdgeConvLinearMax(torch.autograd.Function):
         return gx, gW, gb, None, None, None
 
 
+def _linear_node_backward(ctx, x, weight, gP, gQ, g_pass):
+    """(gx, gW, gb) of the split dense layer P = x (W1-W2)^T + b, Q = x W2^T from gP and gQ: the fused node-level kernel
+    for H = 32 -> 32 (csrc/edgeconv_bwd.hip, gP in the place of g_out, no arg), else addmm / xty."""
+    H = x.shape[1]
+    need = ctx.needs_input_grad
+    if H == 32 and tuple(weight.shape) == (32, 64):
+        gx, gW, gb = _native.edgeconv_linear_bwd(x, weight.detach(), gP, None, gQ, want_bias=ctx.has_bias, g_add=g_pass)
+        return gx if need[0] else None, gW if need[1] else None, gb if (ctx.has_bias and need[2]) else None
+    Wd = weight[:, :H] - weight[:, H:]
+    W2 = weight[:, H:]
+    gx = gW = gb = None
+    if need[0]:
+        gx = torch.addmm(gP @ Wd, gQ, W2)
+        if g_pass is not None:
+            gx = gx + g_pass
+    if need[1]:
+        # a node whose gP and gQ rows are zero (no edge reads it) adds nothing, not 0 * NaN
+        idle = ((gP != 0).any(1) | (gQ != 0).any(1)).logical_not()
+        xw = x.masked_fill(idle.view(-1, 1), 0.0)
+        gWd = _native.xty(gP, xw)
+        gW2 = _native.xty(gQ, xw)
+        gW = torch.cat([gWd, gW2 - gWd], dim=1)
+    if ctx.has_bias and need[2]:
+        gb = gP.sum(0)
+    return gx, gW, gb
+
+
+class _EdgeConvLinearSum(torch.autograd.Function):
+    """out[i] = sum_s (W.[x_i || x_j - x_i] + b) over the valid sources j of i (aggr 'add' / 'sum'), or that sum over
+    their number (aggr 'mean'), through P = x.(W1-W2)^T + b, Q = x.W2^T: out_i = deg_i P_i + sum_j Q_j, or
+    P_i + sum_j Q_j / deg_i; 0 without in-edges (R3).  One gather of Q rows per edge (csrc/edgeconv_sum.hip), over a
+    neighbour table or a by-target edge list: no [E, 2F] edge features, no per-edge messages.  The backward walks a
+    by-source index (NeighborTable.reverse() / EdgeList.by_source()) and hands gP, gQ to the node-level backward of
+    _EdgeConvLinearMax.  No host sync, except in the backward over a counted radius table: its reverse index sorts the
+    valid slots only and learns their number with `torch.nonzero`.  `once_differentiable`: DMET_EDGE_LINEAR_SUM=0 gives
+    the generic route, e.g. for double backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, graph, mean: bool, passthrough: bool = False):
+        P, Q = _native.node_linear_split(x, weight, bias)
+        if isinstance(graph, NeighborTable):
+            graph.join()    # a table still being built on a side stream: the dense layer above ran beside it
+            out, deg = _native.gather_sum_table(P, Q, graph.nbr, graph.cnt, mean)
+        else:
+            out, deg = _native.gather_sum_csr(P, Q, graph.rowptr, graph.src, mean)
+        ctx.save_for_backward(x, weight, deg)
+        ctx.graph, ctx.mean, ctx.has_bias = graph, mean, bias is not None
+        if passthrough:
+            return out, x.view_as(x)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_pass=None):
+        x, weight, deg = ctx.saved_tensors
+        graph = ctx.graph
+        if isinstance(graph, NeighborTable):
+            rev_ptr, rev_pos = graph.reverse()
+            gP, gQ = _native.gather_sum_bwd(g_out, deg, rev_ptr, rev_pos, None, graph.k, ctx.mean)
+        else:
+            srcptr, srcperm = graph.by_source()
+            gP, gQ = _native.gather_sum_bwd(g_out, deg, srcptr, srcperm, graph.tgt, 0, ctx.mean)
+        gx, gW, gb = _linear_node_backward(ctx, x, weight, gP, gQ, g_pass)
+        return gx, gW, gb, None, None, None
+
+
 def _as_mlp2(nn_module):
     """(lin1, lin2, act2, bn) when `nn` is Sequential(Linear, ELU, Linear[, ELU][, BatchNorm1d]) (ELU alpha = 1): the
     edge MLP of model/dynamic_reduction_network.py:59-70, with or without its trailing BatchNorm (bn = None); else None."""
@@ -383,7 +449,10 @@ class EdgeConv(torch.nn.Module):
     [2,E] edge index.
 
     Fused routes by ``nn``: a single ``Linear(2F, F')`` with max aggregation (F, F' in {32, 64}) runs through the
-    per-node split (csrc/edgeconv.hip); ``Sequential(Linear(2F, H1), ELU, Linear(H1, H2)[, ELU][, BatchNorm1d(H2)])``
+    per-node split (csrc/edgeconv.hip); with add / sum / mean aggregation the same ``Linear`` runs through the split and a
+    gather-sum over any graph, forward and backward, in fp32 when no 16 bits and no autocast are requested
+    (csrc/edgeconv_sum.hip; no host sync over a table, except the one of a counted radius table's reverse index in the
+    backward; ``DMET_EDGE_LINEAR_SUM=0`` restores the generic route, e.g. for double backward); ``Sequential(Linear(2F, H1), ELU, Linear(H1, H2)[, ELU][, BatchNorm1d(H2)])``
     (ELU alpha 1, fp32, BatchNorm momentum not None) runs fused in fp32 over any graph, forward and backward, for
     H2 in {16, 32, 64, 128}, H1 <= min(192, 2 H2), F <= 128 (csrc/edgemlp_f32.hip; ``DMET_EDGE_MLP_F32=0`` restores
     the generic route, e.g. for double backward), or on the bf16 matrix cores when bf16 is requested (autocast or
@@ -433,6 +502,10 @@ class EdgeConv(torch.nn.Module):
             if table.cnt is not None:
                 self._take_prebuilt_pq(x, table)
             return _EdgeConvLinearMax.apply(x, lin.weight, lin.bias, table, self._use_bf16(lin, table), passthrough)
+        lin = self._linear_sum(x)
+        if lin is not None and table.k <= (1024 if table.cnt is not None else 64):   # dmet_gather_sum_table_f32
+            # add / mean over the table itself: no edge list, no host sync in the forward
+            return _EdgeConvLinearSum.apply(x, lin.weight, lin.bias, table, self.aggr == "mean", passthrough)
         table.join()
         mlp = _as_mlp2(self.nn) if self.aggr in ("max", "add", "sum") else None
         if (mlp is not None and table.cnt is None and self._wants_bf16()
@@ -467,12 +540,29 @@ class EdgeConv(torch.nn.Module):
     def _forward_edge_list(self, x: torch.Tensor, edges: EdgeList) -> torch.Tensor:
         """The layer over a grouped edge list: the first fused route that takes the call (bf16, fp16, fp32), else the
         generic one."""
+        lin = self._linear_sum(x)
+        if lin is not None:
+            return _EdgeConvLinearSum.apply(x, lin.weight, lin.bias, edges, self.aggr == "mean")
         out = self._forward_edge_mlp_bf16(x, edges)
         if out is None:
             out = self._forward_edge_mlp_f16(x, edges)
         if out is None:
             out = self._forward_edge_mlp_f32(x, edges)
         return out if out is not None else self._forward_edges(x, edges)
+
+    def _linear_sum(self, x: torch.Tensor) -> Optional[torch.nn.Linear]:
+        """The Linear of the fused add / sum / mean route (_EdgeConvLinearSum), or None when this call keeps its old route:
+        aggr 'max', another `nn`, x not fp32 on the GPU, 16 bits or autocast requested, DMET_EDGE_LINEAR_SUM=0."""
+        if self.aggr not in ("add", "sum", "mean") or os.environ.get("DMET_EDGE_LINEAR_SUM", "1") == "0":
+            return None
+        if not x.is_cuda or x.dtype != torch.float32:
+            return None
+        if self.compute_dtype not in (None, torch.float32) or torch.is_autocast_enabled():
+            return None
+        lin = _as_fusable_linear(self.nn)
+        if lin is None or lin.in_features != 2 * x.shape[1] or (lin.bias is not None and lin.bias.dtype != torch.float32):
+            return None
+        return lin
 
     def _use_bf16(self, lin: torch.nn.Linear, table: NeighborTable) -> bool:
         dt = self.compute_dtype

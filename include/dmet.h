@@ -399,6 +399,35 @@ int dmet_gather_max_bwd_j16_sliced_f32(const float *g_out, const uint16_t *argj,
 int dmet_edgeconv_linear_bwd_sliced_f32(const float *x, const float *W, const float *g_out, const void *arg,
                                         int arg_is_j16, const float *gQs, const float *g_add, int64_t N, int H, float *gx,
                                         float *gW, float *gb, void *ws, size_t ws_bytes, dmet_stream_t stream);
+/* ---- K2+K3 fused: EdgeConv with nn = Linear(2*Hin -> Hout), aggr = 'add' / 'sum' / 'mean', any graph -----------
+ * replaces torch_geometric.nn.EdgeConv(nn=Sequential(Linear(2H,H')), aggr='add'|'mean').forward
+ *   the layer constructed at model/graph_met_network.py:36-38 with aggr switched from 'max'.
+ * With P, Q from dmet_node_linear_split_f32 and deg[i] the number of valid in-edges of node i:
+ *   add / sum (mean = 0): out[i] = deg[i] P[i] + sum_j Q[j]
+ *   mean      (mean = 1): out[i] = P[i] + (sum_j Q[j]) / deg[i]
+ *   deg[i] = 0: out[i] = 0 exactly, also where P[i] is not finite (R3).
+ * sum_j runs in ascending slot / edge order in fp32, no float atomics: a table and the by-target edge list of the same
+ * graph give identical bits, and every run gives the same bits.  deg[N] int32 is written for the backward.
+ * H = Hout in {32, 64} (Hin in {32, 64} is dmet_node_linear_split_f32's); P, Q, out 16-B aligned.
+ * Table form: nbr[N, k] int32, -1 = no neighbour; cnt NULL: k <= DMET_MAX_K; cnt[N] given (radius tables): only the
+ * first cnt[i] slots of row i are read, k <= 1024 (radius_graph with loop=False is max_num_neighbors + 1 = 256 wide).  CSR form: rowptr[N+1], src[E] grouped by target (see K2 / K3
+ * un-fused below), any in-degree; src may be NULL when E = 0. */
+int dmet_gather_sum_table_f32(const float *P, const float *Q, const int32_t *nbr, const int32_t *cnt, int64_t N, int k,
+                              int H, int mean, float *out, int32_t *deg, dmet_stream_t stream);
+int dmet_gather_sum_csr_f32(const float *P, const float *Q, const int32_t *rowptr, const int32_t *src, int64_t N, int H,
+                            int mean, float *out, int32_t *deg, dmet_stream_t stream);
+/* Backward of the two entries above, w.r.t. P and Q (g_out[N,H], deg from the forward):
+ *   gP[i] = deg[i] g_out[i] (add) or [deg[i] > 0] g_out[i] (mean);  0 where deg[i] = 0 (R3)
+ *   gQ[j] = sum over the edges j -> i of s_i g_out[i],  s_i = 1 (add) or 1 / deg[i] (mean)
+ * walked through a by-source index rev_ptr[N+1], rev_idx[] in ascending order (deterministic, no float atomics):
+ *   k >= 1 (table): rev_idx = table positions i*k+s of NeighborTable.reverse() (dmet_reverse_index of nbr), k <= 1024,
+ *                   tgt unused;
+ *   k == 0 (CSR):   rev_idx = edge positions of dmet_reverse_index(src), the target of entry t is tgt[rev_idx[t]]
+ *                   (tgt may be NULL when E = 0).
+ * gx, gW, gb follow from gP, gQ through dmet_edgeconv_linear_bwd_f32 with g_out = gP and arg = NULL (H = 32). */
+int dmet_gather_sum_bwd_f32(const float *g_out, const int32_t *deg, const int32_t *rev_ptr, const int32_t *rev_idx,
+                            const int32_t *tgt, int64_t N, int k, int H, int mean, float *gP, float *gQ,
+                            dmet_stream_t stream);
 /* Reverse index: a stable sort of the positions 0..M-1 of an int32 key array by key value.
  *   rev_ptr[num_keys+1]: rev_pos[rev_ptr[j] .. rev_ptr[j+1]-1] = the positions holding key j, ascending.
  * Keys outside [0, num_keys) (the -1 "no neighbour" entries) sort last and are not indexed.
