@@ -40,6 +40,9 @@ SIGNATURES = {
     "dmet_radius_workspace_bytes": (_sz, [_i64]),
     "dmet_radius_windowed_f32": (_i, [_vp, _vp, _i, _i64, _i, _f, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dmet_radius_windowed_local_f32": (_i, [_vp, _vp, _i, _i64, _i, _f, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "dmet_radius_periodic_f32": (_i, [_vp, _vp, _i, _i64, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dmet_radius_windowed_periodic_f32": (_i, [_vp, _vp, _i, _i64, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz,
+                                               _vp]),
     "dmet_edgeconv_linear_workspace_bytes": (_sz, [_i64, _i]),
     "dmet_edgeconv_linear_max_fwd_f32": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dmet_edgeconv_fused_lds_f32": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -314,6 +314,51 @@ def radius(x: torch.Tensor, ptr: torch.Tensor, r: float, max_nbr: int, skip_self
     return nbr, cnt
 
 
+def radius_periodic(x: torch.Tensor, ptr: torch.Tensor, r: float, max_nbr: int, period, skip_self: bool = False,
+                    pad: bool = True, local: bool = False, int32_rows: bool = True):
+    """radius() with periodic coordinates: period = D floats, period[c] > 0 the circumference of coordinate c, 0 a plain
+    coordinate (dmet_radius_periodic_f32 / dmet_radius_windowed_periodic_f32).  Same outputs as radius().  The window
+    runs on coordinate 0, so period[0] > 0 takes the all-pairs form (rows16 = None, as RADIUS_FORM == "sweep" does)."""
+    import ctypes
+    dev = _require_device(x, ptr)
+    L = _lib.load()
+    x = _f32c(x.detach(), "x")
+    N, D = x.shape
+    B = ptr.numel() - 1
+    if len(period) != D:
+        raise ValueError(f"period has {len(period)} entries for {D} coordinates")
+    per = (ctypes.c_float * D)(*[float(p) for p in period])    # host array, read by the C entry before it returns
+    per_p = ctypes.cast(per, ctypes.c_void_p)
+    windowed = RADIUS_FORM != "sweep" and per[0] == 0.0
+    if local and windowed:
+        stride16 = (max_nbr + 7) // 8 * 8
+        nbr = None if (not int32_rows and not pad) else torch.empty((N, max_nbr), dtype=torch.int32, device=dev)
+        cnt = torch.empty((N,), dtype=torch.int32, device=dev)
+        rows16 = torch.empty((N, stride16), dtype=torch.int16, device=dev)
+        ws = _ws(L.dmet_radius_workspace_bytes(N), dev)
+        with _on(dev):
+            _lib.check(L.dmet_radius_windowed_periodic_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr,
+                                                           1 if skip_self else 0, 1 if pad else 0, per_p,
+                                                           nbr.data_ptr() if nbr is not None else None, cnt.data_ptr(),
+                                                           rows16.data_ptr(), stride16, ws.data_ptr(), ws.numel(),
+                                                           _stream(dev)), "dmet_radius_windowed_periodic_f32")
+        return nbr, cnt, rows16
+    nbr = torch.empty((N, max_nbr), dtype=torch.int32, device=dev)
+    cnt = torch.empty((N,), dtype=torch.int32, device=dev)
+    with _on(dev):
+        if windowed:
+            ws = _ws(L.dmet_radius_workspace_bytes(N), dev)
+            _lib.check(L.dmet_radius_windowed_periodic_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr,
+                                                           1 if skip_self else 0, 1 if pad else 0, per_p,
+                                                           nbr.data_ptr(), cnt.data_ptr(), None, 0, ws.data_ptr(),
+                                                           ws.numel(), _stream(dev)), "dmet_radius_windowed_periodic_f32")
+        else:                            # all pairs of an event
+            _lib.check(L.dmet_radius_periodic_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr,
+                                                  1 if skip_self else 0, 1 if pad else 0, per_p, nbr.data_ptr(),
+                                                  cnt.data_ptr(), _stream(dev)), "dmet_radius_periodic_f32")
+    return (nbr, cnt, None) if local else (nbr, cnt)
+
+
 # ---- K2+K3 fused -----------------------------------------------------------------------------------------------
 def node_linear_split(x: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor],
                       sliced: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:

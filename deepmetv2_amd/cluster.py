@@ -6,7 +6,10 @@ model/dynamic_reduction_network.py:86,94 (knn_graph); train.py:48, evaluate.py:8
 """
 from __future__ import annotations
 
+import math
+import numbers
 import os
+import struct
 from typing import Optional
 
 import torch
@@ -120,14 +123,53 @@ def knn(x: torch.Tensor, y: torch.Tensor, k: int, batch_x: Optional[torch.Tensor
     return table.edge_index("target_to_source")
 
 
+def _check_period(period, D: int) -> Optional[list]:
+    """radius_graph's `period`: None, or D entries each None / 0 (a plain coordinate) or a positive finite number (the
+    circumference of a periodic coordinate, rounded to fp32).  Returns the D fp32-representable floats, or None when no
+    coordinate is periodic (the plain build then runs exactly as without the keyword)."""
+    if period is None:
+        return None
+    if isinstance(period, (str, bytes)) or not isinstance(period, (list, tuple)):
+        raise TypeError(f"period must be None or a list / tuple of {D} entries, got {type(period).__name__}")
+    if len(period) != D:
+        raise ValueError(f"period has {len(period)} entries, x has {D} coordinates")
+    out = []
+    for c, p in enumerate(period):
+        if p is None:
+            out.append(0.0)
+            continue
+        if isinstance(p, bool) or not isinstance(p, numbers.Real):
+            raise TypeError(f"period[{c}] must be None, 0 or a positive number, got {p!r}")
+        v = float(p)
+        if v == 0.0:
+            out.append(0.0)
+            continue
+        try:
+            v32 = struct.unpack("f", struct.pack("f", v))[0] if math.isfinite(v) else v
+        except OverflowError:       # beyond the fp32 range
+            v32 = math.inf
+        if not (v > 0.0 and math.isfinite(v32) and v32 > 0.0):
+            raise ValueError(f"period[{c}]={p!r} is not 0 or a positive finite number (in fp32)")
+        out.append(v32)
+    return out if any(v > 0.0 for v in out) else None
+
+
 def radius_table(x: torch.Tensor, r: float, batch: Optional[torch.Tensor] = None, loop: bool = False,
-                 max_num_neighbors: int = 32, num_events: Optional[int] = None, int32_rows: Optional[bool] = None) -> NeighborTable:
+                 max_num_neighbors: int = 32, num_events: Optional[int] = None, int32_rows: Optional[bool] = None,
+                 period=None) -> NeighborTable:
     """The radius graph as a NeighborTable.  int32_rows=False: only the event-local uint16 rows are written (what the
     fused EdgeConv reads on events of at most 65534 nodes); `.nbr` is expanded from them if somebody asks.  None: False
-    when the caller registered the batch's largest event (register_batch(max_nodes=) <= 65534), else True."""
+    when the caller registered the batch's largest event (register_batch(max_nodes=) <= 65534), else True.
+
+    period: None (torch_cluster's plain distance), or one entry per coordinate: None / 0 for a plain coordinate, or the
+    circumference of a periodic one, e.g. [None, 2 * math.pi] for (eta, phi) -- phi = +3.1 and -3.1 are then 0.08
+    apart, not 6.2.  The periodic difference is min(|d|, L - |d|) in fp32 (include/dmet.h), the circular distance as
+    long as every value of a periodic coordinate lies within one period (atan2 output does).  The build is windowed on
+    coordinate 0: put a periodic coordinate first ([phi, eta]) and the slower all-pairs build runs."""
     x = _check_x(x)
     if x.shape[1] > 8:
         raise ValueError("radius_graph supports up to 8 coordinates")
+    per = _check_period(period, x.shape[1])
     # upstream's loop=False: search max_num_neighbors + 1 and drop the node itself (done inside the kernel)
     m = max_num_neighbors if loop else max_num_neighbors + 1
     info = batch_info(batch, x.shape[0], x.device, num_events)
@@ -135,7 +177,11 @@ def radius_table(x: torch.Tensor, r: float, batch: Optional[torch.Tensor] = None
     if int32_rows is None:
         int32_rows = not (info.max_nodes is not None and info.max_nodes <= 65534
                           and os.environ.get("DMET_RADIUS_INT32", "lazy") == "lazy")
-    nbr, _cnt, rows16 = _native.radius(x, info.ptr, r, m, skip_self=not loop, pad=False, local=True, int32_rows=int32_rows)
+    if per is None:
+        nbr, _cnt, rows16 = _native.radius(x, info.ptr, r, m, skip_self=not loop, pad=False, local=True, int32_rows=int32_rows)
+    else:
+        nbr, _cnt, rows16 = _native.radius_periodic(x, info.ptr, r, m, per, skip_self=not loop, pad=False, local=True,
+                                                    int32_rows=int32_rows)
     # with self loops every node finds at least itself (the cap counts hits in index order, but a full row is not empty)
     return NeighborTable(nbr, info.ptr, dense=False, max_nodes=info.max_nodes, cnt=_cnt, nonempty=bool(loop),
                          rows16=rows16, shape=(x.shape[0], m))
@@ -143,9 +189,11 @@ def radius_table(x: torch.Tensor, r: float, batch: Optional[torch.Tensor] = None
 
 def radius_graph(x: torch.Tensor, r: float, batch: Optional[torch.Tensor] = None, loop: bool = False,
                  max_num_neighbors: int = 32, flow: str = "source_to_target", num_workers: int = 1,
-                 batch_size: Optional[int] = None) -> torch.Tensor:
-    """torch_cluster.radius_graph (train.py:48 passes r=0.4, loop=True, max_num_neighbors=255)."""
+                 batch_size: Optional[int] = None, period=None) -> torch.Tensor:
+    """torch_cluster.radius_graph (train.py:48 passes r=0.4, loop=True, max_num_neighbors=255).  period: periodic
+    coordinates, see radius_table (None: torch_cluster's behaviour)."""
     if flow not in ("source_to_target", "target_to_source"):
         raise ValueError(f"flow must be 'source_to_target' or 'target_to_source', got {flow!r}")
     # the [2,E] view is cut from the int32 table: have the build write it (radius_table alone leaves it out when it can)
-    return radius_table(x, r, batch, loop, max_num_neighbors, batch_size, int32_rows=True).edge_index(flow)
+    return radius_table(x, r, batch, loop, max_num_neighbors, batch_size, int32_rows=True,
+                        period=period).edge_index(flow)

@@ -2930,12 +2930,36 @@ int dispatch_k(const float *x, const int64_t *ptr, int B, int64_t N, int D, int 
 // `skip_self` reproduces upstream's loop=False: the search limit counts the node itself, the node is not stored.
 constexpr int kRadTile = 64;   // candidates per LDS tile and wavefront
 
-template <int DP>
+// Periodic coordinates (radius_graph(..., period=)): L[c] is the circumference of coordinate c, passed to the kernel BY
+// VALUE (a captured graph replays the periods of its capture).  The host turns "not periodic" into L = +inf.
+// The contract wraps the fp32 difference d as  a = |d|;  a = (a > L/2) ? L - a : a.  The kernels form the same value
+// as  min(|d|, L - |d|):  for a > L/2, L - a < a so fp32(L - a) <= a; for a <= L/2, L - a >= L/2 >= a so fp32(L - a) >= a
+// (rounding is monotone, L/2 is exact); NaN stays NaN, |d| = inf gives L - inf = -inf.  With L = +inf the result is
+// |d| for every d (inf - inf = NaN loses to |d| = inf in min), so a plain coordinate keeps its bits.
+struct RadPeriod { float L[8]; };
+
+template <bool PER>
+__device__ __forceinline__ f2 rad_wrap(f2 df, float L)
+{
+    if (!PER) return df;
+    const float ax = fabsf(df.x), ay = fabsf(df.y);
+    return f2{fminf(ax, L - ax), fminf(ay, L - ay)};
+}
+
+// the periods ride as an optional trailing kernel argument: an empty pack is the plain kernel (same arguments, same
+// code as without periods), Per = RadPeriod wraps every coordinate c with L[c]
+__device__ __forceinline__ RadPeriod rad_periods() { return RadPeriod{}; }
+__device__ __forceinline__ RadPeriod rad_periods(const RadPeriod &p) { return p; }
+
+template <int DP, typename... Per>
 __global__ __launch_bounds__(kWave * 4) void radius_kernel(const float *__restrict__ x,
                                                             const int64_t *__restrict__ ptr, int B, int64_t N, int D,
                                                             float r2, int max_nbr, int skip_self,
-                                                            int32_t *__restrict__ nbr, int32_t *__restrict__ cntout)
+                                                            int32_t *__restrict__ nbr, int32_t *__restrict__ cntout,
+                                                            Per... per_arg)
 {
+    constexpr bool PER = sizeof...(Per) > 0;
+    const RadPeriod per = rad_periods(per_arg...);
     __shared__ f2 tile_all[4][(kRadTile / 2) * DP];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     f2 *tile = tile_all[wv];
@@ -2977,7 +3001,7 @@ __global__ __launch_bounds__(kWave * 4) void radius_kernel(const float *__restri
             f2 acc = {0.0f, 0.0f};
 #pragma unroll
             for (int c = 0; c < DP; ++c) {
-                const f2 df = tile[(cc >> 1) * DP + c] - q[c];
+                const f2 df = rad_wrap<PER>(tile[(cc >> 1) * DP + c] - q[c], per.L[c]);
                 acc = __builtin_elementwise_fma(df, df, acc);
             }
             if (cc < 32) {
@@ -3075,15 +3099,20 @@ __global__ __launch_bounds__(kRadBins) void radius_order_kernel(const float *__r
 
 constexpr int kRadQueue = 128;   // pending candidate ids per wavefront (a compaction step adds at most 64)
 
-template <int DP>
+// Per = RadPeriod wraps coordinates 1 .. DP-1 with L[c]; coordinate 0 must be plain (the window is not wrap-aware).
+// The window stays exact: the coordinate-0 term is the first of the chain and the later terms are >= 0 or NaN.
+template <int DP, typename... Per>
 __global__ __launch_bounds__(kWave * 4) void radius_window_kernel(const float *__restrict__ x,
                                                                    const int64_t *__restrict__ ptr, int B, int64_t N,
                                                                    int D, float r2, int max_nbr, int skip_self,
                                                                    const int32_t *__restrict__ order,
                                                                    int32_t *__restrict__ nbr,
                                                                    int32_t *__restrict__ cntout,
-                                                                   uint16_t *__restrict__ nbr16, int stride16)
+                                                                   uint16_t *__restrict__ nbr16, int stride16,
+                                                                   Per... per_arg)
 {
+    constexpr bool PER = sizeof...(Per) > 0;
+    const RadPeriod per = rad_periods(per_arg...);
     __shared__ f2 tile_all[4][(kRadTile / 2) * DP];
     __shared__ int queue_all[4][kRadQueue];
     // hits leave the lane through 16-byte staging slots (4 int32 ids / 8 uint16 ids) and reach memory as one 16-byte
@@ -3153,7 +3182,9 @@ __global__ __launch_bounds__(kWave * 4) void radius_window_kernel(const float *_
             f2 acc = {0.0f, 0.0f};
 #pragma unroll
             for (int c = 0; c < DP; ++c) {
-                const f2 df = tile[(cc >> 1) * DP + c] - q[c];
+                // coordinate 0 is never periodic here (it is the window's coordinate)
+                const f2 d = tile[(cc >> 1) * DP + c] - q[c];
+                const f2 df = (c > 0) ? rad_wrap<PER>(d, per.L[c]) : d;
                 acc = __builtin_elementwise_fma(df, df, acc);
             }
             if (cc < 32) {
@@ -3366,8 +3397,21 @@ extern "C" int dmet_knn_fallback_stats(const void *ws, int64_t N, int B, int D, 
     return 0;
 }
 
+template <int DP>
+static void launch_radius(int64_t blocks, hipStream_t st, const float *x, const int64_t *ptr, int B, int64_t N, int D,
+                          float r2, int max_nbr, int skip_self, int32_t *nbr, int32_t *cnt, const RadPeriod *per)
+{
+    if (per)
+        hipLaunchKernelGGL((radius_kernel<DP, RadPeriod>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr, B, N,
+                           D, r2, max_nbr, skip_self, nbr, cnt, *per);
+    else
+        hipLaunchKernelGGL((radius_kernel<DP>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr, B, N, D, r2,
+                           max_nbr, skip_self, nbr, cnt);
+}
+
 static int radius_impl(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r, int max_nbr,
-                       int skip_self, bool fill, int32_t *nbr, int32_t *cnt, dmet_stream_t stream)
+                       int skip_self, bool fill, int32_t *nbr, int32_t *cnt, dmet_stream_t stream,
+                       const RadPeriod *per = nullptr)
 {
     DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647, "dmet_radius_f32: N out of range");
     DMET_REQUIRE(D >= 1 && D <= 8, "dmet_radius_f32: D=%d not in [1,8]", D);
@@ -3384,14 +3428,11 @@ static int radius_impl(const float *x, const int64_t *ptr, int B, int64_t N, int
         if (me != hipSuccess) return hip_fail(me, "hipMemsetAsync(nbr)");
     }
     if (D <= 2)
-        hipLaunchKernelGGL((radius_kernel<2>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr, B, N, D, r2,
-                           max_nbr, skip_self, nbr, cnt);
+        launch_radius<2>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, nbr, cnt, per);
     else if (D <= 4)
-        hipLaunchKernelGGL((radius_kernel<4>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr, B, N, D, r2,
-                           max_nbr, skip_self, nbr, cnt);
+        launch_radius<4>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, nbr, cnt, per);
     else
-        hipLaunchKernelGGL((radius_kernel<8>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr, B, N, D, r2,
-                           max_nbr, skip_self, nbr, cnt);
+        launch_radius<8>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, nbr, cnt, per);
     DMET_LAUNCH_CHECK("radius_kernel");
     return 0;
 }
@@ -3413,10 +3454,22 @@ extern "C" size_t dmet_radius_workspace_bytes(int64_t N)
     return N > 0 ? sizeof(int32_t) * (size_t)N + 512 : 0;
 }
 
-extern "C" int dmet_radius_windowed_local_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r,
-                                              int max_nbr, int skip_self, int fill, int32_t *nbr, int32_t *cnt,
-                                              uint16_t *nbr16, int stride16, void *ws, size_t ws_bytes,
-                                              dmet_stream_t stream)
+template <int DP>
+static void launch_radius_window(int64_t blocks, hipStream_t st, const float *x, const int64_t *ptr, int B, int64_t N,
+                                 int D, float r2, int max_nbr, int skip_self, const int32_t *order, int32_t *nbr,
+                                 int32_t *cnt, uint16_t *nbr16, int stride16, const RadPeriod *per)
+{
+    if (per)
+        hipLaunchKernelGGL((radius_window_kernel<DP, RadPeriod>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr,
+                           B, N, D, r2, max_nbr, skip_self, order, nbr, cnt, nbr16, stride16, *per);
+    else
+        hipLaunchKernelGGL((radius_window_kernel<DP>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr, B, N, D,
+                           r2, max_nbr, skip_self, order, nbr, cnt, nbr16, stride16);
+}
+
+static int radius_windowed_impl(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r, int max_nbr,
+                                int skip_self, int fill, int32_t *nbr, int32_t *cnt, uint16_t *nbr16, int stride16,
+                                void *ws, size_t ws_bytes, dmet_stream_t stream, const RadPeriod *per)
 {
     DMET_REQUIRE(!nbr16 || (stride16 >= max_nbr && stride16 % 8 == 0 && aligned16(nbr16)),
                  "dmet_radius_windowed_local_f32: nbr16 rows need a 16-byte aligned stride of >= max_nbr ids (stride16=%d)",
@@ -3440,16 +3493,22 @@ extern "C" int dmet_radius_windowed_local_f32(const float *x, const int64_t *ptr
     hipLaunchKernelGGL(radius_order_kernel, dim3((unsigned)B), dim3(kRadBins), 0, st, x, ptr, B, D, order);
     DMET_LAUNCH_CHECK("radius_order_kernel");
     if (D <= 2)
-        hipLaunchKernelGGL((radius_window_kernel<2>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr, B, N, D, r2,
-                           max_nbr, skip_self, order, nbr, cnt, nbr16, stride16);
+        launch_radius_window<2>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, order, nbr, cnt, nbr16, stride16, per);
     else if (D <= 4)
-        hipLaunchKernelGGL((radius_window_kernel<4>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr, B, N, D, r2,
-                           max_nbr, skip_self, order, nbr, cnt, nbr16, stride16);
+        launch_radius_window<4>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, order, nbr, cnt, nbr16, stride16, per);
     else
-        hipLaunchKernelGGL((radius_window_kernel<8>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr, B, N, D, r2,
-                           max_nbr, skip_self, order, nbr, cnt, nbr16, stride16);
+        launch_radius_window<8>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, order, nbr, cnt, nbr16, stride16, per);
     DMET_LAUNCH_CHECK("radius_window_kernel");
     return 0;
+}
+
+extern "C" int dmet_radius_windowed_local_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r,
+                                              int max_nbr, int skip_self, int fill, int32_t *nbr, int32_t *cnt,
+                                              uint16_t *nbr16, int stride16, void *ws, size_t ws_bytes,
+                                              dmet_stream_t stream)
+{
+    return radius_windowed_impl(x, ptr, B, N, D, r, max_nbr, skip_self, fill, nbr, cnt, nbr16, stride16, ws, ws_bytes,
+                                stream, nullptr);
 }
 
 extern "C" int dmet_radius_windowed_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r,
@@ -3458,4 +3517,49 @@ extern "C" int dmet_radius_windowed_f32(const float *x, const int64_t *ptr, int 
 {
     return dmet_radius_windowed_local_f32(x, ptr, B, N, D, r, max_nbr, skip_self, fill, nbr, cnt, nullptr, 0, ws, ws_bytes,
                                           stream);
+}
+
+// Periodic coordinates (train.py:47-48: phi wraps at +-pi).  period[c] > 0: circumference of coordinate c; 0: plain.
+// Host-side check of the D periods; *any = some coordinate is periodic.  per gets +inf for the plain ones (and for
+// the padding coordinates c >= D), which the kernels' wrap turns into the identity.
+static int radius_periods(const char *who, int D, const float *period, RadPeriod *per, bool *any)
+{
+    DMET_REQUIRE(D >= 1 && D <= 8, "%s: D=%d not in [1,8]", who, D);
+    DMET_REQUIRE(period, "%s: null period", who);
+    *any = false;
+    for (int c = 0; c < 8; ++c) per->L[c] = __builtin_inff();
+    for (int c = 0; c < D; ++c) {
+        const float L = period[c];
+        DMET_REQUIRE(L == L && L >= 0.0f && L < __builtin_inff(), "%s: period[%d]=%g is not 0 or a positive finite number",
+                     who, c, (double)L);
+        if (L > 0.0f) { per->L[c] = L; *any = true; }
+    }
+    return 0;
+}
+
+extern "C" int dmet_radius_periodic_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r,
+                                        int max_nbr, int skip_self, int fill, const float *period, int32_t *nbr,
+                                        int32_t *cnt, dmet_stream_t stream)
+{
+    RadPeriod per;
+    bool any = false;
+    const int rc = radius_periods("dmet_radius_periodic_f32", D, period, &per, &any);
+    if (rc) return rc;
+    // all periods 0: the plain kernel (bit-identical to dmet_radius_f32 / dmet_radius_counted_f32 by construction)
+    return radius_impl(x, ptr, B, N, D, r, max_nbr, skip_self, fill != 0, nbr, cnt, stream, any ? &per : nullptr);
+}
+
+extern "C" int dmet_radius_windowed_periodic_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r,
+                                                 int max_nbr, int skip_self, int fill, const float *period,
+                                                 int32_t *nbr, int32_t *cnt, uint16_t *nbr16, int stride16, void *ws,
+                                                 size_t ws_bytes, dmet_stream_t stream)
+{
+    RadPeriod per;
+    bool any = false;
+    const int rc = radius_periods("dmet_radius_windowed_periodic_f32", D, period, &per, &any);
+    if (rc) return rc;
+    DMET_REQUIRE(period[0] == 0.0f, "dmet_radius_windowed_periodic_f32: coordinate 0 is periodic (period[0]=%g): the "
+                 "window runs on coordinate 0; use dmet_radius_periodic_f32", (double)period[0]);
+    return radius_windowed_impl(x, ptr, B, N, D, r, max_nbr, skip_self, fill, nbr, cnt, nbr16, stride16, ws, ws_bytes,
+                                stream, any ? &per : nullptr);
 }

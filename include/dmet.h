@@ -132,6 +132,27 @@ int dmet_radius_windowed_f32(const float *x, const int64_t *ptr, int B, int64_t 
 int dmet_radius_windowed_local_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r, int max_nbr,
                                    int skip_self, int fill, int32_t *nbr, int32_t *cnt, uint16_t *nbr16, int stride16,
                                    void *ws, size_t ws_bytes, dmet_stream_t stream);
+/* Periodic coordinates, for the reference's (eta, phi) graph (train.py:47-48: phi is an angle, and the plain distance
+ * puts phi = +3.1 and phi = -3.1 6.2 apart instead of 0.08).  period: host array of D floats; period[c] > 0 is the
+ * circumference of coordinate c, 0 leaves it plain.  The only change to the contract above is the per-coordinate
+ * difference of a periodic coordinate c with period L (fp32; exact by Sterbenz for a <= 2L):
+ *     d = x[j,c] - x[i,c];  a = |d|;  a = (a > 0.5f * L) ? L - a : a;  acc = fmaf(a, a, acc)
+ * This is the circular distance whenever |d| <= 1.5 L, i.e. when every value of a periodic coordinate lies within one
+ * period (atan2 output in [-pi_f32, pi_f32] does); outside that the formula still defines the result.  Non-finite
+ * coordinates give no hit, as in the plain form.  Returns -EINVAL for D outside [1, 8], a NULL period, or a period that
+ * is NaN, inf or negative.  An all-zero period gives exactly the table of the plain entry.  The periods are read on the
+ * host and passed by value: a captured graph replays the periods of its capture.
+ * dmet_radius_periodic_f32: all pairs of an event (the arguments of dmet_radius_f32, fill != 0: its -1 fill, fill == 0:
+ * the counted form of dmet_radius_counted_f32). */
+int dmet_radius_periodic_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r, int max_nbr,
+                             int skip_self, int fill, const float *period, int32_t *nbr, int32_t *cnt,
+                             dmet_stream_t stream);
+/* The windowed form of the same table (arguments of dmet_radius_windowed_local_f32 plus period), bit-identical to
+ * dmet_radius_periodic_f32.  The window runs on coordinate 0, so period[0] must be 0 (-EINVAL otherwise): the
+ * reference's [eta, phi] layout qualifies, a [phi, eta] layout must take the slower all-pairs entry (train.py:47-48). */
+int dmet_radius_windowed_periodic_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r, int max_nbr,
+                                      int skip_self, int fill, const float *period, int32_t *nbr, int32_t *cnt,
+                                      uint16_t *nbr16, int stride16, void *ws, size_t ws_bytes, dmet_stream_t stream);
 
 /* ---- K2+K3 fused: EdgeConv with nn = Linear(2*Hin -> Hout), aggr = 'max', fixed-width table ---------
  * replaces torch_geometric.nn.EdgeConv(nn=Sequential(Linear(2H,H)), aggr='max').forward
