@@ -94,10 +94,12 @@ __global__ __launch_bounds__(256) void batch_to_ptr_kernel(const int64_t *__rest
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i > N) return;
-    // ptr[b] = first i with batch[i] >= b ; written by the thread sitting on each boundary
+    // ptr[b] = first i with batch[i] >= b ; written by the thread sitting on each boundary.  b is clamped to [0, B]:
+    // whatever the vector holds (unsorted, negative), nothing outside ptr[0..B] is written, and every entry is
+    // (the walk -1, batch[0], ..., batch[N-1], B steps up past each b).  The host validates the vector afterwards.
     const int64_t prev = (i == 0) ? -1 : batch[i - 1];
     const int64_t cur = (i == N) ? (int64_t)B : batch[i];
-    for (int64_t b = prev + 1; b <= cur && b <= B; ++b) ptr[b] = i;
+    for (int64_t b = (prev + 1 > 0 ? prev + 1 : 0); b <= cur && b <= B; ++b) ptr[b] = i;
 }
 
 // rev_ptr from the sorted source keys: rev_ptr[j] = first sorted position whose key >= j

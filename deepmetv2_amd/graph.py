@@ -20,15 +20,16 @@ from . import _native
 # batch vector -> (ptr, B)
 # ---------------------------------------------------------------------------------------------------------------
 class BatchInfo:
-    __slots__ = ("ptr", "num_events", "num_nodes", "max_nodes", "min_nodes")
+    __slots__ = ("ptr", "num_events", "num_nodes", "max_nodes", "min_nodes", "inferred")
 
     def __init__(self, ptr: torch.Tensor, num_events: int, num_nodes: int, max_nodes: Optional[int] = None,
-                 min_nodes: Optional[int] = None):
+                 min_nodes: Optional[int] = None, inferred: bool = False):
         self.ptr = ptr
         self.num_events = num_events
         self.num_nodes = num_nodes
         self.max_nodes = max_nodes      # largest event (None = unknown): picks the LDS-resident EdgeConv kernel
         self.min_nodes = min_nodes      # smallest event (None = unknown): >= k means a kNN table without empty slots
+        self.inferred = inferred        # num_events = batch[-1] + 1, read from the vector itself (not register_batch's)
 
 
 _batch_registry: Dict[int, Tuple[weakref.ref, int, BatchInfo]] = {}
@@ -59,7 +60,8 @@ def _registry_put(reg, t: torch.Tensor, val) -> None:
 def register_batch(batch: torch.Tensor, ptr: torch.Tensor, num_events: int,
                    max_nodes: Optional[int] = None, min_nodes: Optional[int] = None) -> BatchInfo:
     """Tell the operators the ptr / event count (/ largest and smallest event) of a batch vector up front (avoids a
-    device->host sync on first use; without `max_nodes` one sync happens here, which then also yields `min_nodes`)."""
+    device->host sync on first use; without `max_nodes` one sync happens here, which then also yields `min_nodes`).
+    The vector's values are not checked: the caller vouches for ptr."""
     ptr = ptr.to(torch.int64).contiguous()
     if max_nodes is None and ptr.numel() > 1:
         d = ptr.diff()
@@ -72,6 +74,19 @@ def register_batch(batch: torch.Tensor, ptr: torch.Tensor, num_events: int,
 
 def batch_info(batch: Optional[torch.Tensor], num_nodes: int, device: torch.device,
                num_events: Optional[int] = None) -> BatchInfo:
+    """ptr / event count of a batch vector.  A registered batch (register_batch) gives what was registered.  Any other
+    vector must be sorted with values in [0, num_events) (num_events given) or >= 0 (num_events = batch[-1] + 1
+    inferred), else ValueError; the check shares the host read that the event sizes need anyway."""
+    info = _batch_info(batch, num_nodes, device, num_events)
+    if isinstance(info, str):
+        raise ValueError(info)
+    return info
+
+
+def _batch_info(batch: Optional[torch.Tensor], num_nodes: int, device: torch.device,
+                num_events: Optional[int] = None):
+    """batch_info, with the reason as a str instead of the ValueError (scatter_add groups such an index instead).
+    Only an inferred event count is remembered for the tensor: a count one caller passes never shapes another call."""
     if batch is None:
         ptr = torch.tensor([0, num_nodes], dtype=torch.int64, device=device)
         return BatchInfo(ptr, 1, num_nodes, num_nodes, num_nodes)
@@ -79,23 +94,45 @@ def batch_info(batch: Optional[torch.Tensor], num_nodes: int, device: torch.devi
         raise ValueError(f"batch must be 1-D with {num_nodes} entries, got {tuple(batch.shape)}")
     info = _registry_get(_batch_registry, batch)
     if info is not None:
-        return info
+        if num_events is None or not info.inferred or num_events == info.num_events:
+            return info
+        if num_events < info.num_events:
+            return f"batch values must lie in [0, {num_events}), found {info.num_events - 1}"
+        # trailing empty events: no read of the device needed, the vector is known sorted and in range
+        ptr = torch.cat([info.ptr, info.ptr[-1:].expand(num_events - info.num_events)])
+        return BatchInfo(ptr, num_events, num_nodes, info.max_nodes, 0)
     if batch.dtype != torch.int64:
         raise TypeError(f"batch must be int64 (torch.long), got {batch.dtype}")
     if num_nodes == 0:
         return BatchInfo(torch.zeros(1, dtype=torch.int64, device=device), 0, 0)
-    # one host sync, like PyG's own `int(batch.max()) + 1`; sortedness is a documented precondition upstream
+    unsorted = (batch[1:] < batch[:-1]).any().to(batch.dtype)
     if num_events is None:
-        last, unsorted = torch.stack([batch[-1], (batch[1:] < batch[:-1]).any().to(batch.dtype)]).tolist()
-        if unsorted:
-            raise ValueError("batch vector must be sorted (torch_cluster / PyG precondition)")
+        # one host sync, like PyG's own `int(batch.max()) + 1`; sortedness is a documented precondition upstream
+        last, first, bad_order = torch.stack([batch[-1], batch[0], unsorted]).tolist()
+        if bad_order:
+            return "batch vector must be sorted (torch_cluster / PyG precondition)"
+        if first < 0:
+            return f"batch values must be >= 0, found {first}"
         num_events = int(last) + 1
-    ptr = _native.batch_to_ptr(batch, num_events)
-    mx = mn = 0
-    if num_events > 0:
+        ptr = _native.batch_to_ptr(batch, num_events)
         d = ptr.diff()
         mx, mn = (int(v) for v in torch.stack([d.max(), d.min()]).tolist())
-    info = BatchInfo(ptr, num_events, num_nodes, mx, mn)
+    else:
+        num_events = int(num_events)
+        if num_events <= 0:
+            return f"batch values must lie in [0, {num_events}), and there are {num_nodes} of them"
+        # the kernel writes ptr[0..B] whatever the vector holds; the statistics read rejects what it made of a bad one
+        ptr = _native.batch_to_ptr(batch, num_events)
+        d = ptr.diff()
+        mx, mn, bad_order, first, last = (int(v) for v in torch.stack([d.max(), d.min(), unsorted, batch[0],
+                                                                         batch[-1]]).tolist())
+        if bad_order:
+            return "batch vector must be sorted (torch_cluster / PyG precondition)"
+        if first < 0 or last >= num_events:
+            return f"batch values must lie in [0, {num_events}), found {first if first < 0 else last}"
+        if last + 1 != num_events:      # trailing empty events: the caller's count, not the vector's own
+            return BatchInfo(ptr, num_events, num_nodes, mx, mn)
+    info = BatchInfo(ptr, num_events, num_nodes, mx, mn, inferred=True)
     _registry_put(_batch_registry, batch, info)
     return info
 
@@ -197,13 +234,21 @@ def edge_list_from_edge_index(edge_index: torch.Tensor, num_nodes: int, flow: st
         z = torch.zeros(num_nodes + 1, dtype=torch.int32, device=dev)
         e = torch.zeros(0, dtype=torch.int32, device=dev)
         return EdgeList(e, e, z, num_nodes)
+    if num_nodes <= 0:
+        raise ValueError(f"edge_index holds {E} edges but the graph has {num_nodes} nodes")
     tgt = tgt64.to(torch.int32).contiguous()
     src = src64.to(torch.int32).contiguous()
     # group by target with the stable reverse-index sort (keeps the caller's order inside a group, so "lowest
-    # edge position wins ties" (R4) is preserved); skip the permutation when the list is already grouped.
+    # edge position wins ties" (R4) is preserved); skip the permutation when the list is already grouped.  The sort is
+    # safe for any key; the node ids are checked (as int64, before the int32 cast can alias them) in the same host
+    # read, before any kernel gathers through them.
     rowptr, perm = _reverse_of_column(tgt, num_nodes)
     ident = torch.arange(E, dtype=torch.int32, device=dev)
-    if bool((perm[:E] == ident).all()):
+    grouped, lo, hi = torch.stack([(perm[:E] == ident).all().to(torch.int64), edge_index.min(),
+                                   edge_index.max()]).tolist()
+    if lo < 0 or hi >= num_nodes:
+        raise ValueError(f"edge_index node ids must lie in [0, {num_nodes}), found {lo if lo < 0 else hi}")
+    if grouped:
         return EdgeList(src, tgt, rowptr, num_nodes, None)
     p = perm[:E].to(torch.int64)
     return EdgeList(src[p].contiguous(), tgt[p].contiguous(), rowptr, num_nodes, perm[:E])

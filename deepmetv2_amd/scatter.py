@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _native
-from .graph import batch_info, edge_list_from_edge_index, _reverse_of_column
+from .graph import _batch_info, _reverse_of_column, batch_info
 
 
 class _SegmentSum1D(torch.autograd.Function):
@@ -63,13 +63,52 @@ def _dim_size(index: torch.Tensor, dim_size: Optional[int]) -> int:
     return int(index.max()) + 1 if index.numel() else 0
 
 
+def _group_rows(index: torch.Tensor, E: int, H: int, dim_size: Optional[int]):
+    """(n, rowptr[n+1] int32, perm[E] int64 or None when the rows are grouped already) for an index of [E], [E,1] or
+    an [E,H] index whose columns agree.  Indices outside [0, n) raise IndexError, differing columns
+    NotImplementedError; both are read in the one host sync of the grouping test, after the reverse-index sort (safe for
+    any key) and before any kernel reads `src` through the grouping."""
+    if index.dtype != torch.int64:
+        raise TypeError(f"index must be int64, got {index.dtype}")
+    if index.dim() == 1:
+        idx, per_column = index, False
+    elif index.dim() == 2 and index.shape[1] in (1, H):
+        idx, per_column = index[:, 0], index.shape[1] > 1
+    else:
+        raise ValueError(f"index must be [E], [E,1] or [E,{H}] for src [E,{H}], got {tuple(index.shape)}")
+    if idx.numel() != E:
+        raise ValueError(f"index has {idx.numel()} rows, src {E}")
+    n = _dim_size(idx, dim_size)
+    if E == 0:
+        return n, torch.zeros(n + 1, dtype=torch.int32, device=index.device), None
+    if n <= 0:
+        raise IndexError(f"scatter: {E} indices into an output of {n} rows")
+    rowptr, perm = _reverse_of_column(idx.to(torch.int32), n)
+    ident = torch.arange(E, dtype=torch.int32, device=idx.device)
+    ragged = (index != index[:, :1]).any() if per_column else torch.zeros((), dtype=torch.bool, device=idx.device)
+    grouped, lo, hi, differ = torch.stack([(perm[:E] == ident).all().to(torch.int64), idx.min(), idx.max(),
+                                           ragged.to(torch.int64)]).tolist()
+    if differ:
+        raise NotImplementedError("scatter: an [E,H] index must hold the same row in every column")
+    if lo < 0 or hi >= n:
+        raise IndexError(f"scatter: index {lo if lo < 0 else hi} is out of range for an output of {n} rows")
+    return n, rowptr, (None if grouped else perm[:E].to(torch.int64))
+
+
+def _grouped_sum(src: torch.Tensor, index: torch.Tensor, dim_size: Optional[int]) -> torch.Tensor:
+    n, rowptr, perm = _group_rows(index, src.shape[0], src.shape[1], dim_size)
+    grouped = src if perm is None else src.index_select(0, perm)
+    return _SegmentSumRows.apply(grouped, rowptr, n)
+
+
 def scatter_add(src: torch.Tensor, index: torch.Tensor, dim: int = -1, out: Optional[torch.Tensor] = None,
                 dim_size: Optional[int] = None) -> torch.Tensor:
     """torch_scatter.scatter_add for the shapes on the hot path:
-    1-D `src` with a sorted `index` (the batch vector): one deterministic segmented sum per event;
+    1-D `src` with a sorted `index` (the batch vector): one deterministic segmented sum per event; any other in-range
+    1-D index is grouped like the 2-D form;
     2-D `src` [E,H] along dim 0 (aggr='add'): grouped by index with a stable sort, then per-row sums.
     A bf16 or fp16 `src` is summed in fp32 by the same kernels and the result returned in src.dtype, as torch_scatter
-    returns it."""
+    returns it.  Indices outside [0, dim_size) raise IndexError."""
     if index.dtype != torch.int64:
         raise TypeError(f"index must be int64, got {index.dtype}")
     if src.dtype in _HALF:
@@ -81,22 +120,19 @@ def scatter_add(src: torch.Tensor, index: torch.Tensor, dim: int = -1, out: Opti
     if src.dim() == 1:
         if index.shape != src.shape:
             raise ValueError("index must have the same shape as a 1-D src")
-        info = batch_info(index, src.numel(), src.device, dim_size)
-        res = _SegmentSum1D.apply(src, index, info.ptr)
-        if dim_size is not None and res.numel() < dim_size:
-            res = torch.cat([res, res.new_zeros(dim_size - res.numel())])
+        info = _batch_info(index, src.numel(), src.device, dim_size)
+        if isinstance(info, str):       # unsorted, or out of range (then the grouping raises IndexError)
+            res = _grouped_sum(src.view(-1, 1), index, dim_size).view(-1)
+        else:
+            res = _SegmentSum1D.apply(src, index, info.ptr)
+            if dim_size is not None and res.numel() < dim_size:
+                res = torch.cat([res, res.new_zeros(dim_size - res.numel())])
         if out is not None:
             out.add_(res)
             return out
         return res
     if src.dim() == 2 and dim in (0, -2):
-        idx = index if index.dim() == 1 else index[:, 0]
-        n = _dim_size(idx, dim_size)
-        rowptr, perm = _reverse_of_column(idx.to(torch.int32), n)
-        E = idx.numel()
-        ident = torch.arange(E, dtype=torch.int32, device=idx.device)
-        grouped = src if bool((perm[:E] == ident).all()) else src.index_select(0, perm[:E].to(torch.int64))
-        res = _SegmentSumRows.apply(grouped, rowptr, n)
+        res = _grouped_sum(src, index, dim_size)
         if out is not None:
             out.add_(res)
             return out
@@ -108,23 +144,19 @@ def scatter_max(src: torch.Tensor, index: torch.Tensor, dim: int = 0, out=None,
                 dim_size: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """torch_scatter.scatter_max for [E,H] rows along dim 0: (out, arg); empty rows -> 0 (R3), arg = winning row
     position in `src` (lowest on ties, R4); rows with no entry report arg = E like upstream.  A bf16 or fp16 `src` is
-    compared in fp32 (exact) and the maxima returned in src.dtype."""
+    compared in fp32 (exact) and the maxima returned in src.dtype.  Indices outside [0, dim_size) raise IndexError."""
     if src.dim() != 2 or dim not in (0, -2) or out is not None:
         raise NotImplementedError("scatter_max: only [E,H] along dim 0 without `out` is implemented")
     if src.dtype in _HALF:
         res, arg = scatter_max(src.float(), index, dim, None, dim_size)
         return res.to(src.dtype), arg
-    idx = index if index.dim() == 1 else index[:, 0]
-    n = _dim_size(idx, dim_size)
-    E = idx.numel()
-    rowptr, perm = _reverse_of_column(idx.to(torch.int32), n)
-    ident = torch.arange(E, dtype=torch.int32, device=idx.device)
-    is_grouped = bool((perm[:E] == ident).all())
-    grouped = src if is_grouped else src.index_select(0, perm[:E].to(torch.int64))
+    E = src.shape[0]
+    n, rowptr, perm = _group_rows(index, E, src.shape[1], dim_size)
+    grouped = src if perm is None else src.index_select(0, perm)
     res, arg = _SegmentMaxRows.apply(grouped, rowptr, n)
     arg64 = arg.to(torch.int64)
-    if not is_grouped:
-        arg64 = torch.where(arg64 >= 0, perm[:E].to(torch.int64)[arg64.clamp(min=0)], arg64)
+    if perm is not None:
+        arg64 = torch.where(arg64 >= 0, perm[arg64.clamp(min=0)], arg64)
     arg64 = torch.where(arg64 < 0, torch.full_like(arg64, E), arg64)
     return res, arg64
 

@@ -526,7 +526,9 @@ int dmet_segment_sum_1d_f32(const float *src, const int64_t *ptr, int B, float *
 int dmet_table_degree(const int32_t *nbr, const int32_t *cnt, int64_t N, int k, int32_t *deg, dmet_stream_t stream);
 int dmet_table_edges(const int32_t *nbr, const int32_t *cnt, const int32_t *rowptr, int64_t N, int k, int swap,
                      int64_t *first, int64_t *second, int32_t *src32, int32_t *tgt32, dmet_stream_t stream);
-/* ptr[B+1] from a SORTED int64 batch vector (ptr[b] = first i with batch[i] >= b). */
+/* ptr[B+1] from a SORTED int64 batch vector with values in [0, B) (ptr[b] = first i with batch[i] >= b).  Safe for any
+ * int64 input: only ptr[0..B] is written, and all of it; for an unsorted vector or values outside [0, B) the content
+ * is unspecified (and may differ between runs), so the caller validates the vector before using ptr. */
 int dmet_batch_to_ptr(const int64_t *batch, int64_t N, int B, int64_t *ptr, dmet_stream_t stream);
 
 /* ---- N3 (first piece): weight gradients of the per-node dense layers ----------------------------------

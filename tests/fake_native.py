@@ -186,7 +186,17 @@ def segment_sum_1d(src, ptr):
 
 
 def batch_to_ptr(batch, B):
-    return ref_ops.batch_to_ptr(batch, batch.numel(), B)
+    """The kernel's own rule, not the oracle's: no check of the vector.  Position i (0..N) writes ptr[b] = i for every
+    b in [max(batch[i-1] + 1, 0), min(batch[i], B)] (batch[-1] = -1, batch[N] = B); every entry gets written.  On an
+    unsorted vector several positions write one entry and the device gives no order: the last writer wins here."""
+    v = torch.cat([torch.tensor([-1]), batch.long().cpu(), torch.tensor([B])])
+    ptr = torch.full((B + 1,), -1, dtype=torch.int64)
+    for i in torch.nonzero(v[1:] > v[:-1]).view(-1).tolist():
+        lo, hi = max(int(v[i]) + 1, 0), min(int(v[i + 1]), B)
+        if lo <= hi:
+            ptr[lo:hi + 1] = i
+    assert bool((ptr >= 0).all())
+    return ptr
 
 
 def xty(A, Bm):

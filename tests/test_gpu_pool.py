@@ -218,8 +218,7 @@ def test_global_pools(dev):
     assert torch.equal(dm.global_max_pool(xd, bd, size=B).detach().cpu(), mx)
     torch.testing.assert_close(dm.global_add_pool(xd, bd, size=B).detach().cpu(), sm, rtol=1e-6, atol=1e-6)
     torch.testing.assert_close(dm.global_mean_pool(xd, bd, size=B).detach().cpu(), sm / cnt, rtol=1e-6, atol=1e-6)
-    bd = batch.to(dev)              # (batch_info remembers the event count it was first asked with)
-    assert dm.global_max_pool(xd, bd).shape == (4, 6)
+    assert dm.global_max_pool(xd, bd).shape == (4, 6)       # the same tensor: size=B above is not remembered
     one = dm.global_mean_pool(xd, None)
     assert one.shape == (1, 6)
     torch.testing.assert_close(one.detach().cpu(), x.mean(0, keepdim=True), rtol=1e-5, atol=1e-6)
