@@ -269,6 +269,35 @@ def knn_local(x: torch.Tensor, ptr: torch.Tensor, k: int, stats: Optional[dict] 
     return _knn(x, ptr, k, stats, True)
 
 
+def knn_periodic(x: torch.Tensor, ptr: torch.Tensor, k: int, period, want_local: bool):
+    """knn() / knn_local() with periodic coordinates (dmet_knn_periodic_f32): period = D floats, period[c] > 0 the
+    circumference of coordinate c, 0 a plain coordinate; D <= 8.  Returns (nbr, dist, loc), loc None unless
+    want_local."""
+    import ctypes
+    dev = _require_device(x, ptr)
+    L = _lib.load()
+    x = _f32c(x.detach(), "x")
+    if x.dim() != 2:
+        raise ValueError(f"x must be 2-D [N, D], got {tuple(x.shape)}")
+    N, D = x.shape
+    B = ptr.numel() - 1
+    if len(period) != D:
+        raise ValueError(f"period has {len(period)} entries for {D} coordinates")
+    per = (ctypes.c_float * D)(*[float(p) for p in period])    # host array, read by the C entry before it returns
+    nbr = torch.empty((N, k), dtype=torch.int32, device=dev)
+    dist = torch.empty((N, k), dtype=torch.float32, device=dev)
+    loc = torch.empty((N, k), dtype=torch.int16, device=dev) if want_local else None
+    ws = _ws(L.dmet_knn_workspace_bytes(N, B, D, k), dev)
+    _t = timer.record('knn', dev)
+    with _on(dev):
+        _lib.check(L.dmet_knn_periodic_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, k, ctypes.cast(per, ctypes.c_void_p),
+                                           nbr.data_ptr(), dist.data_ptr(), loc.data_ptr() if want_local else None,
+                                           ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_knn_periodic_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return nbr, dist, loc
+
+
 def radius(x: torch.Tensor, ptr: torch.Tensor, r: float, max_nbr: int, skip_self: bool = False,
            pad: bool = True, local: bool = False, int32_rows: bool = True):
     """(nbr[N,max_nbr] int32, cnt[N] int32).  pad=False leaves the slots >= cnt[i] unwritten instead of filling them

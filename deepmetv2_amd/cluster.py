@@ -40,17 +40,26 @@ def _check_x(x: torch.Tensor) -> torch.Tensor:
 
 
 def knn_table(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loop: bool = True,
-              num_events: Optional[int] = None, dense=None) -> NeighborTable:
+              num_events: Optional[int] = None, dense=None, period=None) -> NeighborTable:
     """Fixed-width neighbour table for `x` (row i = the message sources of node i).  loop=False searches k+1
     and blanks j == i, exactly like upstream's `row != col` mask (a node whose k+1 nearest do not include itself,
     possible only with >= k+1 duplicates at lower index, keeps all k+1).  A bf16 `x`, or an fp16 one under fp16
-    autocast, is upcast first, an exact conversion: the result is the kNN of x.float()."""
+    autocast, is upcast first, an exact conversion: the result is the kNN of x.float().
+
+    period: None (torch_cluster's plain distance), or one entry per coordinate as in radius_table: None / 0 for a plain
+    coordinate, or the circumference of a periodic one, e.g. [None, 2 * math.pi] for (eta, phi).  The periodic
+    difference is min(|d|, L - |d|) in fp32 (include/dmet.h, dmet_knn_periodic_f32); up to 8 coordinates.  A periodic
+    table with loop=True and k in (8, 16, 20, 32) carries the event-local ids, like a plain one, so the EdgeConvs take
+    the same route over it."""
     x = _check_x(x)
     if not isinstance(k, int) or k < 1:
         raise ValueError(f"k must be a positive int, got {k!r}")
     kk = k if loop else k + 1
     if kk > MAX_K:
         raise ValueError(f"k={k} (searching {kk}) exceeds the supported maximum {MAX_K}")
+    per = _check_period(period, x.shape[1])
+    if per is not None and x.shape[1] > 8:
+        raise ValueError(f"periodic coordinates are supported for up to 8 coordinates, x has {x.shape[1]}")
     info = batch_info(batch, x.shape[0], x.device, num_events)
     # the LDS gather kernel reads the table as event-local uint16 ids when the kNN kernels wrote them alongside
     # dense = (W, b, sliced_of(max_nodes)): DynamicEdgeConv asks the build to carry the node-level dense layer of its
@@ -58,7 +67,9 @@ def knn_table(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loo
     loc = None
     pq = None
     _native.knn_size_hint(info.min_nodes, info.max_nodes)    # what the loader knows about the event sizes (spent by the build below)
-    if loop and kk in _native.LDS_GATHER_K and dense is not None and x.shape[1] == 32:
+    if per is not None:    # D <= 8: never the dense-carrying build (32 features)
+        nbr, dist, loc = _native.knn_periodic(x, info.ptr, kk, per, want_local=loop and kk in _native.LDS_GATHER_K)
+    elif loop and kk in _native.LDS_GATHER_K and dense is not None and x.shape[1] == 32:
         W, b, sliced_of = dense
         nbr, dist, loc, pq = _native.knn_local_dense(x, info.ptr, kk, W, b, sliced_of(info.max_nodes))
     elif loop and kk in _native.LDS_GATHER_K:
@@ -86,15 +97,16 @@ def knn_table(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loo
 
 def knn_graph(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loop: bool = False,
               flow: str = "source_to_target", cosine: bool = False, num_workers: int = 1,
-              batch_size: Optional[int] = None) -> torch.Tensor:
+              batch_size: Optional[int] = None, period=None) -> torch.Tensor:
     """torch_cluster.knn_graph: edge_index[2,E] int64; [0] = neighbour j, [1] = centre i for
-    flow='source_to_target'; edges grouped by ascending i, ascending (distance, j) inside a group."""
+    flow='source_to_target'; edges grouped by ascending i, ascending (distance, j) inside a group.  period: periodic
+    coordinates, see knn_table (None: torch_cluster's behaviour)."""
     if cosine:
         raise NotImplementedError("cosine=True is not on the DeepMETv2 hot path")
     if flow not in ("source_to_target", "target_to_source"):
         raise ValueError(f"flow must be 'source_to_target' or 'target_to_source', got {flow!r}")
     _deferred.poll()
-    table = knn_table(x, k, batch, loop=loop, num_events=batch_size)
+    table = knn_table(x, k, batch, loop=loop, num_events=batch_size, period=period)
     _check_full_rows(table, x, "knn_graph")
     return table.edge_index(flow)
 
@@ -111,20 +123,21 @@ def _check_full_rows(table: NeighborTable, x: torch.Tensor, who: str) -> None:
 
 
 def knn(x: torch.Tensor, y: torch.Tensor, k: int, batch_x: Optional[torch.Tensor] = None,
-        batch_y: Optional[torch.Tensor] = None, cosine: bool = False, num_workers: int = 1) -> torch.Tensor:
+        batch_y: Optional[torch.Tensor] = None, cosine: bool = False, num_workers: int = 1,
+        period=None) -> torch.Tensor:
     """torch_cluster.knn restricted to the self-query form (y is x) that DynamicEdgeConv uses:
-    returns [2,E] with row 0 = query index, row 1 = neighbour index."""
+    returns [2,E] with row 0 = query index, row 1 = neighbour index.  period: periodic coordinates, see knn_table."""
     if cosine:
         raise NotImplementedError("cosine=True is not on the DeepMETv2 hot path")
     if y is not x or (batch_y is not batch_x):
         raise NotImplementedError("knn(x, y): only the self-query form y is x is implemented (DynamicEdgeConv)")
-    table = knn_table(x, k, batch_x, loop=True)
+    table = knn_table(x, k, batch_x, loop=True, period=period)
     _check_full_rows(table, x, "knn")
     return table.edge_index("target_to_source")
 
 
 def _check_period(period, D: int) -> Optional[list]:
-    """radius_graph's `period`: None, or D entries each None / 0 (a plain coordinate) or a positive finite number (the
+    """radius_graph's and knn_graph's `period`: None, or D entries each None / 0 (a plain coordinate) or a positive finite number (the
     circumference of a periodic coordinate, rounded to fp32).  Returns the D fp32-representable floats, or None when no
     coordinate is periodic (the plain build then runs exactly as without the keyword)."""
     if period is None:

@@ -90,6 +90,65 @@ __device__ __forceinline__ void pk_dist_step4(f2 &accA, f2 &accB, f2 vxy, f2 vzw
           [q3] "v"(q3));
 }
 
+// Periodic coordinates (radius_graph / knn_graph(..., period=)): L[c] is the circumference of coordinate c, passed to
+// the kernel BY VALUE (a captured graph replays the periods of its capture).  The host turns "not periodic" into L = +inf.
+// The contract wraps the fp32 difference d as  a = |d|;  a = (a > L/2) ? L - a : a.  The kernels form the same value
+// as  min(|d|, L - |d|):  for a > L/2, L - a < a so fp32(L - a) <= a; for a <= L/2, L - a >= L/2 >= a so fp32(L - a) >= a
+// (rounding is monotone, L/2 is exact); NaN stays NaN, |d| = inf gives L - inf = -inf.  With L = +inf the result is
+// |d| for every d (inf - inf = NaN loses to |d| = inf in min), so a plain coordinate keeps its bits.
+struct RadPeriod { float L[8]; };
+
+// the periods ride as an optional trailing kernel argument: an empty pack is the plain kernel (same arguments, same
+// code as without periods), Per = RadPeriod wraps every coordinate c with L[c]
+__device__ __forceinline__ RadPeriod rad_periods() { return RadPeriod{}; }
+__device__ __forceinline__ RadPeriod rad_periods(const RadPeriod &p) { return p; }
+
+// The periodic kNN sweep (knn_kernel with Per = RadPeriod) takes one coordinate at a time: the candidate feature is
+// broadcast and the query pair subtracted as in pk_dist_step4 (tA / tB: candidates A / B), a periodic coordinate is then
+// wrapped half by half, and the squares enter the two chains in coordinate order (R1).
+template <bool HI>
+__device__ __forceinline__ void pk_sub2(f2 &tA, f2 &tB, f2 v, f2 w, f2 q)
+{
+    if (HI)
+        asm("v_pk_add_f32 %[ta], %[v], %[q]" DMET_PKSUB_HI "v_pk_add_f32 %[tb], %[w], %[q]" DMET_PKSUB_HI
+            : [ta] "=&v"(tA), [tb] "=&v"(tB) : [v] "v"(v), [w] "v"(w), [q] "v"(q));
+    else
+        asm("v_pk_add_f32 %[ta], %[v], %[q]" DMET_PKSUB_LO "v_pk_add_f32 %[tb], %[w], %[q]" DMET_PKSUB_LO
+            : [ta] "=&v"(tA), [tb] "=&v"(tB) : [v] "v"(v), [w] "v"(w), [q] "v"(q));
+}
+
+__device__ __forceinline__ void pk_fma2(f2 &accA, f2 &accB, f2 tA, f2 tB)
+{
+    asm("v_pk_fma_f32 %[a], %[ta], %[ta], %[a]\n\t"
+        "v_pk_fma_f32 %[b], %[tb], %[tb], %[b]"
+        : [a] "+v"(accA), [b] "+v"(accB) : [ta] "v"(tA), [tb] "v"(tB));
+}
+
+// min(|d|, L - |d|) of one fp32 lane (RadPeriod above).  v_sub_f32 / v_min_f32 with abs source modifiers: gfx950 has
+// no packed fp32 min, and fminf on an asm result would add canonicalising v_max_f32s.
+__device__ __forceinline__ float wrap1(float d, float L)
+{
+    float a, t;
+    asm("v_sub_f32 %[t], %[L], |%[d]|\n\t"
+        "v_min_f32 %[a], |%[d]|, %[t]"
+        : [a] "=v"(a), [t] "=&v"(t) : [d] "v"(d), [L] "s"(L));
+    return a;
+}
+
+// One coordinate of the periodic sweep for candidates A (v) and B (w).  `wrap` (L < inf) is wave-uniform: a plain or
+// padding coordinate branches around the 8 wrap instructions (the compiler adds two 64-bit moves on that side).
+template <bool HI>
+__device__ __forceinline__ void pk_dist_step1_per(f2 &accA, f2 &accB, f2 v, f2 w, f2 q, float L, bool wrap)
+{
+    f2 tA, tB;
+    pk_sub2<HI>(tA, tB, v, w, q);
+    if (wrap) {
+        tA = f2{wrap1(tA.x, L), wrap1(tA.y, L)};
+        tB = f2{wrap1(tB.x, L), wrap1(tB.y, L)};
+    }
+    pk_fma2(accA, accB, tA, tB);
+}
+
 template <int DP, int TQ>
 struct KnnShared {
     float4 tile[(kTileC + 1) * DP / 4];  // +1 row kept at +inf: the paired sweep reads one row past the tile's last
@@ -532,9 +591,16 @@ __device__ __forceinline__ void knn_requery_body(const KnnArgs &a, float *__rest
     }
 }
 
-template <int DP, int KP, int TQ, bool EXACT_D>
-__global__ __launch_bounds__(kWave * kWavesPerGroup, 3) void knn_kernel(const KnnArgs a)
+// Per = RadPeriod (dmet_knn_periodic_f32): coordinate c is wrapped with L[c] when L[c] < inf; the host sets L = +inf on
+// plain coordinates and on the padding coordinates c >= D, so those take the plain step.  An empty pack is the plain
+// kernel.  Padded coordinates (0 - 0) and rows past a partial tile (+inf) behave as in the plain kernel: a periodic
+// coordinate turns inf - q into |.| = inf, L - inf = -inf, squared +inf, so such a candidate is never admitted.
+template <int DP, int KP, int TQ, bool EXACT_D, typename... Per>
+__global__ __launch_bounds__(kWave * kWavesPerGroup, 3) void knn_kernel(const KnnArgs a, Per... per_arg)
 {
+    constexpr bool PER = sizeof...(Per) > 0;
+    static_assert(!PER || TQ == 2, "the periodic sweep is the packed two-query form (D <= 8)");
+    const RadPeriod per = rad_periods(per_arg...);
     // A workgroup is kWavesPerGroup INDEPENDENT wavefronts (one work item each, no workgroup barrier): the hardware
     // spreads a workgroup's waves over the CU's 4 SIMDs, so each SIMD receives one item of every resident workgroup
     // and whole-sweep and sub-sweep items mix evenly per SIMD (single-wave workgroups left some SIMDs with 3 whole
@@ -669,8 +735,16 @@ __global__ __launch_bounds__(kWave * kWavesPerGroup, 3) void knn_kernel(const Kn
                     const float4 v = sh.tile[cc * (DP / 4) + c4];        // wave-uniform address: LDS broadcast
                     const float4 w = sh.tile[(cc + 1) * (DP / 4) + c4];
                     const f2 vxy = {v.x, v.y}, vzw = {v.z, v.w}, wxy = {w.x, w.y}, wzw = {w.z, w.w};
-                    pk_dist_step4(accA, accB, vxy, vzw, wxy, wzw, q2[4 * c4 + 0], q2[4 * c4 + 1], q2[4 * c4 + 2],
-                                  q2[4 * c4 + 3]);
+                    if constexpr (PER) {
+                        const float *L = per.L + 4 * c4;
+                        pk_dist_step1_per<false>(accA, accB, vxy, wxy, q2[4 * c4 + 0], L[0], L[0] < inf);
+                        pk_dist_step1_per<true>(accA, accB, vxy, wxy, q2[4 * c4 + 1], L[1], L[1] < inf);
+                        pk_dist_step1_per<false>(accA, accB, vzw, wzw, q2[4 * c4 + 2], L[2], L[2] < inf);
+                        pk_dist_step1_per<true>(accA, accB, vzw, wzw, q2[4 * c4 + 3], L[3], L[3] < inf);
+                    } else {
+                        pk_dist_step4(accA, accB, vxy, vzw, wxy, wzw, q2[4 * c4 + 0], q2[4 * c4 + 1], q2[4 * c4 + 2],
+                                      q2[4 * c4 + 3]);
+                    }
                 }
                 dA[0] = accA.x; dB[0] = accB.x;
                 dA[TQ - 1] = accA.y; dB[TQ - 1] = accB.y;
@@ -2834,7 +2908,7 @@ int launch_filter(const KnnFilterArgs &f, const KnnWorkspace &w, int simds, cons
 
 template <int DP, int KP>
 int launch_knn(const float *x, const int64_t *ptr, int B, int64_t N, int D, int k, int32_t *nbr, float *dist,
-               uint16_t *nbr16, const KnnWorkspace &w, hipStream_t st)
+               uint16_t *nbr16, const KnnWorkspace &w, hipStream_t st, const RadPeriod *per)
 {
     constexpr int TQ = (DP <= 32) ? 2 : 1;
     constexpr int QT = kWave * TQ;
@@ -2896,7 +2970,16 @@ int launch_knn(const float *x, const int64_t *ptr, int B, int64_t N, int D, int 
 #ifdef DMET_KNN_EXPERIMENT
     if (const char *e = getenv("DMET_KNN_EXTRA_LDS")) dyn = (unsigned)atoi(e);
 #endif
-    if (D == DP && aligned16(x))
+    if (per) {   // periodic coordinates (dmet_knn_periodic_f32 checked D <= 8): never the matrix-core path
+        if constexpr (DP <= 8) {
+            if (D == DP && aligned16(x))
+                hipLaunchKernelGGL((knn_kernel<DP, KP, TQ, true, RadPeriod>), dim3((unsigned)blocks),
+                                   dim3(kWave * kWavesPerGroup), dyn, st, a, *per);
+            else
+                hipLaunchKernelGGL((knn_kernel<DP, KP, TQ, false, RadPeriod>), dim3((unsigned)blocks),
+                                   dim3(kWave * kWavesPerGroup), dyn, st, a, *per);
+        }
+    } else if (D == DP && aligned16(x))
         hipLaunchKernelGGL((knn_kernel<DP, KP, TQ, true>), dim3((unsigned)blocks), dim3(kWave * kWavesPerGroup), dyn, st, a);
     else
         hipLaunchKernelGGL((knn_kernel<DP, KP, TQ, false>), dim3((unsigned)blocks), dim3(kWave * kWavesPerGroup), dyn, st, a);
@@ -2912,14 +2995,14 @@ int launch_knn(const float *x, const int64_t *ptr, int B, int64_t N, int D, int 
 
 template <int DP>
 int dispatch_k(const float *x, const int64_t *ptr, int B, int64_t N, int D, int k, int32_t *nbr, float *dist,
-               uint16_t *nbr16, void *ws, hipStream_t st)
+               uint16_t *nbr16, void *ws, hipStream_t st, const RadPeriod *per)
 {
     const int KP = padded_k(k);
     const KnnWorkspace w = carve_workspace(ws, N, B, KP);
-    if (k <= 8) return launch_knn<DP, 8>(x, ptr, B, N, D, k, nbr, dist, nbr16, w, st);
-    if (k <= 16) return launch_knn<DP, 16>(x, ptr, B, N, D, k, nbr, dist, nbr16, w, st);
-    if (k <= 32) return launch_knn<DP, 32>(x, ptr, B, N, D, k, nbr, dist, nbr16, w, st);
-    return launch_knn<DP, 64>(x, ptr, B, N, D, k, nbr, dist, nbr16, w, st);
+    if (k <= 8) return launch_knn<DP, 8>(x, ptr, B, N, D, k, nbr, dist, nbr16, w, st, per);
+    if (k <= 16) return launch_knn<DP, 16>(x, ptr, B, N, D, k, nbr, dist, nbr16, w, st, per);
+    if (k <= 32) return launch_knn<DP, 32>(x, ptr, B, N, D, k, nbr, dist, nbr16, w, st, per);
+    return launch_knn<DP, 64>(x, ptr, B, N, D, k, nbr, dist, nbr16, w, st, per);
 }
 
 // ---- radius graph (N1): first max_nbr candidates in ascending index with d < r^2 ------------------------
@@ -2930,14 +3013,6 @@ int dispatch_k(const float *x, const int64_t *ptr, int B, int64_t N, int D, int 
 // `skip_self` reproduces upstream's loop=False: the search limit counts the node itself, the node is not stored.
 constexpr int kRadTile = 64;   // candidates per LDS tile and wavefront
 
-// Periodic coordinates (radius_graph(..., period=)): L[c] is the circumference of coordinate c, passed to the kernel BY
-// VALUE (a captured graph replays the periods of its capture).  The host turns "not periodic" into L = +inf.
-// The contract wraps the fp32 difference d as  a = |d|;  a = (a > L/2) ? L - a : a.  The kernels form the same value
-// as  min(|d|, L - |d|):  for a > L/2, L - a < a so fp32(L - a) <= a; for a <= L/2, L - a >= L/2 >= a so fp32(L - a) >= a
-// (rounding is monotone, L/2 is exact); NaN stays NaN, |d| = inf gives L - inf = -inf.  With L = +inf the result is
-// |d| for every d (inf - inf = NaN loses to |d| = inf in min), so a plain coordinate keeps its bits.
-struct RadPeriod { float L[8]; };
-
 template <bool PER>
 __device__ __forceinline__ f2 rad_wrap(f2 df, float L)
 {
@@ -2945,11 +3020,6 @@ __device__ __forceinline__ f2 rad_wrap(f2 df, float L)
     const float ax = fabsf(df.x), ay = fabsf(df.y);
     return f2{fminf(ax, L - ax), fminf(ay, L - ay)};
 }
-
-// the periods ride as an optional trailing kernel argument: an empty pack is the plain kernel (same arguments, same
-// code as without periods), Per = RadPeriod wraps every coordinate c with L[c]
-__device__ __forceinline__ RadPeriod rad_periods() { return RadPeriod{}; }
-__device__ __forceinline__ RadPeriod rad_periods(const RadPeriod &p) { return p; }
 
 template <int DP, typename... Per>
 __global__ __launch_bounds__(kWave * 4) void radius_kernel(const float *__restrict__ x,
@@ -3280,10 +3350,10 @@ extern "C" size_t dmet_knn_workspace_bytes(int64_t N, int B, int D, int k)
     return carve_workspace(nullptr, N, B, padded_k(k)).bytes + 512;
 }
 
-extern "C" int dmet_knn_local_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, int k, int32_t *nbr,
-                                  float *dist, uint16_t *nbr16, void *ws, size_t ws_bytes, dmet_stream_t stream)
+// the body of dmet_knn_local_f32; per != nullptr: the periodic sweep (dmet_knn_periodic_f32, D <= 8, checked there)
+static int knn_local_impl(const float *x, const int64_t *ptr, int B, int64_t N, int D, int k, int32_t *nbr, float *dist,
+                          uint16_t *nbr16, void *ws, size_t ws_bytes, dmet_stream_t stream, const RadPeriod *per)
 {
-    struct HintScope { ~HintScope() { g_size_hint = KnnSizeHint{}; } } hint_scope;   // the hint describes one batch: it is spent by one build, whatever the outcome
     DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647 - 4096, "dmet_knn_f32/dmet_knn_local_f32: N=%lld out of range", (long long)N);
     DMET_REQUIRE(B >= 0, "dmet_knn_f32/dmet_knn_local_f32: B=%d", B);
     DMET_REQUIRE(k >= 1 && k <= DMET_MAX_K, "dmet_knn_f32/dmet_knn_local_f32: k=%d not in [1,%d]", k, DMET_MAX_K);
@@ -3294,12 +3364,19 @@ extern "C" int dmet_knn_local_f32(const float *x, const int64_t *ptr, int B, int
     DMET_REQUIRE(!nbr16 || (reinterpret_cast<uintptr_t>(nbr16) & 3u) == 0, "dmet_knn_local_f32: nbr_local must be 4-byte aligned");
     hipStream_t st = as_stream(stream);
     int rc;
-    if (D <= 4) rc = dispatch_k<4>(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, st);
-    else if (D <= 8) rc = dispatch_k<8>(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, st);
-    else if (D <= 16) rc = dispatch_k<16>(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, st);
-    else if (D <= 32) rc = dispatch_k<32>(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, st);
-    else rc = dispatch_k<64>(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, st);
+    if (D <= 4) rc = dispatch_k<4>(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, st, per);
+    else if (D <= 8) rc = dispatch_k<8>(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, st, per);
+    else if (D <= 16) rc = dispatch_k<16>(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, st, per);
+    else if (D <= 32) rc = dispatch_k<32>(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, st, per);
+    else rc = dispatch_k<64>(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, st, per);
     return rc;
+}
+
+extern "C" int dmet_knn_local_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, int k, int32_t *nbr,
+                                  float *dist, uint16_t *nbr16, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    struct HintScope { ~HintScope() { g_size_hint = KnnSizeHint{}; } } hint_scope;   // the hint describes one batch: it is spent by one build, whatever the outcome
+    return knn_local_impl(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, ws_bytes, stream, nullptr);
 }
 
 extern "C" int dmet_knn_size_hint(int min_nodes, int max_nodes)
@@ -3562,4 +3639,18 @@ extern "C" int dmet_radius_windowed_periodic_f32(const float *x, const int64_t *
                  "window runs on coordinate 0; use dmet_radius_periodic_f32", (double)period[0]);
     return radius_windowed_impl(x, ptr, B, N, D, r, max_nbr, skip_self, fill, nbr, cnt, nbr16, stride16, ws, ws_bytes,
                                 stream, any ? &per : nullptr);
+}
+
+// Periodic kNN (train.py:47: phi wraps at +-pi): the K1 contract with the radius graph's periodic difference.  D <= 8
+// only, so the build is always the exact packed sweep; all-zero periods take the plain kernels.
+extern "C" int dmet_knn_periodic_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, int k,
+                                     const float *period, int32_t *nbr, float *dist, uint16_t *nbr16, void *ws,
+                                     size_t ws_bytes, dmet_stream_t stream)
+{
+    struct HintScope { ~HintScope() { g_size_hint = KnnSizeHint{}; } } hint_scope;   // spent as by dmet_knn_local_f32
+    RadPeriod per;
+    bool any = false;
+    const int rc = radius_periods("dmet_knn_periodic_f32", D, period, &per, &any);
+    if (rc) return rc;
+    return knn_local_impl(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, ws_bytes, stream, any ? &per : nullptr);
 }

@@ -58,6 +58,21 @@ int dmet_knn_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, in
  * dmet_gather_max_lds16_f32.  Rows of events with more than 65535 nodes are unspecified. */
 int dmet_knn_local_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, int k, int32_t *nbr,
                        float *dist, uint16_t *nbr_local, void *ws, size_t ws_bytes, dmet_stream_t stream);
+/* Periodic coordinates, for a kNN graph in the reference's (eta, phi) space (train.py:47: phi is an angle; the plain
+ * distance puts phi = +3.1 and -3.1 6.2 apart instead of 0.08).  The contract above (R1, R2, the 1e10 sentinel, self
+ * a candidate like any other) with one change, the one dmet_radius_periodic_f32 makes: for a coordinate c with
+ * period L = period[c] > 0 the fp32 difference is wrapped before it is squared into the chain,
+ *     d = x[j,c] - x[i,c];  a = |d|;  a = (a > 0.5f * L) ? L - a : a;  acc = fmaf(a, a, acc)
+ * Ordering stays (d, j) ascending; candidates at d >= 1e10 or NaN are never selected; dist holds the wrapped R1
+ * distance.  Two nodes at phi = +pi_f32 and -pi_f32 are at distance 0 in phi, so a query's seam twin ties with the query
+ * itself and R2 decides.  period: host array of D floats, 0 = a plain coordinate; read on the host and passed by value
+ * (a captured graph replays the periods of its capture).  Arguments and workspace (dmet_knn_workspace_bytes) as
+ * dmet_knn_local_f32, whose per-thread size hint it spends the same way.  Returns -EINVAL for D outside [1, 8], a NULL
+ * period, or a period that is NaN, inf or negative, before any device work.  An all-zero period gives exactly the
+ * result of dmet_knn_local_f32. */
+int dmet_knn_periodic_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, int k, const float *period,
+                          int32_t *nbr, float *dist, uint16_t *nbr_local, void *ws, size_t ws_bytes,
+                          dmet_stream_t stream);
 /* dmet_knn_local_f32 for the DynamicEdgeConv call shape (model/graph_met_network.py:63: the graph is built in the
  * space of the rows the convolution then consumes): the node-level dense layer of the fused EdgeConv,
  *   P = x.(W1-W2)^T + b, Q = x.W2^T   (W[32,64], D = 32),
