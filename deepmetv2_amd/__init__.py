@@ -4,7 +4,7 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
 /root/reference/model/graph_met_network.py:7,9, model/net.py:8, train.py:10):
 
     from deepmetv2_amd import EdgeConv, DynamicEdgeConv      # torch_geometric.nn
-    from deepmetv2_amd import knn_graph, radius_graph, knn   # torch_cluster
+    from deepmetv2_amd import knn_graph, radius_graph, knn, radius   # torch_cluster
     from deepmetv2_amd import scatter_add, scatter_max       # torch_scatter
     from deepmetv2_amd import graclus                        # torch_cluster
     from deepmetv2_amd import normalized_cut, max_pool, max_pool_x, global_max_pool   # torch_geometric
@@ -13,10 +13,10 @@ All of them run hand-written HIP kernels for gfx950 through the C ABI in include
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
 calling an operator without the library or with non-GPU tensors raises.
 """
-from .cluster import knn, knn_graph, knn_table, radius_graph, radius_table
+from .cluster import knn, knn_graph, knn_table, knn_xy_table, radius, radius_graph, radius_table, radius_xy_table
 from .conv import DynamicEdgeConv, EdgeConv
 from .data import Batch, DeviceLoader, EventLoader, collate, events_from_padded
-from .graph import GraphFuture, NeighborTable, build_async, raise_deferred_errors, register_batch, to_undirected
+from .graph import BipartiteTable, GraphFuture, NeighborTable, build_async, raise_deferred_errors, register_batch, to_undirected
 from .metrics import metrics, resolution, u_perp_par_loss
 from .scatter import met_reduce, scatter_add, scatter_max
 from .nn import accelerate
@@ -25,7 +25,8 @@ from .pool import (avg_pool, avg_pool_x, global_add_pool, global_max_pool, globa
 from .drn import DynamicReductionNetwork
 
 __all__ = [
-    "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "radius_graph", "radius_table",
+    "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "knn_xy_table", "radius", "radius_graph", "radius_table",
+    "radius_xy_table", "BipartiteTable",
     "scatter_add", "scatter_max", "met_reduce", "NeighborTable", "register_batch", "metrics", "resolution",
     "u_perp_par_loss", "to_undirected", "raise_deferred_errors", "accelerate", "build_async", "GraphFuture", "Batch", "EventLoader", "DeviceLoader", "collate", "events_from_padded",
     "graclus", "normalized_cut", "normalized_cut_2d", "max_pool", "max_pool_x", "avg_pool", "avg_pool_x",

@@ -26,6 +26,11 @@ SIGNATURES = {
     "dmet_knn_f32": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dmet_knn_local_f32": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dmet_knn_periodic_f32": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dmet_knn_xy_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i]),
+    "dmet_knn_xy_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dmet_radius_xy_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp]),
+    "dmet_edge_features_xy_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    "dmet_edge_features_xy_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
     "dmet_adamw_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _d, _d, _d, _d, _d, _vp]),
     "dmet_adamw_lr_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _d, _d, _d, _d, _vp]),
     "dmet_bn_knn_local_dense_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _i,

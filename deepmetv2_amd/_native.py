@@ -298,6 +298,65 @@ def knn_periodic(x: torch.Tensor, ptr: torch.Tensor, k: int, period, want_local:
     return nbr, dist, loc
 
 
+def _period_array(period, D: int):
+    """(host float array kept alive by the caller, its address) for a `period` of D floats, or (None, None)."""
+    if period is None:
+        return None, None
+    import ctypes
+    if len(period) != D:
+        raise ValueError(f"period has {len(period)} entries for {D} coordinates")
+    per = (ctypes.c_float * D)(*[float(p) for p in period])    # host array, read by the C entry before it returns
+    return per, ctypes.cast(per, ctypes.c_void_p)
+
+
+def _xy_operands(x: torch.Tensor, ptr_x: torch.Tensor, y: torch.Tensor, ptr_y: torch.Tensor):
+    dev = _require_device(x, ptr_x, y, ptr_y)
+    x = _f32c(x.detach(), "x")
+    y = _f32c(y.detach(), "y")
+    if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
+        raise ValueError(f"x and y must be [Nx, D] and [Ny, D], got {tuple(x.shape)} and {tuple(y.shape)}")
+    if ptr_x.numel() != ptr_y.numel() or ptr_x.dtype != torch.int64 or ptr_y.dtype != torch.int64:
+        raise ValueError("ptr_x and ptr_y must be int64 vectors over the same events")
+    return dev, x, y, ptr_x.contiguous(), ptr_y.contiguous()
+
+
+def knn_xy(x: torch.Tensor, ptr_x: torch.Tensor, y: torch.Tensor, ptr_y: torch.Tensor, k: int, period=None):
+    """Two point sets (dmet_knn_xy_f32): for every row of y the k nearest rows of x of the same event.  nbr[Ny,k] int32
+    (global x ids, -1 padded), dist[Ny,k] fp32 (1e10 padded).  period: None, or D floats as knn_periodic (D <= 8)."""
+    dev, x, y, ptr_x, ptr_y = _xy_operands(x, ptr_x, y, ptr_y)
+    L = _lib.load()
+    (Nx, D), Ny, B = x.shape, y.shape[0], ptr_y.numel() - 1
+    _per, per_p = _period_array(period, D)
+    nbr = torch.empty((Ny, k), dtype=torch.int32, device=dev)
+    dist = torch.empty((Ny, k), dtype=torch.float32, device=dev)
+    ws = _ws(L.dmet_knn_xy_workspace_bytes(Nx, Ny, B, D, k), dev)
+    _t = timer.record('knn', dev)
+    with _on(dev):
+        _lib.check(L.dmet_knn_xy_f32(x.data_ptr(), ptr_x.data_ptr(), Nx, y.data_ptr(), ptr_y.data_ptr(), Ny, B, D, k, per_p,
+                                     nbr.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+                   "dmet_knn_xy_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return nbr, dist
+
+
+def radius_xy(x: torch.Tensor, ptr_x: torch.Tensor, y: torch.Tensor, ptr_y: torch.Tensor, r: float, max_nbr: int,
+              period=None, pad: bool = True):
+    """Two point sets (dmet_radius_xy_f32): for every row of y the first max_nbr rows of x (ascending id) of the same
+    event within r.  (nbr[Ny,max_nbr] int32, cnt[Ny] int32); pad=False leaves the slots >= cnt[i] unwritten."""
+    dev, x, y, ptr_x, ptr_y = _xy_operands(x, ptr_x, y, ptr_y)
+    L = _lib.load()
+    (Nx, D), Ny, B = x.shape, y.shape[0], ptr_y.numel() - 1
+    _per, per_p = _period_array(period, D)
+    nbr = torch.empty((Ny, max_nbr), dtype=torch.int32, device=dev)
+    cnt = torch.empty((Ny,), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(L.dmet_radius_xy_f32(x.data_ptr(), ptr_x.data_ptr(), Nx, y.data_ptr(), ptr_y.data_ptr(), Ny, B, D,
+                                        float(r), max_nbr, per_p, 1 if pad else 0, nbr.data_ptr(), cnt.data_ptr(),
+                                        _stream(dev)), "dmet_radius_xy_f32")
+    return nbr, cnt
+
+
 def radius(x: torch.Tensor, ptr: torch.Tensor, r: float, max_nbr: int, skip_self: bool = False,
            pad: bool = True, local: bool = False, int32_rows: bool = True):
     """(nbr[N,max_nbr] int32, cnt[N] int32).  pad=False leaves the slots >= cnt[i] unwritten instead of filling them
@@ -1080,6 +1139,37 @@ def edge_features_bwd(g_feat: torch.Tensor, rowptr: torch.Tensor, srcptr: torch.
                                                 srcperm.data_ptr(), N, H, gx.data_ptr(), _stream(dev)),
                    "dmet_edge_features_bwd_f32")
     return gx
+
+
+def edge_features_xy(x_src: torch.Tensor, x_dst: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
+    """feat[e] = [x_dst[tgt[e]] || x_src[src[e]] - x_dst[tgt[e]]]; the ids must be in range (dmet_edge_features_xy_f32)."""
+    dev = _require_device(x_src, x_dst, src, tgt)
+    L = _lib.load()
+    x_src, x_dst = _f32c(x_src, "x_src"), _f32c(x_dst, "x_dst")
+    E = src.numel()
+    H = x_dst.shape[1]
+    feat = torch.empty((E, 2 * H), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(L.dmet_edge_features_xy_f32(x_src.data_ptr(), x_dst.data_ptr(), src.data_ptr(), tgt.data_ptr(), E, H,
+                                               feat.data_ptr(), _stream(dev)), "dmet_edge_features_xy_f32")
+    return feat
+
+
+def edge_features_xy_bwd(g_feat: torch.Tensor, rowptr: torch.Tensor, srcptr: torch.Tensor, srcperm: torch.Tensor,
+                         N_src: int, N_dst: int, H: int, want_src: bool = True, want_dst: bool = True):
+    """(g_x_src [N_src, H] or None, g_x_dst [N_dst, H] or None) of edge_features_xy (dmet_edge_features_xy_bwd_f32)."""
+    dev = _require_device(g_feat, rowptr, srcptr, srcperm)
+    L = _lib.load()
+    g_feat = _f32c(g_feat, "g_feat")
+    g_src = torch.empty((N_src, H), dtype=torch.float32, device=dev) if want_src else None
+    g_dst = torch.empty((N_dst, H), dtype=torch.float32, device=dev) if want_dst else None
+    with _on(dev):
+        _lib.check(L.dmet_edge_features_xy_bwd_f32(g_feat.data_ptr(), rowptr.data_ptr(), srcptr.data_ptr(),
+                                                   srcperm.data_ptr(), N_src, N_dst, H,
+                                                   g_src.data_ptr() if want_src else None,
+                                                   g_dst.data_ptr() if want_dst else None, _stream(dev)),
+                   "dmet_edge_features_xy_bwd_f32")
+    return g_src, g_dst
 
 
 def segment_max(msg: torch.Tensor, rowptr: torch.Tensor, N: int) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -1,4 +1,4 @@
-"""Graph builders with the torch_cluster signatures (`knn`, `knn_graph`, `radius_graph`).
+"""Graph builders with the torch_cluster signatures (`knn`, `knn_graph`, `radius`, `radius_graph`).
 
 Reference call sites (relative to /root/reference): model/graph_met_network.py:63 and
 model/dynamic_reduction_network.py:86,94 (knn_graph); train.py:48, evaluate.py:88, plt_weight.py:122
@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 
 from . import _native
-from .graph import NeighborTable, _deferred, batch_info
+from .graph import BipartiteTable, NeighborTable, _deferred, batch_info
 
 MAX_K = 64  # DMET_MAX_K
 
@@ -124,16 +124,93 @@ def _check_full_rows(table: NeighborTable, x: torch.Tensor, who: str) -> None:
 
 def knn(x: torch.Tensor, y: torch.Tensor, k: int, batch_x: Optional[torch.Tensor] = None,
         batch_y: Optional[torch.Tensor] = None, cosine: bool = False, num_workers: int = 1,
-        period=None) -> torch.Tensor:
-    """torch_cluster.knn restricted to the self-query form (y is x) that DynamicEdgeConv uses:
-    returns [2,E] with row 0 = query index, row 1 = neighbour index.  period: periodic coordinates, see knn_table."""
+        batch_size: Optional[int] = None, period=None) -> torch.Tensor:
+    """torch_cluster.knn: for every row of `y` (a query) the k nearest rows of `x` (the candidates) of the same event.
+    Returns int64 [2,E]: row 0 = index into y, row 1 = index into x; grouped by ascending query, ascending (distance, x
+    index) inside a query.  period: periodic coordinates, see knn_table.
+
+    The self-query form (`y is x and batch_y is batch_x`, what DynamicEdgeConv uses) is knn_table(x, k, batch_x,
+    loop=True) as it always was.  Any other call is the two-set build (knn_xy_table): separate index spaces, so no self
+    to exclude (a point present in both sets finds its twin at distance 0), a short row for a query whose event holds
+    fewer than k admissible candidates, no edge for a query event without candidates.  Its [2,E] result is sized by one
+    device-to-host read of the edge count (upstream returns an exact-size tensor too); knn_xy_table has none."""
     if cosine:
         raise NotImplementedError("cosine=True is not on the DeepMETv2 hot path")
-    if y is not x or (batch_y is not batch_x):
-        raise NotImplementedError("knn(x, y): only the self-query form y is x is implemented (DynamicEdgeConv)")
-    table = knn_table(x, k, batch_x, loop=True, period=period)
-    _check_full_rows(table, x, "knn")
-    return table.edge_index("target_to_source")
+    if y is x and batch_y is batch_x:
+        table = knn_table(x, k, batch_x, loop=True, num_events=batch_size, period=period)
+        _check_full_rows(table, x, "knn")
+        return table.edge_index("target_to_source")
+    return knn_xy_table(x, y, k, batch_x, batch_y, batch_size=batch_size, period=period).edge_index()
+
+
+def _xy_events(x: torch.Tensor, y: torch.Tensor, batch_x, batch_y, batch_size: Optional[int]):
+    """(ptr_x, ptr_y) over the same B events for the two-set builders: both batch vectors or neither; each sorted,
+    checked and cached like `batch` in knn_graph (graph.batch_info); B = the larger event count of the two, or
+    batch_size."""
+    if (batch_x is None) != (batch_y is None):
+        raise ValueError("batch_x and batch_y must be given together (or neither: one event)")
+    if x.device != y.device:
+        raise RuntimeError("deepmetv2_amd: x and y must live on the same device")
+    ix = batch_info(batch_x, x.shape[0], x.device, batch_size)
+    iy = batch_info(batch_y, y.shape[0], y.device, batch_size)
+    B = max(ix.num_events, iy.num_events)
+
+    def upto(ptr):      # trailing events without nodes
+        return ptr if ptr.numel() == B + 1 else torch.cat([ptr, ptr[-1:].expand(B + 1 - ptr.numel())])
+    return upto(ix.ptr), upto(iy.ptr)
+
+
+def _check_xy(x: torch.Tensor, y: torch.Tensor, period, max_dim: int, who: str):
+    x, y = _check_x(x), _check_x(y)
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"x has {x.shape[1]} coordinates, y has {y.shape[1]}")
+    per = _check_period(period, x.shape[1])
+    if x.shape[1] > max_dim:
+        raise ValueError(f"{who} supports up to {max_dim} coordinates, x has {x.shape[1]}")
+    if per is not None and x.shape[1] > 8:
+        raise ValueError(f"periodic coordinates are supported for up to 8 coordinates, x has {x.shape[1]}")
+    return x, y, per
+
+
+def knn_xy_table(x: torch.Tensor, y: torch.Tensor, k: int, batch_x: Optional[torch.Tensor] = None,
+                 batch_y: Optional[torch.Tensor] = None, batch_size: Optional[int] = None, period=None) -> BipartiteTable:
+    """The two-set kNN as a fixed-width table, without sizing E on the host: nbr [Ny, k] int32 ids into x (-1 in empty
+    slots), dist [Ny, k] fp32 (1e10 there).  With both batch vectors registered (register_batch) the call never
+    synchronises.  Contract: include/dmet.h, dmet_knn_xy_f32 (the fp32 chain of knn_table, `period` included; k <= 64,
+    up to 64 coordinates, 8 with a period)."""
+    x, y, per = _check_xy(x, y, period, 64, "knn")
+    if not isinstance(k, int) or isinstance(k, bool) or k < 1:
+        raise ValueError(f"k must be a positive int, got {k!r}")
+    if k > MAX_K:
+        raise ValueError(f"k={k} exceeds the supported maximum {MAX_K}")
+    ptr_x, ptr_y = _xy_events(x, y, batch_x, batch_y, batch_size)
+    nbr, dist = _native.knn_xy(x, ptr_x, y, ptr_y, k, per)
+    return BipartiteTable(nbr, ptr_x, ptr_y, x.shape[0], dist=dist)
+
+
+def radius_xy_table(x: torch.Tensor, y: torch.Tensor, r: float, batch_x: Optional[torch.Tensor] = None,
+                    batch_y: Optional[torch.Tensor] = None, max_num_neighbors: int = 32,
+                    batch_size: Optional[int] = None, period=None, pad: bool = False) -> BipartiteTable:
+    """The two-set radius search as a fixed-width table: nbr [Ny, max_num_neighbors] int32 ids into x, cnt [Ny] int32;
+    row i holds the first cnt[i] rows of x (ascending id) of the query's event with squared distance < fp32(r) * fp32(r).
+    Slots beyond cnt[i] are unwritten unless pad=True (-1).  No host sync once both batch vectors are registered.
+    Contract: include/dmet.h, dmet_radius_xy_f32 (up to 8 coordinates)."""
+    x, y, per = _check_xy(x, y, period, 8, "radius")
+    if not isinstance(max_num_neighbors, int) or isinstance(max_num_neighbors, bool) or max_num_neighbors < 1:
+        raise ValueError(f"max_num_neighbors must be a positive int, got {max_num_neighbors!r}")
+    ptr_x, ptr_y = _xy_events(x, y, batch_x, batch_y, batch_size)
+    nbr, cnt = _native.radius_xy(x, ptr_x, y, ptr_y, r, max_num_neighbors, per, pad)
+    return BipartiteTable(nbr, ptr_x, ptr_y, x.shape[0], cnt=cnt)
+
+
+def radius(x: torch.Tensor, y: torch.Tensor, r: float, batch_x: Optional[torch.Tensor] = None,
+           batch_y: Optional[torch.Tensor] = None, max_num_neighbors: int = 32, num_workers: int = 1,
+           batch_size: Optional[int] = None, period=None) -> torch.Tensor:
+    """torch_cluster.radius: for every row of `y` all rows of `x` of the same event within r (squared distance
+    < fp32(r) * fp32(r)), the first max_num_neighbors hits in ascending x index (radius_graph's rule).  int64 [2,E]: row 0 =
+    index into y, row 1 = index into x.  period: periodic coordinates, see radius_table.  Sized by one device-to-host
+    read of the edge count; radius_xy_table has none."""
+    return radius_xy_table(x, y, r, batch_x, batch_y, max_num_neighbors, batch_size, period).edge_index()
 
 
 def _check_period(period, D: int) -> Optional[list]:

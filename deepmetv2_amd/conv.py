@@ -16,8 +16,8 @@ from typing import Callable, Optional, Tuple, Union
 import torch
 
 from . import _native
-from .cluster import fp16_autocast, knn_table
-from .graph import EdgeList, GraphFuture, NeighborTable, batch_info, edge_list_from_edge_index, lookup_graph
+from .cluster import fp16_autocast, knn_table, knn_xy_table
+from .graph import BipartiteTable, EdgeList, GraphFuture, NeighborTable, batch_info, edge_list_from_edge_index, lookup_graph
 from .scatter import _SegmentMaxRows, _SegmentSumRows
 from torch.autograd.function import once_differentiable
 
@@ -441,12 +441,33 @@ class _EdgeFeatures(torch.autograd.Function):
         return _native.edge_features_bwd(g_feat.contiguous(), edges.rowptr, srcptr, srcperm, N, H), None
 
 
+class _EdgeFeaturesXY(torch.autograd.Function):
+    """feat[e] = [x_dst[tgt] || x_src[src] - x_dst[tgt]] for a by-target grouped edge list over two node sets."""
+
+    @staticmethod
+    def forward(ctx, x_src, x_dst, edges: EdgeList):
+        ctx.edges = edges
+        ctx.n_src, ctx.n_dst, ctx.width = x_src.shape[0], x_dst.shape[0], x_dst.shape[1]
+        return _native.edge_features_xy(x_src, x_dst, edges.src, edges.tgt)
+
+    @staticmethod
+    def backward(ctx, g_feat):
+        edges: EdgeList = ctx.edges
+        srcptr, srcperm = edges.by_source()
+        g_src, g_dst = _native.edge_features_xy_bwd(g_feat.contiguous(), edges.rowptr, srcptr, srcperm, ctx.n_src, ctx.n_dst,
+                                                    ctx.width, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return g_src, g_dst, None
+
+
 class EdgeConv(torch.nn.Module):
     r"""torch_geometric.nn.EdgeConv: :math:`x_i' = \mathrm{aggr}_{j \in N(i)} \; nn([x_i \,\|\, x_j - x_i])`.
 
     Args mirror PyG: ``nn`` (any callable mapping [*, 2F_in] -> [*, F_out]), ``aggr`` in {'max','add','sum','mean'},
     ``flow`` keyword.  ``forward(x, edge_index)`` takes a [N,F] tensor (or a pair of identical tensors) and an int64
-    [2,E] edge index.
+    [2,E] edge index.  A pair of DIFFERENT tensors ``(x_src, x_dst)`` is the two-set form: ``edge_index[0]`` indexes
+    ``x_src`` and ``edge_index[1]`` ``x_dst`` for ``flow='source_to_target'`` (reversed for the other flow), the output is
+    [N_dst, F_out], rows of ``x_dst`` without an edge give 0; it always runs the generic route below
+    (csrc/edgeconv.hip, ``dmet_edge_features_xy_f32``).
 
     Fused routes by ``nn``: a single ``Linear(2F, F')`` with max aggregation (F, F' in {32, 64}) runs through the
     per-node split (csrc/edgeconv.hip); with add / sum / mean aggregation the same ``Linear`` runs through the split and a
@@ -626,12 +647,13 @@ class EdgeConv(torch.nn.Module):
         return _EdgeMLP2F32.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, bn.weight if bn is not None else None,
                                   bn.bias if bn is not None else None, edges, act2, self.aggr, bn)
 
-    def _forward_edges(self, x: torch.Tensor, edges: EdgeList) -> torch.Tensor:
+    def _forward_edges(self, x: torch.Tensor, edges: EdgeList, x_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The generic route.  x_src: the sources' own node set (two-set form); x is then x_dst, the targets."""
         N = x.shape[0]
         if edges.num_edges == 0:
             probe = self.nn(x.new_zeros((1, 2 * x.shape[1])))
             return x.new_zeros((N, probe.shape[-1]))
-        feat = _EdgeFeatures.apply(x, edges)
+        feat = _EdgeFeatures.apply(x, edges) if x_src is None else _EdgeFeaturesXY.apply(x_src, x, edges)
         msg = self.nn(feat)
         if msg.dim() != 2 or msg.shape[0] != edges.num_edges:
             raise ValueError("nn must map [E, 2F] -> [E, F_out]")
@@ -650,14 +672,9 @@ class EdgeConv(torch.nn.Module):
     def forward(self, x: Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]], edge_index: torch.Tensor) -> torch.Tensor:
         if isinstance(x, (tuple, list)):
             if x[1] is not None and x[1] is not x[0]:
-                raise NotImplementedError("bipartite EdgeConv (x_src is not x_dst) is outside the hot path")
+                return self._forward_pair(x[0], x[1], edge_index)
             x = x[0]
-        if x.dim() != 2:
-            raise ValueError(f"x must be [N, F], got {tuple(x.shape)}")
-        if x.dtype == torch.bfloat16 or (x.dtype == torch.float16 and self._takes_fp16()):
-            x = x.float()       # autocast upstream: exact upcast, gradients flow back through it in x's dtype
-        if x.dtype != torch.float32:
-            raise TypeError(f"x must be float32, got {x.dtype}")
+        x = self._check_features(x, "x")
         if isinstance(edge_index, GraphFuture):
             # built on a side stream (graph.build_async): the consumer joins as late as it can (NeighborTable.join)
             edge_index = edge_index.peek() if isinstance(edge_index.peek(), NeighborTable) else edge_index.result()
@@ -669,6 +686,31 @@ class EdgeConv(torch.nn.Module):
         if hit is not None and hit[1] == self.flow and hit[0].num_nodes == x.shape[0]:
             return self._forward_table(x, hit[0])
         return self._forward_edge_list(x, edge_list_from_edge_index(edge_index, x.shape[0], self.flow))
+
+    def _check_features(self, x: torch.Tensor, name: str) -> torch.Tensor:
+        if x.dim() != 2:
+            raise ValueError(f"{name} must be [N, F], got {tuple(x.shape)}")
+        if x.dtype == torch.bfloat16 or (x.dtype == torch.float16 and self._takes_fp16()):
+            x = x.float()       # autocast upstream: exact upcast, gradients flow back through it in x's dtype
+        if x.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {x.dtype}")
+        return x
+
+    def _forward_pair(self, x_src: torch.Tensor, x_dst: torch.Tensor, edge_index) -> torch.Tensor:
+        """Two node sets: out[i] = aggr over the edges (j, i) of nn([x_dst[i] || x_src[j] - x_dst[i]]), [N_dst, F_out].
+        edge_index: int64 [2,E] (range-checked against the two sizes), or a BipartiteTable whose queries are x_dst and
+        whose candidates are x_src (its empty slots are no edges).  Generic route only."""
+        x_src, x_dst = self._check_features(x_src, "x_src"), self._check_features(x_dst, "x_dst")
+        if x_src.shape[1] != x_dst.shape[1]:
+            raise ValueError(f"x_src has {x_src.shape[1]} features, x_dst has {x_dst.shape[1]}")
+        if isinstance(edge_index, BipartiteTable):
+            if (edge_index.num_candidates, edge_index.num_queries) != (x_src.shape[0], x_dst.shape[0]):
+                raise ValueError(f"the table connects {edge_index.num_queries} queries to {edge_index.num_candidates} "
+                                 f"candidates, x_dst / x_src have {x_dst.shape[0]} / {x_src.shape[0]} rows")
+            edges = edge_index.edge_list()
+        else:
+            edges = edge_list_from_edge_index(edge_index, x_dst.shape[0], self.flow, num_src=x_src.shape[0])
+        return self._forward_edges(x_dst, edges, x_src)
 
     # -- BatchNorm transform of the PREVIOUS block fused into this layer's node-level dense layer (static graphs) --------
     def prebuild_hook(self, batch=None, graph=None):
@@ -728,7 +770,9 @@ class EdgeConv(torch.nn.Module):
 
 class DynamicEdgeConv(EdgeConv):
     r"""torch_geometric.nn.DynamicEdgeConv: the graph is the k nearest neighbours of every node in the CURRENT
-    feature space (self included), rebuilt on every call: ``knn(x, x, k, batch, batch).flip(0)`` upstream."""
+    feature space (self included), rebuilt on every call: ``knn(x, x, k, batch, batch).flip(0)`` upstream.
+    ``forward((x_src, x_dst), (batch_src, batch_dst))`` with different tensors connects every row of ``x_dst`` to its k
+    nearest rows of ``x_src`` (``knn(x_src, x_dst, k, batch_src, batch_dst)``) and runs the two-set EdgeConv over them."""
 
     def __init__(self, nn: Callable, k: int, aggr: str = "max", num_workers: int = 1, **kwargs):
         super().__init__(nn=nn, aggr=aggr, **kwargs)
@@ -741,7 +785,10 @@ class DynamicEdgeConv(EdgeConv):
                 batch: Union[None, torch.Tensor, Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
         if isinstance(x, (tuple, list)):
             if x[1] is not None and x[1] is not x[0]:
-                raise NotImplementedError("bipartite DynamicEdgeConv is outside the hot path")
+                # two node sets: the k nearest rows of x_src for every row of x_dst, in the current feature space
+                x_src, x_dst = self._check_features(x[0], "x_src"), self._check_features(x[1], "x_dst")
+                b_src, b_dst = batch if isinstance(batch, (tuple, list)) else (batch, batch)
+                return self._forward_pair(x_src, x_dst, knn_xy_table(x_src, x_dst, self.k, b_src, b_dst))
             x = x[0]
         if isinstance(batch, (tuple, list)):
             batch = batch[0]

@@ -1087,6 +1087,66 @@ __global__ __launch_bounds__(256) void edge_features_bwd_kernel(const float *__r
     gx[gid] = s;
 }
 
+// Two node sets (EdgeConv((x_src, x_dst), edge_index)): src[e] indexes x_src, tgt[e] indexes x_dst.  V = 4: float4 pieces
+// (H a multiple of 4, rows 16-byte aligned), V = 1: any H.
+template <int V>
+__global__ __launch_bounds__(256) void edge_features_xy_kernel(const float *__restrict__ x_src,
+                                                                const float *__restrict__ x_dst,
+                                                                const int32_t *__restrict__ src,
+                                                                const int32_t *__restrict__ tgt, int64_t E, int H,
+                                                                float *__restrict__ feat)
+{
+    const int hv = H / V;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e = gid / hv;
+    const int c = (int)(gid - e * hv);
+    if (e >= E) return;
+    const int64_t i = tgt[e], j = src[e];
+    if (V == 4) {
+        const float4 xi = reinterpret_cast<const float4 *>(x_dst)[i * hv + c];
+        const float4 xj = reinterpret_cast<const float4 *>(x_src)[j * hv + c];
+        float4 *o = reinterpret_cast<float4 *>(feat) + e * (2 * hv);
+        o[c] = xi;
+        o[hv + c] = make_float4(xj.x - xi.x, xj.y - xi.y, xj.z - xi.z, xj.w - xi.w);
+    } else {
+        const float xi = x_dst[i * H + c], xj = x_src[j * H + c];
+        feat[e * (2 * H) + c] = xi;
+        feat[e * (2 * H) + H + c] = xj - xi;
+    }
+}
+
+// g_x_dst[i] = sum over the edges of row i of (g_a - g_b), ascending e
+__global__ __launch_bounds__(256) void edge_features_xy_bwd_dst_kernel(const float *__restrict__ g_feat,
+                                                                        const int32_t *__restrict__ rowptr, int64_t N_dst,
+                                                                        int H, float *__restrict__ g_x_dst)
+{
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = gid / H;
+    const int c = (int)(gid - i * H);
+    if (i >= N_dst) return;
+    float s = 0.0f;
+    for (int e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+        const float *g = g_feat + (int64_t)e * (2 * H);
+        s += g[c] - g[H + c];
+    }
+    g_x_dst[gid] = s;
+}
+
+// g_x_src[j] = sum over the edges leaving j of g_b, in ascending edge position (srcperm is sorted inside a group)
+__global__ __launch_bounds__(256) void edge_features_xy_bwd_src_kernel(const float *__restrict__ g_feat,
+                                                                        const int32_t *__restrict__ srcptr,
+                                                                        const int32_t *__restrict__ srcperm, int64_t N_src,
+                                                                        int H, float *__restrict__ g_x_src)
+{
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t j = gid / H;
+    const int c = (int)(gid - j * H);
+    if (j >= N_src) return;
+    float s = 0.0f;
+    for (int rp = srcptr[j]; rp < srcptr[j + 1]; ++rp) s += g_feat[(int64_t)srcperm[rp] * (2 * H) + H + c];
+    g_x_src[gid] = s;
+}
+
 template <int HIN, int HOUT, bool SLICED = false>
 int launch_node_linear(const float *x, int64_t N, const float *W, const float *b, float *P, float *Q,
                        hipStream_t st)
@@ -1702,5 +1762,46 @@ extern "C" int dmet_edge_features_bwd_f32(const float *g_feat, const int32_t *ro
     hipLaunchKernelGGL(edge_features_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        as_stream(stream), g_feat, rowptr, srcptr, srcperm, N, H, gx);
     DMET_LAUNCH_CHECK("edge_features_bwd_kernel");
+    return 0;
+}
+
+extern "C" int dmet_edge_features_xy_f32(const float *x_src, const float *x_dst, const int32_t *src, const int32_t *tgt,
+                                         int64_t E, int H, float *feat, dmet_stream_t stream)
+{
+    DMET_REQUIRE(E >= 0 && H > 0, "dmet_edge_features_xy_f32: bad sizes (E=%lld, H=%d)", (long long)E, H);
+    if (E == 0) return 0;
+    DMET_REQUIRE(x_src && x_dst && src && tgt && feat, "dmet_edge_features_xy_f32: null pointer");
+    if (H % 4 == 0 && aligned16(x_src) && aligned16(x_dst) && aligned16(feat)) {
+        const int64_t total = E * (H / 4);
+        hipLaunchKernelGGL((edge_features_xy_kernel<4>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                           as_stream(stream), x_src, x_dst, src, tgt, E, H, feat);
+    } else {
+        const int64_t total = E * H;
+        hipLaunchKernelGGL((edge_features_xy_kernel<1>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                           as_stream(stream), x_src, x_dst, src, tgt, E, H, feat);
+    }
+    DMET_LAUNCH_CHECK("edge_features_xy_kernel");
+    return 0;
+}
+
+extern "C" int dmet_edge_features_xy_bwd_f32(const float *g_feat, const int32_t *rowptr, const int32_t *srcptr,
+                                             const int32_t *srcperm, int64_t N_src, int64_t N_dst, int H, float *g_x_src,
+                                             float *g_x_dst, dmet_stream_t stream)
+{
+    DMET_REQUIRE(N_src >= 0 && N_dst >= 0 && H > 0, "dmet_edge_features_xy_bwd_f32: bad sizes");
+    if (g_x_dst && N_dst > 0) {
+        DMET_REQUIRE(rowptr, "dmet_edge_features_xy_bwd_f32: null rowptr");
+        const int64_t total = N_dst * H;
+        hipLaunchKernelGGL(edge_features_xy_bwd_dst_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                           as_stream(stream), g_feat, rowptr, N_dst, H, g_x_dst);
+        DMET_LAUNCH_CHECK("edge_features_xy_bwd_dst_kernel");
+    }
+    if (g_x_src && N_src > 0) {
+        DMET_REQUIRE(srcptr && srcperm, "dmet_edge_features_xy_bwd_f32: null by-source index");
+        const int64_t total = N_src * H;
+        hipLaunchKernelGGL(edge_features_xy_bwd_src_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                           as_stream(stream), g_feat, srcptr, srcperm, N_src, H, g_x_src);
+        DMET_LAUNCH_CHECK("edge_features_xy_bwd_src_kernel");
+    }
     return 0;
 }

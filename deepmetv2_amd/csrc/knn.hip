@@ -34,6 +34,8 @@
 //     partial top-k lists a small merge kernel combines.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "nls_body.h"
 
@@ -102,6 +104,19 @@ struct RadPeriod { float L[8]; };
 // code as without periods), Per = RadPeriod wraps every coordinate c with L[c]
 __device__ __forceinline__ RadPeriod rad_periods() { return RadPeriod{}; }
 __device__ __forceinline__ RadPeriod rad_periods(const RadPeriod &p) { return p; }
+
+// Two point sets (dmet_knn_xy_f32 / dmet_radius_xy_f32) ride the same way, after the periods: with a KnnQuerySet in the
+// pack the QUERY rows and their events come from it and the kernel's x / ptr are the candidates alone; without one both
+// sides are x / ptr, and the kernel is the one-set kernel, argument for argument and instruction for instruction.
+struct KnnQuerySet { const float *qx; const int64_t *qptr; };
+__device__ __forceinline__ RadPeriod rad_periods(const KnnQuerySet &) { return RadPeriod{}; }
+__device__ __forceinline__ RadPeriod rad_periods(const RadPeriod &p, const KnnQuerySet &) { return p; }
+__device__ __forceinline__ KnnQuerySet query_set(const float *x, const int64_t *ptr) { return KnnQuerySet{x, ptr}; }
+__device__ __forceinline__ KnnQuerySet query_set(const float *x, const int64_t *ptr, const RadPeriod &) { return KnnQuerySet{x, ptr}; }
+__device__ __forceinline__ KnnQuerySet query_set(const float *, const int64_t *, const KnnQuerySet &q) { return q; }
+__device__ __forceinline__ KnnQuerySet query_set(const float *, const int64_t *, const RadPeriod &, const KnnQuerySet &q) { return q; }
+template <typename T, typename... Pack>
+constexpr bool pack_has = (std::is_same<T, Pack>::value || ...);
 
 // The periodic kNN sweep (knn_kernel with Per = RadPeriod) takes one coordinate at a time: the candidate feature is
 // broadcast and the query pair subtracted as in pk_dist_step4 (tA / tB: candidates A / B), a periodic coordinate is then
@@ -304,7 +319,13 @@ __device__ __forceinline__ int xcd_dealt_position(int rank, int B)
 }
 
 // blockIdx.x selects one of up to two plans (exact kernel: 128-query tiles; matrix-core filter: 64-query tiles)
-__device__ __forceinline__ void knn_plan_body(const int64_t *__restrict__ ptr, int B, const KnnPlanOut &o)
+// XY (dmet_knn_xy_f32): `ptr` cuts the QUERIES into tiles and `cptr` holds the candidates of the same events.  A tile
+// sweeps its event's nx candidates whatever number of queries it holds, so "longest first" ranks the events by nx
+// (ties: more queries first); tiles (from ny) times sweep length (nx) is the event's pair count.  The tail is cut into
+// sub-sweeps when the events that have queries hold 512 candidates on average.
+template <bool XY = false>
+__device__ __forceinline__ void knn_plan_body(const int64_t *__restrict__ ptr, int B, const KnnPlanOut &o,
+                                              const int64_t *__restrict__ cptr = nullptr)
 {
     const int tile_queries = o.tile_queries, simds = o.simds, max_split = o.max_split;
     int32_t *__restrict__ order = o.order, *__restrict__ pos_of = o.pos_of, *__restrict__ tile_ptr = o.tile_ptr;
@@ -315,9 +336,18 @@ __device__ __forceinline__ void knn_plan_body(const int64_t *__restrict__ ptr, i
         for (int b = tid; b < B; b += 256) {
             const int64_t nb = ptr[b + 1] - ptr[b];
             int rank = 0;
-            for (int c = 0; c < B; ++c) {
-                const int64_t nc = ptr[c + 1] - ptr[c];
-                rank += (nc > nb || (nc == nb && c < b)) ? 1 : 0;
+            if constexpr (XY) {
+                const int64_t xb = nb > 0 ? cptr[b + 1] - cptr[b] : -1;     // events without queries go last: no tiles
+                for (int c = 0; c < B; ++c) {
+                    const int64_t nc = ptr[c + 1] - ptr[c];
+                    const int64_t xc = nc > 0 ? cptr[c + 1] - cptr[c] : -1;
+                    rank += (xc > xb || (xc == xb && (nc > nb || (nc == nb && c < b)))) ? 1 : 0;
+                }
+            } else {
+                for (int c = 0; c < B; ++c) {
+                    const int64_t nc = ptr[c + 1] - ptr[c];
+                    rank += (nc > nb || (nc == nb && c < b)) ? 1 : 0;
+                }
             }
             const int p = xcd_dealt_position(rank, B);
             order[p] = b;
@@ -335,6 +365,20 @@ __device__ __forceinline__ void knn_plan_body(const int64_t *__restrict__ ptr, i
         const int64_t nb = ptr[b + 1] - ptr[b];
         sum += (int)((nb + tile_queries - 1) / tile_queries);
         nf1 += (nb > 0 && !(nb >= kF2MinNodes && nb <= kF2MaxNodes)) ? 1 : 0;
+    }
+    // XY: candidates of the events that have queries, and the number of such events (for the tail rule below)
+    __shared__ unsigned long long xy_cand;
+    __shared__ int xy_events;
+    if constexpr (XY) {
+        if (tid == 0) { xy_cand = 0ull; xy_events = 0; }
+        __syncthreads();
+        unsigned long long cand = 0ull;
+        int evs = 0;
+        for (int p = lo; p < hi; ++p) {
+            const int b = order[p];
+            if (ptr[b + 1] > ptr[b]) { cand += (unsigned long long)(cptr[b + 1] - cptr[b]); ++evs; }
+        }
+        if (evs) { atomicAdd(&xy_cand, cand); atomicAdd(&xy_events, evs); }   // integer sums: order does not matter
     }
     // exclusive prefix of the per-thread tile counts and the number of first-form events: wavefront scans + four
     // wavefront totals (a serial walk of thread 0 over 256 LDS cells was a third of the prep launch: it sits on the
@@ -364,7 +408,10 @@ __device__ __forceinline__ void knn_plan_body(const int64_t *__restrict__ ptr, i
         // would be a handful of candidates)
         const int full = (tiles / simds) * simds;
         const int rem = tiles - full;
-        if (rem > 0 && B > 0 && (ptr[B] - ptr[0]) >= (int64_t)512 * B) {
+        bool cut = rem > 0;
+        if constexpr (XY) cut = cut && xy_events > 0 && xy_cand >= 512ull * (unsigned long long)xy_events;
+        else cut = cut && B > 0 && (ptr[B] - ptr[0]) >= (int64_t)512 * B;
+        if (cut) {
             int f = simds / rem;
             if (f > max_split) f = max_split;
             if (f >= 2) { n_full = full; split = f; }
@@ -418,6 +465,12 @@ __device__ __forceinline__ void knn_plan_body(const int64_t *__restrict__ ptr, i
 __global__ __launch_bounds__(256) void knn_plan_kernel(const int64_t *__restrict__ ptr, int B, KnnPlanOut o0, KnnPlanOut o1)
 {
     knn_plan_body(ptr, B, blockIdx.x == 0 ? o0 : o1);
+}
+
+__global__ __launch_bounds__(256) void knn_plan_xy_kernel(const int64_t *__restrict__ qptr, const int64_t *__restrict__ cptr,
+                                                          int B, KnnPlanOut o)
+{
+    knn_plan_body<true>(qptr, B, o, cptr);
 }
 
 // Position (in the longest-first order) that owns tile t: the p with tile_ptr[p] <= t < tile_ptr[p+1].
@@ -595,10 +648,13 @@ __device__ __forceinline__ void knn_requery_body(const KnnArgs &a, float *__rest
 // plain coordinates and on the padding coordinates c >= D, so those take the plain step.  An empty pack is the plain
 // kernel.  Padded coordinates (0 - 0) and rows past a partial tile (+inf) behave as in the plain kernel: a periodic
 // coordinate turns inf - q into |.| = inf, L - inf = -inf, squared +inf, so such a candidate is never admitted.
+// XY (a KnnQuerySet after the periods, dmet_knn_xy_f32): the queries are the rows of qx cut into tiles by qptr, the
+// candidates of a tile are the rows [ptr[ev], ptr[ev+1]) of a.x, and a.nbr / a.dist / a.wsd / a.wsj are indexed by query;
+// everything else -- staging, sweep, lists, split tail -- is the same code.
 template <int DP, int KP, int TQ, bool EXACT_D, typename... Per>
 __global__ __launch_bounds__(kWave * kWavesPerGroup, 3) void knn_kernel(const KnnArgs a, Per... per_arg)
 {
-    constexpr bool PER = sizeof...(Per) > 0;
+    constexpr bool PER = pack_has<RadPeriod, Per...>, XY = pack_has<KnnQuerySet, Per...>;
     static_assert(!PER || TQ == 2, "the periodic sweep is the packed two-query form (D <= 8)");
     const RadPeriod per = rad_periods(per_arg...);
     // A workgroup is kWavesPerGroup INDEPENDENT wavefronts (one work item each, no workgroup barrier): the hardware
@@ -610,7 +666,7 @@ __global__ __launch_bounds__(kWave * kWavesPerGroup, 3) void knn_kernel(const Kn
     const int wv_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     KnnShared<DP, TQ> &sh = sh_all[wv_];
     int first_group = 0;
-    if constexpr (DP == 32) {
+    if constexpr (DP == 32 && !XY) {
         if (a.qlist) {    // (kernel-uniform) matrix-core path: the leading workgroups are the per-query fallback
             if (a.any && *a.any == 0) return;
             if ((int)blockIdx.x < a.requery_groups) {
@@ -638,6 +694,9 @@ __global__ __launch_bounds__(kWave * kWavesPerGroup, 3) void knn_kernel(const Kn
 #endif
     const float *__restrict__ x = a.x;
     const int64_t *__restrict__ ptr = a.ptr;
+    const KnnQuerySet qs = query_set(a.x, a.ptr, per_arg...);
+    const float *__restrict__ qx = qs.qx;            // query rows and their events (x / ptr unless XY)
+    const int64_t *__restrict__ qptr = qs.qptr;
     const int D = a.D;
     constexpr int QT = kWave * TQ;  // queries per tile
 
@@ -657,11 +716,11 @@ __global__ __launch_bounds__(kWave * kWavesPerGroup, 3) void knn_kernel(const Kn
     if (a.flags && a.flags[tile] < a.flag_min) return;
     const int pos = find_tile_event(a.tile_ptr, a.B, tile);
     const int ev = a.order[pos];
-    const int ev_lo = (int)ptr[ev], ev_hi = (int)ptr[ev + 1];
+    const int ev_lo = (int)qptr[ev], ev_hi = (int)qptr[ev + 1];
     const int q_first = ev_lo + (tile - a.tile_ptr[pos]) * QT;
 
     // candidate range = the tile's own event (or one chunk of it for a split tile)
-    int clo = ev_lo, chi = ev_hi;
+    int clo = XY ? (int)ptr[ev] : ev_lo, chi = XY ? (int)ptr[ev + 1] : ev_hi;
     if (nsub > 1) {
         const int chunk = (((chi - clo) + nsub - 1) / nsub + 1) & ~1;  // even: candidate pairs never straddle chunks
         clo = min(chi, clo + sub * chunk);
@@ -684,7 +743,7 @@ __global__ __launch_bounds__(kWave * kWavesPerGroup, 3) void knn_kernel(const Kn
 #pragma unroll
         for (int c = 0; c < DP; ++c) {
             float v;
-            if (EXACT_D) v = x[qq * DP + c]; else v = (c < D) ? x[qq * D + c] : 0.0f;
+            if (EXACT_D) v = qx[qq * DP + c]; else v = (c < D) ? qx[qq * D + c] : 0.0f;
             if (TQ == 2) { if (t == 0) q2[c].x = v; else q2[c].y = v; }
             else q1[c] = v;
         }
@@ -818,8 +877,8 @@ __global__ __launch_bounds__(kWave * kWavesPerGroup, 3) void knn_kernel(const Kn
 
 // Merge the `split` sorted partial lists of every query of the split tiles: k steps of a `split`-way merge by
 // (d, j); sentinels (1e10, -1) sort last.  One lane per query slot of the tail tiles (worst-case grid).
-template <int KP>
-__global__ __launch_bounds__(256) void knn_merge_kernel(const KnnArgs a, int tile_queries)
+template <int KP, typename... Qs>
+__global__ __launch_bounds__(256) void knn_merge_kernel(const KnnArgs a, int tile_queries, Qs... qs_arg)
 {
     if (a.any && *a.any == 0) return;
     const int n_full = a.plan->n_full, split = a.plan->split, total = a.plan->total_tiles;
@@ -830,8 +889,9 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const KnnArgs a, int til
     if (a.flags && a.flags[tile] < a.flag_min) return;
     const int pos = find_tile_event(a.tile_ptr, a.B, tile);
     const int ev = a.order[pos];
-    const int64_t qi = a.ptr[ev] + (int64_t)(tile - a.tile_ptr[pos]) * tile_queries + (slot % tile_queries);
-    if (qi >= a.ptr[ev + 1]) return;
+    const int64_t *__restrict__ qptr = query_set(a.x, a.ptr, qs_arg...).qptr;     // the queries' events
+    const int64_t qi = qptr[ev] + (int64_t)(tile - a.tile_ptr[pos]) * tile_queries + (slot % tile_queries);
+    if (qi >= qptr[ev + 1]) return;
     const float *pd = a.psd + slot * split * KP;
     const int32_t *pj = a.psj + slot * split * KP;
     int head[kMaxSplit];
@@ -3005,6 +3065,76 @@ int dispatch_k(const float *x, const int64_t *ptr, int B, int64_t N, int D, int 
     return launch_knn<DP, 64>(x, ptr, B, N, D, k, nbr, dist, nbr16, w, st, per);
 }
 
+// ---- two-set build (dmet_knn_xy_f32): the exact kernel with the queries cut from y and the candidates from x ----------
+// The workspace holds the exact kernel's part only: plan, order, tile prefix, the running lists of the Ny queries, the
+// partial lists of the split tail.
+inline KnnWorkspace carve_workspace_xy(void *ws, int64_t Ny, int B, int KP)
+{
+    KnnWorkspace w{};
+    uintptr_t p = (reinterpret_cast<uintptr_t>(ws) + 255u) & ~(uintptr_t)255u;
+    auto take = [&](size_t nbytes) { uintptr_t r = p; p = (p + nbytes + 255u) & ~(uintptr_t)255u; return r; };
+    size_t split_q = (size_t)kMaxSimds * 128;
+    if ((size_t)Ny + 128 * ((size_t)B + 1) < split_q) split_q = (size_t)Ny + 128 * ((size_t)B + 1);
+    const size_t ps_elems = split_q * kMaxSplit * KP;
+    w.plan = reinterpret_cast<KnnPlan *>(take(sizeof(KnnPlan)));
+    w.order = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * ((size_t)B + 1)));
+    w.pos_of = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * ((size_t)B + 1)));
+    w.tile_ptr = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * ((size_t)B + 1)));
+    w.wsd = reinterpret_cast<float *>(take(sizeof(float) * (size_t)Ny * KP));
+    w.wsj = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * (size_t)Ny * KP));
+    w.psd = reinterpret_cast<float *>(take(sizeof(float) * ps_elems));
+    w.psj = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * ps_elems));
+    w.bytes = (size_t)(p - reinterpret_cast<uintptr_t>(ws));
+    return w;
+}
+
+template <int DP, int KP>
+int launch_knn_xy(const float *x, const int64_t *ptr_x, const float *y, const int64_t *ptr_y, int64_t Ny, int B, int D, int k,
+                  int32_t *nbr, float *dist, const KnnWorkspace &w, hipStream_t st, const RadPeriod *per)
+{
+    constexpr int TQ = (DP <= 32) ? 2 : 1;
+    constexpr int QT = kWave * TQ;
+    int simds = num_simds();
+    if (simds > kMaxSimds) simds = kMaxSimds;
+    const KnnPlanOut px{QT, simds, kMaxSplit, w.order, w.pos_of, w.tile_ptr, w.plan};
+    hipLaunchKernelGGL(knn_plan_xy_kernel, dim3(1), dim3(256), 0, st, ptr_y, ptr_x, B, px);
+    DMET_LAUNCH_CHECK("knn_plan_xy_kernel");
+    KnnArgs a{x, ptr_x, B, Ny, D, k, nbr, dist, nullptr, w.wsd, w.wsj, w.plan, w.order, w.tile_ptr, w.psd, w.psj, nullptr, 0,
+              nullptr, nullptr, nullptr, 0, QT};
+    const KnnQuerySet qs{y, ptr_y};
+    const int64_t tiles_max = (Ny + QT - 1) / QT + B;   // as launch_knn: a worst-case grid, surplus wavefronts exit at once
+    const int64_t blocks = (tiles_max + simds + kWavesPerGroup - 1) / kWavesPerGroup;
+    const bool exact_d = D == DP && aligned16(x) && aligned16(y);
+    const dim3 grid((unsigned)blocks), block(kWave * kWavesPerGroup);
+    if (per) {   // (dmet_knn_xy_f32 checked D <= 8)
+        if constexpr (DP <= 8) {
+            if (exact_d) hipLaunchKernelGGL((knn_kernel<DP, KP, TQ, true, RadPeriod, KnnQuerySet>), grid, block, 0, st, a, *per, qs);
+            else hipLaunchKernelGGL((knn_kernel<DP, KP, TQ, false, RadPeriod, KnnQuerySet>), grid, block, 0, st, a, *per, qs);
+        }
+    } else if (exact_d)
+        hipLaunchKernelGGL((knn_kernel<DP, KP, TQ, true, KnnQuerySet>), grid, block, 0, st, a, qs);
+    else
+        hipLaunchKernelGGL((knn_kernel<DP, KP, TQ, false, KnnQuerySet>), grid, block, 0, st, a, qs);
+    DMET_LAUNCH_CHECK("knn_kernel (two sets)");
+    int64_t slots = (int64_t)simds * QT;
+    if (tiles_max * QT < slots) slots = tiles_max * QT;
+    hipLaunchKernelGGL((knn_merge_kernel<KP, KnnQuerySet>), dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, a, QT, qs);
+    DMET_LAUNCH_CHECK("knn_merge_kernel (two sets)");
+    return 0;
+}
+
+template <int DP>
+int dispatch_k_xy(const float *x, const int64_t *ptr_x, const float *y, const int64_t *ptr_y, int64_t Ny, int B, int D, int k,
+                  int32_t *nbr, float *dist, void *ws, hipStream_t st, const RadPeriod *per)
+{
+    const int KP = padded_k(k);
+    const KnnWorkspace w = carve_workspace_xy(ws, Ny, B, KP);
+    if (k <= 8) return launch_knn_xy<DP, 8>(x, ptr_x, y, ptr_y, Ny, B, D, k, nbr, dist, w, st, per);
+    if (k <= 16) return launch_knn_xy<DP, 16>(x, ptr_x, y, ptr_y, Ny, B, D, k, nbr, dist, w, st, per);
+    if (k <= 32) return launch_knn_xy<DP, 32>(x, ptr_x, y, ptr_y, Ny, B, D, k, nbr, dist, w, st, per);
+    return launch_knn_xy<DP, 64>(x, ptr_x, y, ptr_y, Ny, B, D, k, nbr, dist, w, st, per);
+}
+
 // ---- radius graph (N1): first max_nbr candidates in ascending index with d < r^2 ------------------------
 // One lane per query, four independent wavefronts per workgroup (no workgroup barrier).  Candidates are staged per
 // wavefront in LDS as [pair][feature][2] so that one broadcast read yields a feature of two candidates in adjacent
@@ -3021,6 +3151,8 @@ __device__ __forceinline__ f2 rad_wrap(f2 df, float L)
     return f2{fminf(ax, L - ax), fminf(ay, L - ay)};
 }
 
+// With a KnnQuerySet after the periods (dmet_radius_xy_f32) the 64 queries of a wavefront are rows of qx (events qptr, N rows
+// in all) and x / ptr hold the candidates of the same events; skip_self is then 0.
 template <int DP, typename... Per>
 __global__ __launch_bounds__(kWave * 4) void radius_kernel(const float *__restrict__ x,
                                                             const int64_t *__restrict__ ptr, int B, int64_t N, int D,
@@ -3028,16 +3160,19 @@ __global__ __launch_bounds__(kWave * 4) void radius_kernel(const float *__restri
                                                             int32_t *__restrict__ nbr, int32_t *__restrict__ cntout,
                                                             Per... per_arg)
 {
-    constexpr bool PER = sizeof...(Per) > 0;
+    constexpr bool PER = pack_has<RadPeriod, Per...>;
     const RadPeriod per = rad_periods(per_arg...);
+    const KnnQuerySet qs = query_set(x, ptr, per_arg...);
+    const float *__restrict__ qx = qs.qx;
+    const int64_t *__restrict__ qptr = qs.qptr;
     __shared__ f2 tile_all[4][(kRadTile / 2) * DP];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     f2 *tile = tile_all[wv];
     const int64_t q_first = ((int64_t)blockIdx.x * 4 + wv) * kWave;
     if (q_first >= N) return;
     const int64_t q_last = min(N, q_first + kWave) - 1;
-    const int b_first = find_event(ptr, B, q_first);
-    const int b_last = find_event(ptr, B, q_last);
+    const int b_first = find_event(qptr, B, q_first);
+    const int b_last = find_event(qptr, B, q_last);
     const int clo = (int)ptr[b_first];
     const int chi = (int)ptr[b_last + 1];
     const bool one_event = b_first == b_last;          // wave-uniform: no per-lane event window needed
@@ -3045,10 +3180,10 @@ __global__ __launch_bounds__(kWave * 4) void radius_kernel(const float *__restri
     const bool valid = qi < N;
     const int64_t qq = valid ? qi : q_last;
     int lo = clo, hi = chi;
-    if (!one_event) { const int b = find_event(ptr, B, qq); lo = (int)ptr[b]; hi = (int)ptr[b + 1]; }
+    if (!one_event) { const int b = find_event(qptr, B, qq); lo = (int)ptr[b]; hi = (int)ptr[b + 1]; }
     f2 q[DP];
 #pragma unroll
-    for (int c = 0; c < DP; ++c) { const float v = (c < D) ? x[qq * D + c] : 0.0f; q[c].x = v; q[c].y = v; }
+    for (int c = 0; c < DP; ++c) { const float v = (c < D) ? qx[qq * D + c] : 0.0f; q[c].x = v; q[c].y = v; }
     int stored = 0, seen = valid ? 0 : max_nbr;        // idle lanes are "full" from the start
     int32_t *row = nbr + qq * max_nbr;
     // hits are rare per lane (a few per thousand pairs): the sweep of a 64-candidate tile only records them as bits
@@ -3103,7 +3238,6 @@ __global__ __launch_bounds__(kWave * 4) void radius_kernel(const float *__restri
     }
     if (valid) cntout[qi] = stored;
 }
-
 
 // ---- radius graph, windowed by the first coordinate --------------------------------------------------------------
 // d(i,j) < r^2 needs |x0_i - x0_j| < r.  Queries are therefore PROCESSED in the order of their first coordinate (a
@@ -3653,4 +3787,88 @@ extern "C" int dmet_knn_periodic_f32(const float *x, const int64_t *ptr, int B, 
     const int rc = radius_periods("dmet_knn_periodic_f32", D, period, &per, &any);
     if (rc) return rc;
     return knn_local_impl(x, ptr, B, N, D, k, nbr, dist, nbr16, ws, ws_bytes, stream, any ? &per : nullptr);
+}
+
+// ---- two point sets: queries y against candidates x of the same events (torch_cluster.knn / radius) -----------------------
+extern "C" size_t dmet_knn_xy_workspace_bytes(int64_t Nx, int64_t Ny, int B, int D, int k)
+{
+    (void)Nx; (void)D;
+    if (Ny <= 0 || B < 0 || k <= 0 || k > DMET_MAX_K) return 0;
+    return carve_workspace_xy(nullptr, Ny, B, padded_k(k)).bytes + 512;
+}
+
+extern "C" int dmet_knn_xy_f32(const float *x, const int64_t *ptr_x, int64_t Nx, const float *y, const int64_t *ptr_y,
+                               int64_t Ny, int B, int D, int k, const float *period, int32_t *nbr, float *dist, void *ws,
+                               size_t ws_bytes, dmet_stream_t stream)
+{
+    const int64_t kMaxRows = (int64_t)2147483647 - 4096;
+    DMET_REQUIRE(Nx >= 0 && Nx < kMaxRows && Ny >= 0 && Ny < kMaxRows, "dmet_knn_xy_f32: Nx=%lld / Ny=%lld out of range",
+                 (long long)Nx, (long long)Ny);
+    DMET_REQUIRE(B >= 0, "dmet_knn_xy_f32: B=%d", B);
+    DMET_REQUIRE(k >= 1 && k <= DMET_MAX_K, "dmet_knn_xy_f32: k=%d not in [1,%d]", k, DMET_MAX_K);
+    DMET_REQUIRE(D >= 1 && D <= DMET_MAX_KNN_DIM, "dmet_knn_xy_f32: D=%d not in [1,%d]", D, DMET_MAX_KNN_DIM);
+    RadPeriod per;
+    bool any = false;
+    if (period) {
+        const int rc = radius_periods("dmet_knn_xy_f32", D, period, &per, &any);   // (D <= 8)
+        if (rc) return rc;
+    }
+    if (Ny == 0) return 0;
+    DMET_REQUIRE(B >= 1, "dmet_knn_xy_f32: %lld queries but no event", (long long)Ny);
+    DMET_REQUIRE((x || Nx == 0) && ptr_x && y && ptr_y && nbr && dist && ws, "dmet_knn_xy_f32: null pointer");
+    DMET_REQUIRE(ws_bytes >= dmet_knn_xy_workspace_bytes(Nx, Ny, B, D, k), "dmet_knn_xy_f32: workspace too small");
+    hipStream_t st = as_stream(stream);
+    const RadPeriod *pp = any ? &per : nullptr;
+    if (D <= 4) return dispatch_k_xy<4>(x, ptr_x, y, ptr_y, Ny, B, D, k, nbr, dist, ws, st, pp);
+    if (D <= 8) return dispatch_k_xy<8>(x, ptr_x, y, ptr_y, Ny, B, D, k, nbr, dist, ws, st, pp);
+    if (D <= 16) return dispatch_k_xy<16>(x, ptr_x, y, ptr_y, Ny, B, D, k, nbr, dist, ws, st, pp);
+    if (D <= 32) return dispatch_k_xy<32>(x, ptr_x, y, ptr_y, Ny, B, D, k, nbr, dist, ws, st, pp);
+    return dispatch_k_xy<64>(x, ptr_x, y, ptr_y, Ny, B, D, k, nbr, dist, ws, st, pp);
+}
+
+template <int DP>
+static void launch_radius_xy(int64_t blocks, hipStream_t st, const float *x, const int64_t *ptr_x, const float *y,
+                             const int64_t *ptr_y, int B, int64_t Ny, int D, float r2, int max_nbr, int32_t *nbr, int32_t *cnt,
+                             const RadPeriod *per)
+{
+    const KnnQuerySet qs{y, ptr_y};
+    if (per)
+        hipLaunchKernelGGL((radius_kernel<DP, RadPeriod, KnnQuerySet>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x,
+                           ptr_x, B, Ny, D, r2, max_nbr, 0, nbr, cnt, *per, qs);
+    else
+        hipLaunchKernelGGL((radius_kernel<DP, KnnQuerySet>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr_x, B, Ny,
+                           D, r2, max_nbr, 0, nbr, cnt, qs);
+}
+
+extern "C" int dmet_radius_xy_f32(const float *x, const int64_t *ptr_x, int64_t Nx, const float *y, const int64_t *ptr_y,
+                                  int64_t Ny, int B, int D, float r, int max_nbr, const float *period, int fill,
+                                  int32_t *nbr, int32_t *cnt, dmet_stream_t stream)
+{
+    DMET_REQUIRE(Nx >= 0 && Nx < (int64_t)2147483647 && Ny >= 0 && Ny < (int64_t)2147483647,
+                 "dmet_radius_xy_f32: Nx=%lld / Ny=%lld out of range", (long long)Nx, (long long)Ny);
+    DMET_REQUIRE(B >= 0, "dmet_radius_xy_f32: B=%d", B);
+    DMET_REQUIRE(D >= 1 && D <= 8, "dmet_radius_xy_f32: D=%d not in [1,8]", D);
+    DMET_REQUIRE(max_nbr >= 1, "dmet_radius_xy_f32: max_nbr=%d", max_nbr);
+    RadPeriod per;
+    bool any = false;
+    if (period) {
+        const int rc = radius_periods("dmet_radius_xy_f32", D, period, &per, &any);
+        if (rc) return rc;
+    }
+    if (Ny == 0) return 0;
+    DMET_REQUIRE(B >= 1, "dmet_radius_xy_f32: %lld queries but no event", (long long)Ny);
+    DMET_REQUIRE((x || Nx == 0) && ptr_x && y && ptr_y && nbr && cnt, "dmet_radius_xy_f32: null pointer");
+    const float r2 = r * r;
+    const int64_t blocks = (Ny + 4 * kWave - 1) / (4 * kWave);
+    hipStream_t st = as_stream(stream);
+    if (fill) {
+        hipError_t me = hipMemsetAsync(nbr, 0xff, sizeof(int32_t) * (size_t)Ny * (size_t)max_nbr, st);
+        if (me != hipSuccess) return hip_fail(me, "hipMemsetAsync(nbr)");
+    }
+    const RadPeriod *pp = any ? &per : nullptr;
+    if (D <= 2) launch_radius_xy<2>(blocks, st, x, ptr_x, y, ptr_y, B, Ny, D, r2, max_nbr, nbr, cnt, pp);
+    else if (D <= 4) launch_radius_xy<4>(blocks, st, x, ptr_x, y, ptr_y, B, Ny, D, r2, max_nbr, nbr, cnt, pp);
+    else launch_radius_xy<8>(blocks, st, x, ptr_x, y, ptr_y, B, Ny, D, r2, max_nbr, nbr, cnt, pp);
+    DMET_LAUNCH_CHECK("radius_kernel (two sets)");
+    return 0;
 }

@@ -191,26 +191,28 @@ def raise_deferred_errors() -> None:
 # CSR edge list (by target), plus the by-source index for the backward pass
 # ---------------------------------------------------------------------------------------------------------------
 class EdgeList:
-    """Edges grouped by target: tgt[e] == i for rowptr[i] <= e < rowptr[i+1]; src/tgt int32."""
+    """Edges grouped by target: tgt[e] == i for rowptr[i] <= e < rowptr[i+1]; src/tgt int32.  num_src: the size of the
+    node set `src` indexes when it is not the targets' own (two-set EdgeConv), else None."""
 
     def __init__(self, src: torch.Tensor, tgt: torch.Tensor, rowptr: torch.Tensor, num_nodes: int,
-                 perm: Optional[torch.Tensor] = None):
+                 perm: Optional[torch.Tensor] = None, num_src: Optional[int] = None):
         self.src = src
         self.tgt = tgt
         self.rowptr = rowptr
         self.num_nodes = num_nodes
+        self.num_src = num_nodes if num_src is None else num_src
         self.num_edges = int(src.numel())
         self.perm = perm  # position in the caller's edge_index of each grouped edge (None = identity)
         self._by_source = None
 
     def by_source(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """srcptr[N+1], srcperm[E]: edges leaving node j, ascending edge position (deterministic backward)."""
+        """srcptr[num_src+1], srcperm[E]: edges leaving node j, ascending edge position (deterministic backward)."""
         if self._by_source is None:
             if self.num_edges == 0:
-                z = torch.zeros(self.num_nodes + 1, dtype=torch.int32, device=self.src.device)
+                z = torch.zeros(self.num_src + 1, dtype=torch.int32, device=self.src.device)
                 self._by_source = (z, torch.zeros(1, dtype=torch.int32, device=self.src.device))
             else:
-                self._by_source = _reverse_of_column(self.src, self.num_nodes)
+                self._by_source = _reverse_of_column(self.src, self.num_src)
         return self._by_source
 
 
@@ -219,8 +221,10 @@ def _reverse_of_column(col: torch.Tensor, num_nodes: int) -> Tuple[torch.Tensor,
     return _native.reverse_index(col.contiguous(), num_nodes)
 
 
-def edge_list_from_edge_index(edge_index: torch.Tensor, num_nodes: int, flow: str) -> EdgeList:
-    """Generic path for an arbitrary caller-supplied edge_index (radius graphs, to_undirected output...)."""
+def edge_list_from_edge_index(edge_index: torch.Tensor, num_nodes: int, flow: str,
+                              num_src: Optional[int] = None) -> EdgeList:
+    """Generic path for an arbitrary caller-supplied edge_index (radius graphs, to_undirected output...).  num_src: the
+    sources index a node set of their own of that size (two-set EdgeConv); num_nodes is then the number of targets."""
     if edge_index.dim() != 2 or edge_index.shape[0] != 2:
         raise ValueError(f"edge_index must be [2, E], got {tuple(edge_index.shape)}")
     if edge_index.dtype != torch.int64:
@@ -233,9 +237,9 @@ def edge_list_from_edge_index(edge_index: torch.Tensor, num_nodes: int, flow: st
     if E == 0:
         z = torch.zeros(num_nodes + 1, dtype=torch.int32, device=dev)
         e = torch.zeros(0, dtype=torch.int32, device=dev)
-        return EdgeList(e, e, z, num_nodes)
-    if num_nodes <= 0:
-        raise ValueError(f"edge_index holds {E} edges but the graph has {num_nodes} nodes")
+        return EdgeList(e, e, z, num_nodes, num_src=num_src)
+    if num_nodes <= 0 or (num_src is not None and num_src <= 0):
+        raise ValueError(f"edge_index holds {E} edges but the graph has {num_nodes if num_nodes <= 0 else num_src} nodes")
     tgt = tgt64.to(torch.int32).contiguous()
     src = src64.to(torch.int32).contiguous()
     # group by target with the stable reverse-index sort (keeps the caller's order inside a group, so "lowest
@@ -244,14 +248,22 @@ def edge_list_from_edge_index(edge_index: torch.Tensor, num_nodes: int, flow: st
     # read, before any kernel gathers through them.
     rowptr, perm = _reverse_of_column(tgt, num_nodes)
     ident = torch.arange(E, dtype=torch.int32, device=dev)
-    grouped, lo, hi = torch.stack([(perm[:E] == ident).all().to(torch.int64), edge_index.min(),
-                                   edge_index.max()]).tolist()
-    if lo < 0 or hi >= num_nodes:
-        raise ValueError(f"edge_index node ids must lie in [0, {num_nodes}), found {lo if lo < 0 else hi}")
+    if num_src is None:
+        grouped, lo, hi = torch.stack([(perm[:E] == ident).all().to(torch.int64), edge_index.min(),
+                                       edge_index.max()]).tolist()
+        if lo < 0 or hi >= num_nodes:
+            raise ValueError(f"edge_index node ids must lie in [0, {num_nodes}), found {lo if lo < 0 else hi}")
+    else:       # each row against its own node set, in the same host read
+        grouped, lo, hi, slo, shi = torch.stack([(perm[:E] == ident).all().to(torch.int64), tgt64.min(), tgt64.max(),
+                                                 src64.min(), src64.max()]).tolist()
+        if lo < 0 or hi >= num_nodes:
+            raise ValueError(f"edge_index target ids must lie in [0, {num_nodes}), found {lo if lo < 0 else hi}")
+        if slo < 0 or shi >= num_src:
+            raise ValueError(f"edge_index source ids must lie in [0, {num_src}), found {slo if slo < 0 else shi}")
     if grouped:
-        return EdgeList(src, tgt, rowptr, num_nodes, None)
+        return EdgeList(src, tgt, rowptr, num_nodes, None, num_src=num_src)
     p = perm[:E].to(torch.int64)
-    return EdgeList(src[p].contiguous(), tgt[p].contiguous(), rowptr, num_nodes, perm[:E])
+    return EdgeList(src[p].contiguous(), tgt[p].contiguous(), rowptr, num_nodes, perm[:E], num_src=num_src)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -380,6 +392,47 @@ class NeighborTable:
 
 
 _graph_registry: Dict[int, Tuple[weakref.ref, int, object]] = {}
+
+
+class BipartiteTable:
+    """The result of knn_xy_table / radius_xy_table: nbr[Ny, k] int32, row i = the ids IN THE CANDIDATE SET x of the
+    neighbours of query i of y (-1 = empty slot; with `cnt` only the first cnt[i] slots of row i are defined).  dist
+    (kNN only): the fp32 distances, 1e10 in empty slots.  The two sets have separate index spaces: num_queries rows,
+    ids in [0, num_candidates).  Nothing here reads the device until the exact-size views are asked for."""
+
+    def __init__(self, nbr: torch.Tensor, ptr_x: torch.Tensor, ptr_y: torch.Tensor, num_candidates: int,
+                 dist: Optional[torch.Tensor] = None, cnt: Optional[torch.Tensor] = None):
+        self.nbr = nbr
+        self.dist = dist
+        self.cnt = cnt
+        self.ptr_x = ptr_x
+        self.ptr_y = ptr_y
+        self.num_queries, self.k = nbr.shape
+        self.num_candidates = num_candidates
+        self._rp = None
+        self._edges = None
+
+    def _rowptr(self):
+        """(rowptr[Ny+1] int32, E) of the valid slots: one device-to-host read of the edge count."""
+        if self._rp is None:
+            rp = _native.table_rowptr(self.nbr, self.cnt)
+            self._rp = (rp, int(rp[-1].item()) if self.num_queries else 0)
+        return self._rp
+
+    def edge_list(self) -> EdgeList:
+        """The valid entries grouped by query, for the two-set EdgeConv (queries = targets, candidates = sources):
+        0 <= src < num_candidates always, an empty slot is no edge."""
+        if self._edges is None:
+            rowptr, E = self._rowptr()
+            _ei, src, tgt = _native.table_edges(self.nbr, self.cnt, rowptr, E, False, False, True)
+            self._edges = EdgeList(src, tgt, rowptr, self.num_queries, num_src=self.num_candidates)
+        return self._edges
+
+    def edge_index(self) -> torch.Tensor:
+        """int64 [2,E], torch_cluster.knn / radius layout: row 0 = index into y, row 1 = index into x; never a -1."""
+        rowptr, E = self._rowptr()
+        ei, _s, _t = _native.table_edges(self.nbr, self.cnt, rowptr, E, True, True, False)
+        return ei
 
 
 class GraphFuture:

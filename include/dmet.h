@@ -73,6 +73,24 @@ int dmet_knn_local_f32(const float *x, const int64_t *ptr, int B, int64_t N, int
 int dmet_knn_periodic_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, int k, const float *period,
                           int32_t *nbr, float *dist, uint16_t *nbr_local, void *ws, size_t ws_bytes,
                           dmet_stream_t stream);
+/* Two point sets (torch_cluster.knn(x, y, k, batch_x, batch_y)): for every row of y (a QUERY, Ny rows, events ptr_y[B+1])
+ * the k rows of x (the CANDIDATES, Nx rows, events ptr_x[B+1]) of the same event with the smallest distance.  The
+ * distance of query i and candidate j is the fp32 chain used everywhere here, in coordinate order:
+ *     d = x[j,c] - y[i,c];  periodic coordinate (period[c] = L > 0): a = |d|; a = (a > 0.5f * L) ? L - a : a;  else a = d;
+ *     acc = fmaf(a, a, acc)
+ * Row i of nbr[Ny,k] / dist[Ny,k]: ascending (acc, j), ties to the lower j (R2); a candidate with acc >= 1e10 or NaN is
+ * never selected; a query whose event holds fewer than k admissible candidates gets a short row (-1 / 1e10 in the
+ * empty slots), a query of an event without candidates an empty one; an event without queries costs nothing.  nbr holds
+ * GLOBAL row numbers of x.  There is no self to exclude: the two sets have separate index spaces, and a point present in
+ * both finds its twin at distance 0 like any other candidate.  period: NULL (all plain), or a host array of D floats as
+ * for dmet_knn_periodic_f32 (then D <= 8).  Always the exact vector-ALU sweep (the kernel of dmet_knn_f32's exact path
+ * with the queries cut from ptr_y and the candidate range taken from ptr_x), so x = y, ptr_x = ptr_y gives the table of
+ * dmet_knn_f32 / dmet_knn_periodic_f32 bit for bit.  1 <= k <= DMET_MAX_K, 1 <= D <= DMET_MAX_KNN_DIM.  Returns -EINVAL
+ * on bad arguments before any device work, 0 at once for Ny == 0. */
+size_t dmet_knn_xy_workspace_bytes(int64_t Nx, int64_t Ny, int B, int D, int k);
+int dmet_knn_xy_f32(const float *x, const int64_t *ptr_x, int64_t Nx, const float *y, const int64_t *ptr_y, int64_t Ny,
+                    int B, int D, int k, const float *period, int32_t *nbr, float *dist, void *ws, size_t ws_bytes,
+                    dmet_stream_t stream);
 /* dmet_knn_local_f32 for the DynamicEdgeConv call shape (model/graph_met_network.py:63: the graph is built in the
  * space of the rows the convolution then consumes): the node-level dense layer of the fused EdgeConv,
  *   P = x.(W1-W2)^T + b, Q = x.W2^T   (W[32,64], D = 32),
@@ -168,6 +186,15 @@ int dmet_radius_periodic_f32(const float *x, const int64_t *ptr, int B, int64_t 
 int dmet_radius_windowed_periodic_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r, int max_nbr,
                                       int skip_self, int fill, const float *period, int32_t *nbr, int32_t *cnt,
                                       uint16_t *nbr16, int stride16, void *ws, size_t ws_bytes, dmet_stream_t stream);
+/* Two point sets (torch_cluster.radius(x, y, r, batch_x, batch_y, max_num_neighbors)): for every row of y the FIRST
+ * max_nbr rows j of x (ascending j) of the same event with acc(i, j) < r * r (strict, fp32 product), acc the chain of
+ * dmet_knn_xy_f32 (period: NULL or D floats).  nbr[Ny,max_nbr] int32 global row numbers of x, cnt[Ny] int32; fill != 0:
+ * slots >= cnt[i] are -1, fill == 0: they are left unwritten (the counted form).  All pairs of an event (the kernel of
+ * dmet_radius_f32 / dmet_radius_periodic_f32 with a second operand; no self to skip).  1 <= D <= 8.  Returns -EINVAL on
+ * bad arguments before any device work, 0 at once for Ny == 0. */
+int dmet_radius_xy_f32(const float *x, const int64_t *ptr_x, int64_t Nx, const float *y, const int64_t *ptr_y, int64_t Ny,
+                       int B, int D, float r, int max_nbr, const float *period, int fill, int32_t *nbr, int32_t *cnt,
+                       dmet_stream_t stream);
 
 /* ---- K2+K3 fused: EdgeConv with nn = Linear(2*Hin -> Hout), aggr = 'max', fixed-width table ---------
  * replaces torch_geometric.nn.EdgeConv(nn=Sequential(Linear(2H,H)), aggr='max').forward
@@ -498,6 +525,18 @@ int dmet_segment_sum_bwd_f32(const float *g_out, const int32_t *rowptr, int64_t 
 int dmet_edge_features_bwd_f32(const float *g_feat, const int32_t *rowptr, const int32_t *srcptr,
                                const int32_t *srcperm, int64_t N, int H, float *gx,
                                dmet_stream_t stream);
+/* The same two pieces for TWO node sets (EdgeConv((x_src, x_dst), edge_index)): src[e] indexes x_src[N_src,H], tgt[e]
+ * indexes x_dst[N_dst,H], edges grouped by target (rowptr[N_dst+1]); both ids unchecked, so 0 <= src[e] < N_src and
+ * 0 <= tgt[e] < N_dst must hold for every e (a table's -1 slots are dropped before, dmet_table_degree).  Any H > 0.
+ *   edge_features_xy: feat[e] = [ x_dst[tgt[e]] || x_src[src[e]] - x_dst[tgt[e]] ]          ([E, 2H])
+ *   edge_features_xy_bwd: g_x_dst[i] = sum_{e in in(i)} (g_feat[e,:H] - g_feat[e,H:])   (by rowptr, ascending e)
+ *                         g_x_src[j] = sum_{e in out(j)} g_feat[e,H:]   (by srcptr[N_src+1], srcperm[E]: ascending e)
+ *   either output may be NULL (not wanted).  Same bits run to run. */
+int dmet_edge_features_xy_f32(const float *x_src, const float *x_dst, const int32_t *src, const int32_t *tgt, int64_t E,
+                              int H, float *feat, dmet_stream_t stream);
+int dmet_edge_features_xy_bwd_f32(const float *g_feat, const int32_t *rowptr, const int32_t *srcptr,
+                                  const int32_t *srcperm, int64_t N_src, int64_t N_dst, int H, float *g_x_src,
+                                  float *g_x_dst, dmet_stream_t stream);
 
 /* ---- K4: per-event MET reduction -------------------------------------------------------------------
  * replaces the two torch_scatter.scatter_add calls at model/net.py:55-56 (and :132-133):

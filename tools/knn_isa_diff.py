@@ -1,6 +1,7 @@
 """Compare the plain (non-periodic) kNN kernels of two device-assembly builds of csrc/knn.hip, ignoring symbol names,
 block labels and comments: knn_kernel (every DP / KP / TQ / EXACT_D instance), knn_merge_kernel, the plan kernel and
-the matrix-core filter kernels.  Instances with a RadPeriod argument (the periodic sweep) are skipped; an empty trailing
+the matrix-core filter kernels.  Instances with a RadPeriod or KnnQuerySet argument (the periodic sweep, the two-set
+build) are skipped; an empty trailing
 pack mangles differently but must compile to the same code.  Exit 1 if any instruction differs or an instance is missing.
 
     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -DNDEBUG --cuda-device-only -S \
@@ -30,7 +31,7 @@ def funcs(path):
 def key(sym):
     """(kernel name, template arguments) of a plain kNN kernel instance, None for anything else."""
     m = re.search(r"\d+(knn_[a-z0-9_]*?kernel)", sym)
-    if not m or "RadPeriod" in sym:
+    if not m or "RadPeriod" in sym or "KnnQuerySet" in sym:
         return None
     return m.group(1), ",".join(re.findall(r"L[ib](\d+)E", sym))   # the integer / bool template arguments
 

@@ -15,7 +15,7 @@ def funcs(path):
     return out
 def key(sym):   # kernel name + DP, plain instances only
     m = re.search(r"(radius_\w*kernel)(?:ILi(\d+)E)?", sym)
-    return None if "RadPeriod" in sym else (m.group(1), m.group(2))
+    return None if "RadPeriod" in sym or "KnnQuerySet" in sym else (m.group(1), m.group(2))
 norm = lambda L: [re.sub(r"\s*;.*$", "", re.sub(r"\.LBB\d+_\d+", "LBB", l)) for l in L]
 a, b = funcs(sys.argv[1]), funcs(sys.argv[2])
 A = {key(k): k for k in a if "radius" in k and key(k)}
