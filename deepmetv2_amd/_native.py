@@ -6,6 +6,7 @@ Every function requires ROCm device tensors and raises otherwise -- there is no 
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import os
 from typing import Optional, Tuple
 
@@ -181,58 +182,66 @@ def knn_size_hint(min_nodes: Optional[int], max_nodes: Optional[int]) -> None:
         _lib.check(_lib.load().dmet_knn_size_hint(int(min_nodes), int(max_nodes)), "dmet_knn_size_hint")
 
 
-def _knn(x: torch.Tensor, ptr: torch.Tensor, k: int, stats: Optional[dict], want_local: bool, dense=None):
-    """dense = (W[32,64], b or None, sliced): also ask the build for the node-level dense layer of the EdgeConv that
-    consumes the graph (dmet_knn_local_dense_f32); a fourth result (P, Q) or None is then returned."""
+def _knn_operands(x: torch.Tensor, ptr: torch.Tensor):
+    """The checks of a one-set build: (dev, x as contiguous fp32, N, D, B)."""
     dev = _require_device(x, ptr)
-    L = _lib.load()
     x = _f32c(x.detach(), "x")
     if x.dim() != 2:
         raise ValueError(f"x must be 2-D [N, D], got {tuple(x.shape)}")
-    N, D = x.shape
-    B = ptr.numel() - 1
-    nbr = torch.empty((N, k), dtype=torch.int32, device=dev)
-    dist = torch.empty((N, k), dtype=torch.float32, device=dev)
+    return (dev, x, *x.shape, ptr.numel() - 1)
+
+
+def _knn_run(dev: torch.device, Nq: int, k: int, want_local: bool, ws_bytes: int, call):
+    """The tables of a build over Nq queries and its workspace; call(nbr, dist, loc pointer or None, ws) runs on dev
+    inside the 'knn' timer bracket.  Returns (nbr, dist, loc, ws, what call returned)."""
+    nbr = torch.empty((Nq, k), dtype=torch.int32, device=dev)
+    dist = torch.empty((Nq, k), dtype=torch.float32, device=dev)
     # uint16 payload in an int16 tensor (torch has no arithmetic on uint16; the kernels only reinterpret the bytes)
-    loc = torch.empty((N, k), dtype=torch.int16, device=dev) if want_local else None
-    nb = L.dmet_knn_workspace_bytes(N, B, D, k)
-    ws = _ws(nb, dev)
-    pq = None
+    loc = torch.empty((Nq, k), dtype=torch.int16, device=dev) if want_local else None
+    ws = _ws(ws_bytes, dev)
+    _t = timer.record('knn', dev)
+    with _on(dev):
+        extra = call(nbr, dist, loc.data_ptr() if want_local else None, ws)
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return nbr, dist, loc, ws, extra
+
+
+def _knn(x: torch.Tensor, ptr: torch.Tensor, k: int, stats: Optional[dict], want_local: bool, dense=None):
+    """dense = (W[32,64], b or None, sliced): also ask the build for the node-level dense layer of the EdgeConv that
+    consumes the graph (dmet_knn_local_dense_f32); a fourth result (P, Q) or None is then returned."""
+    dev, x, N, D, B = _knn_operands(x, ptr)
+    L = _lib.load()
     asked = dense is not None
     if dense is not None and (D != 32 or N == 0 or B == 0 or tuple(dense[0].shape) != (32, 64)):
         dense = None
-    _t = timer.record('knn', dev)
-    with _on(dev):
+
+    def call(nbr, dist, loc_p, ws):     # -> (P, Q, sliced) if the build carried the dense layer, else None
         if dense is None:
             _lib.check(L.dmet_knn_local_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, k, nbr.data_ptr(), dist.data_ptr(),
-                                            loc.data_ptr() if want_local else None, ws.data_ptr(), ws.numel(),
-                                            _stream(dev)), "dmet_knn_local_f32")
+                                            loc_p, ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_knn_local_f32")
+            return None
+        W, b, sliced = dense            # sliced: False / True, or "bf16" (P fp32, Q bf16: node_linear_split_bf16)
+        W = _f32c(W.detach(), "W")
+        bp = _f32c(b.detach(), "b").data_ptr() if b is not None else None
+        if sliced == "bf16":
+            Pt = torch.empty((N, 32), dtype=torch.float32, device=dev)
+            Qt = torch.empty((N, 32), dtype=torch.bfloat16, device=dev)
+            layout = 2
         else:
-            import ctypes
-            W, b, sliced = dense            # sliced: False / True, or "bf16" (P fp32, Q bf16: node_linear_split_bf16)
-            W = _f32c(W.detach(), "W")
-            bp = _f32c(b.detach(), "b").data_ptr() if b is not None else None
-            if sliced == "bf16":
-                Pt = torch.empty((N, 32), dtype=torch.float32, device=dev)
-                Qt = torch.empty((N, 32), dtype=torch.bfloat16, device=dev)
-                layout = 2
-            else:
-                PQ = torch.empty((2, 4, N, 8) if sliced else (2, N, 32), dtype=torch.float32, device=dev)
-                Pt, Qt = PQ[0], PQ[1]
-                layout, sliced = (1 if sliced else 0), bool(sliced)
-            done = ctypes.c_int(0)
-            _lib.check(L.dmet_knn_local_dense_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, k, nbr.data_ptr(),
-                                                  dist.data_ptr(), loc.data_ptr() if want_local else None,
-                                                  W.data_ptr(), bp, layout, Pt.data_ptr(),
-                                                  Qt.data_ptr(), ctypes.cast(ctypes.pointer(done), ctypes.c_void_p),
-                                                  ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_knn_local_dense_f32")
-            if done.value:
-                pq = (Pt, Qt, sliced)
-    if _t is not None:
-        _t.record(torch.cuda.current_stream(dev))
+            PQ = torch.empty((2, 4, N, 8) if sliced else (2, N, 32), dtype=torch.float32, device=dev)
+            Pt, Qt = PQ[0], PQ[1]
+            layout, sliced = (1 if sliced else 0), bool(sliced)
+        done = ctypes.c_int(0)
+        _lib.check(L.dmet_knn_local_dense_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, k, nbr.data_ptr(),
+                                              dist.data_ptr(), loc_p, W.data_ptr(), bp, layout, Pt.data_ptr(),
+                                              Qt.data_ptr(), ctypes.cast(ctypes.pointer(done), ctypes.c_void_p),
+                                              ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_knn_local_dense_f32")
+        return (Pt, Qt, sliced) if done.value else None
+
+    nbr, dist, loc, ws, pq = _knn_run(dev, N, k, want_local, L.dmet_knn_workspace_bytes(N, B, D, k), call)
     if stats is not None and N > 0 and B > 0:
         with _on(dev):
-            import ctypes
             out = (ctypes.c_int64 * 2)()
             _lib.check(L.dmet_knn_fallback_stats(ws.data_ptr(), N, B, D, k, ctypes.cast(out, ctypes.c_void_p),
                                                  _stream(dev)), "dmet_knn_fallback_stats")
@@ -269,44 +278,29 @@ def knn_local(x: torch.Tensor, ptr: torch.Tensor, k: int, stats: Optional[dict] 
     return _knn(x, ptr, k, stats, True)
 
 
-def knn_periodic(x: torch.Tensor, ptr: torch.Tensor, k: int, period, want_local: bool):
-    """knn() / knn_local() with periodic coordinates (dmet_knn_periodic_f32): period = D floats, period[c] > 0 the
-    circumference of coordinate c, 0 a plain coordinate; D <= 8.  Returns (nbr, dist, loc), loc None unless
-    want_local."""
-    import ctypes
-    dev = _require_device(x, ptr)
-    L = _lib.load()
-    x = _f32c(x.detach(), "x")
-    if x.dim() != 2:
-        raise ValueError(f"x must be 2-D [N, D], got {tuple(x.shape)}")
-    N, D = x.shape
-    B = ptr.numel() - 1
-    if len(period) != D:
-        raise ValueError(f"period has {len(period)} entries for {D} coordinates")
-    per = (ctypes.c_float * D)(*[float(p) for p in period])    # host array, read by the C entry before it returns
-    nbr = torch.empty((N, k), dtype=torch.int32, device=dev)
-    dist = torch.empty((N, k), dtype=torch.float32, device=dev)
-    loc = torch.empty((N, k), dtype=torch.int16, device=dev) if want_local else None
-    ws = _ws(L.dmet_knn_workspace_bytes(N, B, D, k), dev)
-    _t = timer.record('knn', dev)
-    with _on(dev):
-        _lib.check(L.dmet_knn_periodic_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, k, ctypes.cast(per, ctypes.c_void_p),
-                                           nbr.data_ptr(), dist.data_ptr(), loc.data_ptr() if want_local else None,
-                                           ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_knn_periodic_f32")
-    if _t is not None:
-        _t.record(torch.cuda.current_stream(dev))
-    return nbr, dist, loc
-
-
 def _period_array(period, D: int):
     """(host float array kept alive by the caller, its address) for a `period` of D floats, or (None, None)."""
     if period is None:
         return None, None
-    import ctypes
     if len(period) != D:
         raise ValueError(f"period has {len(period)} entries for {D} coordinates")
     per = (ctypes.c_float * D)(*[float(p) for p in period])    # host array, read by the C entry before it returns
     return per, ctypes.cast(per, ctypes.c_void_p)
+
+
+def knn_periodic(x: torch.Tensor, ptr: torch.Tensor, k: int, period, want_local: bool):
+    """knn() / knn_local() with periodic coordinates (dmet_knn_periodic_f32): period = D floats, period[c] > 0 the
+    circumference of coordinate c, 0 a plain coordinate; D <= 8.  Returns (nbr, dist, loc), loc None unless
+    want_local."""
+    dev, x, N, D, B = _knn_operands(x, ptr)
+    L = _lib.load()
+    _per, per_p = _period_array(period, D)
+
+    def call(nbr, dist, loc_p, ws):
+        _lib.check(L.dmet_knn_periodic_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, k, per_p, nbr.data_ptr(),
+                                           dist.data_ptr(), loc_p, ws.data_ptr(), ws.numel(), _stream(dev)),
+                   "dmet_knn_periodic_f32")
+    return _knn_run(dev, N, k, want_local, L.dmet_knn_workspace_bytes(N, B, D, k), call)[:3]
 
 
 def _xy_operands(x: torch.Tensor, ptr_x: torch.Tensor, y: torch.Tensor, ptr_y: torch.Tensor):
@@ -327,17 +321,12 @@ def knn_xy(x: torch.Tensor, ptr_x: torch.Tensor, y: torch.Tensor, ptr_y: torch.T
     L = _lib.load()
     (Nx, D), Ny, B = x.shape, y.shape[0], ptr_y.numel() - 1
     _per, per_p = _period_array(period, D)
-    nbr = torch.empty((Ny, k), dtype=torch.int32, device=dev)
-    dist = torch.empty((Ny, k), dtype=torch.float32, device=dev)
-    ws = _ws(L.dmet_knn_xy_workspace_bytes(Nx, Ny, B, D, k), dev)
-    _t = timer.record('knn', dev)
-    with _on(dev):
+
+    def call(nbr, dist, _loc_p, ws):
         _lib.check(L.dmet_knn_xy_f32(x.data_ptr(), ptr_x.data_ptr(), Nx, y.data_ptr(), ptr_y.data_ptr(), Ny, B, D, k, per_p,
                                      nbr.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
                    "dmet_knn_xy_f32")
-    if _t is not None:
-        _t.record(torch.cuda.current_stream(dev))
-    return nbr, dist
+    return _knn_run(dev, Ny, k, False, L.dmet_knn_xy_workspace_bytes(Nx, Ny, B, D, k), call)[:2]
 
 
 def radius_xy(x: torch.Tensor, ptr_x: torch.Tensor, y: torch.Tensor, ptr_y: torch.Tensor, r: float, max_nbr: int,
@@ -407,16 +396,12 @@ def radius_periodic(x: torch.Tensor, ptr: torch.Tensor, r: float, max_nbr: int, 
     """radius() with periodic coordinates: period = D floats, period[c] > 0 the circumference of coordinate c, 0 a plain
     coordinate (dmet_radius_periodic_f32 / dmet_radius_windowed_periodic_f32).  Same outputs as radius().  The window
     runs on coordinate 0, so period[0] > 0 takes the all-pairs form (rows16 = None, as RADIUS_FORM == "sweep" does)."""
-    import ctypes
     dev = _require_device(x, ptr)
     L = _lib.load()
     x = _f32c(x.detach(), "x")
     N, D = x.shape
     B = ptr.numel() - 1
-    if len(period) != D:
-        raise ValueError(f"period has {len(period)} entries for {D} coordinates")
-    per = (ctypes.c_float * D)(*[float(p) for p in period])    # host array, read by the C entry before it returns
-    per_p = ctypes.cast(per, ctypes.c_void_p)
+    per, per_p = _period_array(period, D)
     windowed = RADIUS_FORM != "sweep" and per[0] == 0.0
     if local and windowed:
         stride16 = (max_nbr + 7) // 8 * 8
@@ -1388,7 +1373,6 @@ def encode_bn_bwd(x_cont: torch.Tensor, x_cat: torch.Tensor, params, h: torch.Te
     """Backward of bn_all(encode(...)) given dL/d(bn output): (encoder grads [9], g_gamma, g_beta), the BatchNorm's
     backward transform applied inside the encoder's backward kernel (dmet_bn_bwd_stats_f32 + dmet_encode_bn_bwd_f32);
     None when nothing was launched beyond the statistics (the caller keeps the separate steps)."""
-    import ctypes
     dev = _require_device(x_cont, x_cat, h, g_y)
     L = _lib.load()
     x, xc = _encode_x(x_cont, x_cat)
@@ -1522,7 +1506,6 @@ def bn_knn_local_dense(raw: torch.Tensor, residual: Optional[torch.Tensor], gamm
     (dmet_bn_knn_local_dense_f32).  Returns (y, nbr, dist, loc, pq) -- pq as in knn_local_dense, None without `dense` or
     when the build could not carry the dense layer -- or None when nothing was launched (the build would not take the
     matrix-core path): the caller then applies the transform and builds the graph itself."""
-    import ctypes
     dev = _require_device(raw, ptr)
     L = _lib.load()
     raw = _f32c(raw.detach(), "raw")
@@ -1713,7 +1696,6 @@ def bn_head_fwd(raw: torch.Tensor, residual: Optional[torch.Tensor], gamma: torc
                 mean: torch.Tensor, invstd: torch.Tensor, params):
     """(emb, out): emb = residual + BatchNorm(raw) (statistics given) formed inside the head's forward launch and out =
     head_fwd(emb, params) (dmet_bn_head_fwd_f32); None when nothing was launched (the caller keeps the two steps)."""
-    import ctypes
     dev = _require_device(raw)
     L = _lib.load()
     raw = _f32c(raw.detach(), "raw")

@@ -2,7 +2,7 @@
 
 Reference call sites (relative to /root/reference): model/graph_met_network.py:63 and
 model/dynamic_reduction_network.py:86,94 (knn_graph); train.py:48, evaluate.py:88, plt_weight.py:122
-(radius_graph).  The kernels are in csrc/knn.hip; this file is argument checking and the int64 `edge_index` view.
+(radius_graph).  The kernels are in csrc/knn.hip and csrc/radius.hip; this file is argument checking and the int64 `edge_index` view.
 """
 from __future__ import annotations
 

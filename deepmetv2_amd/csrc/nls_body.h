@@ -1,7 +1,7 @@
 // nls_body.h -- the wavefront-level body of the node-level dense layer of the fused EdgeConv (K2),
 //   P = x.(W1-W2)^T + b,  Q = x.W2^T      (W = [W1 | W2] as torch's Linear(2H -> H).weight, /root/reference/model/graph_met_network.py:36)
 // shared by node_linear_split_kernel (edgeconv.hip) and by the trailing "rider" workgroups of the kNN filter launch
-// (knn.hip: the dense layer of a DynamicEdgeConv depends on x only, like the graph build, and fills the wavefront
+// (knn_filter.h: the dense layer of a DynamicEdgeConv depends on x only, like the graph build, and fills the wavefront
 // slots the build's last round leaves empty).  No workgroup barrier inside: a wavefront owns its tiles and its LDS.
 #pragma once
 #include <hip/hip_bf16.h>

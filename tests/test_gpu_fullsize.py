@@ -5,7 +5,7 @@
   weights, per-event MET, loss, gradients.  Reference call sites: model/graph_met_network.py:63, train.py:48-51.
 * configs[4]: DynamicEdgeConv forward / backward on a ragged batch with events of 5120..8000 nodes (too large for the
   LDS-resident gather: L2-form gather, multi-pass backward scatter) against `ref_ops.dynamic_edge_conv`.
-* kNN matrix-core filter (both forms: events below / above 800 nodes, csrc/knn.hip kF2MinNodes) on inputs built to break it: non-finite rows,
+* kNN matrix-core filter (both forms: events below / above 800 nodes, csrc/knn.hip kF2MinNodes; the filter is csrc/knn_filter.h) on inputs built to break it: non-finite rows,
   coordinates whose distances exceed the 1e10 sentinel, per-feature heavy tails, a large common offset, mirrored pairs
   that tie to the last ulp.  The result must still be the C oracle's bits; where the certificate cannot hold, the
   exact fallback must have run (flagged_queries > 0).

@@ -1,12 +1,12 @@
 """K1, second filter form: the squared norms and the admission threshold are folded into the matrix product
-(csrc/knn.hip f2_block / f2_tau16), so each key block comes out as |x_j|^2 - 2 x_i.x_j - tau_rep.  These cases aim at
+(csrc/knn_filter.h f2_block / f2_tau16), so each key block comes out as |x_j|^2 - 2 x_i.x_j - tau_rep.  These cases aim at
 that arithmetic -- the fixed fp16 scales of the norm terms and of the two threshold terms, the directed rounding of
 tau_rep and of the tile minima, the forced rows at the norm limit -- and compare the table with the C oracle bit for
 bit, on events of exactly 800 nodes (the form's lower limit) and 4500 nodes, at 32 and 64 features."""
 import pytest
 import torch
 
-NORM_MAX = 65504.0 * 2.0 ** 15     # csrc/knn.hip kF2NormMax: a row at or beyond this squared norm is a forced candidate
+NORM_MAX = 65504.0 * 2.0 ** 15     # csrc/knn_filter.h kF2NormMax: a row at or beyond this squared norm is a forced candidate
 
 
 def _ptr(sizes):

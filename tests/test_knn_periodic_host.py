@@ -193,6 +193,33 @@ def test_abi_rejects_bad_periods(lib):
     assert b"null pointer" in lib.dmet_last_error()
 
 
+def test_abi_output_flags_are_stored_before_the_first_check(lib):
+    """dense_done / fused are written as 0 before any argument check, so a caller never reads a stale 1 after a
+    refused or an ineligible call (all of these return before a HIP call)."""
+    def flag():
+        v = ctypes.c_int(7)
+        return v, ctypes.cast(ctypes.pointer(v), ctypes.c_void_p)
+    # dmet_knn_local_dense_f32(x, ptr, B, N, D, k, nbr, dist, nbr16, W, bias, layout, P, Q, dense_done, ws, ws_bytes, stream)
+    done, done_p = flag()
+    assert lib.dmet_knn_local_dense_f32(None, None, 1, 10, 32, 8, None, None, None, None, None, 0, None, None, done_p,
+                                        None, 0, None) == -22
+    assert b"null pointer" in lib.dmet_last_error() and done.value == 0
+    # dmet_bn_knn_local_dense_f32(raw, residual, gamma, beta, mean, invstd, y, ptr, B, N, D, k, nbr, dist, nbr16, W, bias,
+    #                             layout, P, Q, dense_done, fused, ws, ws_bytes, stream)
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    done, done_p = flag()
+    fused, fused_p = flag()
+    assert lib.dmet_bn_knn_local_dense_f32(p, None, p, p, p, p, p, None, 1, 10, 16, 8, None, None, None, None, None, 0,
+                                           None, None, done_p, fused_p, None, 0, None) == 0        # D != 32: not eligible
+    assert fused.value == 0 and done.value == 0
+    done, done_p = flag()
+    fused, fused_p = flag()
+    assert lib.dmet_bn_knn_local_dense_f32(p, None, None, p, p, p, p, None, 1, 10, 32, 8, None, None, None, None, None, 0,
+                                           None, None, done_p, fused_p, None, 0, None) == -22      # null gamma
+    assert b"null pointer" in lib.dmet_last_error() and fused.value == 0 and done.value == 0
+
+
 # ---- the restatement ---------------------------------------------------------------------------------------------
 def test_reference_matches_the_oracle_on_plain_inputs():
     from oracle import ref_ops
