@@ -1080,6 +1080,86 @@ def gather_sum_bwd(g_out: torch.Tensor, deg: torch.Tensor, rev_ptr: torch.Tensor
     return gPQ[0], gPQ[1]
 
 
+GRAVNET_MAX_S = 16      # coordinates of the learned space (include/dmet.h, "GravNet aggregation")
+GRAVNET_MAX_P = 128     # DMET_MAX_H
+GRAVNET_MAX_K = 64      # DMET_MAX_K
+
+
+def gravnet_check_shapes(h: torch.Tensor, s_src: torch.Tensor, s_tgt: torch.Tensor, nbr: torch.Tensor) -> None:
+    """The argument errors of the GravNet entries, raised from shapes alone (before any device is asked for)."""
+    if h.dim() != 2 or s_src.dim() != 2 or s_tgt.dim() != 2 or nbr.dim() != 2:
+        raise ValueError(f"gravnet: h [Ns, P], s [N, S] and nbr [Nt, k] must be 2-D, got {tuple(h.shape)}, "
+                         f"{tuple(s_src.shape)}, {tuple(s_tgt.shape)}, {tuple(nbr.shape)}")
+    P, S, k = h.shape[1], s_src.shape[1], nbr.shape[1]
+    if not 1 <= S <= GRAVNET_MAX_S:
+        raise ValueError(f"gravnet: S={S} coordinates, supported 1..{GRAVNET_MAX_S}")
+    if not 1 <= P <= GRAVNET_MAX_P:
+        raise ValueError(f"gravnet: P={P} propagated features, supported 1..{GRAVNET_MAX_P}")
+    if not 1 <= k <= GRAVNET_MAX_K:
+        raise ValueError(f"gravnet: k={k}, supported 1..{GRAVNET_MAX_K}")
+    if s_tgt.shape[1] != S:
+        raise ValueError(f"gravnet: source coordinates have {S} columns, target coordinates {s_tgt.shape[1]}")
+    if h.shape[0] != s_src.shape[0]:
+        raise ValueError(f"gravnet: h has {h.shape[0]} rows, the source coordinates {s_src.shape[0]}")
+    if nbr.shape[0] != s_tgt.shape[0]:
+        raise ValueError(f"gravnet: the table has {nbr.shape[0]} rows, the target coordinates {s_tgt.shape[0]}")
+
+
+def gravnet_fwd(h: torch.Tensor, s_src: torch.Tensor, s_tgt: torch.Tensor,
+                nbr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(out[Nt, 2P] = [mean | max] of exp(-10 d) h_j over row i of nbr, arg[Nt, P] uint8, cnt[Nt] int32); see
+    include/dmet.h, dmet_gravnet_fwd_f32.  The one-set form passes the same tensor as s_src and s_tgt."""
+    gravnet_check_shapes(h, s_src, s_tgt, nbr)
+    dev = _require_device(h, s_src, s_tgt, nbr)
+    L = _lib.load()
+    h = _f32c(h, "h"); s_src = _f32c(s_src, "s"); s_tgt = _f32c(s_tgt, "s_dst"); nbr = _i32c(nbr, "nbr")
+    (Ns, P), S = h.shape, s_src.shape[1]
+    Nt, k = nbr.shape
+    out = torch.empty((Nt, 2 * P), dtype=torch.float32, device=dev)
+    arg = torch.empty((Nt, P), dtype=torch.uint8, device=dev)
+    cnt = torch.empty((Nt,), dtype=torch.int32, device=dev)
+    _t = timer.record('gravnet_fwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_gravnet_fwd_f32(s_tgt.data_ptr(), s_src.data_ptr(), h.data_ptr(), nbr.data_ptr(), Nt, Ns, k, S, P,
+                                          out.data_ptr(), arg.data_ptr(), cnt.data_ptr(), _stream(dev)),
+                   "dmet_gravnet_fwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, arg, cnt
+
+
+def gravnet_bwd(g_out: torch.Tensor, h: torch.Tensor, s_src: torch.Tensor, s_tgt: torch.Tensor, nbr: torch.Tensor,
+                rev_ptr: torch.Tensor, rev_pos: torch.Tensor, arg: torch.Tensor,
+                cnt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(g_h[Ns, P], g_s_src[Ns, S], g_s_tgt[Nt, S]) of gravnet_fwd; (rev_ptr, rev_pos) = the table's reverse index over
+    the Ns sources.  See include/dmet.h, dmet_gravnet_bwd_f32."""
+    gravnet_check_shapes(h, s_src, s_tgt, nbr)
+    dev = _require_device(g_out, h, s_src, s_tgt, nbr, rev_ptr, rev_pos, arg, cnt)
+    L = _lib.load()
+    h = _f32c(h, "h"); s_src = _f32c(s_src, "s"); s_tgt = _f32c(s_tgt, "s_dst"); nbr = _i32c(nbr, "nbr")
+    g_out = _f32c(g_out, "g_out")
+    rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_pos = _i32c(rev_pos, "rev_pos"); cnt = _i32c(cnt, "cnt")
+    (Ns, P), S = h.shape, s_src.shape[1]
+    Nt, k = nbr.shape
+    if g_out.shape != (Nt, 2 * P) or arg.shape != (Nt, P) or arg.dtype != torch.uint8 or not arg.is_contiguous():
+        raise ValueError(f"gravnet_bwd: g_out must be [{Nt}, {2 * P}] and arg a contiguous uint8 [{Nt}, {P}]")
+    if rev_ptr.numel() != Ns + 1 or rev_pos.numel() < Nt * k or cnt.numel() != Nt:
+        raise ValueError(f"gravnet_bwd: reverse index / cnt do not fit a [{Nt}, {k}] table over {Ns} sources")
+    g_h = torch.empty((Ns, P), dtype=torch.float32, device=dev)
+    g_s_src = torch.empty((Ns, S), dtype=torch.float32, device=dev)
+    g_s_tgt = torch.empty((Nt, S), dtype=torch.float32, device=dev)
+    g_d = torch.empty((Nt, k), dtype=torch.float32, device=dev)      # the one per-edge buffer: 4 B per slot
+    _t = timer.record('gravnet_bwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_gravnet_bwd_f32(s_tgt.data_ptr(), s_src.data_ptr(), h.data_ptr(), nbr.data_ptr(),
+                                          rev_ptr.data_ptr(), rev_pos.data_ptr(), arg.data_ptr(), cnt.data_ptr(),
+                                          g_out.data_ptr(), Nt, Ns, k, S, P, g_d.data_ptr(), g_s_tgt.data_ptr(),
+                                          g_s_src.data_ptr(), g_h.data_ptr(), _stream(dev)), "dmet_gravnet_bwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return g_h, g_s_src, g_s_tgt
+
+
 def reverse_index(keys: torch.Tensor, num_keys: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Stable sort of positions by int32 key: rev_ptr[num_keys+1] int32, rev_pos[M] int32 (see include/dmet.h)."""
     dev = _require_device(keys)

@@ -411,6 +411,16 @@ class BipartiteTable:
         self.num_candidates = num_candidates
         self._rp = None
         self._edges = None
+        self._rev = None
+
+    def reverse(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """rev_ptr[num_candidates+1], rev_pos[...]: the table positions i*k+s that hold candidate j, ascending, for every
+        j (a -1-padded table, cnt None; nothing is read back from the device)."""
+        if self.cnt is not None:
+            raise ValueError("BipartiteTable.reverse() needs a -1-padded table without cnt (knn_xy_table)")
+        if self._rev is None:
+            self._rev = _native.reverse_index(self.nbr.view(-1), self.num_candidates)
+        return self._rev
 
     def _rowptr(self):
         """(rowptr[Ny+1] int32, E) of the valid slots: one device-to-host read of the edge count."""

@@ -491,6 +491,37 @@ int dmet_gather_sum_csr_f32(const float *P, const float *Q, const int32_t *rowpt
 int dmet_gather_sum_bwd_f32(const float *g_out, const int32_t *deg, const int32_t *rev_ptr, const int32_t *rev_idx,
                             const int32_t *tgt, int64_t N, int k, int H, int mean, float *gP, float *gQ,
                             dmet_stream_t stream);
+/* ---- GravNet aggregation --------------------------------------------------------------------------------------
+ * replaces the propagate step of torch_geometric.nn.GravNetConv (message x_j * exp(-10 d^2), aggr ['mean', 'max']) and
+ * its autograd graph, which index_select the [E, P] messages twice and scatter them twice (csrc/gravnet.hip).
+ * Inputs: a fixed-width table nbr[Nt, k] int32 of ids into the SOURCE set (-1 = empty slot, anywhere in a row; an id
+ *   outside [0, Ns) is treated as empty), s_tgt[Nt, S] and s_src[Ns, S] the learned coordinates of the targets (the
+ *   table's rows) and of the sources, h[Ns, P] the features that are propagated.  The one-set form passes
+ *   s_src == s_tgt and Ns == Nt.  1 <= k <= DMET_MAX_K, 1 <= S <= 16, 1 <= P <= DMET_MAX_H (any P: 22 is the usual one).
+ * dmet_gravnet_fwd_f32, for target i and every valid slot t, j = nbr[i,t]:
+ *   d = sum_c fmaf(a, a, acc), a = s_src[j,c] - s_tgt[i,c], in coordinate order (R1: on a table of dmet_knn_f32 /
+ *       dmet_knn_xy_f32 built in the same space d has the bits of that table's dist);  w = expf(-10.0f * d)
+ *   out[i, 0:P]  = (sum_t w h[j,:]) / cnt_i   slots added in ascending t, cnt_i = the number of valid slots (PyG's mean)
+ *   out[i, P:2P] = max_t w h[j,p]             arg[Nt, P] uint8 = the winning slot, ties to the lowest slot (R4)
+ *   cnt[Nt] int32 = cnt_i.  A row without a valid slot gives zeros in both halves (R3), cnt 0 and arg = 255 ("no winner").
+ *   Nothing per edge is written.
+ * dmet_gravnet_bwd_f32, with g_msg[i,t,p] = g_out[i,p] / cnt_i + (arg[i,p] == t ? g_out[i,P+p] : 0):
+ *   g_h[j,p]     = sum over the (i,t) with nbr[i,t] == j of w g_msg[i,t,p]
+ *   g_w[i,t]     = sum_p g_msg[i,t,p] h[j,p],   g_d[i,t] = -10 w g_w   (0 in an empty slot)
+ *   g_s_tgt[i,c] = sum_t 2 g_d (s_tgt[i,c] - s_src[j,c]),   g_s_src[j,c] = sum over (i,t) of 2 g_d (s_src[j,c] - s_tgt[i,c])
+ *   in two launches: by target (g_d, g_s_tgt; ascending t), then by source over the reverse index rev_ptr[Ns+1],
+ *   rev_pos[] of dmet_reverse_index(nbr, Nt*k, Ns) (g_h, g_s_src; positions ascending).  g_d[Nt, k] fp32, 4 B per slot,
+ *   is the only per-edge buffer (caller's scratch, every slot written).  w is recomputed, never stored; an underflowed
+ *   w == 0 gives zero gradients, never NaN.  Every gradient is written, not accumulated; the caller of the one-set
+ *   form adds g_s = g_s_tgt + g_s_src.  No float atomics: sums run in a fixed order, two runs give identical bits.
+ * Both return -EINVAL on bad arguments before any device work.  Nt == 0: the forward returns 0 at once; the backward
+ * zero-fills g_h and g_s_src (Ns > 0) and returns. */
+int dmet_gravnet_fwd_f32(const float *s_tgt, const float *s_src, const float *h, const int32_t *nbr, int64_t Nt,
+                         int64_t Ns, int k, int S, int P, float *out, uint8_t *arg, int32_t *cnt, dmet_stream_t stream);
+int dmet_gravnet_bwd_f32(const float *s_tgt, const float *s_src, const float *h, const int32_t *nbr,
+                         const int32_t *rev_ptr, const int32_t *rev_pos, const uint8_t *arg, const int32_t *cnt,
+                         const float *g_out, int64_t Nt, int64_t Ns, int k, int S, int P, float *g_d, float *g_s_tgt,
+                         float *g_s_src, float *g_h, dmet_stream_t stream);
 /* Reverse index: a stable sort of the positions 0..M-1 of an int32 key array by key value.
  *   rev_ptr[num_keys+1]: rev_pos[rev_ptr[j] .. rev_ptr[j+1]-1] = the positions holding key j, ascending.
  * Keys outside [0, num_keys) (the -1 "no neighbour" entries) sort last and are not indexed.
