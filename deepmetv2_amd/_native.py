@@ -495,6 +495,29 @@ def bn_node_linear_split(raw: torch.Tensor, residual: Optional[torch.Tensor], ga
     return y, PQ[0], PQ[1]
 
 
+def _gather_run(dev: torch.device, key: str, note: Optional[str], entry: str, *args) -> None:
+    """One gather / scatter entry of the C ABI on dev's current stream (appended to args), inside a `key` bracket of the
+    timer; `note`, if given, becomes last_gather_kernel.  A failure is reported under the name of the entry called."""
+    _t = timer.record(key, dev)
+    if note is not None:
+        _note_gather(note)
+    with _on(dev):
+        _lib.check(getattr(_lib.load(), entry)(*args, _stream(dev)), entry)
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+
+
+def _pq_shape(P: torch.Tensor, sliced: bool) -> Tuple[int, int]:
+    """(N, H) of a row-major [N, H] table or of a slice-major [H/8, N, 8] one (node_linear_split(..., sliced=True))."""
+    return (P.shape[1], P.shape[0] * 8) if sliced else (P.shape[0], P.shape[1])
+
+
+def _check_nbr_local(nbr_local: Optional[torch.Tensor], nbr: torch.Tensor) -> None:
+    if nbr_local is not None and (nbr_local.shape != nbr.shape or nbr_local.dtype != torch.int16
+                                  or not nbr_local.is_contiguous()):
+        raise ValueError("nbr_local must be the contiguous int16 [N, k] table of knn_local()")
+
+
 def gather_max(P: torch.Tensor, Q: torch.Tensor, nbr: torch.Tensor, ptr: Optional[torch.Tensor],
                want_arg: bool, cnt: Optional[torch.Tensor] = None, lds: bool = False,
                nbr_local: Optional[torch.Tensor] = None, sliced: bool = False, mixed: bool = False,
@@ -504,91 +527,49 @@ def gather_max(P: torch.Tensor, Q: torch.Tensor, nbr: torch.Tensor, ptr: Optiona
     the form is chosen per event inside the call (row-major P / Q); else gathers come from L2.  max_nodes: the batch's
     largest event when the caller knows it (a hint: batches of small events run two 512-thread workgroups per CU)."""
     dev = _require_device(P, Q, nbr)
-    L = _lib.load()
-    if mixed and cnt is None and not sliced and ptr is not None and GATHER_MAX_FORM == "auto":
-        N, H = P.shape
-        k = nbr.shape[1]
-        out = torch.empty((N, H), dtype=torch.float32, device=dev)
-        arg = torch.empty((N, H), dtype=torch.uint8, device=dev) if want_arg else None
-        if nbr_local is not None and (nbr_local.shape != nbr.shape or nbr_local.dtype != torch.int16
-                                      or not nbr_local.is_contiguous()):
-            raise ValueError("nbr_local must be the contiguous int16 [N, k] table of knn_local()")
-        _t = timer.record('gather_max', dev)
-        _note_gather("gather_max_lds_kernel (events <= 5119 nodes: Q slice resident in LDS) + gather_max_mlp_kernel "
-                     "(larger events: row gathers from L2), chosen per event in one call; row-major P/Q")
-        with _on(dev):
-            _lib.check(L.dmet_gather_max_mixed_f32(P.data_ptr(), Q.data_ptr(), nbr.data_ptr(),
-                                                   nbr_local.data_ptr() if nbr_local is not None else None,
-                                                   ptr.data_ptr(), ptr.numel() - 1, N, k, H, out.data_ptr(),
-                                                   arg.data_ptr() if want_arg else None, _stream(dev)),
-                       "dmet_gather_max_mixed_f32")
-        if _t is not None:
-            _t.record(torch.cuda.current_stream(dev))
-        return out, arg
-    if sliced:      # [H/8, N, 8] tables of node_linear_split(..., sliced=True)
-        N, H = P.shape[1], P.shape[0] * 8
-    else:
-        N, H = P.shape
+    N, H = _pq_shape(P, sliced)
     k = nbr.shape[1]
     out = torch.empty((N, H), dtype=torch.float32, device=dev)
     arg = torch.empty((N, H), dtype=torch.uint8, device=dev) if want_arg else None
-    if sliced and cnt is None:
+    table = (P.data_ptr(), Q.data_ptr(), nbr.data_ptr())
+    local = nbr_local.data_ptr() if nbr_local is not None else None
+    events = (ptr.data_ptr(), ptr.numel() - 1) if ptr is not None else (None, 0)
+    outs = (out.data_ptr(), arg.data_ptr() if want_arg else None)
+    tail = (N, k, H) + outs
+    lds_form = ptr is not None and H % 8 == 0 and GATHER_MAX_FORM != "l2-only"
+    # the route: (entry, its arguments, what bench.py prints as the kernel)
+    if mixed and cnt is None and not sliced and ptr is not None and GATHER_MAX_FORM == "auto":
+        _check_nbr_local(nbr_local, nbr)
+        entry, args = "dmet_gather_max_mixed_f32", table + (local,) + events + tail
+        note = ("gather_max_lds_kernel (events <= 5119 nodes: Q slice resident in LDS) + gather_max_mlp_kernel "
+                "(larger events: row gathers from L2), chosen per event in one call; row-major P/Q")
+    elif sliced and cnt is None:      # [H/8, N, 8] tables of node_linear_split(..., sliced=True)
         if ptr is None or k not in LDS_GATHER_K or GATHER_MAX_FORM == "l2-only":
             raise ValueError("gather_max: slice-major tables are only read by the LDS-resident kernels")
-        _t = timer.record('gather_max', dev)
-        _note_gather("gather_max_lds_kernel (per-event Q slice resident in LDS; slice-major P/Q, "
-                     + ("uint16 event-local ids)" if nbr_local is not None else "int32 ids)"))
-        with _on(dev):
-            _lib.check(L.dmet_gather_max_lds_sliced_cap_f32(P.data_ptr(), Q.data_ptr(), nbr.data_ptr(),
-                                                            nbr_local.data_ptr() if nbr_local is not None else None,
-                                                            ptr.data_ptr(), ptr.numel() - 1, N, k, H, out.data_ptr(),
-                                                            arg.data_ptr() if want_arg else None, int(max_nodes or 0),
-                                                            _stream(dev)),
-                       "dmet_gather_max_lds_sliced_cap_f32")
-        if _t is not None:
-            _t.record(torch.cuda.current_stream(dev))
-        return out, arg
-    if cnt is not None:
-        _t = timer.record('gather_max', dev)
-        with _on(dev):
-            if lds and ptr is not None and H % 8 == 0 and GATHER_MAX_FORM != "l2-only":
-                _note_gather("gather_max_lds_kernel, counted rows (radius table; Q slice resident in LDS"
-                             + (", slice-major P/Q)" if sliced else ")"))
-                _lib.check(L.dmet_gather_max_counted_lds_f32(P.data_ptr(), Q.data_ptr(), nbr.data_ptr(), cnt.data_ptr(),
-                                                             ptr.data_ptr(), ptr.numel() - 1, N, k, H,
-                                                             1 if sliced else 0, out.data_ptr(),
-                                                             arg.data_ptr() if want_arg else None, _stream(dev)),
-                           "dmet_gather_max_counted_lds_f32")
-            elif sliced:
-                raise ValueError("gather_max: slice-major tables are only read by the LDS-resident kernels")
-            else:
-                _note_gather("gather_max_kernel, counted rows (radius table; gathers from L2)")
-                _lib.check(L.dmet_gather_max_counted_f32(P.data_ptr(), Q.data_ptr(), nbr.data_ptr(), cnt.data_ptr(), N, k,
-                                                         H, out.data_ptr(), arg.data_ptr() if want_arg else None,
-                                                         _stream(dev)), "dmet_gather_max_counted_f32")
-        if _t is not None:
-            _t.record(torch.cuda.current_stream(dev))
-        return out, arg
-    _t = timer.record('gather_max', dev)
-    use_lds = (lds or GATHER_MAX_FORM == "lds") and GATHER_MAX_FORM != "l2-only" and ptr is not None and H % 8 == 0
-    with _on(dev):
-        if use_lds and nbr_local is not None and k in LDS_GATHER_K:
-            if nbr_local.shape != nbr.shape or nbr_local.dtype != torch.int16 or not nbr_local.is_contiguous():
-                raise ValueError("nbr_local must be the contiguous int16 [N, k] table of knn_local()")
-            _note_gather("gather_max_lds_kernel (per-event Q slice resident in LDS; row-major P/Q, uint16 ids)")
-            _lib.check(L.dmet_gather_max_lds16_f32(P.data_ptr(), Q.data_ptr(), nbr.data_ptr(), nbr_local.data_ptr(),
-                                                   ptr.data_ptr(), ptr.numel() - 1, N, k, H, out.data_ptr(),
-                                                   arg.data_ptr() if want_arg else None, _stream(dev)),
-                       "dmet_gather_max_lds16_f32")
-        else:
-            fn = L.dmet_gather_max_lds_f32 if use_lds else L.dmet_gather_max_f32
-            _note_gather("gather_max_lds_kernel (per-event Q slice resident in LDS; row-major P/Q, int32 ids)" if use_lds
-                         else "gather_max_mlp_kernel (row gathers from L2; events too large for the LDS image)")
-            _lib.check(fn(P.data_ptr(), Q.data_ptr(), nbr.data_ptr(), ptr.data_ptr() if ptr is not None else None,
-                          (ptr.numel() - 1) if ptr is not None else 0, N, k, H, out.data_ptr(),
-                          arg.data_ptr() if want_arg else None, _stream(dev)), "dmet_gather_max_f32")
-    if _t is not None:
-        _t.record(torch.cuda.current_stream(dev))
+        entry, args = "dmet_gather_max_lds_sliced_cap_f32", table + (local,) + events + tail + (int(max_nodes or 0),)
+        note = ("gather_max_lds_kernel (per-event Q slice resident in LDS; slice-major P/Q, "
+                + ("uint16 event-local ids)" if nbr_local is not None else "int32 ids)"))
+    elif cnt is not None and lds and lds_form:
+        entry = "dmet_gather_max_counted_lds_f32"
+        args = table + (cnt.data_ptr(),) + events + (N, k, H, 1 if sliced else 0) + outs
+        note = ("gather_max_lds_kernel, counted rows (radius table; Q slice resident in LDS"
+                + (", slice-major P/Q)" if sliced else ")"))
+    elif sliced:
+        raise ValueError("gather_max: slice-major tables are only read by the LDS-resident kernels")
+    elif cnt is not None:
+        entry, args = "dmet_gather_max_counted_f32", table + (cnt.data_ptr(),) + tail
+        note = "gather_max_kernel, counted rows (radius table; gathers from L2)"
+    elif (lds or GATHER_MAX_FORM == "lds") and lds_form and nbr_local is not None and k in LDS_GATHER_K:
+        _check_nbr_local(nbr_local, nbr)
+        entry, args = "dmet_gather_max_lds16_f32", table + (local,) + events + tail
+        note = "gather_max_lds_kernel (per-event Q slice resident in LDS; row-major P/Q, uint16 ids)"
+    elif (lds or GATHER_MAX_FORM == "lds") and lds_form:
+        entry, args = "dmet_gather_max_lds_f32", table + events + tail
+        note = "gather_max_lds_kernel (per-event Q slice resident in LDS; row-major P/Q, int32 ids)"
+    else:
+        entry, args = "dmet_gather_max_f32", table + events + tail
+        note = "gather_max_mlp_kernel (row gathers from L2; events too large for the LDS image)"
+    _gather_run(dev, 'gather_max', note, entry, *args)
     return out, arg
 
 
@@ -608,24 +589,14 @@ def gather_max_counted_j16(P: torch.Tensor, Q: torch.Tensor, nbr: torch.Tensor, 
                            order: Optional[torch.Tensor], ptr: torch.Tensor, sliced: bool):
     """(out[N,H], argj[N,H] int16-typed uint16 winner ids) of the counted LDS gather (radius tables)."""
     dev = _require_device(P, Q, nbr, cnt, ptr)
-    L = _lib.load()
-    if sliced:
-        N, H = P.shape[1], P.shape[0] * 8
-    else:
-        N, H = P.shape
+    N, H = _pq_shape(P, sliced)
     k = nbr.shape[1]
     out = torch.empty((N, H), dtype=torch.float32, device=dev)
     argj = torch.empty((N, H), dtype=torch.int16, device=dev)
-    _t = timer.record('gather_max', dev)
-    _note_gather("gather_max_lds_kernel, counted rows (radius table; Q slice resident in LDS, winner ids, rows ordered by "
-                 "depth" + (", slice-major P/Q)" if sliced else ")"))
-    with _on(dev):
-        _lib.check(L.dmet_gather_max_counted_lds_j16_f32(P.data_ptr(), Q.data_ptr(), nbr.data_ptr(), cnt.data_ptr(),
-                                                         order.data_ptr() if order is not None else None, ptr.data_ptr(),
-                                                         ptr.numel() - 1, N, k, H, 1 if sliced else 0, out.data_ptr(),
-                                                         argj.data_ptr(), _stream(dev)), "dmet_gather_max_counted_lds_j16_f32")
-    if _t is not None:
-        _t.record(torch.cuda.current_stream(dev))
+    _gather_run(dev, 'gather_max', "gather_max_lds_kernel, counted rows (radius table; Q slice resident in LDS, winner ids, "
+                "rows ordered by depth" + (", slice-major P/Q)" if sliced else ")"), "dmet_gather_max_counted_lds_j16_f32",
+                P.data_ptr(), Q.data_ptr(), nbr.data_ptr(), cnt.data_ptr(), order.data_ptr() if order is not None else None,
+                ptr.data_ptr(), ptr.numel() - 1, N, k, H, 1 if sliced else 0, out.data_ptr(), argj.data_ptr())
     return out, argj
 
 
@@ -634,24 +605,14 @@ def gather_max_local_j16(P: torch.Tensor, Q: torch.Tensor, rows16: torch.Tensor,
     """gather_max_counted_j16 reading the ids from the uint16 rows of radius(..., local=True): identical (out, argj);
     want_arg=False (inference): (out, None)."""
     dev = _require_device(P, Q, rows16, cnt, ptr)
-    L = _lib.load()
-    if sliced:
-        N, H = P.shape[1], P.shape[0] * 8
-    else:
-        N, H = P.shape
+    N, H = _pq_shape(P, sliced)
     out = torch.empty((N, H), dtype=torch.float32, device=dev)
     argj = torch.empty((N, H), dtype=torch.int16, device=dev) if want_arg else None
-    _t = timer.record('gather_max', dev)
-    _note_gather("gather_max_lds_kernel, counted rows (radius table as event-local uint16 rows; Q slice resident in LDS, "
-                 "winner ids, rows ordered by depth" + (", slice-major P/Q)" if sliced else ")"))
-    with _on(dev):
-        _lib.check(L.dmet_gather_max_local_j16_f32(P.data_ptr(), Q.data_ptr(), rows16.data_ptr(), rows16.shape[1],
-                                                   cnt.data_ptr(), order.data_ptr() if order is not None else None,
-                                                   ptr.data_ptr(), ptr.numel() - 1, N, kmax, H, 1 if sliced else 0,
-                                                   out.data_ptr(), argj.data_ptr() if argj is not None else None, _stream(dev)),
-                   "dmet_gather_max_local_j16_f32")
-    if _t is not None:
-        _t.record(torch.cuda.current_stream(dev))
+    _gather_run(dev, 'gather_max', "gather_max_lds_kernel, counted rows (radius table as event-local uint16 rows; Q slice "
+                "resident in LDS, winner ids, rows ordered by depth" + (", slice-major P/Q)" if sliced else ")"),
+                "dmet_gather_max_local_j16_f32", P.data_ptr(), Q.data_ptr(), rows16.data_ptr(), rows16.shape[1],
+                cnt.data_ptr(), order.data_ptr() if order is not None else None, ptr.data_ptr(), ptr.numel() - 1, N, kmax, H,
+                1 if sliced else 0, out.data_ptr(), argj.data_ptr() if argj is not None else None)
     return out, argj
 
 
@@ -661,21 +622,14 @@ def gather_max_bwd_j16(g_out: torch.Tensor, argj: torch.Tensor, ptr: torch.Tenso
     sliced: gQ comes back slice-major, [8, N, 4] (for edgeconv_linear_bwd(..., gq_sliced=True): a scatter workgroup then
     writes one contiguous run instead of 16-byte pieces of 128-byte rows)."""
     dev = _require_device(g_out, argj, ptr)
-    L = _lib.load()
     g_out = _f32c(g_out, "g_out")
     N, H = g_out.shape
     if argj.dtype != torch.int16 or argj.shape != g_out.shape or not argj.is_contiguous():
         raise TypeError("gather_max_bwd_j16: argj must be the contiguous int16 [N,H] tensor of gather_max_counted_j16")
     sliced = bool(sliced and H == 32)
     gQ = torch.empty((8, N, 4) if sliced else (N, H), dtype=torch.float32, device=dev)
-    _t = timer.record('gather_max_bwd', dev)
-    with _on(dev):
-        entry = L.dmet_gather_max_bwd_j16_sliced_f32 if sliced else L.dmet_gather_max_bwd_j16_cap_f32
-        _lib.check(entry(g_out.data_ptr(), argj.data_ptr(), ptr.data_ptr(), ptr.numel() - 1, N, H,
-                         gQ.data_ptr(), int(max_nodes or 0), _stream(dev)),
-                   "dmet_gather_max_bwd_j16_sliced_f32" if sliced else "dmet_gather_max_bwd_j16_cap_f32")
-    if _t is not None:
-        _t.record(torch.cuda.current_stream(dev))
+    _gather_run(dev, 'gather_max_bwd', None, "dmet_gather_max_bwd_j16_sliced_f32" if sliced else "dmet_gather_max_bwd_j16_cap_f32",
+                g_out.data_ptr(), argj.data_ptr(), ptr.data_ptr(), ptr.numel() - 1, N, H, gQ.data_ptr(), int(max_nodes or 0))
     return gQ
 
 
@@ -1704,27 +1658,16 @@ def gather_max_bwd_lds(g_out: torch.Tensor, arg: torch.Tensor, nbr: torch.Tensor
     max_nodes: the batch's largest event when the caller knows it (a hint: workgroups sized for small events).
     sliced: gQ comes back slice-major, [8, N, 4] (for edgeconv_linear_bwd(..., gq_sliced=True))."""
     dev = _require_device(g_out, arg, nbr, ptr)
-    L = _lib.load()
     g_out = _f32c(g_out, "g_out")
     N, H = g_out.shape
     if arg.dtype != torch.uint8 or not arg.is_contiguous() or nbr.dtype != torch.int32 or not nbr.is_contiguous():
         raise TypeError("gather_max_bwd_lds: arg must be contiguous uint8, nbr contiguous int32")
-    B = ptr.numel() - 1
+    _check_nbr_local(nbr_local, nbr)
     sliced = bool(sliced and H == 32)
     gQ = torch.empty((8, N, 4) if sliced else (N, H), dtype=torch.float32, device=dev)
-    _t = timer.record('gather_max_bwd', dev)
-    with _on(dev):
-        if nbr_local is not None and (nbr_local.shape != nbr.shape or nbr_local.dtype != torch.int16
-                                      or not nbr_local.is_contiguous()):
-            raise ValueError("nbr_local must be the contiguous int16 [N, k] table of knn_local()")
-        entry = L.dmet_gather_max_bwd_sliced_f32 if sliced else L.dmet_gather_max_bwd_lds16_cap_f32
-        _lib.check(entry(g_out.data_ptr(), arg.data_ptr(), nbr.data_ptr(),
-                         nbr_local.data_ptr() if nbr_local is not None else None,
-                         ptr.data_ptr(), B, N, nbr.shape[1], H, gQ.data_ptr(),
-                         int(max_nodes or 0), _stream(dev)),
-                   "dmet_gather_max_bwd_sliced_f32" if sliced else "dmet_gather_max_bwd_lds16_cap_f32")
-    if _t is not None:
-        _t.record(torch.cuda.current_stream(dev))
+    _gather_run(dev, 'gather_max_bwd', None, "dmet_gather_max_bwd_sliced_f32" if sliced else "dmet_gather_max_bwd_lds16_cap_f32",
+                g_out.data_ptr(), arg.data_ptr(), nbr.data_ptr(), nbr_local.data_ptr() if nbr_local is not None else None,
+                ptr.data_ptr(), ptr.numel() - 1, N, nbr.shape[1], H, gQ.data_ptr(), int(max_nodes or 0))
     return gQ
 
 

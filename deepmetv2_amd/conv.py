@@ -72,6 +72,12 @@ def _lds_eligible(x, weight, table: NeighborTable, any_size: bool = False) -> bo
             and (not table.has_int32_table() or table.nbr.data_ptr() % 16 == 0))
 
 
+def _pq_sliced(lds: bool) -> bool:
+    """The LDS-resident gather reads P / Q slice by slice: have the dense layer write them slice-major (DMET_PQ_SLICED=0:
+    row-major)."""
+    return bool(lds and _native.GATHER_MAX_FORM != "l2-only" and os.environ.get("DMET_PQ_SLICED", "1") != "0")
+
+
 class _EdgeConvLinearMax(torch.autograd.Function):
     """out[i] = max_s (W.[x_i || x_j - x_i] + b), j = nbr[i,s], through P = x.(W1-W2)^T + b, Q = x.W2^T."""
 
@@ -95,27 +101,27 @@ class _EdgeConvLinearMax(torch.autograd.Function):
         elif table.cnt is not None:
             lds = (x.shape[1] == 32 and weight.shape[0] == 32 and table.ptr is not None
                    and table.max_nodes is not None and table.max_nodes <= _LDS_MAX_EVENT_NODES)
-            sliced = lds and _native.GATHER_MAX_FORM != "l2-only" and os.environ.get("DMET_PQ_SLICED", "1") != "0"
+            sliced = _pq_sliced(lds)
             pq = table.pq
             table.pq = None
-            if pq is not None and pq[2] is bool(sliced) and pq[0].shape[-2 if sliced else 0] == x.shape[0]:
+            if pq is not None and pq[2] is sliced and pq[0].shape[-2 if sliced else 0] == x.shape[0]:
                 P, Q = pq[0], pq[1]     # formed together with x by the BatchNorm before (EdgeConv.prebuild_hook)
             else:
                 P, Q = _native.node_linear_split(x, weight, bias, sliced=sliced)
             table.join()    # a table still being built on a side stream (graph.build_async): the dense layer ran beside it
             # radius tables with self loops (train.py:48): remember the winner's id, not its slot, so that the backward
             # needs no look-up in the 255-wide table, and walk the rows in order of their depth
-            ctx.j16 = (lds and need_grad and table.nonempty and _native.GATHER_MAX_FORM == "auto"
-                       and os.environ.get("DMET_RADIUS_J16", "1") != "0")
-            if ctx.j16 and table.rows16 is not None and os.environ.get("DMET_RADIUS_IDS", "rows16") == "rows16":
+            auto = lds and _native.GATHER_MAX_FORM == "auto"
+            ctx.j16 = auto and need_grad and table.nonempty and os.environ.get("DMET_RADIUS_J16", "1") != "0"
+            rows16 = table.rows16 is not None and os.environ.get("DMET_RADIUS_IDS", "rows16") == "rows16"
+            if ctx.j16 and rows16:
                 # ids from the event-local uint16 copy of the rows that the radius kernel wrote
                 out, arg = _native.gather_max_local_j16(P, Q, table.rows16, table.cnt, table.order_by_count(), table.ptr,
                                                         table.k, sliced)
             elif ctx.j16:
                 out, arg = _native.gather_max_counted_j16(P, Q, table.nbr, table.cnt, table.order_by_count(), table.ptr,
                                                           sliced)
-            elif (lds and not need_grad and table.rows16 is not None and _native.GATHER_MAX_FORM == "auto"
-                  and os.environ.get("DMET_RADIUS_IDS", "rows16") == "rows16"):
+            elif auto and not need_grad and rows16:
                 # inference over a radius table: the same uint16 rows, the maximum alone
                 out, arg = _native.gather_max_local_j16(P, Q, table.rows16, table.cnt, table.order_by_count(), table.ptr,
                                                         table.k, sliced, want_arg=False)
@@ -133,11 +139,10 @@ class _EdgeConvLinearMax(torch.autograd.Function):
             # kernel runs one (event, slice) workgroup per CU, so ragged sizes leave CUs idle behind the largest event
             mixed = (not lds and _lds_eligible(x, weight, table, any_size=True) and table.max_nodes is not None
                      and os.environ.get("DMET_GATHER_MIXED", "0") == "1")
-            # the LDS-resident gather reads P / Q slice by slice: have the dense layer write them slice-major
-            sliced = lds and _native.GATHER_MAX_FORM != "l2-only" and os.environ.get("DMET_PQ_SLICED", "1") != "0"
+            sliced = _pq_sliced(lds)
             pq = table.pq
             table.pq = None   # one consumer: the tables must not outlive this forward inside a cached graph
-            if pq is not None and pq[2] is bool(sliced) and pq[0].shape[-2 if sliced else 0] == x.shape[0]:
+            if pq is not None and pq[2] is sliced and pq[0].shape[-2 if sliced else 0] == x.shape[0]:
                 P, Q = pq[0], pq[1]   # the kNN build of this x carried the dense layer (dmet_knn_local_dense_f32)
             else:
                 P, Q = _native.node_linear_split(x, weight, bias, sliced=sliced)
@@ -731,7 +736,7 @@ class EdgeConv(torch.nn.Module):
         if not isinstance(table, NeighborTable) or table.cnt is None:
             return None
         lds = table.ptr is not None and table.max_nodes is not None and table.max_nodes <= _LDS_MAX_EVENT_NODES
-        sliced = bool(lds and _native.GATHER_MAX_FORM != "l2-only" and os.environ.get("DMET_PQ_SLICED", "1") != "0")
+        sliced = _pq_sliced(lds)
 
         def build(raw, residual, gamma, beta, mean, invstd):
             if not raw.is_cuda or raw.dim() != 2 or raw.shape[0] != table.num_nodes:

@@ -1233,64 +1233,275 @@ extern "C" int dmet_bn_node_linear_split_f32(const float *raw, const float *resi
     return 0;
 }
 
-extern "C" int dmet_gather_max_counted_f32(const float *P, const float *Q, const int32_t *nbr, const int32_t *cnt,
-                                           int64_t N, int k, int H, float *out, uint8_t *arg, dmet_stream_t stream);
+// ---- K3 host path: every dmet_gather_max_* forward entry fills a GatherMax and calls gather_max_launch once ------------
+namespace {
+
+constexpr int kLdsGatherRowsHalf = kLdsGatherRows / 2;       // 2 560 rows = 80 KB
+constexpr int kLdsGatherThreadsHalf = kLdsGatherThreads / 2; // 512 threads: two such workgroups per CU
+
+// Host side of the kernels' template ladders (cf. with_pack in knn_common.h): a run-time value reaches a generic lambda
+// as a std::integral_constant, so that each kernel's launch expression is written once.
+// with_int<Vs...>(v, f): f(integral_constant<int, V>) for the V among Vs that equals v; false when none does.
+template <int... Vs, typename F>
+bool with_int(int v, F &&f)
+{
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+// with_flags(f, b...): f(std::true_type or std::false_type, ...), one per bool.
+template <typename F>
+void with_flags(F &&f) { f(); }
+template <typename F, typename... Rest>
+void with_flags(F &&f, bool b, Rest... rest)
+{
+    if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// what the entry promises about the batch; gather_max_launch makes one of its seven forms of it
+enum GatherFamily {
+    kGatherL2,          // nothing: row gathers from L2
+    kGatherLds,         // a kNN table whose events fit the LDS image (with skip_big: those that do)
+    kGatherCountedLds   // the same for counted rows (radius tables)
+};
+
+struct GatherMax {
+    const char *entry;                  // the exported function the caller called: every message names it
+    GatherFamily family;
+    const float *P, *Q;                 // [N, H], or slice-major [H/8][N][8] (pq_sliced)
+    int64_t N;
+    int k, H;                           // slots of a table row, channels
+    float *out;
+    dmet_stream_t stream;
+    const int32_t *nbr = nullptr;       // [N, k] node ids
+    const uint16_t *nbr16 = nullptr;    // event-local ids: an [N, k] copy beside nbr, or (rows16) the table itself, rows of
+    bool rows16 = false;                //   stride16 ids, and nbr is not read
+    int stride16 = 0;
+    const int32_t *cnt = nullptr;       // counted rows: the first cnt[i] slots of row i are used
+    const int32_t *order = nullptr;     // counted rows: optional order in which an event's nodes are walked
+    const int64_t *ptr = nullptr;       // the B events (LDS families)
+    int B = 0;
+    void *arg = nullptr;                // optional winners: uint8 slots, or (arg16) uint16 event-local ids
+    bool arg16 = false;
+    bool pq_sliced = false;
+    int skip_big = 0;                   // mixed: the LDS launch leaves events beyond its image to a second, L2 launch
+    int64_t max_nodes = 0;              // hint: the batch's largest event (0 = unknown)
+};
+
+int gather_max_launch(const GatherMax &r)
+{
+    const int64_t N = r.N;
+    const int k = r.k, H = r.H, B = r.B;
+    const bool k_mlp = k == 8 || k == 16 || k == 32, k_lds = k_mlp || k == 20;
+    // the mixed entry is an LDS request only where both of its kernels are built, and an L2 request elsewhere
+    const GatherFamily fam = (r.skip_big && !(H == 32 && k_mlp && B != 0)) ? kGatherL2 : r.family;
+    DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647, "%s: N out of range", r.entry);
+    DMET_REQUIRE(k >= 1 && k <= 255, "%s: k=%d not in [1,255] (arg is uint8, 255 = none)", r.entry, k);
+    DMET_REQUIRE(!r.rows16 || (r.stride16 >= k && r.stride16 % 8 == 0), "%s: kmax=%d stride16=%d", r.entry, k, r.stride16);
+    DMET_REQUIRE(r.max_nodes >= 0, "%s: max_nodes=%lld", r.entry, (long long)r.max_nodes);
+    DMET_REQUIRE(fam == kGatherL2 || (H >= kSliceC && H % kSliceC == 0 && H <= DMET_MAX_H), "%s: H=%d must be a multiple of %d",
+                 r.entry, H, kSliceC);
+    if (N == 0 || (fam != kGatherL2 && B == 0)) return 0;
+    const void *table = r.rows16 ? static_cast<const void *>(r.nbr16) : r.nbr;
+    // (winner ids out of the int32 table are built for training alone: that entry must be given arg)
+    DMET_REQUIRE(r.P && r.Q && table && r.out && (fam == kGatherL2 || r.ptr) && (fam != kGatherCountedLds || r.cnt) &&
+                     (r.arg || !r.arg16 || r.rows16),
+                 "%s: null pointer", r.entry);
+    DMET_REQUIRE(aligned16(r.P) && aligned16(r.Q) && aligned16(r.out) && (fam != kGatherLds || aligned16(r.nbr)) &&
+                     (fam == kGatherL2 || aligned16(r.nbr16)) && (!r.arg16 || (reinterpret_cast<uintptr_t>(r.arg) & 7u) == 0),
+                 "%s: pointers must be 16-B (uint16 winners: 8-B) aligned", r.entry);
+    hipStream_t st = as_stream(r.stream);
+    uint8_t *arg = static_cast<uint8_t *>(r.arg);
+    const int nsl = H / kSliceC;
+    // one workgroup per (event, slice), the events padded to a multiple of the XCD count
+    const int64_t per_event = (int64_t)((B + kNumXcd - 1) / kNumXcd) * kNumXcd * nsl;
+
+    // the deep-MLP L2 kernel over all nodes, or (only_big) over those of the events beyond the LDS image
+    auto launch_mlp = [&](bool only_big) {
+        with_int<8, 16, 32>(k, [&](auto kk) {
+            constexpr int K4 = decltype(kk)::value / 4;
+            with_flags([&](auto with_arg, auto big) {
+                hipLaunchKernelGGL((gather_max_mlp_kernel<32, with_arg(), K4, big()>), dim3((unsigned)((N + 31) / 32)), dim3(256),
+                                   0, st, r.P, r.Q, r.nbr, N, r.out, arg, r.ptr, B, kLdsGatherRows);
+            }, arg != nullptr, only_big);
+        });
+    };
+
+    // The form: the first of the seven whose condition holds.
+    if (fam == kGatherCountedLds) {
+        // 1. counted rows, winner ids (arg16; read from the uint16 rows or the int32 table);  2. counted rows, slots
+        with_flags([&](auto with_arg, auto sliced, auto ids, auto loc16) {
+            if constexpr (ids() ? (with_arg() || loc16()) : !loc16())      // the instances that are built
+                hipLaunchKernelGGL((gather_max_lds_counted_kernel<with_arg(), sliced(), ids(), loc16()>),
+                                   dim3((unsigned)per_event), dim3(kLdsGatherThreads), 0, st, r.P, r.Q, r.nbr, r.cnt, r.ptr, B, k, H,
+                                   r.out, arg, N, r.order, r.nbr16, r.stride16);
+        }, arg != nullptr, r.pq_sliced, r.arg16, r.rows16);
+        DMET_LAUNCH_CHECK(!r.arg16 ? "gather_max_lds_counted_kernel" : !r.rows16 ? "gather_max_lds_counted_kernel (winner ids)"
+                          : arg     ? "gather_max_lds_counted_kernel (uint16 rows)"
+                                    : "gather_max_lds_counted_kernel (uint16 rows, no winners)");
+        return 0;
+    }
+    if (fam == kGatherLds && k_lds) {
+        // 3. batches of small events (the caller's hint; an event beyond it would take the in-kernel L2 path: slower, never
+        //    wrong): the half image, one workgroup per (event, slice), two per CU
+        const bool half = r.pq_sliced && r.nbr16 && r.max_nodes > 0 && r.max_nodes + 1 <= kLdsGatherRowsHalf &&
+                          !env_is("DMET_GATHER_HALF_IMAGE", "0");
+        // 4. the full image, balanced or one workgroup per (event, slice).
+        // Measured at 4500-node events on 256 CUs (tools/gather_sweep.py, us, one workgroup per (event, slice) / balanced):
+        // B = 32: 35.8 / 29.5, 48: 37.2 / 41.0, 64: 39.6 / 40.8, 65: 56.6 / 45.0, 96: 65.2 / 67.2, 128: 69.8 / 94.2 -- a range
+        // that cuts an (event, slice) stages its slice twice, and independent workgroups drift apart so that one CU's staging
+        // hides under its neighbours' gathers, which the lock-step ranges of the balanced form do not.  It wins when the
+        // (event, slice) units fill well under the chip or leave a short tail round.  DMET_GATHER_BALANCED=0/1 forces either.
+        const int cus = num_cus();
+        const int64_t units = (int64_t)B * nsl;
+        int balanced = units * 16 <= (int64_t)cus * 9 || (units > cus && units % cus != 0 && units % cus <= cus / 8);
+        if (const char *e = getenv("DMET_GATHER_BALANCED")) balanced = atoi(e) != 0;
+        if (half) balanced = 0;
+        int64_t blocks = per_event;
+        if (balanced) {
+            blocks = cus;
+            const int64_t most = ((int64_t)nsl * N + 63) / 64;
+            if (blocks > most) blocks = most;
+        }
+        bool timed = false;
+#ifdef DMET_KNN_EXPERIMENT
+        // phase timing (tools/build_variant.sh exp -DDMET_KNN_EXPERIMENT): DMET_GML_MODE=1 skips the staging of the Q
+        // slice, =2 the LDS gather + compare chain (results are then meaningless)
+        const char *e = (!half && arg && r.nbr16 && k == 16) ? getenv("DMET_GML_MODE") : nullptr;
+        timed = with_int<1, 2>(e ? atoi(e) : 0, [&](auto mode) {
+            hipLaunchKernelGGL((gather_max_lds_kernel<true, 4, decltype(mode)::value, true>), dim3((unsigned)blocks),
+                               dim3(kLdsGatherThreads), 0, st, r.P, r.Q, r.nbr, r.nbr16, r.ptr, B, k, H, r.out, arg, N, r.skip_big,
+                               balanced);
+        });
+#endif
+        if (!timed)
+            with_int<8, 16, 20, 32>(k, [&](auto kk) {
+                constexpr int K4 = decltype(kk)::value / 4;
+                with_flags([&](auto with_arg, auto ids16, auto sliced, auto small) {
+                    constexpr int ROWS = small() ? kLdsGatherRowsHalf : kLdsGatherRows;
+                    constexpr int THREADS = small() ? kLdsGatherThreadsHalf : kLdsGatherThreads;
+                    if constexpr (!small() || (ids16() && sliced()))     // the half image reads slice-major tables by uint16 ids
+                        hipLaunchKernelGGL((gather_max_lds_kernel<with_arg(), K4, 0, ids16(), sliced(), ROWS, THREADS>),
+                                           dim3((unsigned)blocks), dim3(THREADS), 0, st, r.P, r.Q, r.nbr, r.nbr16, r.ptr, B, k, H, r.out,
+                                           arg, N, r.skip_big, balanced);
+                }, arg != nullptr, r.nbr16 != nullptr, r.pq_sliced, half);
+            });
+        DMET_LAUNCH_CHECK(half ? "gather_max_lds_kernel (80 KB image)" : "gather_max_lds_kernel");
+        if (!r.skip_big) return 0;
+        // 5. mixed, the per-EVENT choice on ragged batches: the launch above has skipped the events beyond its image, this
+        //    one computes them and skips the others; both read the row-major tables
+        launch_mlp(true);
+        DMET_LAUNCH_CHECK("gather_max_mlp_kernel (large events)");
+        return 0;
+    }
+    // other widths k of a row-major LDS request, and every L2 request: gathers from L2
+    DMET_REQUIRE(!r.pq_sliced, "%s: k=%d (slice-major tables need k in {8,16,20,32})", r.entry, k);
+    bool built = true;
+    if (H == 32 && !r.cnt && k_mlp && aligned16(r.nbr))
+        launch_mlp(false);      // 6. the kNN tables of the hot path: the deep-MLP kernel
+    else                        // 7. any k, counted rows or not, by H
+        built = with_int<16, 32, 64, 128>(H, [&](auto hh) {
+            constexpr int HH = decltype(hh)::value, NPB = 256 / (HH / 4);
+            with_flags([&](auto with_arg) {
+                hipLaunchKernelGGL((gather_max_kernel<HH, with_arg()>), dim3((unsigned)((N + NPB - 1) / NPB)), dim3(256), 0, st, r.P,
+                                   r.Q, r.nbr, r.cnt, N, k, r.out, arg);
+            }, arg != nullptr);
+        });
+    DMET_REQUIRE(built, "%s: unsupported H=%d (16/32/64/128)", r.entry, H);
+    DMET_LAUNCH_CHECK("gather_max_kernel");
+    return 0;
+}
+
+}  // namespace
 
 extern "C" int dmet_gather_max_f32(const float *P, const float *Q, const int32_t *nbr, const int64_t *ptr, int B,
                                    int64_t N, int k, int H, float *out, uint8_t *arg, dmet_stream_t stream)
 {
-    (void)ptr; (void)B;
-    return dmet_gather_max_counted_f32(P, Q, nbr, nullptr, N, k, H, out, arg, stream);
+    (void)ptr; (void)B;     // the L2 form reads no events
+    GatherMax r{"dmet_gather_max_f32", kGatherL2, P, Q, N, k, H, out, stream};
+    r.nbr = nbr; r.arg = arg;
+    return gather_max_launch(r);
 }
 
 extern "C" int dmet_gather_max_counted_f32(const float *P, const float *Q, const int32_t *nbr, const int32_t *cnt,
                                            int64_t N, int k, int H, float *out, uint8_t *arg, dmet_stream_t stream)
 {
-    DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647, "dmet_gather_max_f32: N out of range");
-    DMET_REQUIRE(k >= 1 && k <= 255, "dmet_gather_max_f32: k=%d not in [1,255] (arg is uint8, 255 = none)", k);
-    if (N == 0) return 0;
-    DMET_REQUIRE(P && Q && nbr && out, "dmet_gather_max_f32: null pointer");
-    DMET_REQUIRE(aligned16(P) && aligned16(Q) && aligned16(out), "dmet_gather_max_f32: pointers must be 16-B aligned");
-    hipStream_t st = as_stream(stream);
-#define DMET_GM(HH)                                                                                             \
-    do {                                                                                                        \
-        constexpr int NPB = 256 / (HH / 4);                                                                     \
-        const int64_t blocks = (N + NPB - 1) / NPB;                                                             \
-        if (arg)                                                                                                \
-            hipLaunchKernelGGL((gather_max_kernel<HH, true>), dim3((unsigned)blocks), dim3(256), 0, st, P, Q,   \
-                               nbr, cnt, N, k, out, arg);                                                       \
-        else                                                                                                    \
-            hipLaunchKernelGGL((gather_max_kernel<HH, false>), dim3((unsigned)blocks), dim3(256), 0, st, P, Q,  \
-                               nbr, cnt, N, k, out, arg);                                                       \
-    } while (0)
-    if (H == 32 && !cnt && (k == 8 || k == 16 || k == 32) && aligned16(nbr)) {
-        // the kNN tables of the hot path: deep-MLP variant
-        const int64_t blocks = (N + 31) / 32;
-#define DMET_GMM(K4_)                                                                                          \
-        do {                                                                                                   \
-            if (arg)                                                                                           \
-                hipLaunchKernelGGL((gather_max_mlp_kernel<32, true, K4_>), dim3((unsigned)blocks), dim3(256),  \
-                                   0, st, P, Q, nbr, N, out, arg);                                             \
-            else                                                                                               \
-                hipLaunchKernelGGL((gather_max_mlp_kernel<32, false, K4_>), dim3((unsigned)blocks), dim3(256), \
-                                   0, st, P, Q, nbr, N, out, arg);                                             \
-        } while (0)
-        if (k == 8) DMET_GMM(2);
-        else if (k == 16) DMET_GMM(4);
-        else DMET_GMM(8);
-#undef DMET_GMM
-    }
-    else if (H == 32) DMET_GM(32);
-    else if (H == 64) DMET_GM(64);
-    else if (H == 128) DMET_GM(128);
-    else if (H == 16) DMET_GM(16);
-    else {
-        set_error("dmet_gather_max_f32: unsupported H=%d (16/32/64/128)", H);
-        return -22;
-    }
-#undef DMET_GM
-    DMET_LAUNCH_CHECK("gather_max_kernel");
-    return 0;
+    GatherMax r{"dmet_gather_max_counted_f32", kGatherL2, P, Q, N, k, H, out, stream};
+    r.nbr = nbr; r.cnt = cnt; r.arg = arg;
+    return gather_max_launch(r);
+}
+
+extern "C" int dmet_gather_max_lds_f32(const float *P, const float *Q, const int32_t *nbr, const int64_t *ptr, int B,
+                                       int64_t N, int k, int H, float *out, uint8_t *arg, dmet_stream_t stream)
+{
+    GatherMax r{"dmet_gather_max_lds_f32", kGatherLds, P, Q, N, k, H, out, stream};
+    r.nbr = nbr; r.ptr = ptr; r.B = B; r.arg = arg;
+    return gather_max_launch(r);
+}
+
+extern "C" int dmet_gather_max_lds16_f32(const float *P, const float *Q, const int32_t *nbr, const uint16_t *nbr_local,
+                                         const int64_t *ptr, int B, int64_t N, int k, int H, float *out,
+                                         uint8_t *arg, dmet_stream_t stream)
+{
+    GatherMax r{"dmet_gather_max_lds16_f32", kGatherLds, P, Q, N, k, H, out, stream};
+    r.nbr = nbr; r.nbr16 = nbr_local; r.ptr = ptr; r.B = B; r.arg = arg;
+    return gather_max_launch(r);
+}
+
+extern "C" int dmet_gather_max_mixed_f32(const float *P, const float *Q, const int32_t *nbr, const uint16_t *nbr_local,
+                                         const int64_t *ptr, int B, int64_t N, int k, int H, float *out,
+                                         uint8_t *arg, dmet_stream_t stream)
+{
+    GatherMax r{"dmet_gather_max_mixed_f32", kGatherLds, P, Q, N, k, H, out, stream};
+    r.nbr = nbr; r.nbr16 = nbr_local; r.ptr = ptr; r.B = B; r.arg = arg; r.skip_big = 1;
+    return gather_max_launch(r);
+}
+
+extern "C" int dmet_gather_max_lds_sliced_f32(const float *P, const float *Q, const int32_t *nbr,
+                                              const uint16_t *nbr_local, const int64_t *ptr, int B, int64_t N, int k,
+                                              int H, float *out, uint8_t *arg, dmet_stream_t stream)
+{
+    GatherMax r{"dmet_gather_max_lds_sliced_f32", kGatherLds, P, Q, N, k, H, out, stream};
+    r.nbr = nbr; r.nbr16 = nbr_local; r.ptr = ptr; r.B = B; r.arg = arg; r.pq_sliced = true;
+    return gather_max_launch(r);
+}
+
+extern "C" int dmet_gather_max_lds_sliced_cap_f32(const float *P, const float *Q, const int32_t *nbr,
+                                                  const uint16_t *nbr_local, const int64_t *ptr, int B, int64_t N, int k,
+                                                  int H, float *out, uint8_t *arg, int64_t max_nodes, dmet_stream_t stream)
+{
+    GatherMax r{"dmet_gather_max_lds_sliced_cap_f32", kGatherLds, P, Q, N, k, H, out, stream};
+    r.nbr = nbr; r.nbr16 = nbr_local; r.ptr = ptr; r.B = B; r.arg = arg; r.pq_sliced = true; r.max_nodes = max_nodes;
+    return gather_max_launch(r);
+}
+
+extern "C" int dmet_gather_max_counted_lds_f32(const float *P, const float *Q, const int32_t *nbr, const int32_t *cnt,
+                                               const int64_t *ptr, int B, int64_t N, int k, int H, int pq_sliced,
+                                               float *out, uint8_t *arg, dmet_stream_t stream)
+{
+    GatherMax r{"dmet_gather_max_counted_lds_f32", kGatherCountedLds, P, Q, N, k, H, out, stream};
+    r.nbr = nbr; r.cnt = cnt; r.ptr = ptr; r.B = B; r.arg = arg; r.pq_sliced = pq_sliced != 0;
+    return gather_max_launch(r);
+}
+
+extern "C" int dmet_gather_max_counted_lds_j16_f32(const float *P, const float *Q, const int32_t *nbr, const int32_t *cnt,
+                                                   const int32_t *order, const int64_t *ptr, int B, int64_t N, int k,
+                                                   int H, int pq_sliced, float *out, uint16_t *argj,
+                                                   dmet_stream_t stream)
+{
+    GatherMax r{"dmet_gather_max_counted_lds_j16_f32", kGatherCountedLds, P, Q, N, k, H, out, stream};
+    r.nbr = nbr; r.cnt = cnt; r.order = order; r.ptr = ptr; r.B = B; r.arg = argj; r.arg16 = true; r.pq_sliced = pq_sliced != 0;
+    return gather_max_launch(r);
+}
+
+extern "C" int dmet_gather_max_local_j16_f32(const float *P, const float *Q, const uint16_t *nbr16, int stride16,
+                                             const int32_t *cnt, const int32_t *order, const int64_t *ptr, int B,
+                                             int64_t N, int kmax, int H, int pq_sliced, float *out, uint16_t *argj,
+                                             dmet_stream_t stream)
+{
+    GatherMax r{"dmet_gather_max_local_j16_f32", kGatherCountedLds, P, Q, N, kmax, H, out, stream};
+    r.nbr16 = nbr16; r.rows16 = true; r.stride16 = stride16; r.cnt = cnt; r.order = order; r.ptr = ptr; r.B = B;
+    r.arg = argj; r.arg16 = true; r.pq_sliced = pq_sliced != 0;
+    return gather_max_launch(r);
 }
 
 extern "C" int dmet_edgeconv_fused_lds_f32(const float *x, const int32_t *nbr, const int64_t *ptr, int B, int64_t N,
@@ -1379,186 +1590,6 @@ extern "C" int dmet_gather_max_bf16q(const float *P, const uint16_t *Qh, const i
     return 0;
 }
 
-constexpr int kLdsGatherRowsHalf = kLdsGatherRows / 2;       // 2 560 rows = 80 KB
-constexpr int kLdsGatherThreadsHalf = kLdsGatherThreads / 2; // 512 threads: two such workgroups per CU
-
-static int gather_max_lds_impl(const float *P, const float *Q, const int32_t *nbr, const uint16_t *nbr16,
-                               const int64_t *ptr, int B, int64_t N, int k, int H, float *out, uint8_t *arg,
-                               bool sliced, dmet_stream_t stream, int skip_big = 0, int64_t max_nodes = 0)
-{
-    DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647, "dmet_gather_max_lds_f32: N out of range");
-    DMET_REQUIRE(k >= 1 && k <= 255, "dmet_gather_max_lds_f32: k=%d not in [1,255]", k);
-    DMET_REQUIRE(H >= kSliceC && H % kSliceC == 0 && H <= DMET_MAX_H, "dmet_gather_max_lds_f32: H=%d must be a multiple of %d", H,
-                 kSliceC);
-    if (N == 0 || B == 0) return 0;
-    DMET_REQUIRE(P && Q && nbr && ptr && out, "dmet_gather_max_lds_f32: null pointer");
-    DMET_REQUIRE(aligned16(P) && aligned16(Q) && aligned16(out) && aligned16(nbr) && aligned16(nbr16),
-                 "dmet_gather_max_lds_f32: pointers must be 16-B aligned");
-    const int nsl = H / kSliceC;
-    const int64_t groups = (B + kNumXcd - 1) / kNumXcd;
-    int64_t blocks = groups * kNumXcd * nsl;
-    // Measured at 4500-node events on 256 CUs (tools/gather_sweep.py, us, one workgroup per (event, slice) / balanced):
-    // B = 32: 35.8 / 29.5, 48: 37.2 / 41.0, 64: 39.6 / 40.8, 65: 56.6 / 45.0, 96: 65.2 / 67.2, 128: 69.8 / 94.2 -- a range
-    // that cuts an (event, slice) stages its slice twice, and independent workgroups drift apart so that one CU's staging
-    // hides under its neighbours' gathers, which the lock-step ranges of the balanced form do not.  It wins when the
-    // (event, slice) units fill well under the chip or leave a short tail round.  DMET_GATHER_BALANCED=0/1 forces either.
-    const int cus = num_cus();
-    const int64_t units = (int64_t)B * nsl;
-    int balanced = units * 16 <= (int64_t)cus * 9 || (units > cus && units % cus != 0 && units % cus <= cus / 8);
-    if (const char *e = getenv("DMET_GATHER_BALANCED")) balanced = atoi(e) != 0;
-    if (balanced) {
-        blocks = cus;
-        const int64_t most = ((int64_t)nsl * N + 63) / 64;
-        if (blocks > most) blocks = most;
-    }
-    hipStream_t st = as_stream(stream);
-    // batches of small events (the caller's hint; an event beyond it would take the in-kernel L2 path: slower, never wrong):
-    // the half form, one workgroup per (event, slice), two per CU
-    if (sliced && nbr16 && max_nodes > 0 && max_nodes + 1 <= kLdsGatherRowsHalf && (k == 8 || k == 16 || k == 20 || k == 32) &&
-        !env_is("DMET_GATHER_HALF_IMAGE", "0")) {
-        const int64_t hblocks = groups * kNumXcd * nsl;
-#define DMET_GMH(K4_)                                                                                                  \
-        do {                                                                                                           \
-            if (arg)                                                                                                   \
-                hipLaunchKernelGGL((gather_max_lds_kernel<true, K4_, 0, true, true, kLdsGatherRowsHalf, kLdsGatherThreadsHalf>), \
-                                   dim3((unsigned)hblocks), dim3(kLdsGatherThreadsHalf), 0, st, P, Q, nbr, nbr16, ptr, B, k, H, \
-                                   out, arg, N, skip_big, 0);                                                          \
-            else                                                                                                       \
-                hipLaunchKernelGGL((gather_max_lds_kernel<false, K4_, 0, true, true, kLdsGatherRowsHalf, kLdsGatherThreadsHalf>), \
-                                   dim3((unsigned)hblocks), dim3(kLdsGatherThreadsHalf), 0, st, P, Q, nbr, nbr16, ptr, B, k, H, \
-                                   out, arg, N, skip_big, 0);                                                          \
-        } while (0)
-        if (k == 8) DMET_GMH(2);
-        else if (k == 16) DMET_GMH(4);
-        else if (k == 20) DMET_GMH(5);
-        else DMET_GMH(8);
-#undef DMET_GMH
-        DMET_LAUNCH_CHECK("gather_max_lds_kernel (80 KB image)");
-        return 0;
-    }
-#define DMET_GML_LAUNCH(ARG_, K4_, I16_)                                                                          \
-    do {                                                                                                          \
-        if (sliced)                                                                                               \
-            hipLaunchKernelGGL((gather_max_lds_kernel<ARG_, K4_, 0, I16_, true>), dim3((unsigned)blocks),         \
-                               dim3(kLdsGatherThreads), 0, st, P, Q, nbr, nbr16, ptr, B, k, H, out, arg, N, skip_big, balanced); \
-        else                                                                                                      \
-            hipLaunchKernelGGL((gather_max_lds_kernel<ARG_, K4_, 0, I16_, false>), dim3((unsigned)blocks),        \
-                               dim3(kLdsGatherThreads), 0, st, P, Q, nbr, nbr16, ptr, B, k, H, out, arg, N, skip_big, balanced); \
-    } while (0)
-#define DMET_GML(K4_)                                                                                          \
-    do {                                                                                                       \
-        if (arg) { if (nbr16) DMET_GML_LAUNCH(true, K4_, true); else DMET_GML_LAUNCH(true, K4_, false); }      \
-        else { if (nbr16) DMET_GML_LAUNCH(false, K4_, true); else DMET_GML_LAUNCH(false, K4_, false); }        \
-    } while (0)
-#ifdef DMET_KNN_EXPERIMENT
-    // phase timing (tools/build_variant.sh exp -DDMET_KNN_EXPERIMENT): DMET_GML_MODE=1 skips the staging of the Q
-    // slice, =2 the LDS gather + compare chain (results are then meaningless)
-    if (const char *e = (arg && nbr16 && k == 16) ? getenv("DMET_GML_MODE") : nullptr) {
-        const int m = atoi(e);
-        if (m == 1) hipLaunchKernelGGL((gather_max_lds_kernel<true, 4, 1, true>), dim3((unsigned)blocks), dim3(kLdsGatherThreads), 0, st, P, Q, nbr, nbr16, ptr, B, k, H, out, arg, N, skip_big, balanced);
-        else if (m == 2) hipLaunchKernelGGL((gather_max_lds_kernel<true, 4, 2, true>), dim3((unsigned)blocks), dim3(kLdsGatherThreads), 0, st, P, Q, nbr, nbr16, ptr, B, k, H, out, arg, N, skip_big, balanced);
-        else DMET_GML(4);
-        DMET_LAUNCH_CHECK("gather_max_lds_kernel");
-        return 0;
-    }
-#endif
-    if (k == 8) DMET_GML(2);
-    else if (k == 16) DMET_GML(4);
-    else if (k == 20) DMET_GML(5);
-    else if (k == 32) DMET_GML(8);
-    else {
-        DMET_REQUIRE(!sliced, "dmet_gather_max_lds_sliced_f32: k=%d (slice-major tables need k in {8,16,20,32})", k);
-        return dmet_gather_max_f32(P, Q, nbr, ptr, B, N, k, H, out, arg, stream);  // other widths: L2 form
-    }
-#undef DMET_GML
-#undef DMET_GML_LAUNCH
-    DMET_LAUNCH_CHECK("gather_max_lds_kernel");
-    return 0;
-}
-
-extern "C" int dmet_gather_max_lds_f32(const float *P, const float *Q, const int32_t *nbr, const int64_t *ptr, int B,
-                                       int64_t N, int k, int H, float *out, uint8_t *arg, dmet_stream_t stream)
-{
-    return gather_max_lds_impl(P, Q, nbr, nullptr, ptr, B, N, k, H, out, arg, false, stream);
-}
-
-extern "C" int dmet_gather_max_lds16_f32(const float *P, const float *Q, const int32_t *nbr, const uint16_t *nbr_local,
-                                         const int64_t *ptr, int B, int64_t N, int k, int H, float *out,
-                                         uint8_t *arg, dmet_stream_t stream)
-{
-    return gather_max_lds_impl(P, Q, nbr, nbr_local, ptr, B, N, k, H, out, arg, false, stream);
-}
-
-extern "C" int dmet_gather_max_mixed_f32(const float *P, const float *Q, const int32_t *nbr, const uint16_t *nbr_local,
-                                         const int64_t *ptr, int B, int64_t N, int k, int H, float *out,
-                                         uint8_t *arg, dmet_stream_t stream)
-{
-    // per-EVENT choice of the gather form on ragged batches: events whose Q slice fits the LDS image go through the
-    // LDS-resident kernel, the others through the L2-form kernel; both read the row-major tables, each skips the
-    // other's events
-    if (!(H == 32 && (k == 8 || k == 16 || k == 32)) || N == 0 || B == 0)
-        return dmet_gather_max_f32(P, Q, nbr, ptr, B, N, k, H, out, arg, stream);
-    const int rc = gather_max_lds_impl(P, Q, nbr, nbr_local, ptr, B, N, k, H, out, arg, false, stream, 1);
-    if (rc) return rc;
-    hipStream_t st = as_stream(stream);
-    const int64_t blocks = (N + 31) / 32;
-#define DMET_GMM_BIG(K4_)                                                                                            \
-    do {                                                                                                             \
-        if (arg)                                                                                                     \
-            hipLaunchKernelGGL((gather_max_mlp_kernel<32, true, K4_, true>), dim3((unsigned)blocks), dim3(256), 0,   \
-                               st, P, Q, nbr, N, out, arg, ptr, B, kLdsGatherRows);                                  \
-        else                                                                                                         \
-            hipLaunchKernelGGL((gather_max_mlp_kernel<32, false, K4_, true>), dim3((unsigned)blocks), dim3(256), 0,  \
-                               st, P, Q, nbr, N, out, arg, ptr, B, kLdsGatherRows);                                  \
-    } while (0)
-    if (k == 8) DMET_GMM_BIG(2);
-    else if (k == 16) DMET_GMM_BIG(4);
-    else DMET_GMM_BIG(8);
-#undef DMET_GMM_BIG
-    DMET_LAUNCH_CHECK("gather_max_mlp_kernel (large events)");
-    return 0;
-}
-
-extern "C" int dmet_gather_max_lds_sliced_f32(const float *P, const float *Q, const int32_t *nbr,
-                                              const uint16_t *nbr_local, const int64_t *ptr, int B, int64_t N, int k,
-                                              int H, float *out, uint8_t *arg, dmet_stream_t stream)
-{
-    return gather_max_lds_impl(P, Q, nbr, nbr_local, ptr, B, N, k, H, out, arg, true, stream);
-}
-
-extern "C" int dmet_gather_max_lds_sliced_cap_f32(const float *P, const float *Q, const int32_t *nbr,
-                                                  const uint16_t *nbr_local, const int64_t *ptr, int B, int64_t N, int k,
-                                                  int H, float *out, uint8_t *arg, int64_t max_nodes, dmet_stream_t stream)
-{
-    DMET_REQUIRE(max_nodes >= 0, "dmet_gather_max_lds_sliced_cap_f32: max_nodes=%lld", (long long)max_nodes);
-    return gather_max_lds_impl(P, Q, nbr, nbr_local, ptr, B, N, k, H, out, arg, true, stream, 0, max_nodes);
-}
-
-extern "C" int dmet_gather_max_counted_lds_f32(const float *P, const float *Q, const int32_t *nbr, const int32_t *cnt,
-                                               const int64_t *ptr, int B, int64_t N, int k, int H, int pq_sliced,
-                                               float *out, uint8_t *arg, dmet_stream_t stream)
-{
-    DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647, "dmet_gather_max_counted_lds_f32: N out of range");
-    DMET_REQUIRE(k >= 1 && k <= 255, "dmet_gather_max_counted_lds_f32: k=%d not in [1,255]", k);
-    DMET_REQUIRE(H >= kSliceC && H % kSliceC == 0 && H <= DMET_MAX_H,
-                 "dmet_gather_max_counted_lds_f32: H=%d must be a multiple of %d", H, kSliceC);
-    if (N == 0 || B == 0) return 0;
-    DMET_REQUIRE(P && Q && nbr && cnt && ptr && out, "dmet_gather_max_counted_lds_f32: null pointer");
-    DMET_REQUIRE(aligned16(P) && aligned16(Q) && aligned16(out), "dmet_gather_max_counted_lds_f32: pointers must be 16-B aligned");
-    const int nsl = H / kSliceC;
-    const int64_t groups = (B + kNumXcd - 1) / kNumXcd;
-    const int64_t blocks = groups * kNumXcd * nsl;
-    hipStream_t st = as_stream(stream);
-#define DMET_GCL(ARG_, SL_)                                                                                     \
-    hipLaunchKernelGGL((gather_max_lds_counted_kernel<ARG_, SL_>), dim3((unsigned)blocks), dim3(kLdsGatherThreads), 0, \
-                       st, P, Q, nbr, cnt, ptr, B, k, H, out, arg, N)
-    if (arg) { if (pq_sliced) DMET_GCL(true, true); else DMET_GCL(true, false); }
-    else { if (pq_sliced) DMET_GCL(false, true); else DMET_GCL(false, false); }
-#undef DMET_GCL
-    DMET_LAUNCH_CHECK("gather_max_lds_counted_kernel");
-    return 0;
-}
-
 extern "C" int dmet_table_order_by_count(const int32_t *cnt, const int64_t *ptr, int B, int64_t N, int32_t *order,
                                          dmet_stream_t stream)
 {
@@ -1567,78 +1598,6 @@ extern "C" int dmet_table_order_by_count(const int32_t *cnt, const int64_t *ptr,
     DMET_REQUIRE(cnt && ptr && order, "dmet_table_order_by_count: null pointer");
     hipLaunchKernelGGL(table_order_kernel, dim3((unsigned)B), dim3(1024), 0, as_stream(stream), cnt, ptr, B, order);
     DMET_LAUNCH_CHECK("table_order_kernel");
-    return 0;
-}
-
-extern "C" int dmet_gather_max_local_j16_f32(const float *P, const float *Q, const uint16_t *nbr16, int stride16,
-                                             const int32_t *cnt, const int32_t *order, const int64_t *ptr, int B,
-                                             int64_t N, int kmax, int H, int pq_sliced, float *out, uint16_t *argj,
-                                             dmet_stream_t stream)
-{
-    DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647, "dmet_gather_max_local_j16_f32: N out of range");
-    DMET_REQUIRE(kmax >= 1 && kmax <= 255 && stride16 >= kmax && stride16 % 8 == 0,
-                 "dmet_gather_max_local_j16_f32: kmax=%d stride16=%d", kmax, stride16);
-    DMET_REQUIRE(H >= kSliceC && H % kSliceC == 0 && H <= DMET_MAX_H,
-                 "dmet_gather_max_local_j16_f32: H=%d must be a multiple of %d", H, kSliceC);
-    if (N == 0 || B == 0) return 0;
-    DMET_REQUIRE(P && Q && nbr16 && cnt && ptr && out, "dmet_gather_max_local_j16_f32: null pointer");
-    DMET_REQUIRE(aligned16(P) && aligned16(Q) && aligned16(out) && aligned16(nbr16) &&
-                     (reinterpret_cast<uintptr_t>(argj) & 7u) == 0,
-                 "dmet_gather_max_local_j16_f32: pointers must be 16-B (argj: 8-B) aligned");
-    const int nsl = H / kSliceC;
-    const int64_t groups = (B + kNumXcd - 1) / kNumXcd;
-    const int64_t blocks = groups * kNumXcd * nsl;
-    hipStream_t st = as_stream(stream);
-    uint8_t *a8 = reinterpret_cast<uint8_t *>(argj);
-    if (!argj) {      // inference: the maximum alone
-        if (pq_sliced)
-            hipLaunchKernelGGL((gather_max_lds_counted_kernel<false, true, true, true>), dim3((unsigned)blocks),
-                               dim3(kLdsGatherThreads), 0, st, P, Q, nullptr, cnt, ptr, B, kmax, H, out, a8, N, order, nbr16,
-                               stride16);
-        else
-            hipLaunchKernelGGL((gather_max_lds_counted_kernel<false, false, true, true>), dim3((unsigned)blocks),
-                               dim3(kLdsGatherThreads), 0, st, P, Q, nullptr, cnt, ptr, B, kmax, H, out, a8, N, order, nbr16,
-                               stride16);
-        DMET_LAUNCH_CHECK("gather_max_lds_counted_kernel (uint16 rows, no winners)");
-        return 0;
-    }
-    if (pq_sliced)
-        hipLaunchKernelGGL((gather_max_lds_counted_kernel<true, true, true, true>), dim3((unsigned)blocks),
-                           dim3(kLdsGatherThreads), 0, st, P, Q, nullptr, cnt, ptr, B, kmax, H, out, a8, N, order, nbr16,
-                           stride16);
-    else
-        hipLaunchKernelGGL((gather_max_lds_counted_kernel<true, false, true, true>), dim3((unsigned)blocks),
-                           dim3(kLdsGatherThreads), 0, st, P, Q, nullptr, cnt, ptr, B, kmax, H, out, a8, N, order, nbr16,
-                           stride16);
-    DMET_LAUNCH_CHECK("gather_max_lds_counted_kernel (uint16 rows)");
-    return 0;
-}
-
-extern "C" int dmet_gather_max_counted_lds_j16_f32(const float *P, const float *Q, const int32_t *nbr, const int32_t *cnt,
-                                                   const int32_t *order, const int64_t *ptr, int B, int64_t N, int k,
-                                                   int H, int pq_sliced, float *out, uint16_t *argj,
-                                                   dmet_stream_t stream)
-{
-    DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647, "dmet_gather_max_counted_lds_j16_f32: N out of range");
-    DMET_REQUIRE(k >= 1 && k <= 255, "dmet_gather_max_counted_lds_j16_f32: k=%d not in [1,255]", k);
-    DMET_REQUIRE(H >= kSliceC && H % kSliceC == 0 && H <= DMET_MAX_H,
-                 "dmet_gather_max_counted_lds_j16_f32: H=%d must be a multiple of %d", H, kSliceC);
-    if (N == 0 || B == 0) return 0;
-    DMET_REQUIRE(P && Q && nbr && cnt && ptr && out && argj, "dmet_gather_max_counted_lds_j16_f32: null pointer");
-    DMET_REQUIRE(aligned16(P) && aligned16(Q) && aligned16(out) && (reinterpret_cast<uintptr_t>(argj) & 7u) == 0,
-                 "dmet_gather_max_counted_lds_j16_f32: pointers must be 16-B (argj: 8-B) aligned");
-    const int nsl = H / kSliceC;
-    const int64_t groups = (B + kNumXcd - 1) / kNumXcd;
-    const int64_t blocks = groups * kNumXcd * nsl;
-    hipStream_t st = as_stream(stream);
-    uint8_t *a8 = reinterpret_cast<uint8_t *>(argj);
-    if (pq_sliced)
-        hipLaunchKernelGGL((gather_max_lds_counted_kernel<true, true, true>), dim3((unsigned)blocks), dim3(kLdsGatherThreads),
-                           0, st, P, Q, nbr, cnt, ptr, B, k, H, out, a8, N, order);
-    else
-        hipLaunchKernelGGL((gather_max_lds_counted_kernel<true, false, true>), dim3((unsigned)blocks),
-                           dim3(kLdsGatherThreads), 0, st, P, Q, nbr, cnt, ptr, B, k, H, out, a8, N, order);
-    DMET_LAUNCH_CHECK("gather_max_lds_counted_kernel (winner ids)");
     return 0;
 }
 

@@ -590,31 +590,97 @@ int bwd_scatter_launch(const float *g_out, const uint8_t *arg, const int32_t *nb
     return bwd_scatter_launch_as<J16, kBwdThreads, kBwdCells>(g_out, arg, nbr, nbr16, ptr, B, k, gQ, st, gq_sliced_n);
 }
 
-// gQ slice-major, [8][N][4] floats (see the kernel): for the pair scatter -> dmet_edgeconv_linear_bwd_sliced_f32
+// Every LDS-scatter entry fills one request; gather_max_bwd_launch holds the one copy of the checks.
+struct GatherMaxBwd {
+    const char *entry;              // the exported function the caller called: every message names it
+    const float *g_out;
+    const void *arg;                // the forward's winners: uint8 slots into nbr / nbr16, or (arg16) uint16 event-local ids
+    const int64_t *ptr;
+    int B;
+    int64_t N;
+    int H;
+    float *gQ;
+    dmet_stream_t stream;
+    bool arg16 = false;
+    const int32_t *nbr = nullptr;   // [N, k] table that the slots index (winner ids need none)
+    const uint16_t *nbr16 = nullptr;// optional event-local copy of it
+    int k = 1;
+    bool gq_sliced = false;         // gQ slice-major, [8][N][4] floats (see the kernel): for dmet_edgeconv_linear_bwd_sliced_f32
+    int64_t max_nodes = 0;          // hint: the batch's largest event (0 = unknown)
+};
+
+static int gather_max_bwd_launch(const GatherMaxBwd &r)
+{
+    DMET_REQUIRE(r.H == kH, "%s: H=%d (only 32 is built)", r.entry, r.H);
+    DMET_REQUIRE(r.N >= 0 && r.B >= 0 && r.k >= 1 && r.k <= 255 && r.max_nodes >= 0, "%s: bad sizes", r.entry);
+    if (r.N == 0 || r.B == 0) return 0;
+    DMET_REQUIRE(r.g_out && r.arg && (r.arg16 || r.nbr) && r.ptr && r.gQ, "%s: null pointer", r.entry);
+    DMET_REQUIRE(aligned16(r.g_out) && aligned16(r.gQ) && (reinterpret_cast<uintptr_t>(r.arg) & (r.arg16 ? 7u : 3u)) == 0,
+                 "%s: rows must be 16-byte (winner ids: 8-byte, slots: 4-byte) aligned", r.entry);
+    const uint8_t *arg = static_cast<const uint8_t *>(r.arg);
+    const int64_t gq_sliced_n = r.gq_sliced ? r.N : 0;
+    const auto launch = r.arg16 ? bwd_scatter_launch<true> : bwd_scatter_launch<false>;
+    return launch(r.g_out, arg, r.nbr, r.nbr16, r.ptr, r.B, r.k, r.gQ, r.max_nodes, as_stream(r.stream), gq_sliced_n);
+}
+
+extern "C" int dmet_gather_max_bwd_lds_f32(const float *g_out, const uint8_t *arg, const int32_t *nbr,
+                                           const int64_t *ptr, int B, int64_t N, int k, int H, float *gQ,
+                                           dmet_stream_t stream)
+{
+    GatherMaxBwd r{"dmet_gather_max_bwd_lds_f32", g_out, arg, ptr, B, N, H, gQ, stream};
+    r.nbr = nbr; r.k = k;
+    return gather_max_bwd_launch(r);
+}
+
+extern "C" int dmet_gather_max_bwd_lds16_f32(const float *g_out, const uint8_t *arg, const int32_t *nbr,
+                                             const uint16_t *nbr_local, const int64_t *ptr, int B, int64_t N, int k,
+                                             int H, float *gQ, dmet_stream_t stream)
+{
+    GatherMaxBwd r{"dmet_gather_max_bwd_lds16_f32", g_out, arg, ptr, B, N, H, gQ, stream};
+    r.nbr = nbr; r.nbr16 = nbr_local; r.k = k;
+    return gather_max_bwd_launch(r);
+}
+
+extern "C" int dmet_gather_max_bwd_lds16_cap_f32(const float *g_out, const uint8_t *arg, const int32_t *nbr,
+                                                 const uint16_t *nbr_local, const int64_t *ptr, int B, int64_t N, int k,
+                                                 int H, float *gQ, int64_t max_nodes, dmet_stream_t stream)
+{
+    GatherMaxBwd r{"dmet_gather_max_bwd_lds16_cap_f32", g_out, arg, ptr, B, N, H, gQ, stream};
+    r.nbr = nbr; r.nbr16 = nbr_local; r.k = k; r.max_nodes = max_nodes;
+    return gather_max_bwd_launch(r);
+}
+
 extern "C" int dmet_gather_max_bwd_sliced_f32(const float *g_out, const uint8_t *arg, const int32_t *nbr,
                                               const uint16_t *nbr_local, const int64_t *ptr, int B, int64_t N, int k, int H,
                                               float *gQs, int64_t max_nodes, dmet_stream_t stream)
 {
-    DMET_REQUIRE(H == kH, "dmet_gather_max_bwd_sliced_f32: H=%d (only 32 is built)", H);
-    DMET_REQUIRE(N >= 0 && B >= 0 && k >= 1 && k <= 255 && max_nodes >= 0, "dmet_gather_max_bwd_sliced_f32: bad sizes");
-    if (N == 0 || B == 0) return 0;
-    DMET_REQUIRE(g_out && arg && nbr && ptr && gQs, "dmet_gather_max_bwd_sliced_f32: null pointer");
-    DMET_REQUIRE(aligned16(g_out) && aligned16(gQs) && (reinterpret_cast<uintptr_t>(arg) & 3u) == 0,
-                 "dmet_gather_max_bwd_sliced_f32: rows must be 16-byte aligned");
-    return bwd_scatter_launch<false>(g_out, arg, nbr, nbr_local, ptr, B, k, gQs, max_nodes, as_stream(stream), N);
+    GatherMaxBwd r{"dmet_gather_max_bwd_sliced_f32", g_out, arg, ptr, B, N, H, gQs, stream};
+    r.nbr = nbr; r.nbr16 = nbr_local; r.k = k; r.gq_sliced = true; r.max_nodes = max_nodes;
+    return gather_max_bwd_launch(r);
+}
+
+extern "C" int dmet_gather_max_bwd_j16_f32(const float *g_out, const uint16_t *argj, const int64_t *ptr, int B, int64_t N,
+                                           int H, float *gQ, dmet_stream_t stream)
+{
+    GatherMaxBwd r{"dmet_gather_max_bwd_j16_f32", g_out, argj, ptr, B, N, H, gQ, stream};
+    r.arg16 = true;
+    return gather_max_bwd_launch(r);
+}
+
+extern "C" int dmet_gather_max_bwd_j16_cap_f32(const float *g_out, const uint16_t *argj, const int64_t *ptr, int B,
+                                               int64_t N, int H, float *gQ, int64_t max_nodes, dmet_stream_t stream)
+{
+    GatherMaxBwd r{"dmet_gather_max_bwd_j16_cap_f32", g_out, argj, ptr, B, N, H, gQ, stream};
+    r.arg16 = true; r.max_nodes = max_nodes;
+    return gather_max_bwd_launch(r);
 }
 
 extern "C" int dmet_gather_max_bwd_j16_sliced_f32(const float *g_out, const uint16_t *argj, const int64_t *ptr, int B,
                                                   int64_t N, int H, float *gQs, int64_t max_nodes, dmet_stream_t stream)
 {
-    DMET_REQUIRE(H == kH, "dmet_gather_max_bwd_j16_sliced_f32: H=%d (only 32 is built)", H);
-    DMET_REQUIRE(N >= 0 && B >= 0 && max_nodes >= 0, "dmet_gather_max_bwd_j16_sliced_f32: bad sizes");
-    if (N == 0 || B == 0) return 0;
-    DMET_REQUIRE(g_out && argj && ptr && gQs, "dmet_gather_max_bwd_j16_sliced_f32: null pointer");
-    DMET_REQUIRE(aligned16(g_out) && aligned16(gQs) && (reinterpret_cast<uintptr_t>(argj) & 7u) == 0,
-                 "dmet_gather_max_bwd_j16_sliced_f32: rows must be 16-byte (argj: 8-byte) aligned");
-    return bwd_scatter_launch<true>(g_out, reinterpret_cast<const uint8_t *>(argj), nullptr, nullptr, ptr, B, 1, gQs, max_nodes,
-                                    as_stream(stream), N);
+    GatherMaxBwd r{"dmet_gather_max_bwd_j16_sliced_f32", g_out, argj, ptr, B, N, H, gQs, stream};
+    r.arg16 = true; r.gq_sliced = true; r.max_nodes = max_nodes;
+    return gather_max_bwd_launch(r);
 }
 
 // dmet_edgeconv_linear_bwd_add_f32 / _add_j16_f32 (arg_is_j16) reading gQ in the slice-major layout those two write
@@ -625,50 +691,4 @@ extern "C" int dmet_edgeconv_linear_bwd_sliced_f32(const float *x, const float *
 {
     return ecb_launch(x, W, g_out, reinterpret_cast<const uint8_t *>(arg), arg_is_j16 != 0, gQs, g_add, N, H, gx, gW, gb, ws,
                       ws_bytes, stream, 1);
-}
-
-extern "C" int dmet_gather_max_bwd_lds16_cap_f32(const float *g_out, const uint8_t *arg, const int32_t *nbr,
-                                                 const uint16_t *nbr_local, const int64_t *ptr, int B, int64_t N, int k,
-                                                 int H, float *gQ, int64_t max_nodes, dmet_stream_t stream)
-{
-    DMET_REQUIRE(H == kH, "dmet_gather_max_bwd_lds_f32: H=%d (only 32 is built)", H);
-    DMET_REQUIRE(N >= 0 && B >= 0 && k >= 1 && k <= 255 && max_nodes >= 0, "dmet_gather_max_bwd_lds_f32: bad sizes");
-    if (N == 0 || B == 0) return 0;
-    DMET_REQUIRE(g_out && arg && nbr && ptr && gQ, "dmet_gather_max_bwd_lds_f32: null pointer");
-    DMET_REQUIRE(aligned16(g_out) && aligned16(gQ) && (reinterpret_cast<uintptr_t>(arg) & 3u) == 0,
-                 "dmet_gather_max_bwd_lds_f32: rows must be 16-byte aligned");
-    return bwd_scatter_launch<false>(g_out, arg, nbr, nbr_local, ptr, B, k, gQ, max_nodes, as_stream(stream));
-}
-
-extern "C" int dmet_gather_max_bwd_lds16_f32(const float *g_out, const uint8_t *arg, const int32_t *nbr,
-                                             const uint16_t *nbr_local, const int64_t *ptr, int B, int64_t N, int k,
-                                             int H, float *gQ, dmet_stream_t stream)
-{
-    return dmet_gather_max_bwd_lds16_cap_f32(g_out, arg, nbr, nbr_local, ptr, B, N, k, H, gQ, 0, stream);
-}
-
-extern "C" int dmet_gather_max_bwd_lds_f32(const float *g_out, const uint8_t *arg, const int32_t *nbr,
-                                           const int64_t *ptr, int B, int64_t N, int k, int H, float *gQ,
-                                           dmet_stream_t stream)
-{
-    return dmet_gather_max_bwd_lds16_f32(g_out, arg, nbr, nullptr, ptr, B, N, k, H, gQ, stream);
-}
-
-extern "C" int dmet_gather_max_bwd_j16_cap_f32(const float *g_out, const uint16_t *argj, const int64_t *ptr, int B,
-                                               int64_t N, int H, float *gQ, int64_t max_nodes, dmet_stream_t stream)
-{
-    DMET_REQUIRE(H == kH, "dmet_gather_max_bwd_j16_f32: H=%d (only 32 is built)", H);
-    DMET_REQUIRE(N >= 0 && B >= 0 && max_nodes >= 0, "dmet_gather_max_bwd_j16_f32: bad sizes");
-    if (N == 0 || B == 0) return 0;
-    DMET_REQUIRE(g_out && argj && ptr && gQ, "dmet_gather_max_bwd_j16_f32: null pointer");
-    DMET_REQUIRE(aligned16(g_out) && aligned16(gQ) && (reinterpret_cast<uintptr_t>(argj) & 7u) == 0,
-                 "dmet_gather_max_bwd_j16_f32: rows must be 16-byte (argj: 8-byte) aligned");
-    return bwd_scatter_launch<true>(g_out, reinterpret_cast<const uint8_t *>(argj), nullptr, nullptr, ptr, B, 1, gQ, max_nodes,
-                                    as_stream(stream));
-}
-
-extern "C" int dmet_gather_max_bwd_j16_f32(const float *g_out, const uint16_t *argj, const int64_t *ptr, int B, int64_t N,
-                                           int H, float *gQ, dmet_stream_t stream)
-{
-    return dmet_gather_max_bwd_j16_cap_f32(g_out, argj, ptr, B, N, H, gQ, 0, stream);
 }
