@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import inspect
 import os
 from typing import Optional, Tuple
 
@@ -718,70 +719,36 @@ def edge_mlp2_bn_bf16(x: torch.Tensor, nbr: torch.Tensor, W1: torch.Tensor, b1: 
     return out
 
 
-def edge_mlp_f32_supported(Hin: int, H1: int, H2: int) -> bool:
-    return bool(_lib.load().dmet_edge_mlp_f32_supported(int(Hin), int(H1), int(H2)))
-
-
 _EMLP_AGGR = {"max": 0, "add": 1, "sum": 1, "mean": 2}
+# per-edge operand type of the three fused edge-MLP routes over a grouped edge list, for the docstrings
+_EMLP_OPERANDS = {"f32": "fp32", "bf16": "bf16 matrix cores", "f16": "fp16 matrix cores (RNE, overflow to inf)"}
 
 
-def _edge_arrays(rowptr, src, tgt, N):
+def _edge_arrays(rowptr, src, tgt, N, route="f32"):
     for name, t in (("rowptr", rowptr), ("src", src), ("tgt", tgt)):
         if t.dtype != torch.int32 or not t.is_contiguous():
-            raise TypeError(f"edge_mlp_f32: {name} must be a contiguous int32 tensor")
+            raise TypeError(f"edge_mlp_{route}: {name} must be a contiguous int32 tensor")
     if rowptr.numel() != N + 1:
-        raise ValueError(f"edge_mlp_f32: rowptr must hold N + 1 = {N + 1} entries, got {rowptr.numel()}")
+        raise ValueError(f"edge_mlp_{route}: rowptr must hold N + 1 = {N + 1} entries, got {rowptr.numel()}")
     if src.numel() != tgt.numel():
-        raise ValueError("edge_mlp_f32: src and tgt differ in length")
+        raise ValueError(f"edge_mlp_{route}: src and tgt differ in length")
     return src.numel()
 
 
-def edge_mlp_fwd_f32(x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, W1: torch.Tensor,
-                     b1: Optional[torch.Tensor], W2: torch.Tensor, b2: Optional[torch.Tensor], act2: bool, aggr: str,
-                     bn: int = 0, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
-                     eps: float = 1e-5, momentum: float = 0.1, running_mean: Optional[torch.Tensor] = None,
-                     running_var: Optional[torch.Tensor] = None, num_batches_tracked: Optional[torch.Tensor] = None):
+def _edge_mlp_supported(route, Hin: int, H1: int, H2: int) -> bool:
+    """The widths dmet_edge_mlp_{route}_supported takes (include/dmet.h)."""
+    return bool(getattr(_lib.load(), f"dmet_edge_mlp_{route}_supported")(int(Hin), int(H1), int(H2)))
+
+
+def _edge_mlp_fwd(route, x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, W1: torch.Tensor,
+                  b1: Optional[torch.Tensor], W2: torch.Tensor, b2: Optional[torch.Tensor], act2: bool, aggr: str,
+                  bn: int = 0, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+                  eps: float = 1e-5, momentum: float = 0.1, running_mean: Optional[torch.Tensor] = None,
+                  running_var: Optional[torch.Tensor] = None, num_batches_tracked: Optional[torch.Tensor] = None):
     """out[N, H2] = aggr_e nn([x_tgt || x_src - x_tgt]) over a grouped edge list, nn = Linear - ELU - Linear [- ELU]
-    [- BatchNorm1d] in fp32 (include/dmet.h: dmet_edge_mlp_fwd_f32).  Returns (out, state); `state` is what
-    edge_mlp_bwd_f32 needs (pq, agg, win, bnstat).  bn: 0 none, 1 training (statistics moved in place), 2 eval."""
-    return _edge_mlp_fwd("f32", x, rowptr, src, tgt, W1, b1, W2, b2, act2, aggr, bn, gamma, beta, eps, momentum,
-                         running_mean, running_var, num_batches_tracked)
-
-
-def edge_mlp_bf16_supported(Hin: int, H1: int, H2: int) -> bool:
-    return bool(_lib.load().dmet_edge_mlp_bf16_supported(int(Hin), int(H1), int(H2)))
-
-
-def edge_mlp_fwd_bf16(x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, W1: torch.Tensor,
-                      b1: Optional[torch.Tensor], W2: torch.Tensor, b2: Optional[torch.Tensor], act2: bool, aggr: str,
-                      bn: int = 0, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
-                      eps: float = 1e-5, momentum: float = 0.1, running_mean: Optional[torch.Tensor] = None,
-                      running_var: Optional[torch.Tensor] = None, num_batches_tracked: Optional[torch.Tensor] = None):
-    """edge_mlp_fwd_f32 with the per-edge product on the bf16 matrix cores (include/dmet.h: dmet_edge_mlp_fwd_bf16):
-    fp32 inputs, parameters and output; h1 and W2 rounded to bf16 inside the kernel.  Returns (out, state) for
-    edge_mlp_bwd_bf16."""
-    return _edge_mlp_fwd("bf16", x, rowptr, src, tgt, W1, b1, W2, b2, act2, aggr, bn, gamma, beta, eps, momentum,
-                         running_mean, running_var, num_batches_tracked)
-
-
-def edge_mlp_f16_supported(Hin: int, H1: int, H2: int) -> bool:
-    return bool(_lib.load().dmet_edge_mlp_f16_supported(int(Hin), int(H1), int(H2)))
-
-
-def edge_mlp_fwd_f16(x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, W1: torch.Tensor,
-                     b1: Optional[torch.Tensor], W2: torch.Tensor, b2: Optional[torch.Tensor], act2: bool, aggr: str,
-                     bn: int = 0, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
-                     eps: float = 1e-5, momentum: float = 0.1, running_mean: Optional[torch.Tensor] = None,
-                     running_var: Optional[torch.Tensor] = None, num_batches_tracked: Optional[torch.Tensor] = None):
-    """edge_mlp_fwd_bf16 with fp16 operands on the fp16 matrix cores (include/dmet.h: dmet_edge_mlp_fwd_f16): fp32
-    inputs, parameters and output; h1 and W2 rounded to fp16 (RNE, overflow to inf) inside the kernel.  Returns (out,
-    state) for edge_mlp_bwd_f16."""
-    return _edge_mlp_fwd("f16", x, rowptr, src, tgt, W1, b1, W2, b2, act2, aggr, bn, gamma, beta, eps, momentum,
-                         running_mean, running_var, num_batches_tracked)
-
-
-def _edge_mlp_fwd(route, x, rowptr, src, tgt, W1, b1, W2, b2, act2, aggr, bn, gamma, beta, eps, momentum, running_mean,
-                  running_var, num_batches_tracked):
+    [- BatchNorm1d] (include/dmet.h: dmet_edge_mlp_fwd_{route}; per-edge products: {operands}).  fp32 inputs, parameters
+    and output; a 16-bit route rounds h1 and W2 inside the kernel only.  Returns (out, state); `state` is what
+    edge_mlp_bwd_{route} needs (pq, agg, win, bnstat).  bn: 0 none, 1 training (statistics moved in place), 2 eval."""
     dev = _require_device(x, rowptr, src, tgt, W1, W2, b1, b2, gamma, beta)
     L = _lib.load()
     x = _f32c(x, "x"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2")
@@ -791,7 +758,7 @@ def _edge_mlp_fwd(route, x, rowptr, src, tgt, W1, b1, W2, b2, act2, aggr, bn, ga
         raise ValueError(f"edge_mlp_{route}: W1 must be [H1, {2 * Hin}] and W2 [H2, H1], got {tuple(W1.shape)}, {tuple(W2.shape)}")
     if aggr not in _EMLP_AGGR:
         raise ValueError(f"edge_mlp_{route}: unsupported aggr {aggr!r}")
-    E = _edge_arrays(rowptr, src, tgt, N)
+    E = _edge_arrays(rowptr, src, tgt, N, route)
     out = torch.empty((N, H2), dtype=torch.float32, device=dev)
     pq = torch.empty((N, 2 * H1), dtype=torch.float32, device=dev)
     agg = torch.empty((2 if aggr == "max" and bn else 1, N, H2), dtype=torch.float32, device=dev)
@@ -827,44 +794,19 @@ def _xty_wide(A: torch.Tensor, Bm: torch.Tensor) -> torch.Tensor:
     return torch.cat(rows, dim=0)
 
 
-def edge_mlp_bwd_f32(g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor,
-                     srcptr: torch.Tensor, srcperm: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
-                     b2: Optional[torch.Tensor], act2: bool, aggr: str, bn: int, state, want_x: bool = True,
-                     want_w1: bool = True, want_b1: bool = True):
-    """Gradients of edge_mlp_fwd_f32 (include/dmet.h: dmet_edge_mlp_bwd_f32): (gx, gW1, gb1, gW2, gb2, ggamma, gbeta);
-    gx / gW1 / gb1 are None when not wanted, ggamma / gbeta when bn == 0."""
-    return _edge_mlp_bwd("f32", g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2, act2, aggr, bn, state, want_x,
-                         want_w1, want_b1)
-
-
-def edge_mlp_bwd_bf16(g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor,
-                      srcptr: torch.Tensor, srcperm: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
-                      b2: Optional[torch.Tensor], act2: bool, aggr: str, bn: int, state, want_x: bool = True,
-                      want_w1: bool = True, want_b1: bool = True):
-    """Gradients of edge_mlp_fwd_bf16 (include/dmet.h: dmet_edge_mlp_bwd_bf16), as edge_mlp_bwd_f32 returns them: the
-    per-edge products g_h1 and gW2 on the bf16 matrix cores, everything else fp32."""
-    return _edge_mlp_bwd("bf16", g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2, act2, aggr, bn, state, want_x,
-                         want_w1, want_b1)
-
-
-def edge_mlp_bwd_f16(g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor,
-                     srcptr: torch.Tensor, srcperm: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
-                     b2: Optional[torch.Tensor], act2: bool, aggr: str, bn: int, state, want_x: bool = True,
-                     want_w1: bool = True, want_b1: bool = True):
-    """Gradients of edge_mlp_fwd_f16 (include/dmet.h: dmet_edge_mlp_bwd_f16), as edge_mlp_bwd_f32 returns them: the
-    per-edge products g_h1 and gW2 on the fp16 matrix cores, everything else fp32."""
-    return _edge_mlp_bwd("f16", g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2, act2, aggr, bn, state, want_x,
-                         want_w1, want_b1)
-
-
-def _edge_mlp_bwd(route, g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2, act2, aggr, bn, state, want_x, want_w1,
-                  want_b1):
+def _edge_mlp_bwd(route, g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor,
+                  srcptr: torch.Tensor, srcperm: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor,
+                  b2: Optional[torch.Tensor], act2: bool, aggr: str, bn: int, state, want_x: bool = True,
+                  want_w1: bool = True, want_b1: bool = True):
+    """Gradients of edge_mlp_fwd_{route} (include/dmet.h: dmet_edge_mlp_bwd_{route}; per-edge products g_h1 and gW2:
+    {operands}, everything else fp32): (gx, gW1, gb1, gW2, gb2, ggamma, gbeta); gx / gW1 / gb1 are None when not wanted,
+    ggamma / gbeta when bn == 0."""
     dev = _require_device(g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2)
     L = _lib.load()
     x = _f32c(x, "x"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2"); g_out = _f32c(g_out, "g_out")
     N, Hin = x.shape
     H1, H2 = W1.shape[0], W2.shape[0]
-    E = _edge_arrays(rowptr, src, tgt, N)
+    E = _edge_arrays(rowptr, src, tgt, N, route)
     if srcptr.dtype != torch.int32 or srcperm.dtype != torch.int32 or srcptr.numel() != N + 1:
         raise TypeError(f"edge_mlp_{route}: srcptr [N + 1] and srcperm must be int32 (EdgeList.by_source())")
     if tuple(g_out.shape) != (N, H2):
@@ -904,6 +846,28 @@ def _edge_mlp_bwd(route, g_out, x, rowptr, src, tgt, srcptr, srcperm, W1, W2, b2
     if want_b1:
         gb1 = xty_wide_ones(gP) if N else torch.zeros((H1,), dtype=torch.float32, device=dev)
     return gx, gW1, gb1, gW2, gb2, ggamma, gbeta
+
+
+def _bind_route(impl, name: str, route: str):
+    """`impl` with its route fixed, under the public name: a module attribute of its own, so that a test can patch it."""
+    def bound(*args, **kwargs):
+        return impl(route, *args, **kwargs)
+    bound.__name__ = bound.__qualname__ = name
+    sig = inspect.signature(impl)
+    bound.__signature__ = sig.replace(parameters=list(sig.parameters.values())[1:])     # impl's, without `route`
+    bound.__doc__ = impl.__doc__.replace("{route}", route).replace("{operands}", _EMLP_OPERANDS[route])
+    return bound
+
+
+edge_mlp_f32_supported = _bind_route(_edge_mlp_supported, "edge_mlp_f32_supported", "f32")
+edge_mlp_bf16_supported = _bind_route(_edge_mlp_supported, "edge_mlp_bf16_supported", "bf16")
+edge_mlp_f16_supported = _bind_route(_edge_mlp_supported, "edge_mlp_f16_supported", "f16")
+edge_mlp_fwd_f32 = _bind_route(_edge_mlp_fwd, "edge_mlp_fwd_f32", "f32")
+edge_mlp_fwd_bf16 = _bind_route(_edge_mlp_fwd, "edge_mlp_fwd_bf16", "bf16")
+edge_mlp_fwd_f16 = _bind_route(_edge_mlp_fwd, "edge_mlp_fwd_f16", "f16")
+edge_mlp_bwd_f32 = _bind_route(_edge_mlp_bwd, "edge_mlp_bwd_f32", "f32")
+edge_mlp_bwd_bf16 = _bind_route(_edge_mlp_bwd, "edge_mlp_bwd_bf16", "bf16")
+edge_mlp_bwd_f16 = _bind_route(_edge_mlp_bwd, "edge_mlp_bwd_f16", "f16")
 
 
 def xty_wide_ones(A: torch.Tensor) -> torch.Tensor:

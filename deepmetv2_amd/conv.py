@@ -189,24 +189,8 @@ class _EdgeConvLinearMax(torch.autograd.Function):
                     gb if (ctx.has_bias and ctx.needs_input_grad[2]) else None, None, None, None)
         # nodes without any neighbour produced 0 (R3): no gradient reaches P there
         none = 0xFFFF if ctx.j16 else 255
-        gP = g_out if table.dense else g_out * ((arg.long() & 0xFFFF) != none).to(g_out.dtype)
-        Wd = weight[:, :H] - weight[:, H:]
-        W2 = weight[:, H:]
-        gx = gW = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.addmm(gP @ Wd, gQ, W2)
-            if g_pass is not None:
-                gx = gx + g_pass
-        if ctx.needs_input_grad[1]:
-            # as the fused kernel: a node whose gP and gQ rows are zero (no edge reads it) adds nothing, not 0 * NaN
-            idle = ((gP != 0).any(1) | (gQ != 0).any(1)).logical_not()
-            xw = x.masked_fill(idle.view(-1, 1), 0.0)
-            gWd = _native.xty(gP.contiguous(), xw)
-            gW2 = _native.xty(gQ, xw)
-            gW = torch.cat([gWd, gW2 - gWd], dim=1)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            gb = gP.sum(0)
-        return gx, gW, gb, None, None, None
+        gP = g_out if table.dense else (g_out * ((arg.long() & 0xFFFF) != none).to(g_out.dtype)).contiguous()
+        return _linear_node_backward(ctx, x, weight, gP, gQ, g_pass) + (None, None, None)
 
 
 def _linear_node_backward(ctx, x, weight, gP, gQ, g_pass):
@@ -350,83 +334,67 @@ class _EdgeMLP2Bf16(torch.autograd.Function):
         return tuple(res)
 
 
-def _edge_mlp2_forward(route, ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
-    """Forward of the fused edge-list routes (route "f32", "bf16" or "f16": _native.edge_mlp_fwd_<route>)."""
-    mode, track = 0, False
-    if bn is not None:
-        track = bn.track_running_stats and bn.running_mean is not None
-        mode = 1 if (bn.training or not track) else 2
-    update = mode == 1 and track
-    out, state = getattr(_native, f"edge_mlp_fwd_{route}")(
-        x, edges.rowptr, edges.src, edges.tgt, W1, b1, W2, b2, act2, aggr, mode, gamma, beta,
-        bn.eps if bn is not None else 1e-5, bn.momentum if bn is not None else 0.1,
-        bn.running_mean if track else None, bn.running_var if track else None,
-        bn.num_batches_tracked if update else None)
-    ctx.save_for_backward(x, W1, W2, b2, *state[:2], state[2], state[3])
-    ctx.edges, ctx.act2, ctx.aggr, ctx.mode = edges, act2, aggr, mode
-    ctx.has_b1, ctx.has_b2 = b1 is not None, b2 is not None
-    return out
+def _edge_mlp2_function(route: str, name: str, doc: str):
+    """The autograd Function `name` of one fused edge-list route ("f32", "bf16" or "f16": _native.edge_mlp_fwd_<route> and
+    _native.edge_mlp_bwd_<route>, looked up at call time)."""
+
+    def forward(ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
+        mode, track = 0, False
+        if bn is not None:
+            track = bn.track_running_stats and bn.running_mean is not None
+            mode = 1 if (bn.training or not track) else 2
+        update = mode == 1 and track
+        out, state = getattr(_native, f"edge_mlp_fwd_{route}")(
+            x, edges.rowptr, edges.src, edges.tgt, W1, b1, W2, b2, act2, aggr, mode, gamma, beta,
+            bn.eps if bn is not None else 1e-5, bn.momentum if bn is not None else 0.1,
+            bn.running_mean if track else None, bn.running_var if track else None,
+            bn.num_batches_tracked if update else None)
+        ctx.save_for_backward(x, W1, W2, b2, *state[:2], state[2], state[3])
+        ctx.edges, ctx.act2, ctx.aggr, ctx.mode = edges, act2, aggr, mode
+        ctx.has_b1, ctx.has_b2 = b1 is not None, b2 is not None
+        return out
+
+    def backward(ctx, g_out):
+        x, W1, W2, b2, pq, agg, win, bnstat = ctx.saved_tensors
+        edges: EdgeList = ctx.edges
+        srcptr, srcperm = edges.by_source()
+        need = ctx.needs_input_grad
+        gx, gW1, gb1, gW2, gb2, gg, gbeta = getattr(_native, f"edge_mlp_bwd_{route}")(
+            g_out, x, edges.rowptr, edges.src, edges.tgt, srcptr, srcperm, W1, W2, b2, ctx.act2, ctx.aggr, ctx.mode,
+            (pq, agg, win, bnstat), want_x=need[0], want_w1=need[1], want_b1=ctx.has_b1 and need[2])
+        return (gx, gW1 if need[1] else None, gb1, gW2 if need[3] else None, gb2 if (ctx.has_b2 and need[4]) else None,
+                gg if need[5] else None, gbeta if need[6] else None, None, None, None, None)
+
+    return type(name, (torch.autograd.Function,), {
+        "__doc__": doc, "__module__": __name__, "__qualname__": name,
+        "forward": staticmethod(forward), "backward": staticmethod(once_differentiable(backward))})
 
 
-def _edge_mlp2_backward(route, ctx, g_out):
-    x, W1, W2, b2, pq, agg, win, bnstat = ctx.saved_tensors
-    edges: EdgeList = ctx.edges
-    srcptr, srcperm = edges.by_source()
-    need = ctx.needs_input_grad
-    gx, gW1, gb1, gW2, gb2, gg, gbeta = getattr(_native, f"edge_mlp_bwd_{route}")(
-        g_out, x, edges.rowptr, edges.src, edges.tgt, srcptr, srcperm, W1, W2, b2, ctx.act2, ctx.aggr, ctx.mode,
-        (pq, agg, win, bnstat), want_x=need[0], want_w1=need[1], want_b1=ctx.has_b1 and need[2])
-    return (gx, gW1 if need[1] else None, gb1, gW2 if need[3] else None, gb2 if (ctx.has_b2 and need[4]) else None,
-            gg if need[5] else None, gbeta if need[6] else None, None, None, None, None)
-
-
-class _EdgeMLP2F32(torch.autograd.Function):
-    """aggr_e nn([x_tgt || x_src - x_tgt]) for nn = Linear - ELU - Linear [- ELU] [- BatchNorm1d] in fp32 over a grouped
+_EDGE_MLP2_DOCS = {
+    "f32": """\
+aggr_e nn([x_tgt || x_src - x_tgt]) for nn = Linear - ELU - Linear [- ELU] [- BatchNorm1d] in fp32 over a grouped
     edge list (csrc/edgemlp_f32.hip): the first Linear split per node, the second one per edge, fused with the
     aggregation and the BatchNorm.  Nothing per edge is kept between the passes: the backward re-computes the messages
     from the node-level state.  The backward is `once_differentiable`: double backward raises (DMET_EDGE_MLP_F32=0 gives
-    the generic route, which supports it)."""
-
-    @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
-        return _edge_mlp2_forward("f32", ctx, x, W1, b1, W2, b2, gamma, beta, edges, act2, aggr, bn)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_out):
-        return _edge_mlp2_backward("f32", ctx, g_out)
-
-
-class _EdgeMLP2Bf16Edges(torch.autograd.Function):
-    """The layer of _EdgeMLP2F32 with its per-edge products on the bf16 matrix cores (csrc/edgemlp_bf16.hip), forward
+    the generic route, which supports it).""",
+    "bf16": """\
+The layer of _EdgeMLP2F32 with its per-edge products on the bf16 matrix cores (csrc/edgemlp_bf16.hip), forward
     and backward: the route taken when bf16 is requested (autocast or compute_dtype) over a grouped edge list.  fp32 in
     and out; h1, W2 and g_z2 are rounded to bf16 inside the kernels only.  `once_differentiable`: DMET_EDGE_MLP_BF16=0
-    gives the generic route, e.g. for double backward."""
-
-    @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
-        return _edge_mlp2_forward("bf16", ctx, x, W1, b1, W2, b2, gamma, beta, edges, act2, aggr, bn)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_out):
-        return _edge_mlp2_backward("bf16", ctx, g_out)
-
-
-class _EdgeMLP2F16Edges(torch.autograd.Function):
-    """_EdgeMLP2Bf16Edges with fp16 operands on the fp16 matrix cores (csrc/edgemlp_bf16.hip, the same kernels): the
+    gives the generic route, e.g. for double backward.""",
+    "f16": """\
+_EdgeMLP2Bf16Edges with fp16 operands on the fp16 matrix cores (csrc/edgemlp_bf16.hip, the same kernels): the
     route taken when fp16 is requested (torch.autocast("cuda") without a dtype, or compute_dtype) over a grouped edge
     list.  fp32 in and out; h1, W2 and g_z2 are rounded to fp16 (RNE, overflow to inf) inside the kernels only.
-    `once_differentiable`: DMET_EDGE_MLP_F16=0 gives the generic route, e.g. for double backward."""
+    `once_differentiable`: DMET_EDGE_MLP_F16=0 gives the generic route, e.g. for double backward.""",
+}
+_EdgeMLP2F32 = _edge_mlp2_function("f32", "_EdgeMLP2F32", _EDGE_MLP2_DOCS["f32"])
+_EdgeMLP2Bf16Edges = _edge_mlp2_function("bf16", "_EdgeMLP2Bf16Edges", _EDGE_MLP2_DOCS["bf16"])
+_EdgeMLP2F16Edges = _edge_mlp2_function("f16", "_EdgeMLP2F16Edges", _EDGE_MLP2_DOCS["f16"])
 
-    @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, gamma, beta, edges: EdgeList, act2: bool, aggr: str, bn):
-        return _edge_mlp2_forward("f16", ctx, x, W1, b1, W2, b2, gamma, beta, edges, act2, aggr, bn)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_out):
-        return _edge_mlp2_backward("f16", ctx, g_out)
+# route -> (autograd Function, the 16-bit dtype whose request selects it; None: no 16 bits and no autocast)
+_EDGE_MLP_ROUTES = {"bf16": (_EdgeMLP2Bf16Edges, torch.bfloat16), "f16": (_EdgeMLP2F16Edges, torch.float16),
+                    "f32": (_EdgeMLP2F32, None)}
 
 
 class _EdgeFeatures(torch.autograd.Function):
@@ -591,29 +559,21 @@ class EdgeConv(torch.nn.Module):
         return lin
 
     def _use_bf16(self, lin: torch.nn.Linear, table: NeighborTable) -> bool:
-        dt = self.compute_dtype
-        if dt is None and torch.is_autocast_enabled():
-            dt = torch.get_autocast_gpu_dtype()
-        return (dt == torch.bfloat16 and lin.in_features == 64 and lin.out_features == 32
-                and table.k in (8, 16, 32))
+        return self._wants_bf16() and lin.in_features == 64 and lin.out_features == 32 and table.k in (8, 16, 32)
 
-    def _forward_edge_mlp_bf16(self, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
-        """The bf16 matrix-core route over a grouped edge list (_EdgeMLP2Bf16Edges), or None when this call does not take
-        it: bf16 not requested (autocast or compute_dtype), another `nn`, non-fp32 parameters, widths outside
-        dmet_edge_mlp_bf16_supported, DMET_EDGE_MLP_BF16=0, or a training-mode BatchNorm over E <= 1 edges.  fp32 out."""
-        return self._forward_edge_mlp_16bit("bf16", x, edges)
-
-    def _forward_edge_mlp_f16(self, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
-        """The fp16 matrix-core route over a grouped edge list (_EdgeMLP2F16Edges), or None when this call does not take
-        it, by the bf16 route's rules: fp16 not requested (autocast or compute_dtype), another `nn`, non-fp32
-        parameters, widths outside dmet_edge_mlp_f16_supported, DMET_EDGE_MLP_F16=0, or a training-mode BatchNorm over
-        E <= 1 edges.  fp32 out."""
-        return self._forward_edge_mlp_16bit("f16", x, edges)
-
-    def _forward_edge_mlp_16bit(self, route: str, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
+    def _forward_edge_mlp(self, route: str, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
+        """The fused route "bf16", "f16" or "f32" over a grouped edge list (_EDGE_MLP_ROUTES), or None when this call does
+        not take it: DMET_EDGE_MLP_<ROUTE>=0, x not fp32 on the GPU, another dtype requested (a 16-bit route wants its
+        dtype from autocast or compute_dtype, the fp32 route no 16 bits and no autocast), another `nn`, non-fp32
+        parameters, widths outside dmet_edge_mlp_<route>_supported, or a training-mode BatchNorm over E <= 1 edges
+        (torch's own error for one value per channel stays).  fp32 out."""
+        fn, want = _EDGE_MLP_ROUTES[route]
         if os.environ.get(f"DMET_EDGE_MLP_{route.upper()}", "1") == "0" or not x.is_cuda or x.dtype != torch.float32:
             return None
-        if self._wants_16bit() != (torch.bfloat16 if route == "bf16" else torch.float16):
+        if want is not None:
+            if self._wants_16bit() != want:
+                return None
+        elif self.compute_dtype not in (None, torch.float32) or torch.is_autocast_enabled():
             return None
         mlp = _as_mlp2(self.nn)
         if mlp is None:
@@ -626,31 +586,17 @@ class EdgeConv(torch.nn.Module):
             return None
         if bn is not None and (bn.training or not bn.track_running_stats) and edges.num_edges <= 1:
             return None
-        fn = _EdgeMLP2Bf16Edges if route == "bf16" else _EdgeMLP2F16Edges
         return fn.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, bn.weight if bn is not None else None,
                         bn.bias if bn is not None else None, edges, act2, self.aggr, bn)
 
+    def _forward_edge_mlp_bf16(self, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
+        return self._forward_edge_mlp("bf16", x, edges)
+
+    def _forward_edge_mlp_f16(self, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
+        return self._forward_edge_mlp("f16", x, edges)
+
     def _forward_edge_mlp_f32(self, x: torch.Tensor, edges: EdgeList) -> Optional[torch.Tensor]:
-        """The fused fp32 route (_EdgeMLP2F32) for a two-layer edge MLP, or None when this call keeps the generic route:
-        another `nn`, widths outside dmet_edge_mlp_f32_supported, 16 bits or autocast requested, DMET_EDGE_MLP_F32=0, or a
-        training-mode BatchNorm over E <= 1 edges (torch's own error for one value per channel stays)."""
-        if os.environ.get("DMET_EDGE_MLP_F32", "1") == "0" or not x.is_cuda or x.dtype != torch.float32:
-            return None
-        if self.compute_dtype not in (None, torch.float32) or torch.is_autocast_enabled():
-            return None
-        mlp = _as_mlp2(self.nn)
-        if mlp is None:
-            return None
-        l1, l2, act2, bn = mlp
-        params = [l1.weight, l1.bias, l2.weight, l2.bias] + ([bn.weight, bn.bias] if bn is not None else [])
-        if any(p is not None and p.dtype != torch.float32 for p in params) or l1.in_features != 2 * x.shape[1]:
-            return None
-        if not _native.edge_mlp_f32_supported(x.shape[1], l1.out_features, l2.out_features):
-            return None
-        if bn is not None and (bn.training or not bn.track_running_stats) and edges.num_edges <= 1:
-            return None
-        return _EdgeMLP2F32.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, bn.weight if bn is not None else None,
-                                  bn.bias if bn is not None else None, edges, act2, self.aggr, bn)
+        return self._forward_edge_mlp("f32", x, edges)
 
     def _forward_edges(self, x: torch.Tensor, edges: EdgeList, x_src: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The generic route.  x_src: the sources' own node set (two-set form); x is then x_dst, the targets."""

@@ -6,6 +6,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/dmet.h"
 
 namespace dmet {
@@ -87,6 +89,24 @@ __device__ __forceinline__ float wave_sum(float v)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+
+// Host side of the kernels' template ladders (cf. with_pack in knn_common.h): a run-time value reaches a generic lambda
+// as a std::integral_constant, so that each kernel's launch expression is written once.
+// with_int<Vs...>(v, f): f(integral_constant<int, V>) for the V among Vs that equals v; false when none does.
+template <int... Vs, typename F>
+bool with_int(int v, F &&f)
+{
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+// with_flags(f, b...): f(std::true_type or std::false_type, ...), one per bool.
+template <typename F>
+void with_flags(F &&f) { f(); }
+template <typename F, typename... Rest>
+void with_flags(F &&f, bool b, Rest... rest)
+{
+    if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 }  // namespace dmet

@@ -1239,24 +1239,6 @@ namespace {
 constexpr int kLdsGatherRowsHalf = kLdsGatherRows / 2;       // 2 560 rows = 80 KB
 constexpr int kLdsGatherThreadsHalf = kLdsGatherThreads / 2; // 512 threads: two such workgroups per CU
 
-// Host side of the kernels' template ladders (cf. with_pack in knn_common.h): a run-time value reaches a generic lambda
-// as a std::integral_constant, so that each kernel's launch expression is written once.
-// with_int<Vs...>(v, f): f(integral_constant<int, V>) for the V among Vs that equals v; false when none does.
-template <int... Vs, typename F>
-bool with_int(int v, F &&f)
-{
-    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
-}
-// with_flags(f, b...): f(std::true_type or std::false_type, ...), one per bool.
-template <typename F>
-void with_flags(F &&f) { f(); }
-template <typename F, typename... Rest>
-void with_flags(F &&f, bool b, Rest... rest)
-{
-    if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
-    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
-}
-
 // what the entry promises about the batch; gather_max_launch makes one of its seven forms of it
 enum GatherFamily {
     kGatherL2,          // nothing: row gathers from L2

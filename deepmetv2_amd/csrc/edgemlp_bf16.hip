@@ -10,8 +10,9 @@
 // to_undirected(knn_graph(...))) when the model runs under torch.autocast(dtype=torch.bfloat16).
 //
 // Only the two edge passes live here.  Everything at node level is the fp32 route's (edgemlp_f32.hip, which also owns
-// the host orchestration): the split of the first Linear PQ = [x (W1a - W1b)^T + b1 | x W1b^T], the BatchNorm finalize
-// and apply kernels, the BatchNorm backward reduction, the gW2 partial sums and gx.  The plan is that route's plan:
+// the entry points and the host orchestration): the split of the first Linear PQ = [x (W1a - W1b)^T + b1 | x W1b^T],
+// the BatchNorm finalize and apply kernels, the BatchNorm backward reduction, the gW2 partial sums and gx.  The plan is
+// that route's plan:
 //   forward edge pass: workgroup b owns the node range whose edges start at b E / nblk; it walks its edges in tiles of
 //     T = 32 consecutive edges that may span targets: h1 = ELU(P_tgt + Q_src) in fp32 -> bf16 tile in LDS,
 //     z2 = h1 W2^T + b2 on v_mfma_f32_16x16x32_bf16 (fp32 accumulation; W2 bf16 in LDS), m = ELU?(z2) in fp32, then
@@ -283,12 +284,7 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_mma_kernel(const float *__r
     for (int64_t pt = p0; pt < p1; pt += kT) {
         const int cnt = (int)(p1 - pt < kT ? p1 - pt : kT);
         __syncthreads();
-        for (int t = threadIdx.x; t < kT; t += blockDim.x) {
-            const int32_t e = t < cnt ? (BY_SRC ? perm[pt + t] : (int32_t)(pt + t)) : 0;
-            ep[t] = e;
-            tg[t] = t < cnt ? tgt[e] : 0;
-            sr[t] = t < cnt ? src[e] : 0;
-        }
+        load_tile_ids<kT, BY_SRC>(src, tgt, perm, pt, cnt, tg, sr, ep);
         __syncthreads();
         fill_h1<Op>(PQ, H1, tg, sr, cnt, h1e, h1c);
         __syncthreads();
@@ -297,22 +293,11 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_mma_kernel(const float *__r
             const int eb = blk & 1, ob = blk >> 1;
             const f32x4 acc = z2_block<Op>(h1e, w2s, H1, eb, ob, lane);
             const int o = 16 * ob + (lane & 15);
-            const float ka = coef[o], k1 = coef[H2 + o], k2 = coef[2 * H2 + o];
-            const float bmean = bnstat[2 * H2 + o], binv = bnstat[3 * H2 + o];
-            const int32_t *winsel = win + ((aggr == 0 && bn != 0 && ka < 0.0f) ? N * H2 : 0);
+            const Gz2<H2> gz2(coef, bnstat, win, N, aggr, bn, o);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int t = 16 * eb + 4 * (lane >> 4) + r;
-                float gzv = 0.0f;
-                if (t < cnt) {
-                    const float z = acc[r] + b2s[o];
-                    const float m = act2 ? elu1f(z) : z;
-                    const float gy = gy_of(g_out, rowptr, winsel, aggr, tg[t], H2, o, ep[t]);
-                    float gm = gy;
-                    if (bn == 1) gm = ka * (gy - k1 - (m - bmean) * binv * k2);
-                    else if (bn == 2) gm = ka * gy;
-                    gzv = act2 ? gm * (z > 0.0f ? 1.0f : m + 1.0f) : gm;
-                }
+                const float gzv = t < cnt ? gz2(acc[r] + b2s[o], g_out, rowptr, act2, aggr, bn, tg, ep, t, o) : 0.0f;
                 gzc[o * kTS + t] = gzv;
                 gze[t * SZ + o] = Op::bits(gzv);
             }
@@ -421,20 +406,14 @@ int fwd_pass(const EdgePassArgs &a, int nblk, float *partial, hipStream_t st)
 {
     const size_t lds = fwd_lds_bytes_mma(a.H1, a.H2);
     int rc = 0;
-#define EMLP_FWD_MMA(kH2)                                                                                                   \
-    {                                                                                                                       \
-        static size_t granted = 0;                                                                                          \
-        rc = grant_lds(edge_mlp_fwd_mma_kernel<Op, kH2>, lds, granted, "hipFuncSetAttribute(edge_mlp_fwd_mma_kernel)");     \
-        if (rc == 0)                                                                                                        \
-            hipLaunchKernelGGL((edge_mlp_fwd_mma_kernel<Op, kH2>), dim3(nblk), dim3(kBlk), lds, st, a.pq, a.rowptr, a.src,  \
-                               a.tgt, a.N, a.E, a.H1, a.W2, a.b2, a.act2, a.aggr, a.bn, a.agg, a.win, partial);             \
-    }
-    switch (a.H2) {
-    case 32: EMLP_FWD_MMA(32) break;
-    case 64: EMLP_FWD_MMA(64) break;
-    default: EMLP_FWD_MMA(128) break;
-    }
-#undef EMLP_FWD_MMA
+    with_int<32, 64, 128>(a.H2, [&](auto h2) {
+        constexpr int kH2 = decltype(h2)::value;
+        static size_t granted = 0;
+        rc = grant_lds(edge_mlp_fwd_mma_kernel<Op, kH2>, lds, granted, "hipFuncSetAttribute(edge_mlp_fwd_mma_kernel)");
+        if (rc == 0)
+            hipLaunchKernelGGL((edge_mlp_fwd_mma_kernel<Op, kH2>), dim3(nblk), dim3(kBlk), lds, st, a.pq, a.rowptr, a.src, a.tgt,
+                               a.N, a.E, a.H1, a.W2, a.b2, a.act2, a.aggr, a.bn, a.agg, a.win, partial);
+    });
     return rc;
 }
 
@@ -444,24 +423,17 @@ int bwd_pass(const EdgePassArgs &a, bool by_src, int nblk, float *partial, hipSt
     const size_t lds = bwd_lds_bytes_mma(a.H1, a.H2);
     const int32_t *optr = by_src ? a.srcptr : a.rowptr, *perm = by_src ? a.srcperm : nullptr;
     int rc = 0;
-#define EMLP_BWD_MMA(kH2, kBS)                                                                                              \
-    {                                                                                                                       \
-        static size_t granted = 0;                                                                                          \
-        rc = grant_lds(edge_mlp_bwd_mma_kernel<Op, kH2, kBS>, lds, granted, "hipFuncSetAttribute(edge_mlp_bwd_mma_kernel)");\
-        if (rc == 0)                                                                                                        \
-            hipLaunchKernelGGL((edge_mlp_bwd_mma_kernel<Op, kH2, kBS>), dim3(nblk), dim3(kBlk), lds, st, a.pq, a.rowptr,    \
-                               optr, perm, a.src, a.tgt, a.N, a.E, a.H1, a.W2, a.b2, a.act2, a.aggr, a.bn, a.g_out, a.cwin, \
-                               a.bnstat, a.coef, a.gpq, partial);                                                           \
-    }
-    switch (a.H2 * 2 + (by_src ? 1 : 0)) {
-    case 64: EMLP_BWD_MMA(32, false) break;
-    case 65: EMLP_BWD_MMA(32, true) break;
-    case 128: EMLP_BWD_MMA(64, false) break;
-    case 129: EMLP_BWD_MMA(64, true) break;
-    case 256: EMLP_BWD_MMA(128, false) break;
-    default: EMLP_BWD_MMA(128, true) break;
-    }
-#undef EMLP_BWD_MMA
+    with_int<32, 64, 128>(a.H2, [&](auto h2) {
+        with_flags([&](auto bs) {
+            constexpr int kH2 = decltype(h2)::value;
+            static size_t granted = 0;
+            rc = grant_lds(edge_mlp_bwd_mma_kernel<Op, kH2, bs()>, lds, granted, "hipFuncSetAttribute(edge_mlp_bwd_mma_kernel)");
+            if (rc == 0)
+                hipLaunchKernelGGL((edge_mlp_bwd_mma_kernel<Op, kH2, bs()>), dim3(nblk), dim3(kBlk), lds, st, a.pq, a.rowptr, optr,
+                                   perm, a.src, a.tgt, a.N, a.E, a.H1, a.W2, a.b2, a.act2, a.aggr, a.bn, a.g_out, a.cwin, a.bnstat,
+                                   a.coef, a.gpq, partial);
+        }, by_src);
+    });
     return rc;
 }
 
@@ -485,75 +457,3 @@ int edge_mlp_bwd_pass_mma(const EdgePassArgs &a, EdgePrec prec, bool by_src, int
 }
 
 }  // namespace dmet
-
-using namespace dmet;
-
-extern "C" int dmet_edge_mlp_bf16_supported(int Hin, int H1, int H2)
-{
-    if (!(H2 == 32 || H2 == 64 || H2 == 128)) return 0;
-    if (Hin < 1 || Hin > 128 || H1 < 16 || H1 % 16 != 0 || H1 > 192 || H1 > 2 * H2) return 0;
-    return 1;
-}
-
-extern "C" size_t dmet_edge_mlp_bf16_workspace_bytes(int64_t N, int64_t E, int Hin, int H1, int H2)
-{
-    // the node-level state and the partials are the fp32 route's
-    if (!dmet_edge_mlp_bf16_supported(Hin, H1, H2)) return 0;
-    return dmet_edge_mlp_f32_workspace_bytes(N, E, Hin, H1, H2);
-}
-
-extern "C" int dmet_edge_mlp_fwd_bf16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
-                                      const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1, const float *W2,
-                                      const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
-                                      const float *beta, float eps, float momentum, float *running_mean, float *running_var,
-                                      int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
-                                      float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
-{
-    return edge_mlp_fwd("dmet_edge_mlp_fwd_bf16", EdgePrec::bf16, x, N, Hin, rowptr, src, tgt, E, W1, b1, H1, W2, b2, H2,
-                        act2, aggr, bn, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq,
-                        agg, win, bnstat, ws, ws_bytes, stream);
-}
-
-extern "C" int dmet_edge_mlp_bwd_bf16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
-                                      const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
-                                      const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr,
-                                      int bn, const float *pq, const float *agg, const int32_t *win, const float *bnstat,
-                                      const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
-                                      float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
-{
-    return edge_mlp_bwd("dmet_edge_mlp_bwd_bf16", EdgePrec::bf16, x, N, Hin, rowptr, src, tgt, E, srcptr, srcperm, W1, H1,
-                        W2, b2, H2, act2, aggr, bn, pq, agg, win, bnstat, g_out, gx, gpq, gW2, gb2, ggamma, gbeta, ws,
-                        ws_bytes, stream);
-}
-
-// fp16: the same widths, workspace and argument checks as bf16
-extern "C" int dmet_edge_mlp_f16_supported(int Hin, int H1, int H2) { return dmet_edge_mlp_bf16_supported(Hin, H1, H2); }
-
-extern "C" size_t dmet_edge_mlp_f16_workspace_bytes(int64_t N, int64_t E, int Hin, int H1, int H2)
-{
-    return dmet_edge_mlp_bf16_workspace_bytes(N, E, Hin, H1, H2);
-}
-
-extern "C" int dmet_edge_mlp_fwd_f16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
-                                     const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1, const float *W2,
-                                     const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
-                                     const float *beta, float eps, float momentum, float *running_mean, float *running_var,
-                                     int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
-                                     float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
-{
-    return edge_mlp_fwd("dmet_edge_mlp_fwd_f16", EdgePrec::f16, x, N, Hin, rowptr, src, tgt, E, W1, b1, H1, W2, b2, H2,
-                        act2, aggr, bn, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq,
-                        agg, win, bnstat, ws, ws_bytes, stream);
-}
-
-extern "C" int dmet_edge_mlp_bwd_f16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
-                                     const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
-                                     const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr,
-                                     int bn, const float *pq, const float *agg, const int32_t *win, const float *bnstat,
-                                     const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
-                                     float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
-{
-    return edge_mlp_bwd("dmet_edge_mlp_bwd_f16", EdgePrec::f16, x, N, Hin, rowptr, src, tgt, E, srcptr, srcperm, W1, H1,
-                        W2, b2, H2, act2, aggr, bn, pq, agg, win, bnstat, g_out, gx, gpq, gW2, gb2, ggamma, gbeta, ws,
-                        ws_bytes, stream);
-}

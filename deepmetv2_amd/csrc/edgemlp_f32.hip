@@ -385,9 +385,7 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_kernel(const float *__restr
     const int64_t n0 = range_start(optr, N, E, blockIdx.x, nblk), n1 = range_start(optr, N, E, blockIdx.x + 1, nblk);
     const int64_t p0 = optr[n0], p1 = optr[n1];
     const int o = threadIdx.x % H2, g = threadIdx.x / H2;
-    const float ka = coef[o], k1 = coef[H2 + o], k2 = coef[2 * H2 + o];
-    const float bmean = bnstat[2 * H2 + o], binv = bnstat[3 * H2 + o];
-    const int32_t *winsel = win + ((aggr == 0 && bn != 0 && ka < 0.0f) ? N * H2 : 0);
+    const Gz2<H2> gz2(coef, bnstat, win, N, aggr, bn, o);
     float gw[BY_SRC ? 1 : NP];
     float gb = 0.0f;
     if (!BY_SRC) {
@@ -400,12 +398,7 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_kernel(const float *__restr
     for (int64_t pt = p0; pt < p1; pt += T) {
         const int cnt = (int)(p1 - pt < T ? p1 - pt : T);
         __syncthreads();
-        for (int t = threadIdx.x; t < T; t += blockDim.x) {
-            const int32_t e = t < cnt ? (BY_SRC ? perm[pt + t] : (int32_t)(pt + t)) : 0;
-            ep[t] = e;
-            tg[t] = t < cnt ? tgt[e] : 0;
-            sr[t] = t < cnt ? src[e] : 0;
-        }
+        load_tile_ids<T, BY_SRC>(src, tgt, perm, pt, cnt, tg, sr, ep);
         __syncthreads();
         fill_h1<H2>(PQ, H1, tg, sr, cnt, h1s);
         __syncthreads();
@@ -415,15 +408,7 @@ __global__ __launch_bounds__(kBlk) void edge_mlp_bwd_kernel(const float *__restr
 #pragma unroll
             for (int u = 0; u < kTpt; ++u) {
                 const int t = kTpt * g + u;
-                float gzv = 0.0f;
-                if (t < cnt) {
-                    const float m = act2 ? elu1f(acc[u]) : acc[u];
-                    const float gy = gy_of(g_out, rowptr, winsel, aggr, tg[t], H2, o, ep[t]);
-                    float gm = gy;
-                    if (bn == 1) gm = ka * (gy - k1 - (m - bmean) * binv * k2);
-                    else if (bn == 2) gm = ka * gy;
-                    gzv = act2 ? gm * (acc[u] > 0.0f ? 1.0f : m + 1.0f) : gm;
-                }
+                const float gzv = t < cnt ? gz2(acc[u], g_out, rowptr, act2, aggr, bn, tg, ep, t, o) : 0.0f;
                 gz[o * TS + t] = gzv;
                 if (!BY_SRC) gbt += gzv;
             }
@@ -540,124 +525,167 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 constexpr int kBnReduceBlocks = 256;
 
-}  // namespace
-}  // namespace dmet
+// ---- K2 host path: every dmet_edge_mlp_{fwd,bwd}_{f32,bf16,f16} entry fills an EdgeMlp and calls edge_mlp_fwd or
+// edge_mlp_bwd once ---------------------------------------------------------------------------------------------------
 
-using namespace dmet;
-
-extern "C" int dmet_edge_mlp_f32_supported(int Hin, int H1, int H2)
+int supported(EdgePrec prec, int Hin, int H1, int H2)
 {
-    if (!(H2 == 16 || H2 == 32 || H2 == 64 || H2 == 128)) return 0;
     if (Hin < 1 || Hin > 128 || H1 < 1 || H1 > 192 || H1 > 2 * H2) return 0;
-    return 1;
+    if (prec == EdgePrec::f32) return H2 == 16 || H2 == 32 || H2 == 64 || H2 == 128;
+    return (H2 == 32 || H2 == 64 || H2 == 128) && H1 % 16 == 0;     // whole 16 x 16 MFMA blocks
 }
 
-extern "C" size_t dmet_edge_mlp_f32_workspace_bytes(int64_t N, int64_t E, int Hin, int H1, int H2)
+// The workspace of either call, the only place that knows its layout.  The forward's statistics partials and the
+// backward's arrays share the bytes after the split weights; nothing is per node or per edge.
+struct Workspace {
+    float *w;           // fwd: Wt [Hin][2 H1], then its bias [2 H1];  bwd: Wc [2 H1][Hin]
+    float *stat;        // fwd: sum m, sum m^2 [kMaxBlocks][2 H2]
+    float *gw;          // bwd: gW2 | gb2 [kMaxBlocks][H2 H1 + H2]
+    float *bnred;       // bwd: BatchNorm reduce partials [kBnReduceBlocks][2 H2]
+    float *coef;        // bwd: [3][H2]
+    size_t bytes;       // from `ws` on, with 256 bytes of slack to align it
+};
+
+Workspace carve(int64_t N, int64_t E, int Hin, int H1, int H2, void *ws)
 {
-    if (N < 0 || E < 0 || !dmet_edge_mlp_f32_supported(Hin, H1, H2)) return 0;
-    const size_t w = align256(sizeof(float) * ((size_t)2 * H1 * Hin + 2 * (size_t)H1));     // split weights + bias
-    const size_t fwd = align256(sizeof(float) * (size_t)kMaxBlocks * 2 * H2);                // statistics partials
-    const size_t bwd = align256(sizeof(float) * (size_t)kMaxBlocks * ((size_t)H2 * H1 + H2)) +
-                       align256(sizeof(float) * (size_t)kBnReduceBlocks * 2 * H2) + align256(sizeof(float) * 3 * (size_t)H2);
-    return 256 + w + (fwd > bwd ? fwd : bwd);
+    (void)N; (void)E;
+    const size_t w = align256(sizeof(float) * ((size_t)2 * H1 * Hin + 2 * (size_t)H1));
+    const size_t stat = align256(sizeof(float) * (size_t)kMaxBlocks * 2 * H2);
+    const size_t gw = align256(sizeof(float) * (size_t)kMaxBlocks * ((size_t)H2 * H1 + H2));
+    const size_t bnred = align256(sizeof(float) * (size_t)kBnReduceBlocks * 2 * H2);
+    const size_t bwd = gw + bnred + align256(sizeof(float) * 3 * (size_t)H2);
+    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255u) & ~(uintptr_t)255u);
+    Workspace c;
+    c.w = reinterpret_cast<float *>(base);
+    c.stat = c.gw = reinterpret_cast<float *>(base + w);
+    c.bnred = reinterpret_cast<float *>(base + w + gw);
+    c.coef = reinterpret_cast<float *>(base + w + gw + bnred);
+    c.bytes = 256 + w + (stat > bwd ? stat : bwd);
+    return c;
 }
 
-#define EMLP_DISPATCH(H2V, ...)                                         \
-    switch (H2V) {                                                      \
-    case 16: { constexpr int kH2 = 16; __VA_ARGS__; } break;            \
-    case 32: { constexpr int kH2 = 32; __VA_ARGS__; } break;            \
-    case 64: { constexpr int kH2 = 64; __VA_ARGS__; } break;            \
-    default: { constexpr int kH2 = 128; __VA_ARGS__; } break;           \
+size_t workspace_bytes(EdgePrec prec, int64_t N, int64_t E, int Hin, int H1, int H2)
+{
+    if (N < 0 || E < 0 || !supported(prec, Hin, H1, H2)) return 0;
+    return carve(N, E, Hin, H1, H2, nullptr).bytes;
+}
+
+struct EdgeMlp {
+    const char *entry;      // the exported function the caller called: every message names it
+    EdgePrec prec;
+    const float *x;
+    int Hin;
+    const float *W1;
+    void *ws;
+    size_t ws_bytes;
+    dmet_stream_t stream;
+    EdgePassArgs p;         // the graph, N, E, H1, H2, the second Linear, the modes and the state: what the edge passes take
+    struct {
+        const float *b1, *gamma, *beta;
+        float eps, momentum;
+        float *running_mean, *running_var;
+        int64_t *num_batches_tracked;
+        float *out, *pq, *bnstat;
+    } fwd;
+    struct {
+        const float *agg;
+        float *gx, *gW2, *gb2, *ggamma, *gbeta;
+    } bwd;
+};
+
+// what the forward and the backward entries hand to the edge passes alike; each adds its own part by name
+EdgePassArgs pass_args(const float *pq, const int32_t *rowptr, const int32_t *src, const int32_t *tgt, int64_t N, int64_t E,
+                       int H1, int H2, const float *W2, const float *b2, int act2, int aggr, int bn)
+{
+    EdgePassArgs p{};
+    p.pq = pq; p.rowptr = rowptr; p.src = src; p.tgt = tgt; p.N = N; p.E = E; p.H1 = H1; p.H2 = H2;
+    p.W2 = W2; p.b2 = b2; p.act2 = act2; p.aggr = aggr; p.bn = bn;
+    return p;
+}
+
+int check_common(const EdgeMlp &r, bool fwd)
+{
+    const char *fn = r.entry;
+    const EdgePassArgs &p = r.p;
+    DMET_REQUIRE(p.N >= 0 && p.N < (int64_t)2147483647 / 384, "%s: N out of range", fn);
+    DMET_REQUIRE(p.E >= 0 && p.E < (int64_t)2147483647, "%s: E out of range", fn);
+    DMET_REQUIRE(supported(r.prec, r.Hin, p.H1, p.H2), "%s: unsupported widths Hin=%d H1=%d H2=%d", fn, r.Hin, p.H1, p.H2);
+    DMET_REQUIRE(p.aggr >= 0 && p.aggr <= 2, "%s: aggr must be 0 (max), 1 (add) or 2 (mean)", fn);
+    DMET_REQUIRE(p.bn >= 0 && p.bn <= 2, "%s: bn must be 0 (none), 1 (training) or 2 (eval)", fn);
+    if (fwd) {
+        DMET_REQUIRE(p.bn != 2 || (r.fwd.running_mean && r.fwd.running_var), "%s: eval mode needs running statistics", fn);
+        DMET_REQUIRE((r.fwd.running_mean == nullptr) == (r.fwd.running_var == nullptr), "%s: running_mean/var go together", fn);
     }
-
-static int check_common(const char *fn, EdgePrec prec, const float *x, int64_t N, int Hin, const int32_t *rowptr,
-                        const int32_t *src, const int32_t *tgt, int64_t E, const float *W1, int H1, const float *W2, int H2,
-                        int aggr, int bn, const float *running_mean, const float *running_var, size_t ws_bytes,
-                        const void *ws, bool fwd)
-{
-    const int supported = prec == EdgePrec::bf16  ? dmet_edge_mlp_bf16_supported(Hin, H1, H2)
-                          : prec == EdgePrec::f16 ? dmet_edge_mlp_f16_supported(Hin, H1, H2)
-                                                  : dmet_edge_mlp_f32_supported(Hin, H1, H2);
-    DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647 / 384, "%s: N out of range", fn);
-    DMET_REQUIRE(E >= 0 && E < (int64_t)2147483647, "%s: E out of range", fn);
-    DMET_REQUIRE(supported, "%s: unsupported widths Hin=%d H1=%d H2=%d", fn, Hin, H1, H2);
-    DMET_REQUIRE(aggr >= 0 && aggr <= 2, "%s: aggr must be 0 (max), 1 (add) or 2 (mean)", fn);
-    DMET_REQUIRE(bn >= 0 && bn <= 2, "%s: bn must be 0 (none), 1 (training) or 2 (eval)", fn);
-    DMET_REQUIRE(!fwd || bn != 2 || (running_mean && running_var), "%s: eval mode needs running statistics", fn);
-    DMET_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "%s: running_mean/var go together", fn);
-    DMET_REQUIRE(N > 0 || E == 0, "%s: E=%lld edges over no nodes", fn, (long long)E);
-    if (N == 0) return 0;      // empty input: nothing is read, the entry points write only the weight gradients
-    DMET_REQUIRE(x && rowptr && W1 && W2, "%s: null pointer", fn);
-    DMET_REQUIRE(E == 0 || (src && tgt), "%s: null edge array", fn);
-    DMET_REQUIRE(ws && ws_bytes >= dmet_edge_mlp_f32_workspace_bytes(N, E, Hin, H1, H2), "%s: workspace too small", fn);
+    DMET_REQUIRE(p.N > 0 || p.E == 0, "%s: E=%lld edges over no nodes", fn, (long long)p.E);
+    if (p.N == 0) return 0;    // empty input: nothing is read, the entry points write only the weight gradients
+    DMET_REQUIRE(r.x && p.rowptr && r.W1 && p.W2, "%s: null pointer", fn);
+    DMET_REQUIRE(p.E == 0 || (p.src && p.tgt), "%s: null edge array", fn);
+    DMET_REQUIRE(r.ws && r.ws_bytes >= carve(p.N, p.E, r.Hin, p.H1, p.H2, nullptr).bytes, "%s: workspace too small", fn);
     return 0;
 }
 
-int dmet::edge_mlp_fwd(const char *fn, EdgePrec prec, const float *x, int64_t N, int Hin, const int32_t *rowptr,
-                       const int32_t *src, const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1,
-                       const float *W2, const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
-                       const float *beta, float eps, float momentum, float *running_mean, float *running_var,
-                       int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win, float *bnstat,
-                       void *ws, size_t ws_bytes, dmet_stream_t stream)
+// Forward: split weights -> P | Q -> edge pass (fp32 or matrix cores) -> BatchNorm finalize -> apply.
+int edge_mlp_fwd(const EdgeMlp &r)
 {
-    if (int rc = check_common(fn, prec, x, N, Hin, rowptr, src, tgt, E, W1, H1, W2, H2, aggr, bn, running_mean, running_var,
-                              ws_bytes, ws, true))
-        return rc;
-    DMET_REQUIRE(bn != 1 || E > 0, "%s: batch statistics need at least one edge", fn);
+    const char *fn = r.entry;
+    const EdgePassArgs &p = r.p;
+    const int64_t N = p.N, E = p.E;
+    const int Hin = r.Hin, H1 = p.H1, H2 = p.H2;
+    if (int rc = check_common(r, true)) return rc;
+    DMET_REQUIRE(p.bn != 1 || E > 0, "%s: batch statistics need at least one edge", fn);
     if (N == 0) return 0;      // out[0, H2]: nothing to write; running statistics do not move (bn != 1)
-    DMET_REQUIRE(out && pq && agg && bnstat && (aggr != 0 || win), "%s: null output pointer", fn);
-    hipStream_t st = as_stream(stream);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255u) & ~(uintptr_t)255u);
-    float *Wt = reinterpret_cast<float *>(base);
-    float *bias = Wt + (size_t)Hin * 2 * H1;
-    float *partial = reinterpret_cast<float *>(base + align256(sizeof(float) * ((size_t)2 * H1 * Hin + 2 * (size_t)H1)));
+    DMET_REQUIRE(r.fwd.out && r.fwd.pq && p.agg && r.fwd.bnstat && (p.aggr != 0 || p.win), "%s: null output pointer", fn);
+    hipStream_t st = as_stream(r.stream);
+    const Workspace c = carve(N, E, Hin, H1, H2, r.ws);
+    float *Wt = c.w, *bias = Wt + (size_t)Hin * 2 * H1;
     const int nw = H1 * Hin > 2 * H1 ? H1 * Hin : 2 * H1;
-    hipLaunchKernelGGL(split_weights_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, W1, b1, Hin, H1, Wt, bias,
+    hipLaunchKernelGGL(split_weights_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, r.W1, r.fwd.b1, Hin, H1, Wt, bias,
                        (float *)nullptr);
     DMET_LAUNCH_CHECK("split_weights_kernel");
-    hipLaunchKernelGGL(rows_linear_kernel, dim3((unsigned)((N + 15) / 16)), dim3(256), 0, st, x, N, Hin, (const float *)Wt,
-                       (const float *)bias, 2 * H1, pq);
+    hipLaunchKernelGGL(rows_linear_kernel, dim3((unsigned)((N + 15) / 16)), dim3(256), 0, st, r.x, N, Hin, (const float *)Wt,
+                       (const float *)bias, 2 * H1, r.fwd.pq);
     DMET_LAUNCH_CHECK("rows_linear_kernel (P | Q)");
     const int nblk = edge_blocks(E);
-    if (E > 0 && prec != EdgePrec::f32) {
-        EdgePassArgs a{};
-        a.pq = pq; a.rowptr = rowptr; a.src = src; a.tgt = tgt; a.N = N; a.E = E; a.H1 = H1; a.H2 = H2;
-        a.W2 = W2; a.b2 = b2; a.act2 = act2; a.aggr = aggr; a.bn = bn; a.agg = agg; a.win = win;
-        if (int rc = edge_mlp_fwd_pass_mma(a, prec, nblk, partial, st)) return rc;
+    if (E > 0 && r.prec != EdgePrec::f32) {
+        if (int rc = edge_mlp_fwd_pass_mma(p, r.prec, nblk, c.stat, st)) return rc;
     } else if (E > 0) {
         const size_t lds = fwd_lds_bytes(H1, H2);
         int rc = 0;
-        EMLP_DISPATCH(H2, static size_t granted = 0;
-                      rc = grant_lds(edge_mlp_fwd_kernel<kH2>, lds, granted, "hipFuncSetAttribute(edge_mlp_fwd_kernel)");
-                      if (rc == 0) hipLaunchKernelGGL((edge_mlp_fwd_kernel<kH2>), dim3(nblk), dim3(kBlk), lds, st,
-                                                      (const float *)pq, rowptr, src, tgt, N, E, H1, W2, b2, act2, aggr, bn,
-                                                      agg, win, partial));
+        with_int<16, 32, 64, 128>(H2, [&](auto h2) {
+            constexpr int kH2 = decltype(h2)::value;
+            static size_t granted = 0;
+            rc = grant_lds(edge_mlp_fwd_kernel<kH2>, lds, granted, "hipFuncSetAttribute(edge_mlp_fwd_kernel)");
+            if (rc == 0)
+                hipLaunchKernelGGL((edge_mlp_fwd_kernel<kH2>), dim3(nblk), dim3(kBlk), lds, st, p.pq, p.rowptr, p.src, p.tgt, N, E,
+                                   H1, p.W2, p.b2, p.act2, p.aggr, p.bn, p.agg, p.win, c.stat);
+        });
         if (rc) return rc;
         DMET_LAUNCH_CHECK("edge_mlp_fwd_kernel");
     }
-    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(1), dim3(128), 0, st, (const float *)partial, nblk, E, H2, bn, gamma, beta,
-                       eps, momentum, running_mean, running_var, num_batches_tracked, bnstat);
+    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(1), dim3(128), 0, st, (const float *)c.stat, nblk, E, H2, p.bn, r.fwd.gamma,
+                       r.fwd.beta, r.fwd.eps, r.fwd.momentum, r.fwd.running_mean, r.fwd.running_var,
+                       r.fwd.num_batches_tracked, r.fwd.bnstat);
     DMET_LAUNCH_CHECK("bn_fwd_finalize_kernel");
     const int64_t total = N * H2;
-    hipLaunchKernelGGL(edge_mlp_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float *)agg,
-                       rowptr, (const float *)bnstat, N, H2, aggr, out);
+    hipLaunchKernelGGL(edge_mlp_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float *)p.agg,
+                       p.rowptr, (const float *)r.fwd.bnstat, N, H2, p.aggr, r.fwd.out);
     DMET_LAUNCH_CHECK("edge_mlp_apply_kernel");
     return 0;
 }
 
-int dmet::edge_mlp_bwd(const char *fn, EdgePrec prec, const float *x, int64_t N, int Hin, const int32_t *rowptr,
-                       const int32_t *src, const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
-                       const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr, int bn,
-                       const float *pq, const float *agg, const int32_t *win, const float *bnstat, const float *g_out,
-                       float *gx, float *gpq, float *gW2, float *gb2, float *ggamma, float *gbeta, void *ws,
-                       size_t ws_bytes, dmet_stream_t stream)
+// Backward: split weights -> BatchNorm reduce -> coef -> zero gpq -> edge pass by target, then by source (fp32 or matrix
+// cores) -> gW2 | gb2 from the partials -> gx.
+int edge_mlp_bwd(EdgeMlp &r)
 {
-    if (int rc = check_common(fn, prec, x, N, Hin, rowptr, src, tgt, E, W1, H1, W2, H2, aggr, bn, nullptr, nullptr, ws_bytes, ws, false))
-        return rc;
-    hipStream_t st = as_stream(stream);
+    const char *fn = r.entry;
+    EdgePassArgs &p = r.p;
+    const int64_t N = p.N, E = p.E;
+    const int Hin = r.Hin, H1 = p.H1, H2 = p.H2, bn = p.bn;
+    if (int rc = check_common(r, false)) return rc;
+    hipStream_t st = as_stream(r.stream);
     if (N == 0) {
         // no nodes, no edges: every weight gradient is 0, and it is written like every other call's
-        float *const zs[4] = {gW2, gb2, ggamma, gbeta};
+        float *const zs[4] = {r.bwd.gW2, r.bwd.gb2, r.bwd.ggamma, r.bwd.gbeta};
         const int64_t ns[4] = {(int64_t)H2 * H1, H2, H2, H2};
         for (int q = 0; q < 4; ++q) {
             if (!zs[q]) continue;
@@ -666,71 +694,80 @@ int dmet::edge_mlp_bwd(const char *fn, EdgePrec prec, const float *x, int64_t N,
         }
         return 0;
     }
-    DMET_REQUIRE(pq && agg && bnstat && g_out && gpq && (aggr != 0 || win), "%s: null pointer", fn);
-    DMET_REQUIRE(E == 0 || (srcptr && srcperm), "%s: null by-source index", fn);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255u) & ~(uintptr_t)255u);
-    float *Wc = reinterpret_cast<float *>(base);
-    char *rest = base + align256(sizeof(float) * ((size_t)2 * H1 * Hin + 2 * (size_t)H1));
-    float *partial = reinterpret_cast<float *>(rest);
-    float *bnpart = reinterpret_cast<float *>(rest + align256(sizeof(float) * (size_t)kMaxBlocks * ((size_t)H2 * H1 + H2)));
-    float *coef = bnpart + (size_t)kBnReduceBlocks * 2 * H2;
-    hipLaunchKernelGGL(split_weights_kernel, dim3((H1 * Hin + 255) / 256), dim3(256), 0, st, W1, (const float *)nullptr, Hin,
-                       H1, (float *)nullptr, (float *)nullptr, Wc);
+    DMET_REQUIRE(p.pq && r.bwd.agg && p.bnstat && p.g_out && p.gpq && (p.aggr != 0 || p.cwin), "%s: null pointer", fn);
+    DMET_REQUIRE(E == 0 || (p.srcptr && p.srcperm), "%s: null by-source index", fn);
+    const Workspace c = carve(N, E, Hin, H1, H2, r.ws);
+    p.coef = c.coef;
+    hipLaunchKernelGGL(split_weights_kernel, dim3((H1 * Hin + 255) / 256), dim3(256), 0, st, r.W1, (const float *)nullptr, Hin,
+                       H1, (float *)nullptr, (float *)nullptr, c.w);
     DMET_LAUNCH_CHECK("split_weights_kernel");
     // BatchNorm sums over the nodes; without a BatchNorm coef = (1, 0, 0)
     const int nbr = bn ? (int)(N < kBnReduceBlocks ? N : kBnReduceBlocks) : 0;
     if (nbr > 0) {
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nbr), dim3(256), 0, st, g_out, agg, rowptr, bnstat, N, H2, aggr, bnpart);
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nbr), dim3(256), 0, st, p.g_out, r.bwd.agg, p.rowptr, p.bnstat, N, H2,
+                           p.aggr, c.bnred);
         DMET_LAUNCH_CHECK("bn_bwd_reduce_kernel");
     }
-    hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3(1), dim3(128), 0, st, (const float *)bnpart, nbr, E, H2, bn, bnstat,
-                       bn ? ggamma : nullptr, bn ? gbeta : nullptr, coef);
+    hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3(1), dim3(128), 0, st, (const float *)c.bnred, nbr, E, H2, bn, p.bnstat,
+                       bn ? r.bwd.ggamma : nullptr, bn ? r.bwd.gbeta : nullptr, c.coef);
     DMET_LAUNCH_CHECK("bn_bwd_coef_kernel");
     const int64_t npq = N * 2 * H1;
-    hipLaunchKernelGGL(zero_kernel, dim3((unsigned)((npq + 255) / 256)), dim3(256), 0, st, gpq, npq);
+    hipLaunchKernelGGL(zero_kernel, dim3((unsigned)((npq + 255) / 256)), dim3(256), 0, st, p.gpq, npq);
     DMET_LAUNCH_CHECK("zero_kernel");
     const int nblk = edge_blocks(E);
-    if (E > 0 && prec != EdgePrec::f32) {
-        EdgePassArgs a{};
-        a.pq = pq; a.rowptr = rowptr; a.src = src; a.tgt = tgt; a.N = N; a.E = E; a.H1 = H1; a.H2 = H2;
-        a.W2 = W2; a.b2 = b2; a.act2 = act2; a.aggr = aggr; a.bn = bn; a.srcptr = srcptr; a.srcperm = srcperm;
-        a.g_out = g_out; a.bnstat = bnstat; a.coef = coef; a.cwin = win; a.gpq = gpq;
-        if (int rc = edge_mlp_bwd_pass_mma(a, prec, false, nblk, partial, st)) return rc;
-        if (int rc = edge_mlp_bwd_pass_mma(a, prec, true, nblk, nullptr, st)) return rc;
+    if (E > 0 && r.prec != EdgePrec::f32) {
+        if (int rc = edge_mlp_bwd_pass_mma(p, r.prec, false, nblk, c.gw, st)) return rc;
+        if (int rc = edge_mlp_bwd_pass_mma(p, r.prec, true, nblk, nullptr, st)) return rc;
     } else if (E > 0) {
         const size_t lds = bwd_lds_bytes(H1, H2);
-        int rc = 0;
-        EMLP_DISPATCH(H2, static size_t granted = 0;
-                      rc = grant_lds(edge_mlp_bwd_kernel<kH2, false>, lds, granted, "hipFuncSetAttribute(edge_mlp_bwd_kernel)");
-                      if (rc == 0) hipLaunchKernelGGL((edge_mlp_bwd_kernel<kH2, false>), dim3(nblk), dim3(kBlk), lds, st, pq,
-                                                      rowptr, rowptr, (const int32_t *)nullptr, src, tgt, N, E, H1, W2, b2,
-                                                      act2, aggr, bn, g_out, win, bnstat, (const float *)coef, gpq, partial));
-        if (rc) return rc;
-        DMET_LAUNCH_CHECK("edge_mlp_bwd_kernel (by target)");
-        EMLP_DISPATCH(H2, static size_t granted = 0;
-                      rc = grant_lds(edge_mlp_bwd_kernel<kH2, true>, lds, granted, "hipFuncSetAttribute(edge_mlp_bwd_kernel)");
-                      if (rc == 0) hipLaunchKernelGGL((edge_mlp_bwd_kernel<kH2, true>), dim3(nblk), dim3(kBlk), lds, st, pq,
-                                                      rowptr, srcptr, srcperm, src, tgt, N, E, H1, W2, b2, act2, aggr, bn,
-                                                      g_out, win, bnstat, (const float *)coef, gpq, (float *)nullptr));
-        if (rc) return rc;
-        DMET_LAUNCH_CHECK("edge_mlp_bwd_kernel (by source)");
+        for (const bool by_src : {false, true}) {
+            int rc = 0;
+            with_int<16, 32, 64, 128>(H2, [&](auto h2) {
+                with_flags([&](auto bs) {
+                    constexpr int kH2 = decltype(h2)::value;
+                    static size_t granted = 0;
+                    rc = grant_lds(edge_mlp_bwd_kernel<kH2, bs()>, lds, granted, "hipFuncSetAttribute(edge_mlp_bwd_kernel)");
+                    if (rc == 0)
+                        hipLaunchKernelGGL((edge_mlp_bwd_kernel<kH2, bs()>), dim3(nblk), dim3(kBlk), lds, st, p.pq, p.rowptr,
+                                           bs() ? p.srcptr : p.rowptr, bs() ? p.srcperm : (const int32_t *)nullptr, p.src, p.tgt,
+                                           N, E, H1, p.W2, p.b2, p.act2, p.aggr, bn, p.g_out, p.cwin, p.bnstat, p.coef, p.gpq,
+                                           bs() ? (float *)nullptr : c.gw);
+                }, by_src);
+            });
+            if (rc) return rc;
+            DMET_LAUNCH_CHECK(by_src ? "edge_mlp_bwd_kernel (by source)" : "edge_mlp_bwd_kernel (by target)");
+        }
     }
     if (E > 0) {
         const int n = H2 * H1 + H2;
-        hipLaunchKernelGGL(sum_partials_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const float *)partial, nblk,
-                           (int64_t)n, n, gW2, H2 * H1, gb2);
+        hipLaunchKernelGGL(sum_partials_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const float *)c.gw, nblk,
+                           (int64_t)n, n, r.bwd.gW2, H2 * H1, r.bwd.gb2);
         DMET_LAUNCH_CHECK("sum_partials_kernel");
     } else {
-        if (gW2) hipLaunchKernelGGL(zero_kernel, dim3((H2 * H1 + 255) / 256), dim3(256), 0, st, gW2, (int64_t)H2 * H1);
-        if (gb2) hipLaunchKernelGGL(zero_kernel, dim3(1), dim3(256), 0, st, gb2, (int64_t)H2);
+        if (r.bwd.gW2) hipLaunchKernelGGL(zero_kernel, dim3((H2 * H1 + 255) / 256), dim3(256), 0, st, r.bwd.gW2, (int64_t)H2 * H1);
+        if (r.bwd.gb2) hipLaunchKernelGGL(zero_kernel, dim3(1), dim3(256), 0, st, r.bwd.gb2, (int64_t)H2);
         DMET_LAUNCH_CHECK("zero_kernel");
     }
-    if (gx) {
-        hipLaunchKernelGGL(rows_linear_kernel, dim3((unsigned)((N + 15) / 16)), dim3(256), 0, st, (const float *)gpq, N, 2 * H1,
-                           (const float *)Wc, (const float *)nullptr, Hin, gx);
+    if (r.bwd.gx) {
+        hipLaunchKernelGGL(rows_linear_kernel, dim3((unsigned)((N + 15) / 16)), dim3(256), 0, st, (const float *)p.gpq, N, 2 * H1,
+                           (const float *)c.w, (const float *)nullptr, Hin, r.bwd.gx);
         DMET_LAUNCH_CHECK("rows_linear_kernel (gx)");
     }
     return 0;
+}
+
+}  // namespace
+}  // namespace dmet
+
+using namespace dmet;
+
+// The entry points of the three routes (include/dmet.h has the contract) differ in their name and EdgePrec alone.
+
+extern "C" int dmet_edge_mlp_f32_supported(int Hin, int H1, int H2) { return supported(EdgePrec::f32, Hin, H1, H2); }
+
+extern "C" size_t dmet_edge_mlp_f32_workspace_bytes(int64_t N, int64_t E, int Hin, int H1, int H2)
+{
+    return workspace_bytes(EdgePrec::f32, N, E, Hin, H1, H2);
 }
 
 extern "C" int dmet_edge_mlp_fwd_f32(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
@@ -740,9 +777,11 @@ extern "C" int dmet_edge_mlp_fwd_f32(const float *x, int64_t N, int Hin, const i
                                      int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
                                      float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
 {
-    return edge_mlp_fwd("dmet_edge_mlp_fwd_f32", EdgePrec::f32, x, N, Hin, rowptr, src, tgt, E, W1, b1, H1, W2, b2, H2, act2, aggr,
-                        bn, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq, agg, win,
-                        bnstat, ws, ws_bytes, stream);
+    EdgeMlp r{"dmet_edge_mlp_fwd_f32", EdgePrec::f32, x, Hin, W1, ws, ws_bytes, stream};
+    r.p = pass_args(pq, rowptr, src, tgt, N, E, H1, H2, W2, b2, act2, aggr, bn);
+    r.p.agg = agg; r.p.win = win;
+    r.fwd = {b1, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq, bnstat};
+    return edge_mlp_fwd(r);
 }
 
 extern "C" int dmet_edge_mlp_bwd_f32(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
@@ -752,6 +791,79 @@ extern "C" int dmet_edge_mlp_bwd_f32(const float *x, int64_t N, int Hin, const i
                                      const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
                                      float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
 {
-    return edge_mlp_bwd("dmet_edge_mlp_bwd_f32", EdgePrec::f32, x, N, Hin, rowptr, src, tgt, E, srcptr, srcperm, W1, H1, W2, b2, H2,
-                        act2, aggr, bn, pq, agg, win, bnstat, g_out, gx, gpq, gW2, gb2, ggamma, gbeta, ws, ws_bytes, stream);
+    EdgeMlp r{"dmet_edge_mlp_bwd_f32", EdgePrec::f32, x, Hin, W1, ws, ws_bytes, stream};
+    r.p = pass_args(pq, rowptr, src, tgt, N, E, H1, H2, W2, b2, act2, aggr, bn);
+    r.p.srcptr = srcptr; r.p.srcperm = srcperm; r.p.g_out = g_out; r.p.bnstat = bnstat; r.p.cwin = win; r.p.gpq = gpq;
+    r.bwd = {agg, gx, gW2, gb2, ggamma, gbeta};
+    return edge_mlp_bwd(r);
+}
+
+extern "C" int dmet_edge_mlp_bf16_supported(int Hin, int H1, int H2) { return supported(EdgePrec::bf16, Hin, H1, H2); }
+
+extern "C" size_t dmet_edge_mlp_bf16_workspace_bytes(int64_t N, int64_t E, int Hin, int H1, int H2)
+{
+    return workspace_bytes(EdgePrec::bf16, N, E, Hin, H1, H2);
+}
+
+extern "C" int dmet_edge_mlp_fwd_bf16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+                                      const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1, const float *W2,
+                                      const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
+                                      const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                                      int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
+                                      float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    EdgeMlp r{"dmet_edge_mlp_fwd_bf16", EdgePrec::bf16, x, Hin, W1, ws, ws_bytes, stream};
+    r.p = pass_args(pq, rowptr, src, tgt, N, E, H1, H2, W2, b2, act2, aggr, bn);
+    r.p.agg = agg; r.p.win = win;
+    r.fwd = {b1, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq, bnstat};
+    return edge_mlp_fwd(r);
+}
+
+extern "C" int dmet_edge_mlp_bwd_bf16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+                                      const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
+                                      const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr,
+                                      int bn, const float *pq, const float *agg, const int32_t *win, const float *bnstat,
+                                      const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
+                                      float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    EdgeMlp r{"dmet_edge_mlp_bwd_bf16", EdgePrec::bf16, x, Hin, W1, ws, ws_bytes, stream};
+    r.p = pass_args(pq, rowptr, src, tgt, N, E, H1, H2, W2, b2, act2, aggr, bn);
+    r.p.srcptr = srcptr; r.p.srcperm = srcperm; r.p.g_out = g_out; r.p.bnstat = bnstat; r.p.cwin = win; r.p.gpq = gpq;
+    r.bwd = {agg, gx, gW2, gb2, ggamma, gbeta};
+    return edge_mlp_bwd(r);
+}
+
+extern "C" int dmet_edge_mlp_f16_supported(int Hin, int H1, int H2) { return supported(EdgePrec::f16, Hin, H1, H2); }
+
+extern "C" size_t dmet_edge_mlp_f16_workspace_bytes(int64_t N, int64_t E, int Hin, int H1, int H2)
+{
+    return workspace_bytes(EdgePrec::f16, N, E, Hin, H1, H2);
+}
+
+extern "C" int dmet_edge_mlp_fwd_f16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+                                     const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1, const float *W2,
+                                     const float *b2, int H2, int act2, int aggr, int bn, const float *gamma,
+                                     const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                                     int64_t *num_batches_tracked, float *out, float *pq, float *agg, int32_t *win,
+                                     float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    EdgeMlp r{"dmet_edge_mlp_fwd_f16", EdgePrec::f16, x, Hin, W1, ws, ws_bytes, stream};
+    r.p = pass_args(pq, rowptr, src, tgt, N, E, H1, H2, W2, b2, act2, aggr, bn);
+    r.p.agg = agg; r.p.win = win;
+    r.fwd = {b1, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, pq, bnstat};
+    return edge_mlp_fwd(r);
+}
+
+extern "C" int dmet_edge_mlp_bwd_f16(const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
+                                     const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm,
+                                     const float *W1, int H1, const float *W2, const float *b2, int H2, int act2, int aggr,
+                                     int bn, const float *pq, const float *agg, const int32_t *win, const float *bnstat,
+                                     const float *g_out, float *gx, float *gpq, float *gW2, float *gb2, float *ggamma,
+                                     float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream)
+{
+    EdgeMlp r{"dmet_edge_mlp_bwd_f16", EdgePrec::f16, x, Hin, W1, ws, ws_bytes, stream};
+    r.p = pass_args(pq, rowptr, src, tgt, N, E, H1, H2, W2, b2, act2, aggr, bn);
+    r.p.srcptr = srcptr; r.p.srcperm = srcperm; r.p.g_out = g_out; r.p.bnstat = bnstat; r.p.cwin = win; r.p.gpq = gpq;
+    r.bwd = {agg, gx, gW2, gb2, ggamma, gbeta};
+    return edge_mlp_bwd(r);
 }

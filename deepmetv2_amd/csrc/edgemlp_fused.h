@@ -1,6 +1,11 @@
 // edgemlp_fused.h -- what the fused edge-MLP routes over a grouped edge list share: the fp32 route (edgemlp_f32.hip),
-// which owns the node-level kernels and the host orchestration, and the bf16 / fp16 matrix-core routes
-// (edgemlp_bf16.hip), which bring their own two edge passes.
+// which owns the node-level kernels, every entry point and the host orchestration, and the bf16 / fp16 matrix-core
+// routes (edgemlp_bf16.hip), which bring their own two edge passes.  The device pieces here are parts of the edge passes
+// that do not depend on the tile geometry: the fp32 kernels (EdgeTile<H2>) and the matrix-core ones (kT) hand their T in.
+// The two per-thread folds over a tile's edges (the forward's running aggregate, the backward's owner sums) stay written
+// out in each kernel: behind a function (a struct with inline members, or free functions over references) their
+// loop-carried state is promoted to registers one pass later and the tile loop comes out in another form (DESIGN.md,
+// "K2 host path", has what was tried).
 #pragma once
 
 #include "common.h"
@@ -37,6 +42,45 @@ __device__ __forceinline__ float gy_of(const float *__restrict__ g_out, const in
     return go;
 }
 
+// Backward: ids of a tile's edges into LDS (beyond cnt: 0) -- the grouped position ep of each edge, which by source
+// (BY_SRC) is perm[pt + t], and its target and source.  (The forward's two-line load of tgt / src at pt + t stays in its
+// kernels: through this function its two address computations come out in the other order.)
+template <int T, bool BY_SRC>
+__device__ __forceinline__ void load_tile_ids(const int32_t *src, const int32_t *tgt, const int32_t *perm, int64_t pt, int cnt,
+                                              int32_t *tg, int32_t *sr, int32_t *ep)
+{
+    for (int t = threadIdx.x; t < T; t += blockDim.x) {
+        const int32_t e = t < cnt ? (BY_SRC ? perm[pt + t] : (int32_t)(pt + t)) : 0;
+        ep[t] = e;
+        tg[t] = t < cnt ? tgt[e] : 0;
+        sr[t] = t < cnt ? src[e] : 0;
+    }
+}
+
+// g_z2 of one (edge, channel o) from the re-computed pre-activation z: g_y through the BatchNorm backward (bn == 1: batch
+// terms, bn == 2: the scale alone) and ELU'.  The constants are channel o's.
+template <int H2>
+struct Gz2 {
+    float ka, k1, k2, bmean, binv;
+    const int32_t *winsel;     // max: the winners in use (those of the min where the BatchNorm scale is < 0)
+
+    __device__ __forceinline__ Gz2(const float *coef, const float *bnstat, const int32_t *win, int64_t N, int aggr, int bn, int o)
+        : ka(coef[o]), k1(coef[H2 + o]), k2(coef[2 * H2 + o]), bmean(bnstat[2 * H2 + o]), binv(bnstat[3 * H2 + o]),
+          winsel(win + ((aggr == 0 && bn != 0 && ka < 0.0f) ? N * H2 : 0)) {}
+
+    // tg[t], ep[t]: the edge's target and grouped position, read from the tile's LDS ids after the ELU as the kernels did
+    __device__ __forceinline__ float operator()(float z, const float *g_out, const int32_t *rowptr, int act2, int aggr, int bn,
+                                                const int32_t *tg, const int32_t *ep, int t, int o) const
+    {
+        const float m = act2 ? elu1f(z) : z;
+        const float gy = gy_of(g_out, rowptr, winsel, aggr, tg[t], H2, o, ep[t]);
+        float gm = gy;
+        if (bn == 1) gm = ka * (gy - k1 - (m - bmean) * binv * k2);
+        else if (bn == 2) gm = ka * gy;
+        return act2 ? gm * (z > 0.0f ? 1.0f : m + 1.0f) : gm;
+    }
+};
+
 inline int edge_blocks(int64_t E)
 {
     int64_t nb = (E + 2047) / 2048;
@@ -57,7 +101,8 @@ int grant_lds(K kernel, size_t lds, size_t &granted, const char *what)
 
 }  // namespace
 
-// Arguments of one edge pass; the forward pass reads the first block, the backward passes all of it.
+// Arguments of one edge pass, filled once by the entry point (coef: by the backward, from its workspace); the forward
+// pass reads the first block, the backward passes all of it.
 struct EdgePassArgs {
     const float *pq;
     const int32_t *rowptr, *src, *tgt;
@@ -81,17 +126,5 @@ enum class EdgePrec { f32, bf16, f16 };
 // matrix-core edge passes (edgemlp_bf16.hip, prec bf16 or f16): launch on `st` over nblk workgroups; 0 or a dmet error code
 int edge_mlp_fwd_pass_mma(const EdgePassArgs &a, EdgePrec prec, int nblk, float *partial, hipStream_t st);
 int edge_mlp_bwd_pass_mma(const EdgePassArgs &a, EdgePrec prec, bool by_src, int nblk, float *partial, hipStream_t st);
-
-// host orchestration of every route (edgemlp_f32.hip): the entry points of include/dmet.h with the route chosen by prec
-int edge_mlp_fwd(const char *fn, EdgePrec prec, const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
-                 const int32_t *tgt, int64_t E, const float *W1, const float *b1, int H1, const float *W2, const float *b2,
-                 int H2, int act2, int aggr, int bn, const float *gamma, const float *beta, float eps, float momentum,
-                 float *running_mean, float *running_var, int64_t *num_batches_tracked, float *out, float *pq, float *agg,
-                 int32_t *win, float *bnstat, void *ws, size_t ws_bytes, dmet_stream_t stream);
-int edge_mlp_bwd(const char *fn, EdgePrec prec, const float *x, int64_t N, int Hin, const int32_t *rowptr, const int32_t *src,
-                 const int32_t *tgt, int64_t E, const int32_t *srcptr, const int32_t *srcperm, const float *W1, int H1,
-                 const float *W2, const float *b2, int H2, int act2, int aggr, int bn, const float *pq, const float *agg,
-                 const int32_t *win, const float *bnstat, const float *g_out, float *gx, float *gpq, float *gW2,
-                 float *gb2, float *ggamma, float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream);
 
 }  // namespace dmet

@@ -368,7 +368,7 @@ int dmet_edge_mlp_bwd_f32(const float *x, int64_t N, int Hin, const int32_t *row
                           const float *b2, int H2, int act2, int aggr, int bn, const float *pq, const float *agg,
                           const int32_t *win, const float *bnstat, const float *g_out, float *gx, float *gpq, float *gW2,
                           float *gb2, float *ggamma, float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream);
-/* --- bf16 matrix-core edge MLP over any grouped edge list (csrc/edgemlp_bf16.hip) ---------------------------------------
+/* --- bf16 matrix-core edge MLP over any grouped edge list (entries csrc/edgemlp_f32.hip, kernels csrc/edgemlp_bf16.hip) --
  * The same layer, arguments, state and outputs as dmet_edge_mlp_fwd_f32 / dmet_edge_mlp_bwd_f32 above (it replaces the
  * same reference lines, model/dynamic_reduction_network.py:59-73,86-87,94-95, as the DRN runs them under bf16
  * autocast), with the per-edge products on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16):
@@ -392,7 +392,7 @@ int dmet_edge_mlp_bwd_bf16(const float *x, int64_t N, int Hin, const int32_t *ro
                            const float *b2, int H2, int act2, int aggr, int bn, const float *pq, const float *agg,
                            const int32_t *win, const float *bnstat, const float *g_out, float *gx, float *gpq, float *gW2,
                            float *gb2, float *ggamma, float *gbeta, void *ws, size_t ws_bytes, dmet_stream_t stream);
-/* --- fp16 matrix-core edge MLP over any grouped edge list (csrc/edgemlp_bf16.hip) ---------------------------------------
+/* --- fp16 matrix-core edge MLP over any grouped edge list (entries csrc/edgemlp_f32.hip, kernels csrc/edgemlp_bf16.hip) --
  * The bf16 entries above with fp16 in place of bf16 (v_mfma_f32_16x16x32_f16; the route of the DRN under fp16 autocast,
  * torch.autocast("cuda") without a dtype, with torch.amp.GradScaler).  Same arguments, argument checks, widths,
  * workspace and state; the same kernels, instantiated for the other operand type.

@@ -48,16 +48,16 @@ def emulate(nn, x, ei, aggr, flow):
     return out, m
 
 
-def kernel_winners(nn, x, ei, flow):
+def kernel_winners(nn, x, ei, flow, route="bf16"):
     """(grouped edge index [2, E], winners [N, H2]): the winning grouped edge position of each target's maximum after
-    the norm, as the kernel's forward state records it (-1: no in-edge).  The float64 composition takes these."""
+    the norm, as the forward state of the route's kernel records it (-1: no in-edge).  The float64 composition takes these."""
     from deepmetv2_amd import _native
     from deepmetv2_amd.conv import _as_mlp2
     from deepmetv2_amd.graph import edge_list_from_edge_index
     l1, l2, act2, bn = _as_mlp2(copy.deepcopy(nn).to(x.device))
     edges = edge_list_from_edge_index(ei, x.shape[0], flow)
     mode = 0 if bn is None else (1 if bn.training else 2)
-    _out, (_pq, _agg, win, bnstat) = _native.edge_mlp_fwd_bf16(
+    _out, (_pq, _agg, win, bnstat) = getattr(_native, f"edge_mlp_fwd_{route}")(
         x, edges.rowptr, edges.src, edges.tgt, l1.weight, l1.bias, l2.weight, l2.bias, act2, "max", mode,
         bn.weight if bn is not None else None, bn.bias if bn is not None else None, 1e-5, 0.1,
         bn.running_mean if mode == 2 else None, bn.running_var if mode == 2 else None, None)
@@ -85,3 +85,15 @@ def ref64(nn, x, ei, aggr, flow, g, win=None):
     out.backward(g.double())
     grads = {n: p.grad.detach() for n, p in nn64.named_parameters() if p.grad is not None}
     return out.detach(), xx.grad.detach(), grads
+
+
+def max64(nn, x, ei, flow):
+    """float64 maximum per target of the same layer's messages, by scatter amax: no winners taken from any kernel"""
+    nn64 = copy.deepcopy(nn).double().to(x.device)
+    tgt, src = ends(ei, flow)
+    with torch.no_grad():
+        xx = x.detach().double()
+        m = nn64(torch.cat([xx[tgt], xx[src] - xx[tgt]], dim=1))
+        idx = tgt.view(-1, 1).expand(-1, m.shape[1])
+        return torch.zeros((x.shape[0], m.shape[1]), dtype=m.dtype, device=m.device).scatter_reduce(0, idx, m, "amax",
+                                                                                                     include_self=False)
