@@ -61,6 +61,17 @@ def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """`t` itself when its storage starts on a 16-byte boundary, else a fresh (aligned) copy.  The kernels read rows and
+    per-channel vectors as float4; a contiguous tensor that is a view into somebody else's flat buffer may start anywhere."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def _f32a(t: torch.Tensor, name: str) -> torch.Tensor:
+    """_f32c, then _aligned16: what an entry asks of an operand its kernel reads as float4."""
+    return _aligned16(_f32c(t, name))
+
+
 def _ws(nbytes: int, dev: torch.device) -> torch.Tensor:
     return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=dev)
 
@@ -1352,7 +1363,7 @@ def encode_bwd(x_cont: torch.Tensor, x_cat: torch.Tensor, params, h: torch.Tenso
     L = _lib.load()
     x, xc = _encode_x(x_cont, x_cat)
     ps = _encode_params(params, dev)
-    h = _f32c(h, "h"); g_h = _f32c(g_h, "g_h")
+    h = _f32a(h, "h"); g_h = _f32a(g_h, "g_h")
     N = x.shape[0]
     grads = [torch.empty_like(t) for t in ps]
     if N == 0:
@@ -1378,6 +1389,10 @@ def encode_bn_bwd(x_cont: torch.Tensor, x_cat: torch.Tensor, params, h: torch.Te
     h = _f32c(h, "h"); g_y = _f32c(g_y, "g_y"); gamma = _f32c(gamma.detach(), "gamma")
     N, H = h.shape
     if N == 0 or H != 32:
+        return None
+    if any(t.data_ptr() % 16 for t in (h, g_y, gamma, mean, invstd)):
+        # dmet_encode_bn_bwd_f32 would decline these, and dmet_bn_bwd_stats_f32 before it requires h, g_y, mean and
+        # invstd aligned (it would fail the call): the caller's separate steps copy what is unaligned
         return None
     grads = [torch.empty_like(t) for t in ps]
     st = torch.empty((4, H), dtype=torch.float32, device=dev)     # g_gamma, g_beta, mean_g, mean_gx
@@ -1407,16 +1422,16 @@ def bn_fwd(x: torch.Tensor, residual: Optional[torch.Tensor], gamma: torch.Tenso
     num_batches_tracked (int64 scalar on the device, training mode only) incremented by the statistics kernel."""
     dev = _require_device(x, gamma, beta)
     L = _lib.load()
-    x = _f32c(x, "x")
+    x = _f32a(x, "x")
     N, H = x.shape
     if residual is not None:
-        residual = _f32c(residual, "residual")
+        residual = _f32a(residual, "residual")
         if residual.shape != x.shape:
             raise ValueError("bn_fwd: residual must have the shape of x")
     for t in (running_mean, running_var):
         if t is not None and (not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != H):
             raise ValueError("bn_fwd: running statistics must be contiguous float32 [H]")
-    gamma = _f32c(gamma, "gamma"); beta = _f32c(beta, "beta")
+    gamma = _f32a(gamma, "gamma"); beta = _f32a(beta, "beta")
     y = torch.empty_like(x)
     stats = torch.empty((2, H), dtype=torch.float32, device=dev)
     with _on(dev):
@@ -1442,7 +1457,7 @@ def bn_stats(x: torch.Tensor, eps: float, momentum: float, running_mean: Optiona
     num_batches_tracked updated like bn_fwd(training=True).  The transform is applied elsewhere (bn_knn_local_dense)."""
     dev = _require_device(x)
     L = _lib.load()
-    x = _f32c(x, "x")
+    x = _f32a(x, "x")
     N, H = x.shape
     stats = torch.empty((2, H), dtype=torch.float32, device=dev)
     with _on(dev):
@@ -1456,11 +1471,6 @@ def bn_stats(x: torch.Tensor, eps: float, momentum: float, running_mean: Optiona
     return stats[0], stats[1]
 
 
-def _aligned16(t: torch.Tensor) -> torch.Tensor:
-    """`t` itself when its storage starts on a 16-byte boundary, else a fresh (aligned) copy."""
-    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
-
-
 def bn_apply(x: torch.Tensor, residual: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
              mean: torch.Tensor, invstd: torch.Tensor) -> torch.Tensor:
     """y = (x - mean) * (gamma * invstd) + beta (+ residual): the transform of bn_fwd with the statistics given
@@ -1468,13 +1478,13 @@ def bn_apply(x: torch.Tensor, residual: Optional[torch.Tensor], gamma: torch.Ten
     16-byte boundary (views into somebody else's flat buffer) are copied first."""
     dev = _require_device(x, gamma, beta, mean, invstd)
     L = _lib.load()
-    x = _aligned16(_f32c(x, "x"))
+    x = _f32a(x, "x")
     N, H = x.shape
     if residual is not None:
-        residual = _aligned16(_f32c(residual, "residual"))
+        residual = _f32a(residual, "residual")
         if residual.shape != x.shape:
             raise ValueError("bn_apply: residual must have the shape of x")
-    vec = [_aligned16(_f32c(t, n)) for t, n in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd"))]
+    vec = [_f32a(t, n) for t, n in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd"))]
     if any(v.numel() != H for v in vec):
         raise ValueError("bn_apply: gamma / beta / mean / invstd must have H elements")
     y = torch.empty_like(x)
@@ -1557,7 +1567,8 @@ def bn_bwd(x: torch.Tensor, g_y: torch.Tensor, gamma: torch.Tensor, save_mean: t
     """(g_x, g_gamma, g_beta) of the training-mode BatchNorm1d."""
     dev = _require_device(x, g_y, gamma)
     L = _lib.load()
-    x = _f32c(x, "x"); g_y = _f32c(g_y, "g_y"); gamma = _f32c(gamma, "gamma")
+    x = _f32a(x, "x"); g_y = _f32a(g_y, "g_y"); gamma = _f32a(gamma, "gamma")
+    save_mean = _f32a(save_mean, "save_mean"); save_invstd = _f32a(save_invstd, "save_invstd")
     N, H = x.shape
     g_x = torch.empty_like(x)
     gg = torch.empty((2, H), dtype=torch.float32, device=dev)
@@ -1667,7 +1678,7 @@ def head_fwd(emb: torch.Tensor, params) -> torch.Tensor:
     """sigmoid(W2 . ELU(W1 . emb + b1) + b2) per node: [N] from emb[N,32]."""
     dev = _require_device(emb)
     L = _lib.load()
-    emb = _f32c(emb, "emb")
+    emb = _f32a(emb, "emb")
     if emb.dim() != 2 or emb.shape[1] != 32:
         raise ValueError("head: emb must be [N,32]")
     ps = _head_params(params, dev)
@@ -1709,7 +1720,8 @@ def head_bwd(emb: torch.Tensor, params, out: torch.Tensor, g_out: torch.Tensor):
     """(g_emb, gW1, gb1, gW2, gb2) of head_fwd."""
     dev = _require_device(emb, out, g_out)
     L = _lib.load()
-    emb = _f32c(emb, "emb"); out = _f32c(out, "out"); g_out = _f32c(g_out, "g_out")
+    # emb rows are read as float4 (copied when unaligned); out and g_out are read one element per node: any 4-byte place
+    emb = _f32a(emb, "emb"); out = _f32c(out, "out"); g_out = _f32c(g_out, "g_out")
     ps = _head_params(params, dev)
     N = emb.shape[0]
     g_emb = torch.empty_like(emb)
