@@ -298,6 +298,17 @@ __device__ __forceinline__ int dpp_swap_pair(int v)
     return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true);   // quad_perm: lane ^ 1
 }
 
+// Does a table row hold a node of its event [lo, lo + n)?  (-1 / 0xFFFF and ids outside the event are empty slots: the LDS
+// kernels map them to the -inf row.)  The cold half of R3 in the fused kernel: called only for rows without a finite maximum.
+template <typename ID>
+__device__ __forceinline__ bool row_has_neighbour(const ID *__restrict__ row, int k, int lo, int n)
+{
+    bool any = false;
+#pragma unroll 1
+    for (int s = 0; s < k; ++s) any = any || (unsigned)((int)row[s] - lo) < (unsigned)n;
+    return any;
+}
+
 template <int K4>
 __device__ __forceinline__ void load_ids_pair(int4 (&ids)[K4], const int4 *__restrict__ row4, int half)
 {
@@ -377,9 +388,11 @@ __device__ __forceinline__ void gather_max_lds_segment(
             const int64_t node = lo + r;
             float4 best = make_float4(ninf, ninf, ninf, ninf);
             int a0 = 255, a1 = 255, a2 = 255, a3 = 255;
+            bool any = false;       // R3 goes by the ids: a neighbour whose values are -inf or NaN is still a neighbour
             for (int s = 0; s < k; ++s) {
                 const int j = nbr[node * k + s];
                 if (j < 0) continue;
+                any = true;
                 const float4 v = Q4[pq_at(j)];
                 if (v.x > best.x) { best.x = v.x; a0 = s; }
                 if (v.y > best.y) { best.y = v.y; a1 = s; }
@@ -387,7 +400,7 @@ __device__ __forceinline__ void gather_max_lds_segment(
                 if (v.w > best.w) { best.w = v.w; a3 = s; }
             }
             float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (a0 != 255) {
+            if (any) {
                 const float4 p = P4[pq_at(node)];
                 o = make_float4(p.x + best.x, p.y + best.y, p.z + best.z, p.w + best.w);
             }
@@ -543,6 +556,10 @@ __device__ __forceinline__ void gather_max_lds_segment(
             }
         }
         }
+        // R3 by the VALUES of the lane's first channel here, where every other gather-max kernel (and this kernel's own L2
+        // path above) goes by the ids: the two differ only for a row whose candidates are all -inf / NaN in that channel, which
+        // include/dmet.h leaves unspecified for the events this kernel keeps in LDS.  Both ways of taking it from the ids were
+        // timed and cost this loop more than the parent's run-to-run spread (profiles/NOTES.md, "K3 empty-row rule").
         const bool any = WITH_ARG ? (a0 != 255) : (bx > ninf);
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
         if (any) o = make_float4(p.x + bx, p.y + by, p.z + bz, p.w + bw);
@@ -690,10 +707,10 @@ __global__ __launch_bounds__(kLdsGatherThreads) void gather_max_lds_counted_kern
         int a0 = kNone, a1 = kNone, a2 = kNone, a3 = kNone;
         bool any = false;
         if (LOC16) {
-            any = m > 0;
             const uint16_t *r16 = nbr16 + node * stride16;
             for (int s0 = 0; s0 < m; s0 += 8) {
                 const uint4 w = *reinterpret_cast<const uint4 *>(r16 + s0);
+                any = any || (w.x & w.y & w.z & w.w) != 0xFFFFFFFFu;     // R3 by the ids: eight 0xFFFF are eight empty slots
                 const unsigned jl[8] = {w.x & 0xFFFFu, w.x >> 16, w.y & 0xFFFFu, w.y >> 16,
                                         w.z & 0xFFFFu, w.z >> 16, w.w & 0xFFFFu, w.w >> 16};   // 0xFFFF = none
                 float4 v[8];
@@ -830,10 +847,12 @@ __global__ __launch_bounds__(kLdsGatherThreads) void edgeconv_fused_lds_kernel(
             const int64_t node = lo + r;
             float best[4] = {ninf, ninf, ninf, ninf};
             int a[4] = {255, 255, 255, 255};
+            bool any = false;       // R3 goes by the ids
 #pragma unroll 1
             for (int s = 0; s < k; ++s) {
                 const int j = nbr[node * k + s];
                 if (j < 0) continue;
+                any = true;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const int o = sl * 8 + half * 4 + c;
@@ -847,7 +866,6 @@ __global__ __launch_bounds__(kLdsGatherThreads) void edgeconv_fused_lds_kernel(
                     if (acc > best[c]) { best[c] = acc; a[c] = s; }
                 }
             }
-            const bool any = a[0] != 255;
             reinterpret_cast<float4 *>(out)[node * h4 + col4] =
                 any ? make_float4(best[0], best[1], best[2], best[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
             if (WITH_ARG)
@@ -961,7 +979,8 @@ __global__ __launch_bounds__(kLdsGatherThreads) void edgeconv_fused_lds_kernel(
                 }
             }
         }
-        const bool any = WITH_ARG ? (a0 != 255) : (bx > ninf);
+        bool any = WITH_ARG ? (a0 != 255) : (bx > ninf);      // R3 by the ids, as in the L2 kernels
+        if (!any) any = row_has_neighbour(nbr + node * k, k, lo, n);
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
         if (any) o = make_float4(p.x + bx, p.y + by, p.z + bz, p.w + bw2);
         reinterpret_cast<float4 *>(out)[node * h4 + col4] = o;

@@ -217,7 +217,24 @@ int dmet_edgeconv_linear_max_fwd_f32(const float *x, const int32_t *nbr, const i
 int dmet_edgeconv_fused_lds_f32(const float *x, const int32_t *nbr, const int64_t *ptr, int B, int64_t N, int k,
                                 int Hin, int Hout, const float *W, const float *b, float *out, uint8_t *arg,
                                 dmet_stream_t stream);
-/* The two steps individually (step 2 is "the gather + scatter_max kernel" of BASELINE.json). */
+/* The two steps individually (step 2 is "the gather + scatter_max kernel" of BASELINE.json).
+ * The contract of step 2, shared by every dmet_gather_max_* forward entry below and by dmet_edgeconv_fused_lds_f32 (stated
+ * exactly by gather_max_ref in tests/gather_max_reference.py, to which all of them are held bit for bit):
+ *   - row i examines its slots in ascending order (the first min(k, cnt[i]) of them where a cnt is given); a slot holding
+ *     -1 (0xFFFF in uint16 rows) is empty and may stand anywhere in the row;
+ *   - per channel the running maximum starts at -inf and is replaced on strict `>` only: the lowest slot wins exact ties
+ *     (R4), +0 and -0 are equal, +inf wins, NaN and -inf candidates never win;
+ *   - whether a row has neighbours is decided by its IDS, never by the values: a row with at least one non-empty slot gives
+ *     out = P + max in every channel -- P + (-inf) = -inf, with arg 255, in a channel whose candidates are all -inf or NaN
+ *     (an overflowed fp16 activation) while the other channels keep their maxima and winners;
+ *   - a row without one gives out = 0 and arg = 255 (0xFFFF as a winner id) in every channel, whatever P holds (R3).
+ * One deviation: for the events that gather_max_lds_kernel keeps in its LDS image (dmet_gather_max_lds_f32, _lds16_f32,
+ * _lds_sliced_f32, _lds_sliced_cap_f32 and _mixed_f32; events of at most 5119 nodes, 2559 under a max_nodes hint) the result
+ * is unspecified where every candidate of a channel is non-finite: there the kernel takes a finite maximum in the first of
+ * a lane's four channels for "has neighbours", so a row whose candidates are all -inf / NaN in a channel c % 4 == 0 comes
+ * out as 0 / 255 in those four channels.  Larger events in the same calls, and the L2, counted, winner-id and fused entries,
+ * follow the id rule.  (Two ways of deciding it from the ids were measured at +4 % and +6 % on that kernel:
+ * profiles/NOTES.md, "K3 empty-row rule".) */
 int dmet_node_linear_split_f32(const float *x, int64_t N, int Hin, int Hout, const float *W,
                                const float *b, float *P, float *Q, dmet_stream_t stream);
 int dmet_gather_max_f32(const float *P, const float *Q, const int32_t *nbr, const int64_t *ptr, int B,
