@@ -9,6 +9,7 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import graclus                        # torch_cluster
     from deepmetv2_amd import normalized_cut, max_pool, max_pool_x, global_max_pool   # torch_geometric
     from deepmetv2_amd import GravNetConv                    # torch_geometric.nn
+    from deepmetv2_amd import TransformerConv                # torch_geometric.nn (attention_aggregate: utils.softmax + sum)
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -25,6 +26,7 @@ from .pool import (avg_pool, avg_pool_x, global_add_pool, global_max_pool, globa
                    max_pool_x, normalized_cut, normalized_cut_2d)
 from .drn import DynamicReductionNetwork
 from .gravnet import GravNetConv, gravnet_aggregate
+from .attention import TransformerConv, attention_aggregate
 
 __all__ = [
     "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "knn_xy_table", "radius", "radius_graph", "radius_table",
@@ -33,6 +35,6 @@ __all__ = [
     "u_perp_par_loss", "to_undirected", "raise_deferred_errors", "accelerate", "build_async", "GraphFuture", "Batch", "EventLoader", "DeviceLoader", "collate", "events_from_padded",
     "graclus", "normalized_cut", "normalized_cut_2d", "max_pool", "max_pool_x", "avg_pool", "avg_pool_x",
     "global_max_pool", "global_mean_pool", "global_add_pool", "DynamicReductionNetwork",
-    "GravNetConv", "gravnet_aggregate",
+    "GravNetConv", "gravnet_aggregate", "TransformerConv", "attention_aggregate",
 ]
 __version__ = "0.1.0"

@@ -99,6 +99,10 @@ SIGNATURES = {
     "dmet_gravnet_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dmet_gravnet_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp,
                                   _vp]),
+    "dmet_attention_supported": (_i, [_i, _i]),
+    "dmet_attention_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dmet_attention_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i,
+                                    _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmet_reverse_index_workspace_bytes": (_sz, [_i64, _i64]),
     "dmet_reverse_index": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dmet_edge_features_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),

@@ -1089,6 +1089,117 @@ def gravnet_bwd(g_out: torch.Tensor, h: torch.Tensor, s_src: torch.Tensor, s_tgt
     return g_h, g_s_src, g_s_tgt
 
 
+ATTENTION_MAX_C = 64     # channels per head (include/dmet.h, "Attention aggregation")
+ATTENTION_MAX_H = 16     # heads
+ATTENTION_MAX_HC = 256   # heads * channels
+ATTENTION_MAX_K = GRAVNET_MAX_K   # DMET_MAX_K: the width of a table, as for GravNet
+
+
+def attention_check_shapes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_targets: int, num_sources: int,
+                           width: Optional[int] = None) -> None:
+    """The argument errors of the attention entries, raised from shapes alone (before any device is asked for).  The graph
+    has num_targets rows over num_sources sources; width: the table form's k (None: an edge list)."""
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise ValueError(f"attention: q [Nt, H, C], k and v [Ns, H, C] must be 3-D, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    H, C = q.shape[1], q.shape[2]
+    if not 1 <= C <= ATTENTION_MAX_C:
+        raise ValueError(f"attention: C={C} channels per head, supported 1..{ATTENTION_MAX_C}")
+    if not 1 <= H <= ATTENTION_MAX_H:
+        raise ValueError(f"attention: H={H} heads, supported 1..{ATTENTION_MAX_H}")
+    if H * C > ATTENTION_MAX_HC:
+        raise ValueError(f"attention: H*C={H * C}, supported up to {ATTENTION_MAX_HC}")
+    if width is not None and not 1 <= width <= ATTENTION_MAX_K:
+        raise ValueError(f"attention: k={width}, supported 1..{ATTENTION_MAX_K}")
+    if tuple(k.shape[1:]) != (H, C) or tuple(v.shape[1:]) != (H, C):
+        raise ValueError(f"attention: q has {H} heads of {C} channels, k {tuple(k.shape[1:])}, v {tuple(v.shape[1:])}")
+    if k.shape[0] != v.shape[0]:
+        raise ValueError(f"attention: k has {k.shape[0]} rows, v has {v.shape[0]}")
+    if q.shape[0] != num_targets:
+        raise ValueError(f"attention: the graph has {num_targets} target rows, q has {q.shape[0]}")
+    if k.shape[0] != num_sources:
+        raise ValueError(f"attention: the graph indexes {num_sources} sources, k and v have {k.shape[0]} rows")
+
+
+def _attention_graph(idx: torch.Tensor, rowptr: Optional[torch.Tensor], Nt: int):
+    """(idx, rowptr, E, width, positions) of a table (rowptr None, idx = nbr[Nt, k]) or a list (idx = src[E])."""
+    idx = _i32c(idx, "nbr" if rowptr is None else "src")
+    if rowptr is None:
+        if idx.dim() != 2 or idx.shape[0] != Nt:
+            raise ValueError(f"attention: nbr must be [{Nt}, k], got {tuple(idx.shape)}")
+        return idx, None, 0, int(idx.shape[1]), Nt * int(idx.shape[1])
+    rowptr = _i32c(rowptr, "rowptr")
+    if idx.dim() != 1 or rowptr.numel() != Nt + 1:
+        raise ValueError(f"attention: src must be [E] and rowptr [{Nt + 1}], got {tuple(idx.shape)} and {tuple(rowptr.shape)}")
+    return idx, rowptr, int(idx.numel()), 0, int(idx.numel())
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx: torch.Tensor, rowptr: Optional[torch.Tensor] = None,
+                  want_alpha: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """(out[Nt, H, C], lse[Nt, H], alpha[Nt*k or E, H] or None) of softmax attention over a table (idx = nbr[Nt, k],
+    rowptr None) or a grouped edge list (idx = src[E], rowptr[Nt+1]); see include/dmet.h, dmet_attention_fwd_f32."""
+    Nt, Ns = q.shape[0], k.shape[0]
+    attention_check_shapes(q, k, v, Nt, Ns, idx.shape[1] if rowptr is None and idx.dim() == 2 else None)
+    dev = _require_device(q, k, v, idx, rowptr)
+    L = _lib.load()
+    q = _f32c(q, "q"); k = _f32c(k, "k"); v = _f32c(v, "v")
+    idx, rowptr, E, width, M = _attention_graph(idx, rowptr, Nt)
+    _n, H, C = q.shape
+    out = torch.empty((Nt, H, C), dtype=torch.float32, device=dev)
+    lse = torch.empty((Nt, H), dtype=torch.float32, device=dev)
+    alpha = torch.empty((M, H), dtype=torch.float32, device=dev) if want_alpha else None
+    _t = timer.record('attention_fwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_attention_fwd_f32(q.data_ptr(), _ptr(k), _ptr(v), _ptr(idx), None if rowptr is None else
+                                            rowptr.data_ptr(), Nt, Ns, E, width, H, C, out.data_ptr(), lse.data_ptr(),
+                                            _ptr(alpha), _stream(dev)), "dmet_attention_fwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, lse, alpha
+
+
+def attention_bwd(g_out: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor,
+                  lse: torch.Tensor, idx: torch.Tensor, rev_ptr: torch.Tensor, rev_pos: torch.Tensor,
+                  rowptr: Optional[torch.Tensor] = None,
+                  tgt: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(g_q[Nt, H, C], g_k[Ns, H, C], g_v[Ns, H, C]) of attention_fwd; (rev_ptr, rev_pos) = the graph's by-source index
+    (table.reverse() / EdgeList.by_source()), tgt = EdgeList.tgt for a list.  See include/dmet.h, dmet_attention_bwd_f32."""
+    Nt, Ns = q.shape[0], k.shape[0]
+    attention_check_shapes(q, k, v, Nt, Ns, idx.shape[1] if rowptr is None and idx.dim() == 2 else None)
+    dev = _require_device(g_out, q, k, v, out, lse, idx, rev_ptr, rev_pos, rowptr, tgt)
+    L = _lib.load()
+    q = _f32c(q, "q"); k = _f32c(k, "k"); v = _f32c(v, "v"); out = _f32c(out, "out"); lse = _f32c(lse, "lse")
+    g_out = _f32c(g_out, "g_out")
+    idx, rowptr, E, width, M = _attention_graph(idx, rowptr, Nt)
+    rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_pos = _i32c(rev_pos, "rev_pos")
+    _n, H, C = q.shape
+    if g_out.shape != (Nt, H, C) or out.shape != (Nt, H, C) or lse.shape != (Nt, H):
+        raise ValueError(f"attention_bwd: g_out and out must be [{Nt}, {H}, {C}] and lse [{Nt}, {H}]")
+    if rev_ptr.numel() != Ns + 1 or rev_pos.numel() < M:
+        raise ValueError(f"attention_bwd: the by-source index does not fit {M} positions over {Ns} sources")
+    if rowptr is not None:
+        if tgt is None or tgt.numel() != E:
+            raise ValueError(f"attention_bwd: an edge list needs tgt [{E}]")
+        tgt = _i32c(tgt, "tgt")
+    g_q = torch.empty((Nt, H, C), dtype=torch.float32, device=dev)
+    g_kv = torch.empty((2, Ns, H, C), dtype=torch.float32, device=dev)
+    work = torch.empty((2, M, H), dtype=torch.float32, device=dev)     # alpha and g_score: the per-edge buffers, 8 B per head
+    _t = timer.record('attention_bwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_attention_bwd_f32(q.data_ptr(), _ptr(k), _ptr(v), out.data_ptr(), lse.data_ptr(), g_out.data_ptr(),
+                                            _ptr(idx), None if rowptr is None else rowptr.data_ptr(), _ptr(tgt),
+                                            rev_ptr.data_ptr(), rev_pos.data_ptr(), Nt, Ns, E, width, H, C,
+                                            _ptr(work[0]), _ptr(work[1]), g_q.data_ptr(), _ptr(g_kv[0]), _ptr(g_kv[1]),
+                                            _stream(dev)), "dmet_attention_bwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return g_q, g_kv[0], g_kv[1]
+
+
 def reverse_index(keys: torch.Tensor, num_keys: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Stable sort of positions by int32 key: rev_ptr[num_keys+1] int32, rev_pos[M] int32 (see include/dmet.h)."""
     dev = _require_device(keys)

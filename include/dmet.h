@@ -539,6 +539,51 @@ int dmet_gravnet_bwd_f32(const float *s_tgt, const float *s_src, const float *h,
                          const int32_t *rev_ptr, const int32_t *rev_pos, const uint8_t *arg, const int32_t *cnt,
                          const float *g_out, int64_t Nt, int64_t Ns, int k, int S, int P, float *g_d, float *g_s_tgt,
                          float *g_s_src, float *g_h, dmet_stream_t stream);
+/* ---- Attention aggregation ------------------------------------------------------------------------------------
+ * replaces torch_geometric.nn.TransformerConv.message (alpha = (query_i * key_j).sum(-1) / sqrt(out_channels),
+ * alpha = softmax(alpha, index, ptr, size_i), out = value_j * alpha.view(-1, heads, 1)), torch_geometric.utils.softmax
+ * (scatter max, exp, scatter sum, divide) and the 'add' aggregation, with their autograd graph: three [E, H*C] gathers,
+ * two scatters for the softmax and one for the sum, all kept for the backward (csrc/attention.hip).
+ * Inputs: q[Nt, H, C] of the targets, k[Ns, H, C] and v[Ns, H, C] of the sources, fp32, contiguous.  The graph in one of
+ * two forms:
+ *   table (rowptr == NULL): idx = nbr[Nt, width] int32, -1 or any id outside [0, Ns) = an empty slot, anywhere in a row;
+ *     position pos = i*width + t belongs to target i; 1 <= width <= DMET_MAX_K; E is ignored.
+ *   list  (rowptr != NULL): the grouped edge list of the K2 / K3 section below: rowptr[Nt+1], idx = src[E], tgt[E] int32,
+ *     any in-degree; width is ignored; src / tgt may be NULL when E == 0.
+ * 1 <= C <= 64, 1 <= H <= 16, H*C <= 256: dmet_attention_supported(H, C) returns 1 for these and 0 otherwise.
+ * dmet_attention_fwd_f32, for target i, head h and every valid entry e of row i, j = src(e):
+ *   score_e = (sum_c q[i,h,c] k[j,h,c]) / sqrtf(C)     a division, as PyG writes it
+ *   m = max_e score_e,  l = sum_e expf(score_e - m),  alpha_e = expf(score_e - m) / l
+ *   out[i,h,:] = sum_e alpha_e v[j,h,:]                  lse[Nt, H]: lse[i,h] = m + logf(l)
+ *   A row is taken in chunks of 16 (C <= 32) or 32 entries with a running (m, l, acc) rescaled once per chunk; the terms
+ *   of l and acc are added in ascending entry order and out = acc / l.  A dot product is the sum of each lane's
+ *   channels c = lane, lane + 16|32 in ascending order, then an xor butterfly over the lanes.  The bits depend on that
+ *   chunking, never on the launch or on the run; a table and a list that hold the same entries in the same order give
+ *   the same bits.  A row with no valid entry gives out = 0 (R3) and lse = 0.
+ *   alpha[E or Nt*width, H] (may be NULL): the weights, 0 in an empty slot (told by its id).  Nothing else per edge is
+ *   written.  Non-finite scores follow the formulas: an entry whose score overflowed to -inf weighs 0 beside a finite
+ *   m; a row whose scores are all -inf (or hold +inf or NaN) gives NaN in out, lse and alpha, as torch's softmax does.
+ * dmet_attention_bwd_f32, two launches.  By target, with delta[i,h] = sum_c g_out[i,h,c] out[i,h,c]:
+ *   alpha_e = expf(score_e - lse[i,h])  (recomputed with the forward's chain),
+ *   g_s_e = alpha_e (sum_c g_out[i,h,c] v[j,h,c] - delta[i,h]),   g_q[i,h,:] = (sum_e g_s_e k[j,h,:]) / sqrtf(C)
+ *   alpha_w, gs_w [E or Nt*width, H] fp32: the caller's scratch, every position written (0 in an empty slot); they are
+ *   the only per-edge buffers.  By source, over the by-source index rev_ptr[Ns+1], rev_pos[] in ascending order --
+ *   dmet_reverse_index(nbr, Nt*width, Ns) for a table (i = pos / width), dmet_reverse_index(src, E, Ns) for a list
+ *   (i = tgt[pos]):
+ *   g_v[j,h,:] = sum alpha_e g_out[i,h,:]       g_k[j,h,:] = (sum g_s_e q[i,h,:]) / sqrtf(C)
+ *   A hub's list is walked by its one owner.  Every gradient is written, not accumulated; rows and sources without
+ *   entries get zeros.  No float atomics: two runs give identical bits.
+ * Both return -EINVAL on anything outside these limits and on NULL or negative arguments, before any device work.
+ * Nt == 0: the forward returns 0 at once; the backward zero-fills g_k and g_v (Ns > 0) and returns. */
+int dmet_attention_supported(int H, int C);
+int dmet_attention_fwd_f32(const float *q, const float *k, const float *v, const int32_t *idx, const int32_t *rowptr,
+                           int64_t Nt, int64_t Ns, int64_t E, int width, int H, int C, float *out, float *lse,
+                           float *alpha, dmet_stream_t stream);
+int dmet_attention_bwd_f32(const float *q, const float *k, const float *v, const float *out, const float *lse,
+                           const float *g_out, const int32_t *idx, const int32_t *rowptr, const int32_t *tgt,
+                           const int32_t *rev_ptr, const int32_t *rev_pos, int64_t Nt, int64_t Ns, int64_t E, int width,
+                           int H, int C, float *alpha_w, float *gs_w, float *g_q, float *g_k, float *g_v,
+                           dmet_stream_t stream);
 /* Reverse index: a stable sort of the positions 0..M-1 of an int32 key array by key value.
  *   rev_ptr[num_keys+1]: rev_pos[rev_ptr[j] .. rev_ptr[j+1]-1] = the positions holding key j, ascending.
  * Keys outside [0, num_keys) (the -1 "no neighbour" entries) sort last and are not indexed.
