@@ -259,6 +259,9 @@ def _knn(x: torch.Tensor, ptr: torch.Tensor, k: int, stats: Optional[dict], want
                                                  _stream(dev)), "dmet_knn_fallback_stats")
             stats["flagged_tiles"], stats["flagged_queries"] = int(out[0]), int(out[1])
             stats["tiles"] = (N + 127) // 128
+            _lib.check(L.dmet_knn_retry_stats(ws.data_ptr(), N, B, D, k, ctypes.cast(out, ctypes.c_void_p),
+                                              _stream(dev)), "dmet_knn_retry_stats")
+            stats["second_attempts"], stats["second_attempt_queries"] = int(out[0]), int(out[1])
     if asked:
         return nbr, dist, loc, pq
     return nbr, dist, loc
@@ -267,7 +270,8 @@ def _knn(x: torch.Tensor, ptr: torch.Tensor, k: int, stats: Optional[dict], want
 def knn(x: torch.Tensor, ptr: torch.Tensor, k: int, stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """nbr[N,k] int32 (global ids, -1 padded), dist[N,k] fp32.  With a `stats` dict the call synchronises and stores
     stats['flagged_tiles'] / stats['flagged_queries'] (what the matrix-core path could not certify and recomputed
-    exactly; diagnostics only)."""
+    exactly) and stats['second_attempts'] / stats['second_attempt_queries'] (wavefronts of the filter that swept their
+    event a second time, and the queries they did it for); diagnostics only."""
     nbr, dist, _ = _knn(x, ptr, k, stats, False)
     return nbr, dist
 

@@ -946,7 +946,7 @@ struct KnnWorkspace {
     float *nrm;
     uint8_t *rec;         // candidate tile records
     int64_t nrec;
-    int32_t *flags;       // flags[...], any[4] and qflag[N] are one zero-filled region
+    int32_t *flags;       // flags[...], any[4] and qflag[N] are one zero-filled region (any[1], any[2]: second attempts)
     int32_t *any;
     uint8_t *qflag;
     int32_t *qlist;       // [N] flagged queries (not cleared: `any` bounds it)
@@ -1019,6 +1019,24 @@ inline int filter_form2()
 {
     const char *e = getenv("DMET_KNN_FILTER");
     return (e && strcmp(e, "1") == 0) ? 0 : 1;
+}
+
+// DMET_KNN_CUT: the margin scale of the second form's final threshold (f2_cut).  Unset: kF2CutScale; "off" or "0": no cut, the
+// threshold stays tk[M-1] (A/B against the cut in one library); any other finite value >= 0 is the scale itself, and a
+// scale of zero ("0.0", "0e0") cuts at tk[k-1]: a query whose k nearest sit in k different tiles then fails its
+// certificate and takes the second attempt (tests).
+// Read per call, as DMET_KNN_PATH is.  Default 1.25: a scale of 1 is the certifying bound itself, the quarter on top is
+// for the two-step estimate of the implicit slack; measured second attempts and flagged queries in
+// profiles/r05_knn_cut.md.
+constexpr float kF2CutScale = 1.25f;
+inline float knn_cut_scale()
+{
+    const char *e = getenv("DMET_KNN_CUT");
+    if (!e || !*e) return kF2CutScale;
+    if (strcmp(e, "0") == 0 || strcmp(e, "off") == 0) return -1.0f;
+    char *end = nullptr;
+    const float v = strtof(e, &end);
+    return (end != e && *end == '\0' && v >= 0.0f && v <= 1e6f) ? v : kF2CutScale;
 }
 
 // prep + filter (+ in-place re-rank) + re-rank of the split tail tiles, for result capacity KF >= k.  affine (32 features
@@ -1126,7 +1144,8 @@ KnnOutcome launch_knn(const KnnBuild &r, const KnnWorkspace &w)
         KnnFilterArgs f{r.x, r.ptr, r.B, r.N, r.k, w.nrm, w.rec, w.fplan, w.forder, w.fpos_of, w.ftile_ptr,
                         w.psd, w.psj, r.nbr, r.dist, r.nbr16, w.flags, w.any, w.qflag, w.qlist, w.tile_ptr, QT, filter_form2(),
                         NH == 1 ? 1.0f : 1.5f, nullptr, nullptr, nullptr, nullptr, 0, 0,
-                        (aligned16(r.nbr) && aligned16(r.dist) && aligned16(r.nbr16) && !env_is("DMET_KNN_EMIT", "lanes")) ? 1 : 0, 0};
+                        (aligned16(r.nbr) && aligned16(r.dist) && aligned16(r.nbr16) && !env_is("DMET_KNN_EMIT", "lanes")) ? 1 : 0, 0,
+                        knn_cut_scale(), w.any + 1};
         // every event is a second-form event (the caller says so): the first form's tail merge has nothing to do
         f.no_rerank = (f.form2 && r.hint.min_nodes >= kF2MinNodes && r.hint.max_nodes >= r.hint.min_nodes &&
                        r.hint.max_nodes <= kF2MaxNodes) ? 1 : 0;
@@ -1379,6 +1398,23 @@ extern "C" int dmet_knn_fallback_stats(const void *ws, int64_t N, int B, int D, 
                 fprintf(stderr, "[dmet] flagged query %d (qflag %d)\n", ids[i], (int)why);
             }
     }
+    return 0;
+}
+
+// Second attempts of the last build's second filter form (diagnostics): out[0] = wavefronts that swept their event a
+// second time, out[1] = the queries those sweeps were for.  Zero for every build that did not take the matrix-core path.
+extern "C" int dmet_knn_retry_stats(const void *ws, int64_t N, int B, int D, int k, int64_t *out, dmet_stream_t stream)
+{
+    (void)D;
+    DMET_REQUIRE(N > 0 && B > 0 && k >= 1 && k <= DMET_MAX_K && ws && out, "dmet_knn_retry_stats: bad arguments");
+    const KnnWorkspace w = carve_workspace(const_cast<void *>(ws), N, B, padded_k(k));
+    int32_t host[2] = {0, 0};
+    hipStream_t st = as_stream(stream);
+    hipError_t e = hipMemcpyAsync(host, w.any + 1, sizeof(host), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e, "dmet_knn_retry_stats");
+    out[0] = host[0];
+    out[1] = host[1];
     return 0;
 }
 

@@ -72,6 +72,9 @@ struct KnnFilterArgs {
     int emit_coalesced;         // 1: nbr / dist / nbr16 are 16-byte aligned: whole-sweep items write their rows as 16-byte pieces
     int no_rerank;              // 1: knn_rerank_kernel is not launched (dmet_knn_size_hint: no first-form event); a first-form
                                 // tail item that shows up anyway hands its queries to the exact kernel
+    float cut_scale;            // second form, final threshold min(tk[M-1], tk[k-1] + cut_scale x (what certifies the bound
+                                // d_k <= tk[k-1] + |x|^2 + slack)): see f2_cut; < 0: no cut (DMET_KNN_CUT, knn_cut_scale)
+    int32_t *retries;           // [2] second attempts of the second form: wavefronts that swept again, queries they carried
 };
 
 // The dense layer a build may carry (dmet_knn_local_dense_f32); P == nullptr: none.
@@ -1000,6 +1003,39 @@ __device__ __forceinline__ float f2_slack(float an, float rn, float scale)
            6e-14f * rn * rn + 1e-12f;
 }
 
+// The smallest threshold that certifies the k-th distance kth of a query with squared norm nx under `slack`:
+// kth - |x|^2 + slack, nudged up by f2_cert_T's margin and a few ulps of the largest term so that the certificate's own
+// fp32 expression holds for it.
+template <int NH = 1>
+__device__ __forceinline__ float f2_cert_threshold(float kth, float nx, float slack)
+{
+    float ts = kth - nx + slack;
+    ts += __builtin_fabsf(ts) * ((NH == 1 ? 0x1p-15f : 0.0f) + 4.8e-7f) + (nx + slack) * 4.8e-7f + (NH == 1 ? 2e-16f : 1e-30f);
+    return ts;
+}
+
+// Final threshold of a first attempt, decoupled from the list length M.  tkk = tk[k-1] is the k-th smallest tile
+// minimum: k tiles each hold a candidate with key <= tkk (up to the rounding-down of f2_key_lower), so the query's k-th
+// distance is at most U = tkk + |x|^2 + slack(U), and every threshold from f2_cert_threshold(U) upwards certifies it.
+// U is implicit (the slack grows with sqrt(U)): two substitutions from U_0 = tkk + |x|^2 settle it far inside the
+// margin, slack / U being a few 1e-3.  `scale` stretches the distance of the cut from tkk: 1 is the bound itself, 0
+// gives tkk, too tight wherever tkk is the k-th key itself (the certificate fails, the second attempt takes over: tests).
+// Nothing rests on this bound: the certificate is evaluated with the threshold that was applied, and a lane whose cut
+// was too tight fails it like any slack-only failure.  A NaN or infinite result (keys near the sentinel) leaves the
+// caller's fminf() with today's threshold.
+template <int NH = 1>
+__device__ __forceinline__ float f2_cut(float tkk, float nx, float scale)
+{
+    const float sc = NH == 1 ? 1.0f : 1.5f;
+    const float an = __builtin_sqrtf(nx) * 1.000001f;
+    const float u0 = fmaxf(tkk + nx, 0.0f);
+    float s = f2_slack(an, an + __builtin_sqrtf(u0) * 1.00002f, sc);
+    s = f2_slack(an, an + __builtin_sqrtf(u0 + s) * 1.00002f, sc);
+    const float U = u0 + s;
+    const float ts = f2_cert_threshold<NH>(U, nx, f2_slack(an, an + __builtin_sqrtf(U) * 1.00002f, sc));
+    return __builtin_fmaf(scale, ts - tkk, tkk);
+}
+
 // threshold list length of the second form: the fp16 slack needs the M-th smallest tile minimum two ranks further out
 // than the split form did (measured on the model's embeddings at k = 16: uncertified queries per 4500-node event
 // ~10 at KP + 4, ~2 at KP + 5, ~0.1 at KP + 6); a lane keeps kF2Slots = 30 entries, so the widest list stays at 24
@@ -1240,12 +1276,14 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         return;
     }
     int clo = ev_lo, chi = ev_hi;
-    bool idle_piece = false;
     if (nsub > 1) {
         if (ev_hi - ev_lo < kF2SplitMinNodes) {
             // a sub-sweep of fewer than ~2 M tiles has no threshold to speak of (it would hand most of its range to the
-            // exact re-rank): the first piece sweeps the whole event, the others bring an empty list to the merge
-            idle_piece = sub != 0;
+            // exact re-rank): the first piece takes the tile as a whole-sweep item -- rows written in place, second
+            // attempt included, so a final threshold that was cut too tight has its safety net here as well -- and
+            // the others have nothing to do (no list, no ticket: nobody merges)
+            if (sub != 0) return;
+            nsub = 1;
         } else {
             const int chunk = (((chi - clo) + nsub - 1) / nsub + 31) & ~31;
             clo = min(chi, clo + sub * chunk);
@@ -1254,7 +1292,7 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
     }
     const int64_t rbase = (ptr[ev] >> 5) + ev;
     const int64_t rlast = rbase + (ev_hi - ev_lo - 1) / 32;
-    const int t_lo = (clo - ev_lo) / 32, t_hi = idle_piece ? t_lo : (chi - ev_lo + 31) / 32;
+    const int t_lo = (clo - ev_lo) / 32, t_hi = (chi - ev_lo + 31) / 32;
 
     const int myq = q_first + hh * 32 + col;
     const bool valid = myq < ev_hi;
@@ -1290,6 +1328,21 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
             const int t_def = min(t_hi, t_lo + kF2Defer);
             f2_sweep<M, true, false, NH>(L, S, rec, rbase, t_lo, t_def, bq, lane, hh, valid);     // tau only
             f2_sweep<M, true, true, NH>(L, S, rec, rbase, t_def, t_hi, bq, lane, hh, valid);
+            // The final threshold: tk[M-1], or the cut above tk[k-1] where that is lower (f2_cut).  The revisit below,
+            // the compaction, the re-rank and the certificate all see the threshold that is applied here.  Lanes whose
+            // list holds fewer than k minima keep tk[M-1]; idle and overflowed lanes stay at -inf.
+            if (a.cut_scale >= 0.0f) {
+                float tkk = kKnnSentinel;
+#pragma unroll
+                for (int p = 0; p < KP; ++p)
+                    if (p == a.k - 1) tkk = L.tk[p];
+                if (tkk < kKnnSentinel) {
+                    int qi = valid ? myq : ev_lo;
+                    asm volatile("" : "+v"(qi));   // (the address is formed here, not carried through the sweeps)
+                    const float cut = f2_cut<NH>(tkk, a.nrm[qi], a.cut_scale);
+                    L.tau = fminf(L.tau, cut);
+                }
+            }
             f2_sweep<M, false, true, NH>(L, S, rec, rbase, t_lo, t_def, bq, lane, hh, valid);     // against the final tau
         } else {
             f2_sweep<M, false, true, NH>(L, S, rec, rbase, t_lo, t_hi, bq, lane, hh, valid);      // against T*
@@ -1509,8 +1562,27 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         kd[p] = __uint_as_float((unsigned)(kk[p] >> 32));
         kj[p] = kd[p] == kKnnSentinel ? -1 : (int32_t)(unsigned)kk[p];
     }
+    // Everything below addresses global memory and LDS by the lane and by the query.  Formed from `lane` and `myq` those
+    // addresses are invariant in the attempt loop: the compiler computes them at the top of the kernel and carries them
+    // through the sweeps, a dozen register pairs (the 64-feature instances spilled them).  Opaque copies keep them here.
+    // What must go through the copies: every per-lane ADDRESS of this section -- the staging area (stg + elane ...), the
+    // rows of nbr / dist / nbr16, nrm[eq], qflag / flag_query(eq).  Predicates and uniform values (valid, act, col, hh,
+    // fslot) may keep the originals: they are a register or a mask each and were live anyway.  This only steers the
+    // register allocation, never the result; the figures it buys are in profiles/r05_knn_cut.md and have to be read
+    // again (-Rpass-analysis=kernel-resource-usage) when the compiler changes.
+    int elane = lane, eq = myq;
+    // 64 features only: there the carried addresses spill (and the final-threshold cut would grow the scratch).  The
+    // 32-feature instances fit without scratch either way and keep the compiler's own allocation -- with the copies
+    // their sweep measured no faster (DMET_F2_PIN32 brings them in for A/B: 251 -> 213 VGPRs at k = 16).
+#ifdef DMET_F2_PIN32
+    asm volatile("" : "+v"(elane), "+v"(eq));
+#else
+    if constexpr (NH != 1) asm volatile("" : "+v"(elane), "+v"(eq));
+#endif
     const int k = a.k;
-    const float tau = attempt == 0 ? L.tk[M - 1] : t_fix;
+    // the threshold that was applied: tk[M-1] or the cut (first attempt), t_fix (second).  -inf: an overflowed lane, which
+    // fails whatever it is compared with, or a lane without a query
+    const float tau = L.tau;
     // the query's rows of the three tables; returns its k-th distance (-1: fewer than k neighbours)
     // coop (whole-sweep items, called by ALL lanes): the 64 queries of the item own 64 consecutive rows of each table, i.e.
     // one contiguous block; written by the lanes themselves that is k 4-byte stores per lane and table, each instruction a
@@ -1531,25 +1603,25 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
                 wave_sync();
 #pragma unroll
                 for (int q = 0; q < RP; ++q)
-                    *reinterpret_cast<uint4 *>(stg + lane * KP + 4 * q) =
+                    *reinterpret_cast<uint4 *>(stg + elane * KP + 4 * q) =
                         make_uint4((unsigned)kj[4 * q], (unsigned)kj[4 * q + 1], (unsigned)kj[4 * q + 2], (unsigned)kj[4 * q + 3]);
                 wave_sync();
 #pragma unroll
                 for (int t = 0; t < RP; ++t) {
-                    const int pi = t * 64 + lane;
+                    const int pi = t * 64 + elane;
                     const uint4 v = *reinterpret_cast<const uint4 *>(stg + 4 * pi);
                     if ((on >> (pi / RP)) & 1ull) *reinterpret_cast<uint4 *>(a.nbr + blk + 4 * pi) = v;
                 }
                 wave_sync();
 #pragma unroll
                 for (int q = 0; q < RP; ++q)
-                    *reinterpret_cast<uint4 *>(stg + lane * KP + 4 * q) =
+                    *reinterpret_cast<uint4 *>(stg + elane * KP + 4 * q) =
                         make_uint4(__float_as_uint(kd[4 * q]), __float_as_uint(kd[4 * q + 1]), __float_as_uint(kd[4 * q + 2]),
                                    __float_as_uint(kd[4 * q + 3]));
                 wave_sync();
 #pragma unroll
                 for (int t = 0; t < RP; ++t) {
-                    const int pi = t * 64 + lane;
+                    const int pi = t * 64 + elane;
                     const uint4 v = *reinterpret_cast<const uint4 *>(stg + 4 * pi);
                     if ((on >> (pi / RP)) & 1ull) *reinterpret_cast<uint4 *>(a.dist + blk + 4 * pi) = v;
                 }
@@ -1564,18 +1636,18 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
                             w.y = (unsigned)local_id16(kj[8 * q + 2], ev_lo) | ((unsigned)local_id16(kj[8 * q + 3], ev_lo) << 16);
                             w.z = (unsigned)local_id16(kj[8 * q + 4], ev_lo) | ((unsigned)local_id16(kj[8 * q + 5], ev_lo) << 16);
                             w.w = (unsigned)local_id16(kj[8 * q + 6], ev_lo) | ((unsigned)local_id16(kj[8 * q + 7], ev_lo) << 16);
-                            *reinterpret_cast<uint4 *>(stg + lane * (KP / 2) + 4 * q) = w;
+                            *reinterpret_cast<uint4 *>(stg + elane * (KP / 2) + 4 * q) = w;
                         }
                         wave_sync();
 #pragma unroll
                         for (int t = 0; t < RH; ++t) {
-                            const int pi = t * 64 + lane;
+                            const int pi = t * 64 + elane;
                             const uint4 v = *reinterpret_cast<const uint4 *>(stg + 4 * pi);
                             if ((on >> (pi / RH)) & 1ull)
                                 *reinterpret_cast<uint4 *>(reinterpret_cast<unsigned *>(a.nbr16 + blk) + 4 * pi) = v;
                         }
                     } else if (rows_on) {
-                        uint16_t *r16 = a.nbr16 + (int64_t)myq * k;
+                        uint16_t *r16 = a.nbr16 + (int64_t)eq * k;
 #pragma unroll
                         for (int p = 0; p + 1 < KP; p += 2)
                             reinterpret_cast<unsigned *>(r16)[p >> 1] =
@@ -1590,12 +1662,12 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
 #pragma unroll
         for (int p = 0; p < KP; ++p) {
             if (p < k) {
-                a.nbr[(int64_t)myq * k + p] = kj[p];
-                a.dist[(int64_t)myq * k + p] = kd[p];
+                a.nbr[(int64_t)eq * k + p] = kj[p];
+                a.dist[(int64_t)eq * k + p] = kd[p];
             }
         }
         if (a.nbr16) {
-            uint16_t *r16 = a.nbr16 + (int64_t)myq * k;
+            uint16_t *r16 = a.nbr16 + (int64_t)eq * k;
             if ((k & 1) == 0) {   // two ids per dword store
 #pragma unroll
                 for (int p = 0; p + 1 < KP; p += 2)
@@ -1616,7 +1688,7 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         if (act) {
             // certificate: every dropped candidate had key >= tau (see the header of this form).  Candidates were
             // dropped (tau below the sentinel) but fewer than k neighbours came back (kth < 0): not certified either
-            const float nx = a.nrm[myq];
+            const float nx = a.nrm[eq];
             const float an = __builtin_sqrtf(nx) * 1.000001f;
             const float rn = an + __builtin_sqrtf(fmaxf(kth, 0.0f)) * 1.00002f;
             const float slack = f2_slack(an, rn, NH == 1 ? 1.0f : 1.5f);
@@ -1625,23 +1697,27 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
             // kF2TauRepMax whatever tau is (f2_cert_T)
             const bool wideq = !(nx < kF16WideLimit * kF16WideLimit);
             const bool fail = L.overflow || wideq || (f2_full<NH>(tau) && !(kth >= 0.0f && f2_cert_T<NH>(tau) + nx - slack > kth));
-            // slack-only failures get the second attempt: the smallest threshold that certifies this k-th distance,
-            // nudged up by f2_cert_T's margin and a few ulps of the largest term so that the same fp32 expression holds
-            float ts = kth - nx + slack;
-            ts += __builtin_fabsf(ts) * ((NH == 1 ? 0x1p-15f : 0.0f) + 4.8e-7f) + (nx + slack) * 4.8e-7f + (NH == 1 ? 2e-16f : 1e-30f);
+            // slack-only failures (and cuts that came out too tight) get the second attempt: the smallest threshold
+            // that certifies this k-th distance
+            const float ts = f2_cert_threshold<NH>(kth, nx, slack);
             retry = fail && attempt == 0 && !L.overflow && !wideq && kth >= 0.0f && f2_cert_T<NH>(ts) + nx - slack > kth &&
                     ts < kKnnSentinel;
             if (fail && !retry) {
-                flag_query(a, myq, a.xtile_ptr[pos] + (myq - ev_lo) / a.xtile_queries);
+                flag_query(a, eq, a.xtile_ptr[pos] + (eq - ev_lo) / a.xtile_queries);
 #ifdef DMET_KNN_WHY
-                a.qflag[myq] = (uint8_t)(1 | (L.overflow ? 2 : 0) | (wideq ? 4 : 0) | (kth < 0.0f ? 8 : 0) | (attempt ? 16 : 0) |
+                a.qflag[eq] = (uint8_t)(1 | (L.overflow ? 2 : 0) | (wideq ? 4 : 0) | (kth < 0.0f ? 8 : 0) | (attempt ? 16 : 0) |
                                          (!(ts < kKnnSentinel) ? 32 : 0) | (!(f2_cert_T<NH>(ts) + nx - slack > kth) ? 64 : 0));
-                a.dist[(int64_t)myq * k + 0] = tau; a.dist[(int64_t)myq * k + 1] = kth; a.dist[(int64_t)myq * k + 2] = slack; a.dist[(int64_t)myq * k + 3] = (float)L.cnt;
+                a.dist[(int64_t)eq * k + 0] = tau; a.dist[(int64_t)eq * k + 1] = kth; a.dist[(int64_t)eq * k + 2] = slack; a.dist[(int64_t)eq * k + 3] = (float)L.cnt;
 #endif
             }
             t_fix = retry ? ts : -__builtin_inff();
         }
         if (!__any(retry)) return;
+        const int nretry = __popcll(__ballot(retry));
+        if (elane == 0) {   // diagnostics (dmet_knn_retry_stats): a retrying lane costs its whole wavefront a sweep
+            atomicAdd(a.retries, 1);
+            atomicAdd(a.retries + 1, nretry);
+        }
         act = retry;
         continue;
     }
@@ -1662,7 +1738,7 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     int arrived = 0;
-    if (lane == 0) arrived = atomicAdd(&tickets[wv >> 1], 1);
+    if (elane == 0) arrived = atomicAdd(&tickets[wv >> 1], 1);
     arrived = __builtin_amdgcn_readfirstlane(arrived);
     if (arrived == 0) return;                 // the other sub-sweep of this tile is still running: it will merge
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -1692,7 +1768,7 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
             kj[p] = kd[p] == kKnnSentinel ? -1 : (int32_t)(unsigned)kk[p];
         }
         const float kth = emit(true, false);      // (inside a divergent branch: every lane writes its own rows)
-        const float nx = a.nrm[myq];
+        const float nx = a.nrm[eq];
         const float an = __builtin_sqrtf(nx) * 1.000001f;
         const float rn = an + __builtin_sqrtf(fmaxf(kth, 0.0f)) * 1.00002f;
         const float slack = f2_slack(an, rn, NH == 1 ? 1.0f : 1.5f);
@@ -1700,7 +1776,7 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         const bool fail_a = f2_full<NH>(tau) && !(kth >= 0.0f && f2_cert_T<NH>(tau) + nx - slack > kth);
         const bool fail_b = f2_full<NH>(tau_o) && !(kth >= 0.0f && f2_cert_T<NH>(tau_o) + nx - slack > kth);
         if (L.overflow || of_o != 0 || wideq || fail_a || fail_b)
-            flag_query(a, myq, a.xtile_ptr[pos] + (myq - ev_lo) / a.xtile_queries);
+            flag_query(a, eq, a.xtile_ptr[pos] + (eq - ev_lo) / a.xtile_queries);
     }
     return;
     }   // attempts

@@ -133,6 +133,10 @@ int dmet_knn_size_hint(int min_nodes, int max_nodes);
  * out[1] = uncertified queries (both 0 when the exact kernel ran alone).  Synchronises the stream.
  * Environment: DMET_KNN_PATH=exact forces the exact kernel for everything. */
 int dmet_knn_fallback_stats(const void *ws, int64_t N, int B, int D, int k, int64_t *out, dmet_stream_t stream);
+/* Second attempts of the last build in `ws` (matrix-core filter, second form): out[0] = wavefronts that swept their
+ * event a second time because a query's certificate failed by the slack or its final threshold was cut too tight,
+ * out[1] = the queries those sweeps were for.  Same arguments and synchronisation as dmet_knn_fallback_stats. */
+int dmet_knn_retry_stats(const void *ws, int64_t N, int B, int D, int k, int64_t *out, dmet_stream_t stream);
 
 /* ---- N1: radius graph build ----------------------------------------------------------------------
  * replaces torch_cluster.radius_graph   call sites: train.py:48, evaluate.py:88, plt_weight.py:122

@@ -1,6 +1,7 @@
 """Flag statistics / timing of the kNN paths on the embeddings the model actually feeds them (layer 1 and 2).
 Usage: python tools/knn_model_stats.py [train_steps]   (train_steps AdamW steps of the benchmark first: the bench measures
-its kNN on the embeddings the run ended with)."""
+its kNN on the embeddings the run ended with).  stats = flagged tiles / queries (recomputed exactly) and second attempts of
+the filter (wavefronts, queries); DMET_KNN_CUT=0 / a number switches the final threshold's cut off / scales its margin."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
