@@ -883,6 +883,19 @@ __device__ __forceinline__ f16x8 f2_fold(unsigned tq)
     return __builtin_bit_cast(f16x8, u);
 }
 
+// The fold operands of both 32-query blocks live across a whole sweep (f2_sweep builds them, f2_tile reads them): only the
+// threshold dword changes, and only where the threshold is converted.  v_permlane32_swap hands every lane the two
+// thresholds of its lane pair (query (0, col), (1, col)); the constant dwords stay where they are.
+__device__ __forceinline__ void f2_fold_tau(f16x8 (&fq)[2], unsigned tq)
+{
+    const auto tt = __builtin_amdgcn_permlane32_swap(tq, tq, false, false);
+    uint4 u0 = __builtin_bit_cast(uint4, fq[0]), u1 = __builtin_bit_cast(uint4, fq[1]);
+    u0.x = tt[0];
+    u1.x = tt[1];
+    fq[0] = __builtin_bit_cast(f16x8, u0);
+    fq[1] = __builtin_bit_cast(f16x8, u1);
+}
+
 // Operands of one candidate tile: single-term fp16 records (see knn_prep_kernel).  32 features: the A fragments + the
 // fold fragment.  64 features: the A fragments + the fp32 accumulator seed (the squared norms of the 16 candidate rows
 // the lane receives results for, rows (e & 3) + 8 (e >> 2) + 4 hh) -- the fold's registers and conversions pushed the
@@ -903,12 +916,12 @@ struct F2Ops<2> {
 // A[row r][k = 8 hh + 0..7].  32 features: 3 MFMAs, the first one from the inline constant 0 -- the fold block (o.f from
 // the record, f2_fold(tq) on the query side) is  sum_k A[j][k] B[k][i] = N1 P1 + .. + N4 P4 + 2^14 y_0(i) +
 // 2^-15 y_1(i) = |x_j|^2 - tau_rep(i) up to the norm's rounding: every product is exact in fp32 and the ones of the zero
-// slots are 0 (every operand there is finite).  64 features: 4 MFMAs from the seed (keys, tq unused).
+// slots are 0 (every operand there is finite).  64 features: 4 MFMAs from the seed (keys, `fold` unused).
 template <int NH = 1>
-__device__ __forceinline__ f32x16 f2_block(const F2Ops<NH> &o, const f16x8 (&bv)[2 * NH], unsigned tq)
+__device__ __forceinline__ f32x16 f2_block(const F2Ops<NH> &o, const f16x8 (&bv)[2 * NH], const f16x8 &fold)
 {
     f32x16 acc;
-    if constexpr (NH == 1) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(o.f, f2_fold(tq), f32x16{}, 0, 0, 0);
+    if constexpr (NH == 1) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(o.f, fold, f32x16{}, 0, 0, 0);
     else acc = o.c;
 #pragma unroll
     for (int m = 0; m < 2 * NH; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(o.a[m], bv[m], acc, 0, 0, 0);
@@ -916,16 +929,33 @@ __device__ __forceinline__ f32x16 f2_block(const F2Ops<NH> &o, const f16x8 (&bv)
 }
 
 // one fp16 candidate tile record: the lane's 2 NH A operands and its part of the fold fragment (or its 16 norms)
+// rofs: 16 x lane, the lane's byte offset inside a fragment (32 features)
 template <int NH = 1>
-__device__ __forceinline__ void f2_load(F2Ops<NH> &o, const uint8_t *__restrict__ rec, int64_t tidx, int lane, int hh)
+__device__ __forceinline__ void f2_load(F2Ops<NH> &o, const uint8_t *__restrict__ rec, int64_t tidx, int lane, int hh,
+                                        unsigned &rofs)
 {
-    const uint8_t *base = rec + tidx * rec_bytes(NH);
-    const f16x8 *g = reinterpret_cast<const f16x8 *>(base);
-#pragma unroll
-    for (int m = 0; m < 2 * NH; ++m) o.a[m] = g[m * 64 + lane];
     if constexpr (NH == 1) {
-        o.f = g[2 * NH * 64 + lane];
+        // the record number is wave-uniform (filter2_wave) but only readfirstlane tells the compiler: the three loads
+        // then take a scalar base, one 32-bit lane offset and the immediates 0 / 1024 / 2048 instead of a 64-bit
+        // multiply-add per lane and tile
+        const uint64_t sb = reinterpret_cast<uint64_t>(rec + tidx * rec_bytes(NH));
+        const uint64_t ub = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(sb >> 32)) << 32) |
+                            (unsigned)__builtin_amdgcn_readfirstlane((int)sb);
+        // (a pointer made from an integer is a global-memory pointer only if its type says so)
+        typedef const f16x8 __attribute__((address_space(1))) *GlobalFrag;
+        // the lane's byte offset, made opaque at every load: left to itself hipcc widens it to 64 bits once, outside
+        // the loop, and adds the base to it per lane and tile.  The copy is handed on (rofs is the caller's), so it
+        // costs no move
+        asm volatile("" : "+v"(rofs));
+        const GlobalFrag g = (GlobalFrag)(ub + (uint64_t)rofs);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) o.a[m] = g[m * 64];
+        o.f = g[2 * 64];
     } else {
+        const uint8_t *base = rec + tidx * rec_bytes(NH);
+        const f16x8 *g = reinterpret_cast<const f16x8 *>(base);
+#pragma unroll
+        for (int m = 0; m < 2 * NH; ++m) o.a[m] = g[m * 64 + lane];
         const float4 *nr = reinterpret_cast<const float4 *>(base + kRec16FragBytes * NH);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -1057,8 +1087,8 @@ __device__ __forceinline__ int f2_mask_row(int p) { return (p & 3) + 8 * ((p & 1
 template <int M, bool UPD, bool REC, bool INS, int NH = 1, bool CONV = true, int LEAD = 2>
 __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *__restrict__ rec, int64_t rbase, int t,
                                         int t_hi, f32x16 &c0, f32x16 &c1, f32x16 &n0, f32x16 &n1, float &rc, float &rn,
-                                        const F2Ops<NH> &use, F2Ops<NH> &ld, const f16x8 (&bq)[2][2 * NH], int lane,
-                                        int hh, bool alive, float &carry)
+                                        const F2Ops<NH> &use, F2Ops<NH> &ld, const f16x8 (&bq)[2][2 * NH], f16x8 (&fq)[2],
+                                        int lane, int hh, bool alive, float &carry, unsigned &rofs)
 {
 #if defined(DMET_F2_ABL) && DMET_F2_ABL >= 2
     constexpr bool kRec = false;     // cycle-budget experiment (tools/knn_budget2.sh)
@@ -1074,31 +1104,25 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
         if (__any(L.cnt >= kF2Slots - 1)) f2_compact<M>(L, S, lane, kF2Slots - 3);
     }
 #if defined(DMET_F2_SAMEREC)
-    f2_load<NH>(ld, rec, rbase + (t & 1), lane, hh);   // experiment: operands always cache-resident
+    f2_load<NH>(ld, rec, rbase + (t & 1), lane, hh, rofs);   // experiment: operands always cache-resident
 #else
-    f2_load<NH>(ld, rec, rbase + min(t + LEAD, t_hi - 1), lane, hh);   // clamped: the last calls re-read the last tile
+    f2_load<NH>(ld, rec, rbase + min(t + LEAD, t_hi - 1), lane, hh, rofs);   // clamped: the last calls re-read the last tile
 #endif
     // the fold against the thresholds as they are now (tile t + 1's keys: stale by one update, i.e. larger -- a
-    // superset); v_permlane32_swap hands every lane the two thresholds of its lane pair (query (0, col), (1, col)).
+    // superset): fq holds them since the last conversion (f2_sweep, or the CONV tile below).
     // Sweeps that record no masks fold threshold 0: their results are the keys themselves.
-    {
-        unsigned q0 = 0u, q1 = 0u;
-        if (NH == 1 && kRec) {
-            const auto tt = __builtin_amdgcn_permlane32_swap(L.tq, L.tq, false, false);
-            q0 = tt[0]; q1 = tt[1];
-        }
-        n0 = f2_block<NH>(use, bq[0], q0);     // (s_setprio 1 around these was measured: 10 % slower)
-        n1 = f2_block<NH>(use, bq[1], q1);
-        rn = L.rep;
-    }
+    n0 = f2_block<NH>(use, bq[0], fq[0]);     // (s_setprio 1 around these was measured: 10 % slower)
+    n1 = f2_block<NH>(use, bq[1], fq[1]);
+    rn = L.rep;
     // The accumulators stay where the MFMAs left them: lane (col, hh) holds, for candidate rows (e & 3) + 8 (e >> 2) + 4 hh,
     // the keys of query (0, col) in c0 and of query (1, col) in c1 -- 16 keys of each of the two queries the lane PAIR
     // (col, 0), (col, 1) owns.  Every lane reduces both halves it holds (hit mask against the owner's threshold, minimum)
     // and the pair exchanges the REDUCED values: v_permlane32_swap(V0, V1) trades V0 of lanes 32..63 for V1 of lanes
     // 0..31, so with V0 = "my part for query (0, col)" and V1 = "my part for query (1, col)" every lane ends up with
-    // V0 = the hh = 0 rows' part and V1 = the hh = 1 rows' part of ITS OWN query.  Three swaps per tile (thresholds,
-    // masks, minima) instead of the sixteen that moved the accumulators themselves (second session of round 2; a swap
-    // costs two issue slots and sat between the MFMA results and everything else).
+    // V0 = the hh = 0 rows' part and V1 = the hh = 1 rows' part of ITS OWN query.  Two swaps per tile (masks, minima;
+    // a third for the thresholds where they are converted, f2_fold_tau) instead of the sixteen that moved the
+    // accumulators themselves (second session of round 2; a swap costs two issue slots and sat between the MFMA results
+    // and everything else).
     unsigned mask = 0u;
     if (kRec) {
         // One VALU op per key: the fold result is key - rep, v_alignbit shifts its sign bit into the mask (a -0 would
@@ -1126,10 +1150,14 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
     }
     float tmin = -__builtin_inff();   // deferred tiles: "never drop" (their tau is already final)
     if (kUpd) {
-        float na = kKnnSentinel, nb = kKnnSentinel;   // (the start value also keeps a NaN key out of the v_med3 chain)
+        // the trees start from the sentinel (the first operand also keeps a NaN key out of the v_med3 chain), taken as
+        // a scalar source: a VOP3 encoding has no literal, and a "+v" start value costs a v_mov per tree and tile
         // v_min3_f32 by hand: fminf() makes hipcc canonicalise every MFMA output with a v_max first (twice the ops)
+        float na, nb;
+        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(na) : "s"(kKnnSentinel), "v"(c0[0]), "v"(c0[1]));
+        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(nb) : "s"(kKnnSentinel), "v"(c1[0]), "v"(c1[1]));
 #pragma unroll
-        for (int e = 0; e < 16; e += 2) {
+        for (int e = 2; e < 16; e += 2) {
             asm("v_min3_f32 %0, %0, %1, %2" : "+v"(na) : "v"(c0[e]), "v"(c0[e + 1]));
             asm("v_min3_f32 %0, %0, %1, %2" : "+v"(nb) : "v"(c1[e]), "v"(c1[e + 1]));
         }
@@ -1155,7 +1183,10 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
             for (int p = M - 1; p >= 1; --p) L.tk[p] = __builtin_amdgcn_fmed3f(L.tk[p - 1], v, L.tk[p]);
             asm("v_min_f32 %0, %0, %1" : "+v"(L.tk[0]) : "v"(v));
             if (alive && !L.overflow) L.tau = L.tk[M - 1];
-            if (NH == 1 && kRec && CONV) L.tq = f2_tau16(L.tau, L.rep);   // (every second tile: see f2_sweep)
+            if (NH == 1 && kRec && CONV) {   // (every second tile: see f2_sweep)
+                L.tq = f2_tau16(L.tau, L.rep);
+                f2_fold_tau(fq, L.tq);
+            }
         } else {
             carry = tmin;
         }
@@ -1177,43 +1208,48 @@ __device__ __forceinline__ void f2_sweep(F2Lane<M> &L, F2Wave &S, const uint8_t 
 {
     if (t_lo >= t_hi) return;
     F2Ops<NH> A, B;
-    f2_load<NH>(A, rec, rbase + t_lo, lane, hh);
-    unsigned q0 = 0u, q1 = 0u;
+    unsigned rofs = (unsigned)lane * 16u;
+    f2_load<NH>(A, rec, rbase + t_lo, lane, hh, rofs);
+    // query side of the fold for both 32-query blocks, built here once per sweep -- from the threshold the sweep starts
+    // with (the cut before the revisit, t_fix in a second attempt), 0 where no mask is recorded -- and kept in registers:
+    // the tiles read them, a CONV tile rewrites their threshold dword.  Opaque, or hipcc rebuilds them (eight moves and
+    // the swap) in every tile rather than hold eight registers
+    f16x8 fq[2] = {f2_fold(0u), f2_fold(0u)};
     if (NH == 1 && REC) {
         L.tq = f2_tau16(L.tau, L.rep);
-        const auto tt = __builtin_amdgcn_permlane32_swap(L.tq, L.tq, false, false);
-        q0 = tt[0]; q1 = tt[1];
+        f2_fold_tau(fq, L.tq);
+        asm volatile("" : "+v"(fq[0]), "+v"(fq[1]));
     }
     float rc = L.rep, rn;
-    f32x16 c0 = f2_block<NH>(A, bq[0], q0);      // prologue: the first tile's keys
-    f32x16 c1 = f2_block<NH>(A, bq[1], q1);
+    f32x16 c0 = f2_block<NH>(A, bq[0], fq[0]);      // prologue: the first tile's keys
+    f32x16 c1 = f2_block<NH>(A, bq[1], fq[1]);
     f32x16 n0, n1;
-    f2_load<NH>(A, rec, rbase + min(t_lo + 1, t_hi - 1), lane, hh);
+    f2_load<NH>(A, rec, rbase + min(t_lo + 1, t_hi - 1), lane, hh, rofs);
     float carry = kKnnSentinel;
     if constexpr (NH == 1 && UPD && REC) {
         // the main sweep keeps THREE tiles of operands in flight (the fold freed the seed registers): call t issues
         // tile t + 1's MFMAs and loads tile t + 3.  Six calls per trip: the operand sets rotate with period 3, the key
         // blocks (c, n) and the threshold conversions with period 2
         F2Ops<NH> C;
-        f2_load<NH>(B, rec, rbase + min(t_lo + 2, t_hi - 1), lane, hh);
+        f2_load<NH>(B, rec, rbase + min(t_lo + 2, t_hi - 1), lane, hh, rofs);
         for (int t = t_lo; t < t_hi; t += 6) {
-            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t, t_hi, c0, c1, n0, n1, rc, rn, A, C, bq, lane, hh,
-                                                     alive, carry);
+            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t, t_hi, c0, c1, n0, n1, rc, rn, A, C, bq, fq, lane, hh,
+                                                     alive, carry, rofs);
             if (t + 1 >= t_hi) break;
-            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 1, t_hi, n0, n1, c0, c1, rn, rc, B, A, bq, lane,
-                                                    hh, alive, carry);
+            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 1, t_hi, n0, n1, c0, c1, rn, rc, B, A, bq, fq, lane,
+                                                    hh, alive, carry, rofs);
             if (t + 2 >= t_hi) break;
-            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t + 2, t_hi, c0, c1, n0, n1, rc, rn, C, B, bq, lane,
-                                                     hh, alive, carry);
+            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t + 2, t_hi, c0, c1, n0, n1, rc, rn, C, B, bq, fq, lane,
+                                                     hh, alive, carry, rofs);
             if (t + 3 >= t_hi) break;
-            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 3, t_hi, n0, n1, c0, c1, rn, rc, A, C, bq, lane,
-                                                    hh, alive, carry);
+            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 3, t_hi, n0, n1, c0, c1, rn, rc, A, C, bq, fq, lane,
+                                                    hh, alive, carry, rofs);
             if (t + 4 >= t_hi) break;
-            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t + 4, t_hi, c0, c1, n0, n1, rc, rn, B, A, bq, lane,
-                                                     hh, alive, carry);
+            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t + 4, t_hi, c0, c1, n0, n1, rc, rn, B, A, bq, fq, lane,
+                                                     hh, alive, carry, rofs);
             if (t + 5 >= t_hi) break;
-            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 5, t_hi, n0, n1, c0, c1, rn, rc, C, B, bq, lane,
-                                                    hh, alive, carry);
+            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 5, t_hi, n0, n1, c0, c1, rn, rc, C, B, bq, fq, lane,
+                                                    hh, alive, carry, rofs);
         }
         return;
     }
@@ -1223,11 +1259,11 @@ __device__ __forceinline__ void f2_sweep(F2Lane<M> &L, F2Wave &S, const uint8_t 
         // -> 3 761 overflowed queries per launch and twice the kernel time
         // the fold's threshold is converted after every second tile only (f2_tau16 is ~15 VALU ops): the masks of
         // the next two tiles are taken against a threshold older by one more update -- larger, a superset
-        f2_tile<M, UPD, REC, true, NH, false>(L, S, rec, rbase, t, t_hi, c0, c1, n0, n1, rc, rn, A, B, bq, lane, hh, alive,
-                                              carry);
+        f2_tile<M, UPD, REC, true, NH, false>(L, S, rec, rbase, t, t_hi, c0, c1, n0, n1, rc, rn, A, B, bq, fq, lane, hh, alive,
+                                              carry, rofs);
         if (t + 1 < t_hi)
-            f2_tile<M, UPD, REC, true, NH, true>(L, S, rec, rbase, t + 1, t_hi, n0, n1, c0, c1, rn, rc, B, A, bq, lane, hh,
-                                                 alive, carry);
+            f2_tile<M, UPD, REC, true, NH, true>(L, S, rec, rbase, t + 1, t_hi, n0, n1, c0, c1, rn, rc, B, A, bq, fq, lane, hh,
+                                                 alive, carry, rofs);
     }
 }
 
@@ -1515,7 +1551,9 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
     // Rounds of rows in flight: three (KP <= 16) were chosen in round 2 -- the kernel has since grown to 256 VGPRs + 56
     // bytes of scratch per lane with them (-Rpass-analysis=kernel-resource-usage), i.e. spill traffic inside this
     // latency-bound loop; with two it needs 237 registers and no scratch and the build is 8-10 us faster (second session
-    // of round 3; DMET_RR_THREE brings the third back for A/B)
+    // of round 3).  Measured again with the registers the opaque copies below freed (224 VGPRs at k = 16, no scratch,
+    // profiles/r06_knn_operands.md): still slower, 48 213 against 48 519 events/s, every one of six runs below every run
+    // with two rounds.  DMET_RR_THREE brings the third back for A/B
 #ifdef DMET_RR_THREE
     constexpr bool kThreeRounds = KP <= 16;
 #else
@@ -1570,15 +1608,11 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
     // fslot) may keep the originals: they are a register or a mask each and were live anyway.  This only steers the
     // register allocation, never the result; the figures it buys are in profiles/r05_knn_cut.md and have to be read
     // again (-Rpass-analysis=kernel-resource-usage) when the compiler changes.
+    // Every instance: at 64 features the carried addresses spilled; at 32 the sweep holds its two fold operands in
+    // registers (f2_sweep) and only fits beside them without these pairs (at k = 16: 256 VGPRs + 20 bytes of scratch
+    // against 223).
     int elane = lane, eq = myq;
-    // 64 features only: there the carried addresses spill (and the final-threshold cut would grow the scratch).  The
-    // 32-feature instances fit without scratch either way and keep the compiler's own allocation -- with the copies
-    // their sweep measured no faster (DMET_F2_PIN32 brings them in for A/B: 251 -> 213 VGPRs at k = 16).
-#ifdef DMET_F2_PIN32
     asm volatile("" : "+v"(elane), "+v"(eq));
-#else
-    if constexpr (NH != 1) asm volatile("" : "+v"(elane), "+v"(eq));
-#endif
     const int k = a.k;
     // the threshold that was applied: tk[M-1] or the cut (first attempt), t_fix (second).  -inf: an overflowed lane, which
     // fails whatever it is compared with, or a lane without a query
