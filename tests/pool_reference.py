@@ -1,6 +1,7 @@
 """CPU restatement (numpy / plain Python) of the graph-coarsening contract of include/dmet.h: the graclus matching of
 dmet_graclus_f32 (colour function, propose / respond rounds, best-candidate rule, sequential finisher), the CSR order
-deepmetv2_amd.graclus builds, and the consecutive numbering of the pooled clusters."""
+deepmetv2_amd.graclus builds, the consecutive numbering of the pooled clusters, the pair-pool index, pair pooling forward
+and backward, and the normalized-cut weights.  Every function restates the header, not the kernels of csrc/pool.hip."""
 from __future__ import annotations
 
 import numpy as np
@@ -142,3 +143,143 @@ def consecutive(cluster: np.ndarray):
     """PyG consecutive_cluster: ids ranked by sorted unique value -> inverse[N]."""
     _u, inv = np.unique(cluster, return_inverse=True)
     return inv
+
+
+# ---- pair pooling of a matching (include/dmet.h, "Pair pooling of a graclus result") -----------------------------------
+def ptr_of(sizes) -> np.ndarray:
+    return np.concatenate([[0], np.cumsum(np.asarray(sizes, np.int64))]).astype(np.int64)
+
+
+def event_of(ptr, nodes) -> np.ndarray:
+    """The event that holds each node: the one with ptr[b] <= u < ptr[b+1], so never an empty one."""
+    return np.searchsorted(np.asarray(ptr, np.int64), np.asarray(nodes, np.int64), side="right") - 1
+
+
+def leaders(partner) -> np.ndarray:
+    """leader[u]: u itself unless its partner is a valid lower index."""
+    partner = np.asarray(partner, np.int64)
+    u = np.arange(len(partner), dtype=np.int64)
+    return np.where((partner >= 0) & (partner < u), partner, u)
+
+
+def pair_index(partner, ptr):
+    """(cid[N] int64, pooled_ptr[B+1] int64): clusters numbered in ascending leader index, pooled_ptr the exclusive prefix
+    sum of the leaders per event."""
+    ptr = np.asarray(ptr, np.int64)
+    lead = leaders(partner)
+    is_lead = lead == np.arange(len(lead))
+    number = np.cumsum(is_lead) - 1                       # ascending leader index, over the whole node range
+    cid = number[lead].astype(np.int64) if len(lead) else np.zeros(0, np.int64)
+    cnt = [int(is_lead[int(a):int(b)].sum()) for a, b in zip(ptr[:-1], ptr[1:])]
+    return cid, ptr_of(cnt)
+
+
+def pool_pairs(x, partner, cid, ptr, C):
+    """(out_max[C,F] f32, arg[C,F] int32, out_mean[C,F] f32, pooled_batch[C] int64) in float32 arithmetic: the partner's
+    value wins only when strictly greater (IEEE >), so the leader keeps ties (and -0.0 against +0.0);
+    out_mean = (x_u + x_v) * 0.5f, x_u for a singleton."""
+    x = np.asarray(x, np.float32)
+    partner = np.asarray(partner, np.int64)
+    cid = np.asarray(cid, np.int64)
+    N, F = x.shape
+    out_max = np.zeros((C, F), np.float32)
+    arg = np.zeros((C, F), np.int32)
+    out_mean = np.zeros((C, F), np.float32)
+    pooled_batch = np.zeros(C, np.int64)
+    u = np.flatnonzero(leaders(partner) == np.arange(N))
+    p = partner[u]
+    pair = p > u
+    xu = x[u]
+    xv = x[np.where(pair, p, u)]                          # a singleton meets itself: never strictly greater
+    with np.errstate(invalid="ignore"):                   # inf + -inf
+        take = xv > xu
+        mean = np.where(pair[:, None], (xu + xv) * np.float32(0.5), xu).astype(np.float32)
+    out_max[cid[u]] = np.where(take, xv, xu)
+    arg[cid[u]] = np.where(take, p[:, None], u[:, None]).astype(np.int32)
+    out_mean[cid[u]] = mean
+    pooled_batch[cid[u]] = event_of(ptr, u)
+    return out_max, arg, out_mean, pooled_batch
+
+
+def pool_pairs_bwd(g_max, arg, g_mean, partner, cid, F):
+    """gx[u,f] = (arg[cid[u],f] == u ? g_max[cid[u],f] : 0) + g_mean[cid[u],f] * (1/2 for a pair, 1 for a singleton) in
+    float32, in this order; a NULL (None) gradient leaves its term out."""
+    partner = np.asarray(partner, np.int64)
+    cid = np.asarray(cid, np.int64)
+    N = len(partner)
+    u = np.arange(N, dtype=np.int64)
+    gx = np.zeros((N, F), np.float32)
+    if g_max is not None:
+        hit = np.asarray(arg, np.int64)[cid] == u[:, None]
+        gx = np.where(hit, np.asarray(g_max, np.float32)[cid], np.float32(0)).astype(np.float32)
+    if g_mean is not None:
+        pair = (partner >= 0) & (partner != u)
+        half = np.where(pair, np.float32(0.5), np.float32(1.0)).astype(np.float32)[:, None]
+        gx = (gx + np.asarray(g_mean, np.float32)[cid] * half).astype(np.float32)
+    return gx
+
+
+def random_matching(ptr, rng, single_share):
+    """partner[N] int64 of a valid matching: partner[partner[u]] == u inside one event, -1 for singletons.  Each event
+    is permuted and the permutation cut into consecutive couples, so pairs straddle any fixed chunk of node indices;
+    a couple stays two singletons with probability single_share (0: all pairs, 1: all singletons)."""
+    ptr = np.asarray(ptr, np.int64)
+    partner = np.full(int(ptr[-1]), -1, np.int64)
+    for lo, hi in zip(ptr[:-1], ptr[1:]):
+        perm = int(lo) + rng.permutation(int(hi - lo))
+        a, b = perm[0:len(perm) - 1:2], perm[1::2]
+        keep = rng.random(len(a)) >= single_share
+        partner[a[keep]] = b[keep]
+        partner[b[keep]] = a[keep]
+    return partner
+
+
+def tie_grid(rng, shape) -> np.ndarray:
+    """float32 values from a small grid: multiples of 0.5, both zeros and both infinities, so that many pairs tie and
+    some meet -0.0 against +0.0 or an infinity.  No NaN: the header does not define it."""
+    grid = np.array([-2.0, -1.5, -1.0, -0.5, 0.5, 1.0, 1.5, 2.0, -0.0, 0.0, np.inf, -np.inf], np.float32)
+    return grid[rng.integers(0, len(grid), shape)]
+
+
+def index_cases():
+    """name -> event sizes: where the pair-pool index can go wrong.  Events past one 256-node chunk (the leader rank is
+    carried across chunks), 255 / 256 / 257 and 700 events (the count scan is carried across chunks of 256 events), empty
+    events at the front, inside and at the end (pooled_ptr repeats)."""
+    rng = np.random.default_rng(2024)
+    cases = {"chunk_edges": [0, 255, 256, 257, 0, 513, 1, 1025, 0], "one_event": [5000]}
+    for B in (255, 256, 257):
+        cases[f"events_{B}"] = rng.integers(0, 9, B).tolist()
+    s = rng.integers(0, 9, 700)
+    s[[0, 1, 255, 256, 349, 698, 699]] = 0
+    s[350] = 300
+    # the carry across the first 256 events must matter: leaders exist on both sides of it
+    cases["scan_carry"] = s.tolist()
+    return cases
+
+
+# ---- normalized cut (include/dmet.h, dmet_normalized_cut_f32 / dmet_normalized_cut_2d_f32) -----------------------------
+def normalized_cut(row, col, N, attr=None, x=None):
+    """w[E] float32 = a * (1/deg[row] + 1/deg[col]) in float32, deg = in-degree counted over the in-range entries of col;
+    a = attr, or ||x[row] - x[col]||_2 with the squares summed in float64 in ascending channel order and one rounding
+    to float32.  An out-of-range endpoint gives NaN."""
+    row, col = np.asarray(row, np.int64), np.asarray(col, np.int64)
+    E = len(row)
+    col_ok = (col >= 0) & (col < N)
+    ok = col_ok & (row >= 0) & (row < N)
+    deg = np.bincount(col[col_ok], minlength=N).astype(np.float32)
+    r, c = row[ok], col[ok]
+    if x is not None:
+        x64 = np.asarray(x, np.float32).astype(np.float64)
+        acc = np.zeros(len(r), np.float64)
+        for d in range(x64.shape[1]):                     # a loop, not np.sum: np.sum adds pairwise
+            t = x64[r, d] - x64[c, d]
+            acc = acc + t * t
+        a = np.sqrt(acc).astype(np.float32)
+    else:
+        a = np.asarray(attr, np.float32).reshape(-1)[ok]
+    w = np.full(E, np.nan, np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):  # 1/0 = inf, 0 * inf = NaN
+        ir = np.float32(1.0) / deg[r]
+        ic = np.float32(1.0) / deg[c]
+        w[ok] = a * (ir + ic)
+    return w

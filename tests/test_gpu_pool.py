@@ -65,18 +65,24 @@ def test_graclus_bit_exact_on_symmetrised_knn(dev, weighted):
     assert not torch.equal(dm.graclus(ei, w, N, batch=bd, seed=78), cl)
 
 
-def test_graclus_radius_graph_self_loops_isolated_ties(dev):
+def _radius_graph_loops_duplicates(dev):
+    """(x, batch, ptr, edge_index): a radius graph with self loops, then unsorted, with 50 duplicated edges and every
+    13th node isolated (all its edges dropped)."""
     import deepmetv2_amd as dm
     x, batch, ptr = _ragged([300, 40, 700], 2, seed=5)
     xd, bd = x.to(dev), batch.to(dev)
     ei = dm.radius_graph(xd, 0.3, bd, loop=True, max_num_neighbors=32)    # self loops present
     assert bool((ei[0] == ei[1]).any())
-    N = xd.shape[0]
-    # an unsorted, duplicated edge list with some nodes isolated (all their edges dropped)
     keep = (ei[0] % 13 != 0) & (ei[1] % 13 != 0)
     ei = ei[:, keep]
     perm = torch.randperm(ei.shape[1], generator=torch.Generator().manual_seed(0)).to(dev)
-    ei = torch.cat([ei[:, perm], ei[:, :50]], 1)
+    return xd, bd, ptr, torch.cat([ei[:, perm], ei[:, :50]], 1)
+
+
+def test_graclus_radius_graph_self_loops_isolated_ties(dev):
+    import deepmetv2_amd as dm
+    xd, bd, ptr, ei = _radius_graph_loops_duplicates(dev)
+    N = xd.shape[0]
     for w in (None, torch.ones(ei.shape[1], device=dev)):           # unweighted, all-equal weights (tie rule)
         for mr in (0, 1, 2):
             cl = dm.graclus(ei, w, N, batch=bd, seed=3, max_rounds=mr)
@@ -231,9 +237,10 @@ def test_global_pools(dev):
     assert torch.equal(xd.grad.cpu(), g)
 
 
-def test_max_pool_edge_coarsening(dev):
+@pytest.mark.parametrize("sizes", [[30, 70], [300, 520]], ids=["30-70", "300-520"])     # inside / past one 256-node chunk
+def test_max_pool_edge_coarsening(dev, sizes):
     import deepmetv2_amd as dm
-    xd, bd, ptr, ei = _knn_sym(dev, [30, 70], 5, 4, seed=12)
+    xd, bd, ptr, ei = _knn_sym(dev, sizes, 5, 4, seed=12)
     N = xd.shape[0]
     cl = dm.graclus(ei, None, N, batch=bd, seed=1)
     attr = torch.rand(ei.shape[1], 2, device=dev)
@@ -258,7 +265,7 @@ def test_max_pool_edge_coarsening(dev):
     assert torch.equal(out.x.cpu(), x_ref) and torch.equal(out.batch.cpu(), pb)
     # this package's Batch: ptr / max_nodes / min_nodes follow
     from deepmetv2_amd.data import Batch
-    b = Batch(xd, torch.zeros(2, 1, device=dev), bd, ptr.to(dev), 70, min_nodes=30)
+    b = Batch(xd, torch.zeros(2, 1, device=dev), bd, ptr.to(dev), max(sizes), min_nodes=min(sizes))
     ob = dm.max_pool(cl, b)
     counts = torch.bincount(pb, minlength=2)
     assert torch.equal(ob.ptr.cpu(), torch.cat([torch.zeros(1, dtype=torch.int64), counts.cumsum(0)]))
@@ -286,7 +293,8 @@ def _drn_by_hand(m, data, seeds, ops):
     return m.output(ops.global_max_pool(x, batch)).squeeze(-1)
 
 
-def test_drn_matches_hand_composition_and_cpu_restatement(dev):
+@pytest.mark.parametrize("sizes", [[40, 9, 60], [300, 9, 700]], ids=["40-9-60", "300-9-700"])
+def test_drn_matches_hand_composition_and_cpu_restatement(dev, sizes):
     import deepmetv2_amd as dm
     from oracle import ref_ops
     torch.manual_seed(0)
@@ -294,7 +302,7 @@ def test_drn_matches_hand_composition_and_cpu_restatement(dev):
     m_cpu = copy.deepcopy(m)
     m_hand = copy.deepcopy(m).to(dev)
     m = m.to(dev)
-    data, ptr = _drn_inputs(dev, [40, 9, 60])
+    data, ptr = _drn_inputs(dev, sizes)
     seeds = (21, 22)
     out = m(data, seeds=seeds)
     out.sum().backward()
