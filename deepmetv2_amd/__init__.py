@@ -7,6 +7,7 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import knn_graph, radius_graph, knn, radius   # torch_cluster
     from deepmetv2_amd import scatter_add, scatter_max       # torch_scatter
     from deepmetv2_amd import graclus                        # torch_cluster
+    from deepmetv2_amd import fps, nearest                   # torch_cluster
     from deepmetv2_amd import normalized_cut, max_pool, max_pool_x, global_max_pool   # torch_geometric
     from deepmetv2_amd import GravNetConv                    # torch_geometric.nn
     from deepmetv2_amd import TransformerConv                # torch_geometric.nn (attention_aggregate: utils.softmax + sum)
@@ -15,7 +16,8 @@ All of them run hand-written HIP kernels for gfx950 through the C ABI in include
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
 calling an operator without the library or with non-GPU tensors raises.
 """
-from .cluster import knn, knn_graph, knn_table, knn_xy_table, radius, radius_graph, radius_table, radius_xy_table
+from .cluster import (fps, knn, knn_graph, knn_table, knn_xy_table, nearest, radius, radius_graph, radius_table,
+                      radius_xy_table)
 from .conv import DynamicEdgeConv, EdgeConv
 from .data import Batch, DeviceLoader, EventLoader, collate, events_from_padded
 from .graph import BipartiteTable, GraphFuture, NeighborTable, build_async, raise_deferred_errors, register_batch, to_undirected
@@ -35,6 +37,6 @@ __all__ = [
     "u_perp_par_loss", "to_undirected", "raise_deferred_errors", "accelerate", "build_async", "GraphFuture", "Batch", "EventLoader", "DeviceLoader", "collate", "events_from_padded",
     "graclus", "normalized_cut", "normalized_cut_2d", "max_pool", "max_pool_x", "avg_pool", "avg_pool_x",
     "global_max_pool", "global_mean_pool", "global_add_pool", "DynamicReductionNetwork",
-    "GravNetConv", "gravnet_aggregate", "TransformerConv", "attention_aggregate",
+    "GravNetConv", "gravnet_aggregate", "TransformerConv", "attention_aggregate", "fps", "nearest",
 ]
 __version__ = "0.1.0"

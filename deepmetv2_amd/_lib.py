@@ -160,6 +160,8 @@ SIGNATURES = {
     "dmet_pool_pairs_index": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dmet_pool_pairs_f32": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dmet_pool_pairs_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i64, _vp, _vp]),
+    "dmet_fps_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "dmet_fps_f32": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -1999,3 +1999,41 @@ def pool_pairs_bwd(g_max: Optional[torch.Tensor], arg: Optional[torch.Tensor], g
         _lib.check(L.dmet_pool_pairs_bwd_f32(_p(g_max), _p(arg), _p(g_mean), partner.data_ptr(), cid.data_ptr(), N, F, C,
                                              gx.data_ptr(), _stream(dev)), "dmet_pool_pairs_bwd_f32")
     return gx
+
+
+# ---- farthest point sampling (csrc/fps.hip) -----------------------------------------------------------------------------
+FPS_THREADS = 1024          # DMET_FPS_THREADS: the workgroup of an event
+FPS_LDS_FLOATS = 36864      # DMET_FPS_LDS_FLOATS
+
+
+def FPS_LDS_NODES(D: int) -> int:
+    """DMET_FPS_LDS_NODES(D): the largest event whose D coordinates and running distances stay in LDS."""
+    return FPS_LDS_FLOATS // (int(D) + 1)
+
+
+def fps(x: torch.Tensor, ptr: torch.Tensor, out_ptr: torch.Tensor, start: Optional[torch.Tensor], M: int) -> torch.Tensor:
+    """out[M] int64 of dmet_fps_f32: event b's out_ptr[b+1] - out_ptr[b] picks as global node ids.  start: int64 [B]
+    event-local first picks, or None (node 0 of every event).  M: out_ptr[B] as the caller knows it."""
+    dev = _require_device(x, ptr, out_ptr, start)
+    L = _lib.load()
+    x = _f32c(x.detach(), "x")
+    if x.dim() != 2:
+        raise ValueError(f"x must be [N, D], got {tuple(x.shape)}")
+    if ptr.dtype != torch.int64 or out_ptr.dtype != torch.int64 or ptr.numel() != out_ptr.numel() or ptr.numel() < 1:
+        raise TypeError("fps: ptr and out_ptr must be int64 vectors over the same events")
+    if start is not None and (start.dtype != torch.int64 or start.numel() != ptr.numel() - 1):
+        raise TypeError("fps: start must be an int64 vector with one entry per event")
+    N, D = x.shape
+    B = ptr.numel() - 1
+    ptr, out_ptr = ptr.contiguous(), out_ptr.contiguous()
+    start = start.contiguous() if start is not None else None
+    out = torch.empty((int(M),), dtype=torch.int64, device=dev)
+    _t = timer.record('fps', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_fps_workspace_bytes(N, B, D), dev)
+        _lib.check(L.dmet_fps_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, out_ptr.data_ptr(),
+                                  start.data_ptr() if start is not None else None, int(M), out.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), _stream(dev)), "dmet_fps_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out

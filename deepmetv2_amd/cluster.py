@@ -1,8 +1,9 @@
-"""Graph builders with the torch_cluster signatures (`knn`, `knn_graph`, `radius`, `radius_graph`).
+"""Graph builders and samplers with the torch_cluster signatures (`knn`, `knn_graph`, `radius`, `radius_graph`, `fps`,
+`nearest`).
 
 Reference call sites (relative to /root/reference): model/graph_met_network.py:63 and
 model/dynamic_reduction_network.py:86,94 (knn_graph); train.py:48, evaluate.py:88, plt_weight.py:122
-(radius_graph).  The kernels are in csrc/knn.hip and csrc/radius.hip; this file is argument checking and the int64 `edge_index` view.
+(radius_graph).  The kernels are in csrc/knn.hip, csrc/radius.hip and csrc/fps.hip; this file is argument checking and the int64 `edge_index` view.
 """
 from __future__ import annotations
 
@@ -287,3 +288,85 @@ def radius_graph(x: torch.Tensor, r: float, batch: Optional[torch.Tensor] = None
     # the [2,E] view is cut from the int32 table: have the build write it (radius_table alone leaves it out when it can)
     return radius_table(x, r, batch, loop, max_num_neighbors, batch_size, int32_rows=True,
                         period=period).edge_index(flow)
+
+
+def _fp32(v: float) -> float:
+    return struct.unpack("f", struct.pack("f", v))[0]
+
+
+def fps(src: torch.Tensor, batch: Optional[torch.Tensor] = None, ratio=0.5, random_start: bool = True,
+        batch_size: Optional[int] = None, ptr: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torch_cluster.fps: farthest point sampling.  int64 [M] global node ids, grouped by event (batch[idx] is sorted); event
+    b contributes m_b = ceil(fp32(n_b) * fp32(ratio_b)) of its n_b nodes: the start node, then again and again the node
+    farthest (rule R1's fp32 squared distance) from everything picked so far, ties to the lowest index (include/dmet.h,
+    dmet_fps_f32; kernel: csrc/fps.hip).  Not differentiable.
+
+    ratio: a float in (0, 1], or a tensor with one entry or one per event (its values are the caller's: a negative entry
+    samples nothing).  ptr: int64 [B+1] event offsets; when given, `batch` is ignored, as upstream does.
+    random_start=True draws every event's start on the device from torch's generator (floor(rand * n_b), clamped);
+    False starts at the event's first node, and the result is then a function of (src, events, ratio) alone.
+
+    The [M] result is sized by one device-to-host read of the sample count (upstream returns an exact-size tensor too),
+    unless `batch` is registered with equal event sizes (register_batch(min_nodes=n, max_nodes=n)) and `ratio` is a float:
+    then M = B * ceil(fp32(n) * fp32(ratio)) is formed on the host and the call never synchronises."""
+    src = _check_x(src)
+    float_ratio = not torch.is_tensor(ratio)
+    if float_ratio:
+        if isinstance(ratio, bool) or not isinstance(ratio, numbers.Real) or not 0.0 < float(ratio) <= 1.0:
+            raise ValueError(f"ratio must be a float in (0, 1] or a tensor, got {ratio!r}")
+        ratio = float(ratio)
+    elif ratio.dim() > 1 or not ratio.is_floating_point():
+        raise ValueError(f"a tensor ratio must be a floating-point scalar or vector, got {ratio.dtype} {tuple(ratio.shape)}")
+    if ptr is not None and (not torch.is_tensor(ptr) or ptr.dtype != torch.int64 or ptr.dim() != 1 or ptr.numel() < 1):
+        raise TypeError("ptr must be a 1-D int64 (torch.long) tensor of B + 1 event offsets")
+    if not src.is_cuda:
+        raise RuntimeError("deepmetv2_amd.fps: src is not on a GPU. The HIP kernel is the only implementation (no CPU "
+                           "fallback); move the inputs to a ROCm device.")
+    _deferred.poll()
+    dev, N = src.device, src.shape[0]
+    n_equal = None
+    if ptr is not None:
+        if ptr.device != dev:
+            raise RuntimeError("deepmetv2_amd: all tensors must live on the same device")
+        B = ptr.numel() - 1
+    else:
+        info = batch_info(batch, N, dev, batch_size)
+        ptr, B = info.ptr, info.num_events
+        if info.min_nodes is not None and info.min_nodes == info.max_nodes:
+            n_equal = info.max_nodes
+    if N == 0 or B == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev)
+    deg = ptr[1:] - ptr[:-1]
+    degf = deg.to(torch.float32)
+    if float_ratio:
+        m = torch.ceil(degf * ratio)
+    else:
+        if ratio.numel() not in (1, B):
+            raise ValueError(f"a tensor ratio must hold 1 or {B} (one per event) entries, got {ratio.numel()}")
+        m = torch.ceil(degf * ratio.to(device=dev, dtype=torch.float32).reshape(-1)).clamp_(min=0)
+    out_ptr = torch.nn.functional.pad(torch.cumsum(m.to(torch.int64), 0), (1, 0))
+    if float_ratio and n_equal is not None:
+        M = B * math.ceil(_fp32(_fp32(float(n_equal)) * _fp32(ratio)))
+    else:
+        M = int(out_ptr[-1].item())
+    start = None
+    if random_start:
+        r = torch.rand(B, device=dev)
+        start = torch.minimum((r * degf).floor().to(torch.int64), deg - 1).clamp_(min=0)
+    return _native.fps(src, ptr, out_ptr, start, M)
+
+
+def nearest(x: torch.Tensor, y: torch.Tensor, batch_x: Optional[torch.Tensor] = None,
+            batch_y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torch_cluster.nearest: for every row of `x` the row of `y` of the same event at the smallest squared distance (rule
+    R1's fp32 chain), ties to the lower y index.  int64 [Nx].  It is the k = 1 column of knn_xy_table(y, x, 1, batch_y,
+    batch_x): no host sync once both batch vectors are registered.  A row of x whose event holds no row of y (or only
+    rows beyond the 1e10 sentinel distance, or non-finite ones) has no answer: its entry is -1 and a deferred check makes
+    the next operator call (or raise_deferred_errors()) raise."""
+    _deferred.poll()
+    nbr = knn_xy_table(y, x, 1, batch_y, batch_x).nbr[:, 0]
+    if nbr.numel() and nbr.is_cuda and not torch.cuda.is_current_stream_capturing():
+        _deferred.post((nbr.min() < 0).to(torch.int32),
+                       "nearest: a row of x found no row of y in its event (an event without y rows, non-finite "
+                       "coordinates, or every candidate beyond the 1e10 sentinel distance): its entry is -1")
+    return nbr.to(torch.int64)

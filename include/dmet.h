@@ -888,6 +888,35 @@ int dmet_pool_pairs_f32(const float *x, int64_t N, int F, const int32_t *partner
 int dmet_pool_pairs_bwd_f32(const float *g_max, const int32_t *arg, const float *g_mean, const int32_t *partner,
                             const int64_t *cid, int64_t N, int F, int64_t C, float *gx, dmet_stream_t stream);
 
+/* ---- Farthest point sampling: replaces torch_cluster.fps (csrc/fps.hip) ----------------------------------------------
+ * dmet_fps_f32: greedy farthest point sampling of every event, one workgroup per event, all picks in one launch.
+ *   Arguments: x[N,D] fp32; event b owns the nodes lo = ptr[b] .. ptr[b+1]-1, n = ptr[b+1] - ptr[b], and writes
+ *   m = out_ptr[b+1] - out_ptr[b] GLOBAL node ids (int64) to out[out_ptr[b] .. out_ptr[b+1]).  M = out_ptr[B] as the
+ *   caller knows it = the size of out (nothing is written at or beyond out[M]).  start[b] = the event-local index of the
+ *   first sample; NULL = 0 for every event; the kernel clamps it into [0, n-1].  An event with n == 0 or m == 0 writes
+ *   nothing.
+ *   Distance: the fp32 chain of rule R1 in coordinate order, d(p, s): a = x[s,c] - x[p,c]; acc = fmaf(a, a, acc) from
+ *   acc = 0.  The chain is bit-symmetric in s and p (a and -a square to the same bits).
+ *   Selection: out[0] = lo + start; dist[p] = d(p, start) for every p of the event; for i = 1 .. m-1: s = the LOWEST
+ *   event-local index whose dist is the maximum, out[i] = lo + s, and every p is updated,
+ *   dist[p] = (d(p,s) < dist[p]) ? d(p,s) : dist[p].  m > n is legal: once every distinct point is taken all distances
+ *   are 0 and the lowest index repeats.
+ *   Numerics: finite coordinates never produce NaN; an overflow gives +inf, which orders normally.  With non-finite
+ *   coordinates the chosen nodes are unspecified, but every id written lies inside its event and the loop ends after m
+ *   iterations.
+ *   Limits: 1 <= D <= DMET_MAX_KNN_DIM, N <= 2^31-1, any n.  An event of up to DMET_FPS_LDS_NODES(D) nodes keeps its
+ *   coordinates (transposed, [D][n]) and running distances in LDS; a larger one keeps the same two arrays in the
+ *   workspace, N (D + 1) floats, and reads them back through L2 (same code, same bits).  Returns -EINVAL with a dmet_last_error() message naming the argument for a bad D, negative
+ *   sizes, a workspace smaller than dmet_fps_workspace_bytes(N, B, D) (monotone in N), or a NULL x / ptr / out_ptr / out
+ *   / ws with N, M > 0; returns 0 at once when B == 0, N == 0 or M == 0.  Asynchronous on `stream`: no host sync, no
+ *   allocation, no global state, capturable in a graph; bit-identical from run to run. */
+#define DMET_FPS_THREADS 1024           /* workgroup size: node p of an event is owned by thread p mod this */
+#define DMET_FPS_LDS_FLOATS 36864       /* 144 KiB: the running distances [n] and the coordinates [D][n] of one event */
+#define DMET_FPS_LDS_NODES(D) (DMET_FPS_LDS_FLOATS / ((D) + 1))
+size_t dmet_fps_workspace_bytes(int64_t N, int B, int D);
+int dmet_fps_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, const int64_t *out_ptr,
+                 const int64_t *start, int64_t M, int64_t *out, void *ws, size_t ws_bytes, dmet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
