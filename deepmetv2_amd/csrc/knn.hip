@@ -36,6 +36,7 @@
 
 #include "common.h"
 #include "knn_common.h"
+#include "knn_key64.h"
 #include "nls_body.h"
 
 namespace dmet {

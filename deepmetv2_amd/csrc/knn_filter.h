@@ -1401,30 +1401,37 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         }
     }
     // sorted top-KP as 64-bit words (distance bits << 32 | j): distances are >= +0, so the unsigned order IS the (d, j)
-    // order of R2, one v_cmp_gt_u64 per slot and no branches.  Empty slots are (sentinel, 0): a candidate at exactly
-    // the sentinel distance (or NaN / inf: larger bit patterns) is never inserted, like the oracle's strict '>'.
-    unsigned long long kk[KP];
+    // order of R2 -- and, the words read as doubles, the f64 order: the insertion is one v_min_f64 + one v_max_f64 per
+    // slot (knn_key64.h), no condition registers and no branches.  Empty slots are (sentinel, 0): a candidate at exactly
+    // the sentinel distance (or NaN / inf: clamped to the sentinel by key64_word) is never inserted, like the oracle's
+    // strict '>'.
+    static_assert(__builtin_bit_cast(unsigned, kKnnSentinel) == kKey64SentinelBits, "knn_key64.h clamps to the sentinel");
+    double kk[KP];
 #pragma unroll
-    for (int p = 0; p < KP; ++p) kk[p] = (unsigned long long)__float_as_uint(kKnnSentinel) << 32;
+    for (int p = 0; p < KP; ++p) kk[p] = key64_as_double(kKey64Empty);
     const int nent = (act && !L.overflow) ? L.cnt : 0;
     int slot = 0;
     unsigned cmask = 0u;
     int ctile = 0;
-    // next candidate of this lane (tiles as appended, mask order inside a tile), -1 when exhausted
+    // The lane's next entry is read one call ahead, unconditionally (slot clamped to the last one: the value is not used
+    // then), and swapped in when the mask runs out: no exec-masked branch around an LDS read and no wait directly behind
+    // it inside a round.
+    uint2 enext = S.ent[0][lane];
+    // next candidate of this lane (tiles as appended, mask order inside a tile) as its row number INSIDE the event
+    // (< ev_hi - ev_lo <= 65536: rows past the event's end have key = +inf and are never set), -1 when exhausted
     auto pop = [&]() __attribute__((always_inline)) -> int32_t {
-        if (cmask == 0u && slot < nent) {
-            const uint2 e = S.ent[slot][lane];
-            cmask = e.x;
-            ctile = (int)(e.y & kF2TileMask);
-            ++slot;
-        }
-        int32_t j = -1;
+        const bool take = cmask == 0u && slot < nent;
+        cmask = take ? enext.x : cmask;
+        ctile = take ? (int)(enext.y & kF2TileMask) : ctile;
+        slot += take ? 1 : 0;
+        enext = S.ent[min(slot, kF2Slots - 1)][lane];
+        int32_t jl = -1;
         if (cmask != 0u) {
             const int r = __builtin_clz(cmask);
             cmask &= ~(0x80000000u >> r);
-            j = ev_lo + ctile * 32 + f2_mask_row(r);   // < ev_hi: rows past the event's end have key = +inf and are never set
+            jl = ctile * 32 + f2_mask_row(r);
         }
-        return j;
+        return jl;
     };
     const float4 *x4 = reinterpret_cast<const float4 *>(a.x);
 #ifdef DMET_RR_PRIO
@@ -1435,9 +1442,10 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         // on it -- none of the cooperative staging of the 32-wide form below, whose register budget (three rounds of
         // half rows in flight) does not carry over; the sweep, not this loop, is the larger part at this width
         for (;;) {
-            const int32_t j = pop();
-            if (!__any(j >= 0)) break;
-            const float4 *row = x4 + (int64_t)(j >= 0 ? j : ev_lo) * (D / 4);
+            const int32_t jl = pop();
+            if (!__any(jl >= 0)) break;
+            const int32_t j = ev_lo + jl;
+            const float4 *row = x4 + (int64_t)(jl >= 0 ? j : ev_lo) * (D / 4);
             float4 v[D / 4];
 #pragma unroll
             for (int c = 0; c < D / 4; ++c) v[c] = row[c];
@@ -1450,14 +1458,7 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
                 df = v[c].z - qrow[4 * c + 2]; dc = __builtin_fmaf(df, df, dc);
                 df = v[c].w - qrow[4 * c + 3]; dc = __builtin_fmaf(df, df, dc);
             }
-            const unsigned long long nk =
-                j >= 0 ? (((unsigned long long)__float_as_uint(dc) << 32) | (unsigned)j) : ~0ull;
-            bool g[KP];
-#pragma unroll
-            for (int p = 0; p < KP; ++p) g[p] = kk[p] > nk;
-#pragma unroll
-            for (int p = KP - 1; p >= 1; --p) kk[p] = g[p - 1] ? kk[p - 1] : (g[p] ? nk : kk[p]);
-            kk[0] = g[0] ? nk : kk[0];
+            key64_insert<KP>(kk, key64_word(__float_as_uint(dc), (unsigned)j, jl >= 0));
         }
     } else {
     // rows are fetched half a row at a time (16 features = 64 bytes): load instruction 4 h + r brings half h of rows
@@ -1466,8 +1467,8 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
 #ifdef DMET_RR_FULLROW
     // experiment: one load instruction brings 8 WHOLE rows (8 lanes x 16 bytes = one 128-byte line per row) instead of 16
     // half rows -- half the line look-ups per round
-    auto fetch = [&](int32_t j) __attribute__((always_inline)) -> HalfRows {
-        const int32_t jc = j >= 0 ? j : ev_lo;
+    auto fetch = [&](int32_t jl) __attribute__((always_inline)) -> HalfRows {
+        const int32_t jc = ev_lo + (jl >= 0 ? jl : 0);
         const int64_t o = lane & 7;
         const int sub = lane >> 3;
         HalfRows R;
@@ -1482,16 +1483,29 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         return R;
     };
 #else
-    auto fetch = [&](int32_t j) __attribute__((always_inline)) -> HalfRows {
-        const int32_t jc = j >= 0 ? j : ev_lo;
-        const int64_t o = 4 * 0 + (lane & 3);
-        const int64_t r0 = (int64_t)__shfl(jc, 0 + (lane >> 2), 64) * 8 + o;
-        const int64_t r1 = (int64_t)__shfl(jc, 16 + (lane >> 2), 64) * 8 + o;
-        const int64_t r2 = (int64_t)__shfl(jc, 32 + (lane >> 2), 64) * 8 + o;
-        const int64_t r3 = (int64_t)__shfl(jc, 48 + (lane >> 2), 64) * 8 + o;
+    // The rows of an item all lie in its event: the event's first row is a scalar base (readfirstlane of both halves,
+    // as f2_load does for the records) and a half row is global_load_dwordx4 v, v_off, s[base:base+1] offset:0 / 64 with
+    // the 32-bit offset 128 x (row inside the event) + 16 x (lane & 3), below 2^23 -- no sign extension and no 64-bit
+    // vector arithmetic per row
+    const uint64_t xb = reinterpret_cast<uint64_t>(a.x + (int64_t)ev_lo * D);
+    const uint64_t xbs = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(xb >> 32)) << 32) |
+                         (unsigned)__builtin_amdgcn_readfirstlane((int)xb);
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef const f32x4 __attribute__((address_space(1))) *GlobalRow;
+    auto ld = [](GlobalRow g, int i) __attribute__((always_inline)) -> float4 {
+        const f32x4 v = g[i];
+        return make_float4(v.x, v.y, v.z, v.w);
+    };
+    auto fetch = [&](int32_t jl) __attribute__((always_inline)) -> HalfRows {
+        const int32_t jc = jl >= 0 ? jl : 0;
+        const unsigned o = 16u * (lane & 3);
+        const GlobalRow r0 = (GlobalRow)(xbs + (uint64_t)(((unsigned)__shfl(jc, 0 + (lane >> 2), 64) << 7) + o));
+        const GlobalRow r1 = (GlobalRow)(xbs + (uint64_t)(((unsigned)__shfl(jc, 16 + (lane >> 2), 64) << 7) + o));
+        const GlobalRow r2 = (GlobalRow)(xbs + (uint64_t)(((unsigned)__shfl(jc, 32 + (lane >> 2), 64) << 7) + o));
+        const GlobalRow r3 = (GlobalRow)(xbs + (uint64_t)(((unsigned)__shfl(jc, 48 + (lane >> 2), 64) << 7) + o));
         HalfRows R;
-        R.v0 = x4[r0]; R.v1 = x4[r1]; R.v2 = x4[r2]; R.v3 = x4[r3];
-        R.v4 = x4[r0 + 4]; R.v5 = x4[r1 + 4]; R.v6 = x4[r2 + 4]; R.v7 = x4[r3 + 4];
+        R.v0 = ld(r0, 0); R.v1 = ld(r1, 0); R.v2 = ld(r2, 0); R.v3 = ld(r3, 0);
+        R.v4 = ld(r0, 4); R.v5 = ld(r1, 4); R.v6 = ld(r2, 4); R.v7 = ld(r3, 4);
         return R;
     };
 #endif
@@ -1508,7 +1522,7 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         }
         return dc;
     };
-    auto round = [&](const HalfRows &R, int32_t j) __attribute__((always_inline)) {
+    auto round = [&](const HalfRows &R, int32_t jl) __attribute__((always_inline)) {
 #ifdef DMET_RR_FULLROW
         float4 *dst = reinterpret_cast<float4 *>(&S.rows[lane >> 3][4 * (lane & 3)]);   // + 8 r rows per register
         constexpr int kS8 = 8 * (kF2RowF + 4) / 4;                                        // float4s per 8 rows
@@ -1539,21 +1553,15 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         wave_sync();
         dc = chain16(dc, 1);
 #endif
-        const unsigned long long nk =
-            j >= 0 ? (((unsigned long long)__float_as_uint(dc) << 32) | (unsigned)j) : ~0ull;
-        bool g[KP];
-#pragma unroll
-        for (int p = 0; p < KP; ++p) g[p] = kk[p] > nk;
-#pragma unroll
-        for (int p = KP - 1; p >= 1; --p) kk[p] = g[p - 1] ? kk[p - 1] : (g[p] ? nk : kk[p]);
-        kk[0] = g[0] ? nk : kk[0];
+        key64_insert<KP>(kk, key64_word(__float_as_uint(dc), (unsigned)(ev_lo + jl), jl >= 0));   // the list keeps global ids
     };
     // Rounds of rows in flight: three (KP <= 16) were chosen in round 2 -- the kernel has since grown to 256 VGPRs + 56
     // bytes of scratch per lane with them (-Rpass-analysis=kernel-resource-usage), i.e. spill traffic inside this
     // latency-bound loop; with two it needs 237 registers and no scratch and the build is 8-10 us faster (second session
     // of round 3).  Measured again with the registers the opaque copies below freed (224 VGPRs at k = 16, no scratch,
     // profiles/r06_knn_operands.md): still slower, 48 213 against 48 519 events/s, every one of six runs below every run
-    // with two rounds.  DMET_RR_THREE brings the third back for A/B
+    // with two rounds.  With the f64 insertion (knn_key64.h) the third round no longer fits at k = 16: 256 VGPRs + 140
+    // bytes of scratch (profiles/r07_knn_rerank.md has the timing).  DMET_RR_THREE brings the third back for A/B
 #ifdef DMET_RR_THREE
     constexpr bool kThreeRounds = KP <= 16;
 #else
@@ -1597,8 +1605,8 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
     int32_t kj[KP];
 #pragma unroll
     for (int p = 0; p < KP; ++p) {
-        kd[p] = __uint_as_float((unsigned)(kk[p] >> 32));
-        kj[p] = kd[p] == kKnnSentinel ? -1 : (int32_t)(unsigned)kk[p];
+        kd[p] = __uint_as_float((unsigned)(key64_as_word(kk[p]) >> 32));
+        kj[p] = kd[p] == kKnnSentinel ? -1 : (int32_t)(unsigned)key64_as_word(kk[p]);
     }
     // Everything below addresses global memory and LDS by the lane and by the query.  Formed from `lane` and `myq` those
     // addresses are invariant in the attempt loop: the compiler computes them at the top of the kernel and carries them
@@ -1788,18 +1796,12 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
             const float od = ld[p];
             const int32_t oj = lj[p];
             // (d, j) pairs of the two candidate ranges are distinct; empty slots are never inserted
-            const unsigned long long nk = oj >= 0 ? (((unsigned long long)__float_as_uint(od) << 32) | (unsigned)oj) : ~0ull;
-            bool g[KP];
-#pragma unroll
-            for (int q = 0; q < KP; ++q) g[q] = kk[q] > nk;
-#pragma unroll
-            for (int q = KP - 1; q >= 1; --q) kk[q] = g[q - 1] ? kk[q - 1] : (g[q] ? nk : kk[q]);
-            kk[0] = g[0] ? nk : kk[0];
+            key64_insert<KP>(kk, key64_word(__float_as_uint(od), (unsigned)oj, oj >= 0));
         }
 #pragma unroll
         for (int p = 0; p < KP; ++p) {
-            kd[p] = __uint_as_float((unsigned)(kk[p] >> 32));
-            kj[p] = kd[p] == kKnnSentinel ? -1 : (int32_t)(unsigned)kk[p];
+            kd[p] = __uint_as_float((unsigned)(key64_as_word(kk[p]) >> 32));
+            kj[p] = kd[p] == kKnnSentinel ? -1 : (int32_t)(unsigned)key64_as_word(kk[p]);
         }
         const float kth = emit(true, false);      // (inside a divergent branch: every lane writes its own rows)
         const float nx = a.nrm[eq];
