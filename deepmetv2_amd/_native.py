@@ -72,6 +72,41 @@ def _f32a(t: torch.Tensor, name: str) -> torch.Tensor:
     return _aligned16(_f32c(t, name))
 
 
+def _ptr(t: Optional[torch.Tensor]):
+    """The address of an optional tensor: None (a null pointer) for None and for an empty tensor."""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _bn_affine_operands(who: str, raw: torch.Tensor, residual: Optional[torch.Tensor], gamma: torch.Tensor,
+                        beta: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor):
+    """The operands of y = residual + BatchNorm(raw) with the statistics given, for every entry that applies or carries the
+    transform (csrc/bn_affine.h): detached contiguous fp32, residual of raw's shape, four vectors of raw.shape[1] elements.
+    Returns (raw, residual or None, [gamma, beta, mean, invstd], whether all of them start on a 16-byte boundary)."""
+    raw = _f32c(raw.detach(), "raw")
+    if raw.dim() != 2:
+        raise ValueError(f"{who}: raw must be 2-D [N, H], got {tuple(raw.shape)}")
+    if residual is not None:
+        residual = _f32c(residual.detach(), "residual")
+        if residual.shape != raw.shape:
+            raise ValueError(f"{who}: residual must have the shape of raw")
+    vec = [_f32c(t.detach(), n) for t, n in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd"))]
+    if any(v.numel() != raw.shape[1] for v in vec):
+        raise ValueError(f"{who}: gamma / beta / mean / invstd must have H elements")
+    aligned = not any(t.data_ptr() % 16 for t in (raw, *vec, *(() if residual is None else (residual,))))
+    return raw, residual, vec, aligned
+
+
+def _pq_tables(N: int, sliced, dev: torch.device):
+    """The outputs of a node-level dense layer 32 -> 32 that another launch carries: (P, Q, layout code of the C ABI,
+    `sliced` as gather_max takes it) -- fp32 [N, 32] (0), fp32 slice-major [4, N, 8] (1), or for sliced == "bf16" P fp32 and
+    Q bf16, both [N, 32] (2: node_linear_split_bf16)."""
+    if sliced == "bf16":
+        return (torch.empty((N, 32), dtype=torch.float32, device=dev), torch.empty((N, 32), dtype=torch.bfloat16, device=dev),
+                2, sliced)
+    PQ = torch.empty((2, 4, N, 8) if sliced else (2, N, 32), dtype=torch.float32, device=dev)
+    return PQ[0], PQ[1], (1 if sliced else 0), bool(sliced)
+
+
 def _ws(nbytes: int, dev: torch.device) -> torch.Tensor:
     return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=dev)
 
@@ -213,7 +248,7 @@ def _knn_run(dev: torch.device, Nq: int, k: int, want_local: bool, ws_bytes: int
     ws = _ws(ws_bytes, dev)
     _t = timer.record('knn', dev)
     with _on(dev):
-        extra = call(nbr, dist, loc.data_ptr() if want_local else None, ws)
+        extra = call(nbr, dist, _ptr(loc), ws)
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
     return nbr, dist, loc, ws, extra
@@ -235,18 +270,11 @@ def _knn(x: torch.Tensor, ptr: torch.Tensor, k: int, stats: Optional[dict], want
             return None
         W, b, sliced = dense            # sliced: False / True, or "bf16" (P fp32, Q bf16: node_linear_split_bf16)
         W = _f32c(W.detach(), "W")
-        bp = _f32c(b.detach(), "b").data_ptr() if b is not None else None
-        if sliced == "bf16":
-            Pt = torch.empty((N, 32), dtype=torch.float32, device=dev)
-            Qt = torch.empty((N, 32), dtype=torch.bfloat16, device=dev)
-            layout = 2
-        else:
-            PQ = torch.empty((2, 4, N, 8) if sliced else (2, N, 32), dtype=torch.float32, device=dev)
-            Pt, Qt = PQ[0], PQ[1]
-            layout, sliced = (1 if sliced else 0), bool(sliced)
+        b = _f32c(b.detach(), "b") if b is not None else None
+        Pt, Qt, layout, sliced = _pq_tables(N, sliced, dev)
         done = ctypes.c_int(0)
         _lib.check(L.dmet_knn_local_dense_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, k, nbr.data_ptr(),
-                                              dist.data_ptr(), loc_p, W.data_ptr(), bp, layout, Pt.data_ptr(),
+                                              dist.data_ptr(), loc_p, W.data_ptr(), _ptr(b), layout, Pt.data_ptr(),
                                               Qt.data_ptr(), ctypes.cast(ctypes.pointer(done), ctypes.c_void_p),
                                               ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_knn_local_dense_f32")
         return (Pt, Qt, sliced) if done.value else None
@@ -386,8 +414,7 @@ def radius(x: torch.Tensor, ptr: torch.Tensor, r: float, max_nbr: int, skip_self
             ws = _ws(L.dmet_radius_workspace_bytes(N), dev)
             with _on(dev):
                 _lib.check(L.dmet_radius_windowed_local_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr,
-                                                            1 if skip_self else 0, 1 if pad else 0,
-                                                            nbr.data_ptr() if nbr is not None else None,
+                                                            1 if skip_self else 0, 1 if pad else 0, _ptr(nbr),
                                                             cnt.data_ptr(), rows16.data_ptr(), stride16, ws.data_ptr(),
                                                             ws.numel(), _stream(dev)), "dmet_radius_windowed_local_f32")
             return nbr, cnt, rows16
@@ -428,7 +455,7 @@ def radius_periodic(x: torch.Tensor, ptr: torch.Tensor, r: float, max_nbr: int, 
         with _on(dev):
             _lib.check(L.dmet_radius_windowed_periodic_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr,
                                                            1 if skip_self else 0, 1 if pad else 0, per_p,
-                                                           nbr.data_ptr() if nbr is not None else None, cnt.data_ptr(),
+                                                           _ptr(nbr), cnt.data_ptr(),
                                                            rows16.data_ptr(), stride16, ws.data_ptr(), ws.numel(),
                                                            _stream(dev)), "dmet_radius_windowed_periodic_f32")
         return nbr, cnt, rows16
@@ -484,31 +511,24 @@ def bn_node_linear_split(raw: torch.Tensor, residual: Optional[torch.Tensor], ga
     L = _lib.load()
     if raw.dim() != 2 or raw.shape[1] != 32 or tuple(W.shape) != (32, 64) or raw.dtype != torch.float32:
         return None
-    raw = _f32c(raw, "raw"); W = _f32c(W, "W")
-    vecs = [_f32c(t, "bn vector") for t in (gamma, beta, mean, invstd)]
-    if residual is not None:
-        residual = _f32c(residual, "residual")
-        if residual.shape != raw.shape:
-            raise ValueError("bn_node_linear_split: residual must have the shape of raw")
-    bp = _f32c(b, "b") if b is not None else None
-    if any(t.data_ptr() % 16 for t in vecs) or raw.data_ptr() % 16 or (residual is not None and residual.data_ptr() % 16):
+    raw, residual, vec, aligned = _bn_affine_operands("bn_node_linear_split", raw, residual, gamma, beta, mean, invstd)
+    W = _f32c(W, "W")
+    b = _f32c(b, "b") if b is not None else None
+    if not aligned:
         return None
     N = raw.shape[0]
     y = torch.empty_like(raw)
-    PQ = torch.empty((2, 4, N, 8) if sliced else (2, N, 32), dtype=torch.float32, device=dev)
+    P, Q, layout, _ = _pq_tables(N, bool(sliced), dev)
     if N == 0:
-        return y, PQ[0], PQ[1]
+        return y, P, Q
     _t = timer.record('node_linear_split', dev)
     with _on(dev):
-        _lib.check(L.dmet_bn_node_linear_split_f32(raw.data_ptr(), residual.data_ptr() if residual is not None else None,
-                                                   vecs[0].data_ptr(), vecs[1].data_ptr(), vecs[2].data_ptr(),
-                                                   vecs[3].data_ptr(), y.data_ptr(), N, 32, W.data_ptr(),
-                                                   bp.data_ptr() if bp is not None else None, 1 if sliced else 0,
-                                                   PQ[0].data_ptr(), PQ[1].data_ptr(), _stream(dev)),
-                   "dmet_bn_node_linear_split_f32")
+        _lib.check(L.dmet_bn_node_linear_split_f32(raw.data_ptr(), _ptr(residual), *[v.data_ptr() for v in vec], y.data_ptr(),
+                                                   N, 32, W.data_ptr(), _ptr(b), layout, P.data_ptr(), Q.data_ptr(),
+                                                   _stream(dev)), "dmet_bn_node_linear_split_f32")
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
-    return y, PQ[0], PQ[1]
+    return y, P, Q
 
 
 def _gather_run(dev: torch.device, key: str, note: Optional[str], entry: str, *args) -> None:
@@ -548,7 +568,7 @@ def gather_max(P: torch.Tensor, Q: torch.Tensor, nbr: torch.Tensor, ptr: Optiona
     out = torch.empty((N, H), dtype=torch.float32, device=dev)
     arg = torch.empty((N, H), dtype=torch.uint8, device=dev) if want_arg else None
     table = (P.data_ptr(), Q.data_ptr(), nbr.data_ptr())
-    local = nbr_local.data_ptr() if nbr_local is not None else None
+    local = _ptr(nbr_local)
     events = (ptr.data_ptr(), ptr.numel() - 1) if ptr is not None else (None, 0)
     outs = (out.data_ptr(), arg.data_ptr() if want_arg else None)
     tail = (N, k, H) + outs
@@ -611,7 +631,7 @@ def gather_max_counted_j16(P: torch.Tensor, Q: torch.Tensor, nbr: torch.Tensor, 
     argj = torch.empty((N, H), dtype=torch.int16, device=dev)
     _gather_run(dev, 'gather_max', "gather_max_lds_kernel, counted rows (radius table; Q slice resident in LDS, winner ids, "
                 "rows ordered by depth" + (", slice-major P/Q)" if sliced else ")"), "dmet_gather_max_counted_lds_j16_f32",
-                P.data_ptr(), Q.data_ptr(), nbr.data_ptr(), cnt.data_ptr(), order.data_ptr() if order is not None else None,
+                P.data_ptr(), Q.data_ptr(), nbr.data_ptr(), cnt.data_ptr(), _ptr(order),
                 ptr.data_ptr(), ptr.numel() - 1, N, k, H, 1 if sliced else 0, out.data_ptr(), argj.data_ptr())
     return out, argj
 
@@ -627,8 +647,8 @@ def gather_max_local_j16(P: torch.Tensor, Q: torch.Tensor, rows16: torch.Tensor,
     _gather_run(dev, 'gather_max', "gather_max_lds_kernel, counted rows (radius table as event-local uint16 rows; Q slice "
                 "resident in LDS, winner ids, rows ordered by depth" + (", slice-major P/Q)" if sliced else ")"),
                 "dmet_gather_max_local_j16_f32", P.data_ptr(), Q.data_ptr(), rows16.data_ptr(), rows16.shape[1],
-                cnt.data_ptr(), order.data_ptr() if order is not None else None, ptr.data_ptr(), ptr.numel() - 1, N, kmax, H,
-                1 if sliced else 0, out.data_ptr(), argj.data_ptr() if argj is not None else None)
+                cnt.data_ptr(), _ptr(order), ptr.data_ptr(), ptr.numel() - 1, N, kmax, H,
+                1 if sliced else 0, out.data_ptr(), _ptr(argj))
     return out, argj
 
 
@@ -726,8 +746,8 @@ def edge_mlp2_bn_bf16(x: torch.Tensor, nbr: torch.Tensor, W1: torch.Tensor, b1: 
         _lib.check(L.dmet_edge_mlp2_bn_bf16(x.data_ptr(), N, Hin, nbr.data_ptr(), k, W1.data_ptr(), ptr(b1), H1, W2.data_ptr(),
                                             ptr(b2), H2, 1 if act2 else 0, 1 if add else 0, ptr(gamma), ptr(beta), float(eps),
                                             float(momentum), ptr(running_mean), ptr(running_var),
-                                            num_batches_tracked.data_ptr() if num_batches_tracked is not None else None,
-                                            1 if training else 0, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+                                            _ptr(num_batches_tracked), 1 if training else 0, out.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), _stream(dev)),
                    "dmet_edge_mlp2_bn_bf16")
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
@@ -787,10 +807,8 @@ def _edge_mlp_fwd(route, x: torch.Tensor, rowptr: torch.Tensor, src: torch.Tenso
         _lib.check(call(x.data_ptr(), N, Hin, rowptr.data_ptr(), src.data_ptr(), tgt.data_ptr(), E,
                         W1.data_ptr(), p(b1), H1, W2.data_ptr(), p(b2), H2, 1 if act2 else 0,
                         _EMLP_AGGR[aggr], int(bn), p(gamma), p(beta), float(eps), float(momentum),
-                        p(running_mean), p(running_var),
-                        num_batches_tracked.data_ptr() if num_batches_tracked is not None else None,
-                        out.data_ptr(), pq.data_ptr(), agg.data_ptr(),
-                        win.data_ptr() if win is not None else None, bnstat.data_ptr(), ws.data_ptr(),
+                        p(running_mean), p(running_var), _ptr(num_batches_tracked),
+                        out.data_ptr(), pq.data_ptr(), agg.data_ptr(), _ptr(win), bnstat.data_ptr(), ws.data_ptr(),
                         ws.numel(), _stream(dev)), f"dmet_edge_mlp_fwd_{route}")
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
@@ -833,17 +851,16 @@ def _edge_mlp_bwd(route, g_out: torch.Tensor, x: torch.Tensor, rowptr: torch.Ten
     gb2 = torch.empty((H2,), dtype=torch.float32, device=dev)
     ggamma = torch.empty((H2,), dtype=torch.float32, device=dev) if bn else None
     gbeta = torch.empty((H2,), dtype=torch.float32, device=dev) if bn else None
-    p = lambda t: t.data_ptr() if t is not None else None
     _t = timer.record(f'edge_mlp_{route}_bwd', dev)
     with _on(dev):
         ws = _ws(getattr(L, f"dmet_edge_mlp_{route}_workspace_bytes")(N, E, Hin, H1, H2), dev)
         call = getattr(L, f"dmet_edge_mlp_bwd_{route}")
         _lib.check(call(x.data_ptr(), N, Hin, rowptr.data_ptr(), src.data_ptr(), tgt.data_ptr(), E,
                         srcptr.data_ptr(), srcperm.data_ptr(), W1.data_ptr(), H1, W2.data_ptr(),
-                        p(_f32c(b2, "b2") if b2 is not None else None), H2, 1 if act2 else 0,
-                        _EMLP_AGGR[aggr], int(bn), pq.data_ptr(), agg.data_ptr(), p(win),
-                        bnstat.data_ptr(), g_out.data_ptr(), p(gx), gpq.data_ptr(), gW2.data_ptr(),
-                        gb2.data_ptr(), p(ggamma), p(gbeta), ws.data_ptr(), ws.numel(), _stream(dev)),
+                        _ptr(_f32c(b2, "b2") if b2 is not None else None), H2, 1 if act2 else 0,
+                        _EMLP_AGGR[aggr], int(bn), pq.data_ptr(), agg.data_ptr(), _ptr(win),
+                        bnstat.data_ptr(), g_out.data_ptr(), _ptr(gx), gpq.data_ptr(), gW2.data_ptr(),
+                        gb2.data_ptr(), _ptr(ggamma), _ptr(gbeta), ws.data_ptr(), ws.numel(), _stream(dev)),
                    f"dmet_edge_mlp_bwd_{route}")
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
@@ -1136,10 +1153,6 @@ def _attention_graph(idx: torch.Tensor, rowptr: Optional[torch.Tensor], Nt: int)
     if idx.dim() != 1 or rowptr.numel() != Nt + 1:
         raise ValueError(f"attention: src must be [E] and rowptr [{Nt + 1}], got {tuple(idx.shape)} and {tuple(rowptr.shape)}")
     return idx, rowptr, int(idx.numel()), 0, int(idx.numel())
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None and t.numel() else None
 
 
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx: torch.Tensor, rowptr: Optional[torch.Tensor] = None,
@@ -1467,7 +1480,7 @@ def encode_fwd(x_cont: torch.Tensor, x_cat: torch.Tensor, params) -> torch.Tenso
     N = x.shape[0]
     h = torch.empty((N, 32), dtype=torch.float32, device=dev)
     with _on(dev):
-        _lib.check(L.dmet_encode_fwd_f32(x.data_ptr(), x.stride(0), xc.data_ptr() if xc is not None else None, N, *[t.data_ptr() for t in ps],
+        _lib.check(L.dmet_encode_fwd_f32(x.data_ptr(), x.stride(0), _ptr(xc), N, *[t.data_ptr() for t in ps],
                                          h.data_ptr(), _stream(dev)), "dmet_encode_fwd_f32")
     return h
 
@@ -1485,7 +1498,7 @@ def encode_bwd(x_cont: torch.Tensor, x_cat: torch.Tensor, params, h: torch.Tenso
         return [g.zero_() for g in grads]
     with _on(dev):
         ws = _ws(L.dmet_encode_bwd_workspace_bytes(N), dev)
-        _lib.check(L.dmet_encode_bwd_f32(x.data_ptr(), x.stride(0), xc.data_ptr() if xc is not None else None, N, *[t.data_ptr() for t in ps],
+        _lib.check(L.dmet_encode_bwd_f32(x.data_ptr(), x.stride(0), _ptr(xc), N, *[t.data_ptr() for t in ps],
                                          h.data_ptr(), g_h.data_ptr(), *[g.data_ptr() for g in grads], ws.data_ptr(),
                                          ws.numel(), _stream(dev)), "dmet_encode_bwd_f32")
         _defer_keep(dev, ws)
@@ -1518,7 +1531,7 @@ def encode_bn_bwd(x_cont: torch.Tensor, x_cat: torch.Tensor, params, h: torch.Te
                                            st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr(), st[3].data_ptr(),
                                            ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_bn_bwd_stats_f32")
         ws2 = _ws(L.dmet_encode_bwd_workspace_bytes(N), dev)
-        _lib.check(L.dmet_encode_bn_bwd_f32(x.data_ptr(), x.stride(0), xc.data_ptr() if xc is not None else None, N,
+        _lib.check(L.dmet_encode_bn_bwd_f32(x.data_ptr(), x.stride(0), _ptr(xc), N,
                                             *[t.data_ptr() for t in ps], h.data_ptr(), g_y.data_ptr(), gamma.data_ptr(),
                                             mean.data_ptr(), invstd.data_ptr(), st[2].data_ptr(), st[3].data_ptr(),
                                             *[g.data_ptr() for g in grads],
@@ -1556,10 +1569,8 @@ def bn_fwd(x: torch.Tensor, residual: Optional[torch.Tensor], gamma: torch.Tenso
             if num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1 or num_batches_tracked.device != dev:
                 raise ValueError("bn_fwd: num_batches_tracked must be an int64 scalar on x's device")
             nbt = num_batches_tracked.data_ptr()
-        _lib.check(L.dmet_bn_fwd_tracked_f32(x.data_ptr(), residual.data_ptr() if residual is not None else None, N, H,
-                                             gamma.data_ptr(), beta.data_ptr(), float(eps), float(momentum),
-                                             running_mean.data_ptr() if running_mean is not None else None,
-                                             running_var.data_ptr() if running_var is not None else None, nbt,
+        _lib.check(L.dmet_bn_fwd_tracked_f32(x.data_ptr(), _ptr(residual), N, H, gamma.data_ptr(), beta.data_ptr(),
+                                             float(eps), float(momentum), _ptr(running_mean), _ptr(running_var), nbt,
                                              1 if training else 0, y.data_ptr(), stats[0].data_ptr(),
                                              stats[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
                    "dmet_bn_fwd_tracked_f32")
@@ -1577,10 +1588,8 @@ def bn_stats(x: torch.Tensor, eps: float, momentum: float, running_mean: Optiona
     stats = torch.empty((2, H), dtype=torch.float32, device=dev)
     with _on(dev):
         ws = _ws(L.dmet_bn_workspace_bytes(N, H), dev)
-        _lib.check(L.dmet_bn_stats_f32(x.data_ptr(), N, H, float(eps), float(momentum),
-                                       running_mean.data_ptr() if running_mean is not None else None,
-                                       running_var.data_ptr() if running_var is not None else None,
-                                       num_batches_tracked.data_ptr() if num_batches_tracked is not None else None,
+        _lib.check(L.dmet_bn_stats_f32(x.data_ptr(), N, H, float(eps), float(momentum), _ptr(running_mean),
+                                       _ptr(running_var), _ptr(num_batches_tracked),
                                        stats[0].data_ptr(), stats[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
                    "dmet_bn_stats_f32")
     return stats[0], stats[1]
@@ -1593,20 +1602,15 @@ def bn_apply(x: torch.Tensor, residual: Optional[torch.Tensor], gamma: torch.Ten
     16-byte boundary (views into somebody else's flat buffer) are copied first."""
     dev = _require_device(x, gamma, beta, mean, invstd)
     L = _lib.load()
-    x = _f32a(x, "x")
+    x, residual, vec, aligned = _bn_affine_operands("bn_apply", x, residual, gamma, beta, mean, invstd)
+    if not aligned:
+        x, vec = _aligned16(x), [_aligned16(v) for v in vec]
+        residual = _aligned16(residual) if residual is not None else None
     N, H = x.shape
-    if residual is not None:
-        residual = _f32a(residual, "residual")
-        if residual.shape != x.shape:
-            raise ValueError("bn_apply: residual must have the shape of x")
-    vec = [_f32a(t, n) for t, n in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd"))]
-    if any(v.numel() != H for v in vec):
-        raise ValueError("bn_apply: gamma / beta / mean / invstd must have H elements")
     y = torch.empty_like(x)
     with _on(dev):
-        _lib.check(L.dmet_bn_apply_f32(x.data_ptr(), residual.data_ptr() if residual is not None else None, N, H,
-                                       vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(),
-                                       y.data_ptr(), _stream(dev)), "dmet_bn_apply_f32")
+        _lib.check(L.dmet_bn_apply_f32(x.data_ptr(), _ptr(residual), N, H, *[v.data_ptr() for v in vec], y.data_ptr(),
+                                       _stream(dev)), "dmet_bn_apply_f32")
     return y
 
 
@@ -1631,48 +1635,30 @@ def bn_knn_local_dense(raw: torch.Tensor, residual: Optional[torch.Tensor], gamm
     matrix-core path): the caller then applies the transform and builds the graph itself."""
     dev = _require_device(raw, ptr)
     L = _lib.load()
-    raw = _f32c(raw.detach(), "raw")
+    raw, residual, vec, _ = _bn_affine_operands("bn_knn_local_dense", raw, residual, gamma, beta, mean, invstd)
     N, D = raw.shape
     B = ptr.numel() - 1
     if D != 32 or N == 0 or B == 0 or k > 20:
         return None
-    if residual is not None:
-        residual = _f32c(residual.detach(), "residual")
-    gamma = _f32c(gamma.detach(), "gamma"); beta = _f32c(beta.detach(), "beta")
     y = torch.empty_like(raw)
-    nbr = torch.empty((N, k), dtype=torch.int32, device=dev)
-    dist = torch.empty((N, k), dtype=torch.float32, device=dev)
-    loc = torch.empty((N, k), dtype=torch.int16, device=dev)
-    Wp = bp = Pp = Qp = None
-    layout, Pt, Qt, sliced = 0, None, None, False
+    W = b = Pt = Qt = None
+    layout, sliced = 0, False
     if dense is not None and tuple(dense[0].shape) == (32, 64):
         W, b, sliced = dense
         W = _f32c(W.detach(), "W")
-        Wp = W.data_ptr()
-        bp = _f32c(b.detach(), "b").data_ptr() if b is not None else None
-        if sliced == "bf16":
-            Pt = torch.empty((N, 32), dtype=torch.float32, device=dev)
-            Qt = torch.empty((N, 32), dtype=torch.bfloat16, device=dev)
-            layout = 2
-        else:
-            PQ = torch.empty((2, 4, N, 8) if sliced else (2, N, 32), dtype=torch.float32, device=dev)
-            Pt, Qt = PQ[0], PQ[1]
-            layout, sliced = (1 if sliced else 0), bool(sliced)
-        Pp, Qp = Pt.data_ptr(), Qt.data_ptr()
-    nb = L.dmet_knn_workspace_bytes(N, B, D, k)
-    ws = _ws(nb, dev)
+        b = _f32c(b.detach(), "b") if b is not None else None
+        Pt, Qt, layout, sliced = _pq_tables(N, sliced, dev)
     done, fused = ctypes.c_int(0), ctypes.c_int(0)
-    _t = timer.record('knn', dev)
-    with _on(dev):
-        _lib.check(L.dmet_bn_knn_local_dense_f32(raw.data_ptr(), residual.data_ptr() if residual is not None else None,
-                                                 gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                                 y.data_ptr(), ptr.data_ptr(), B, N, D, k, nbr.data_ptr(), dist.data_ptr(),
-                                                 loc.data_ptr(), Wp, bp, layout, Pp, Qp,
+
+    def call(nbr, dist, loc_p, ws):     # an unaligned operand goes to the entry as it is: the entry declines
+        _lib.check(L.dmet_bn_knn_local_dense_f32(raw.data_ptr(), _ptr(residual), *[v.data_ptr() for v in vec], y.data_ptr(),
+                                                 ptr.data_ptr(), B, N, D, k, nbr.data_ptr(), dist.data_ptr(), loc_p, _ptr(W),
+                                                 _ptr(b), layout, _ptr(Pt), _ptr(Qt),
                                                  ctypes.cast(ctypes.pointer(done), ctypes.c_void_p),
                                                  ctypes.cast(ctypes.pointer(fused), ctypes.c_void_p), ws.data_ptr(),
                                                  ws.numel(), _stream(dev)), "dmet_bn_knn_local_dense_f32")
-    if _t is not None:
-        _t.record(torch.cuda.current_stream(dev))
+
+    nbr, dist, loc, _, _ = _knn_run(dev, N, k, True, L.dmet_knn_workspace_bytes(N, B, D, k), call)
     if not fused.value:
         return None
     return y, nbr, dist, loc, ((Pt, Qt, sliced) if done.value else None)
@@ -1723,19 +1709,14 @@ def edgeconv_linear_bwd(x: torch.Tensor, weight: torch.Tensor, g_out: torch.Tens
                 raise ValueError("edgeconv_linear_bwd: g_add must have the shape of x")
         if gq_sliced:
             _lib.check(L.dmet_edgeconv_linear_bwd_sliced_f32(x.data_ptr(), weight.data_ptr(), g_out.data_ptr(),
-                                                             arg.data_ptr() if arg is not None else None, int(j16), gQ.data_ptr(),
-                                                             g_add.data_ptr() if g_add is not None else None, N, H,
-                                                             gx.data_ptr(), gW.data_ptr(), gb.data_ptr() if gb is not None else None,
+                                                             _ptr(arg), int(j16), gQ.data_ptr(), _ptr(g_add), N, H,
+                                                             gx.data_ptr(), gW.data_ptr(), _ptr(gb),
                                                              ws.data_ptr(), ws.numel(), _stream(dev)),
                        "dmet_edgeconv_linear_bwd_sliced_f32")
         else:
             entry = L.dmet_edgeconv_linear_bwd_add_j16_f32 if j16 else L.dmet_edgeconv_linear_bwd_add_f32
-            _lib.check(entry(x.data_ptr(), weight.data_ptr(), g_out.data_ptr(),
-                             arg.data_ptr() if arg is not None else None, gQ.data_ptr(),
-                             g_add.data_ptr() if g_add is not None else None, N, H,
-                             gx.data_ptr(), gW.data_ptr(),
-                             gb.data_ptr() if gb is not None else None,
-                             ws.data_ptr(), ws.numel(), _stream(dev)),
+            _lib.check(entry(x.data_ptr(), weight.data_ptr(), g_out.data_ptr(), _ptr(arg), gQ.data_ptr(), _ptr(g_add), N, H,
+                             gx.data_ptr(), gW.data_ptr(), _ptr(gb), ws.data_ptr(), ws.numel(), _stream(dev)),
                        "dmet_edgeconv_linear_bwd_add_j16_f32" if j16 else "dmet_edgeconv_linear_bwd_add_f32")
         _defer_keep(dev, ws)
     return gx, gW, gb
@@ -1756,7 +1737,7 @@ def gather_max_bwd_lds(g_out: torch.Tensor, arg: torch.Tensor, nbr: torch.Tensor
     sliced = bool(sliced and H == 32)
     gQ = torch.empty((8, N, 4) if sliced else (N, H), dtype=torch.float32, device=dev)
     _gather_run(dev, 'gather_max_bwd', None, "dmet_gather_max_bwd_sliced_f32" if sliced else "dmet_gather_max_bwd_lds16_cap_f32",
-                g_out.data_ptr(), arg.data_ptr(), nbr.data_ptr(), nbr_local.data_ptr() if nbr_local is not None else None,
+                g_out.data_ptr(), arg.data_ptr(), nbr.data_ptr(), _ptr(nbr_local),
                 ptr.data_ptr(), ptr.numel() - 1, N, nbr.shape[1], H, gQ.data_ptr(), int(max_nodes or 0))
     return gQ
 
@@ -1811,21 +1792,17 @@ def bn_head_fwd(raw: torch.Tensor, residual: Optional[torch.Tensor], gamma: torc
     head_fwd(emb, params) (dmet_bn_head_fwd_f32); None when nothing was launched (the caller keeps the two steps)."""
     dev = _require_device(raw)
     L = _lib.load()
-    raw = _f32c(raw.detach(), "raw")
     if raw.dim() != 2 or raw.shape[1] != 32:
         return None
-    if residual is not None:
-        residual = _f32c(residual.detach(), "residual")
-    gamma = _f32c(gamma.detach(), "gamma"); beta = _f32c(beta.detach(), "beta")
+    raw, residual, vec, _ = _bn_affine_operands("bn_head_fwd", raw, residual, gamma, beta, mean, invstd)
     ps = _head_params(params, dev)
     N = raw.shape[0]
     emb = torch.empty_like(raw)
     out = torch.empty((N,), dtype=torch.float32, device=dev)
     fused = ctypes.c_int(0)
-    with _on(dev):
-        _lib.check(L.dmet_bn_head_fwd_f32(raw.data_ptr(), residual.data_ptr() if residual is not None else None,
-                                          gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                          emb.data_ptr(), N, *[t.data_ptr() for t in ps], out.data_ptr(),
+    with _on(dev):   # an unaligned operand goes to the entry as it is: the entry declines
+        _lib.check(L.dmet_bn_head_fwd_f32(raw.data_ptr(), _ptr(residual), *[v.data_ptr() for v in vec], emb.data_ptr(), N,
+                                          *[t.data_ptr() for t in ps], out.data_ptr(),
                                           ctypes.cast(ctypes.pointer(fused), ctypes.c_void_p), _stream(dev)),
                    "dmet_bn_head_fwd_f32")
     return (emb, out) if fused.value else None
@@ -1862,7 +1839,7 @@ def table_rowptr(nbr: torch.Tensor, cnt: Optional[torch.Tensor]) -> torch.Tensor
     if N:
         deg = torch.empty((N,), dtype=torch.int32, device=dev)
         with _on(dev):
-            _lib.check(L.dmet_table_degree(nbr.data_ptr(), cnt.data_ptr() if cnt is not None else None, N, k,
+            _lib.check(L.dmet_table_degree(nbr.data_ptr(), _ptr(cnt), N, k,
                                            deg.data_ptr(), _stream(dev)), "dmet_table_degree")
         torch.cumsum(deg, 0, dtype=torch.int32, out=rowptr[1:])
     return rowptr
@@ -1879,12 +1856,10 @@ def table_edges(nbr: torch.Tensor, cnt: Optional[torch.Tensor], rowptr: torch.Te
     t32 = torch.empty((num_edges,), dtype=torch.int32, device=dev) if want_int32 else None
     if N and num_edges:
         with _on(dev):
-            _lib.check(L.dmet_table_edges(nbr.data_ptr(), cnt.data_ptr() if cnt is not None else None, rowptr.data_ptr(),
-                                          N, k, 1 if swap else 0,
+            _lib.check(L.dmet_table_edges(nbr.data_ptr(), _ptr(cnt), rowptr.data_ptr(), N, k, 1 if swap else 0,
                                           ei[0].data_ptr() if ei is not None else None,
                                           ei[1].data_ptr() if ei is not None else None,
-                                          s32.data_ptr() if s32 is not None else None,
-                                          t32.data_ptr() if t32 is not None else None, _stream(dev)), "dmet_table_edges")
+                                          _ptr(s32), _ptr(t32), _stream(dev)), "dmet_table_edges")
     return ei, s32, t32
 
 
@@ -1906,10 +1881,10 @@ def graclus(rowptr: torch.Tensor, col: torch.Tensor, weight: Optional[torch.Tens
     _t = timer.record('graclus', dev)
     with _on(dev):
         ws = _ws(L.dmet_graclus_workspace_bytes(N), dev)
-        _lib.check(L.dmet_graclus_f32(rowptr.data_ptr(), col.data_ptr(), weight.data_ptr() if weight is not None else None,
+        _lib.check(L.dmet_graclus_f32(rowptr.data_ptr(), col.data_ptr(), _ptr(weight),
                                       ptr.data_ptr(), B, N, int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_rounds),
                                       cluster.data_ptr(), partner.data_ptr(),
-                                      rounds.data_ptr() if rounds is not None else None, ws.data_ptr(), ws.numel(),
+                                      _ptr(rounds), ws.data_ptr(), ws.numel(),
                                       _stream(dev)), "dmet_graclus_f32")
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
@@ -1976,11 +1951,10 @@ def pool_pairs(x: torch.Tensor, partner: torch.Tensor, cid: torch.Tensor, ptr: O
     arg = torch.empty((C, F), dtype=torch.int32, device=dev) if want_max else None
     out_mean = torch.empty((C, F), dtype=torch.float32, device=dev) if want_mean else None
     pb = torch.empty((C,), dtype=torch.int64, device=dev) if want_batch else None
-    _p = lambda t: t.data_ptr() if t is not None else None
     _t = timer.record('pool_pairs', dev)
     with _on(dev):
-        _lib.check(L.dmet_pool_pairs_f32(x.data_ptr(), N, F, partner.data_ptr(), cid.data_ptr(), _p(ptr), B, C,
-                                         _p(out_max), _p(arg), _p(out_mean), _p(pb), _stream(dev)), "dmet_pool_pairs_f32")
+        _lib.check(L.dmet_pool_pairs_f32(x.data_ptr(), N, F, partner.data_ptr(), cid.data_ptr(), _ptr(ptr), B, C,
+                                         _ptr(out_max), _ptr(arg), _ptr(out_mean), _ptr(pb), _stream(dev)), "dmet_pool_pairs_f32")
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
     return out_max, arg, out_mean, pb
@@ -1994,9 +1968,8 @@ def pool_pairs_bwd(g_max: Optional[torch.Tensor], arg: Optional[torch.Tensor], g
     g_max = _f32c(g_max, "g_max") if g_max is not None else None
     g_mean = _f32c(g_mean, "g_mean") if g_mean is not None else None
     gx = torch.empty((N, F), dtype=torch.float32, device=dev)
-    _p = lambda t: t.data_ptr() if t is not None else None
     with _on(dev):
-        _lib.check(L.dmet_pool_pairs_bwd_f32(_p(g_max), _p(arg), _p(g_mean), partner.data_ptr(), cid.data_ptr(), N, F, C,
+        _lib.check(L.dmet_pool_pairs_bwd_f32(_ptr(g_max), _ptr(arg), _ptr(g_mean), partner.data_ptr(), cid.data_ptr(), N, F, C,
                                              gx.data_ptr(), _stream(dev)), "dmet_pool_pairs_bwd_f32")
     return gx
 
@@ -2032,7 +2005,7 @@ def fps(x: torch.Tensor, ptr: torch.Tensor, out_ptr: torch.Tensor, start: Option
     with _on(dev):
         ws = _ws(L.dmet_fps_workspace_bytes(N, B, D), dev)
         _lib.check(L.dmet_fps_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, out_ptr.data_ptr(),
-                                  start.data_ptr() if start is not None else None, int(M), out.data_ptr(), ws.data_ptr(),
+                                  _ptr(start), int(M), out.data_ptr(), ws.data_ptr(),
                                   ws.numel(), _stream(dev)), "dmet_fps_f32")
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))

@@ -40,10 +40,10 @@ __global__ __launch_bounds__(256) void node_linear_split_kernel(const float *__r
     node_linear_split_wave<HIN, HOUT, SLICED>(x, N, W, bias, P, Q, tpose[SLICED ? wv : 0], wave, nwaves, threadIdx.x & 63);
 }
 
-// the same with the rows FORMED as residual + BatchNorm(raw) and written to aff.y (NlsAffine, csrc/nls_body.h)
+// the same with the rows FORMED as residual + BatchNorm(raw) and written to y (AFFINE, csrc/nls_body.h)
 template <int HIN, int HOUT, bool SLICED>
-__global__ __launch_bounds__(256) void node_linear_split_bn_kernel(NlsAffine aff, int64_t N, const float *__restrict__ W,
-                                                                    const float *__restrict__ bias,
+__global__ __launch_bounds__(256) void node_linear_split_bn_kernel(BnAffine aff, float *y, int64_t N,
+                                                                    const float *__restrict__ W, const float *__restrict__ bias,
                                                                     float *__restrict__ P, float *__restrict__ Q)
 {
     __shared__ __attribute__((aligned(16))) float tpose[SLICED ? 4 : 1][SLICED ? kNlsLdsFloats : 1];
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void node_linear_split_bn_kernel(NlsAffine aff
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + wv;
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
     node_linear_split_wave<HIN, HOUT, SLICED, true>(nullptr, N, W, bias, P, Q, tpose[SLICED ? wv : 0], wave, nwaves,
-                                                    threadIdx.x & 63, aff);
+                                                    threadIdx.x & 63, aff, y);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1235,19 +1235,18 @@ extern "C" int dmet_bn_node_linear_split_f32(const float *raw, const float *resi
     if (N == 0) return 0;
     DMET_REQUIRE(H == 32, "dmet_bn_node_linear_split_f32: H=%d (built for 32 -> 32)", H);
     DMET_REQUIRE(raw && gamma && beta && mean && invstd && y && W && P && Q, "dmet_bn_node_linear_split_f32: null pointer");
-    DMET_REQUIRE(aligned16(raw) && aligned16(y) && aligned16(P) && aligned16(Q) && aligned16(gamma) && aligned16(beta) &&
-                     aligned16(mean) && aligned16(invstd) && (!residual || aligned16(residual)),
+    const BnAffine aff{raw, residual, gamma, beta, mean, invstd};
+    DMET_REQUIRE(bn_affine_aligned16(aff, y) && aligned16(P) && aligned16(Q),
                  "dmet_bn_node_linear_split_f32: pointers must be 16-B aligned");
-    NlsAffine aff{raw, residual, gamma, beta, mean, invstd, y};
     const int64_t ntiles = (N + 31) / 32;
     int64_t blocks = (ntiles + 3) / 4;
     if (blocks > num_cus()) blocks = num_cus();
     if (blocks < 1) blocks = 1;
     hipStream_t st = as_stream(stream);
     if (sliced)
-        hipLaunchKernelGGL((node_linear_split_bn_kernel<32, 32, true>), dim3((unsigned)blocks), dim3(256), 0, st, aff, N, W, b, P, Q);
+        hipLaunchKernelGGL((node_linear_split_bn_kernel<32, 32, true>), dim3((unsigned)blocks), dim3(256), 0, st, aff, y, N, W, b, P, Q);
     else
-        hipLaunchKernelGGL((node_linear_split_bn_kernel<32, 32, false>), dim3((unsigned)blocks), dim3(256), 0, st, aff, N, W, b, P, Q);
+        hipLaunchKernelGGL((node_linear_split_bn_kernel<32, 32, false>), dim3((unsigned)blocks), dim3(256), 0, st, aff, y, N, W, b, P, Q);
     DMET_LAUNCH_CHECK("node_linear_split_bn_kernel");
     return 0;
 }

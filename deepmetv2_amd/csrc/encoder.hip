@@ -13,6 +13,7 @@
 // second kernel => bitwise reproducible, no float atomics).
 #include <stdlib.h>
 
+#include "bn_affine.h"
 #include "common.h"
 
 namespace dmet {
@@ -445,7 +446,8 @@ __device__ __forceinline__ float column_half_sum32(const float *__restrict__ A, 
 }
 
 // BNB (dmet_encode_bn_bwd_f32): `gh` is the gradient with respect to bn_all's OUTPUT; the BatchNorm's backward
-// transform  g = gamma * invstd * (g_y - mean_g - (h - mean) * invstd * mean_gx)  (expression of bn_bwd_apply_kernel) is
+// transform  g = gamma * invstd * (g_y - mean_g - (h - mean) * invstd * mean_gx)  (bn_bwd4 of bn_affine.h, which
+// bn_bwd_apply_kernel calls) is
 // applied to the values as they are loaded -- h, the BatchNorm's input, is the encoder's own output, which this kernel
 // reads anyway: the transform pass (17 us, 111 MB) disappears.
 struct EncBnBwd {
@@ -546,19 +548,16 @@ __global__ __launch_bounds__(64 * kEncBwdWaves, 2) void encode_bwd_mfma_kernel(c
             const float4 *hp = reinterpret_cast<const float4 *>(hout + ii * 32 + 4 * hh);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const float4 gv = gp[2 * g], hv = hp[2 * g];
-                float gg[4] = {gv.x, gv.y, gv.z, gv.w};
-                const float hh4[4] = {hv.x, hv.y, hv.z, hv.w};
+                float4 gv = gp[2 * g];
+                const float4 hv = hp[2 * g];
                 if constexpr (BNB) {
                     const int c0 = 8 * g + 4 * hh;      // this lane's channels of group g
                     const float4 ga = *reinterpret_cast<const float4 *>(bnb.gamma + c0), mu = *reinterpret_cast<const float4 *>(bnb.mean + c0);
                     const float4 is = *reinterpret_cast<const float4 *>(bnb.invstd + c0), mg = *reinterpret_cast<const float4 *>(bnb.mean_g + c0);
                     const float4 mx = *reinterpret_cast<const float4 *>(bnb.mean_gx + c0);
-                    gg[0] = ga.x * is.x * (gg[0] - mg.x - (hh4[0] - mu.x) * is.x * mx.x);
-                    gg[1] = ga.y * is.y * (gg[1] - mg.y - (hh4[1] - mu.y) * is.y * mx.y);
-                    gg[2] = ga.z * is.z * (gg[2] - mg.z - (hh4[2] - mu.z) * is.z * mx.z);
-                    gg[3] = ga.w * is.w * (gg[3] - mg.w - (hh4[3] - mu.w) * is.w * mx.w);
+                    gv = bn_bwd4(gv, hv, ga, mu, is, mg, mx);
                 }
+                const float gg[4] = {gv.x, gv.y, gv.z, gv.w}, hh4[4] = {hv.x, hv.y, hv.z, hv.w};
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const float d = hh4[u] > 0.0f ? 1.0f : (hh4[u] + 1.0f);

@@ -918,7 +918,7 @@ struct KnnBuild {
     size_t ws_bytes;
     hipStream_t st;
     KnnRider rider;             // P != nullptr: the dense layer to carry if the build takes the second filter form
-    KnnAffine affine;           // raw != nullptr: the BatchNorm transform the prep launch has to apply (x is its output)
+    BnAffine affine;            // raw != nullptr: the BatchNorm transform the prep launch has to apply (x is its output)
     KnnSizeHint hint;
 };
 
@@ -1045,18 +1045,18 @@ inline float knn_cut_scale()
 // carries; nullptr: none.
 template <int KF, int NH = 1>
 int launch_filter(const KnnFilterArgs &f, const KnnWorkspace &w, int simds, const KnnPlanOut &px, const KnnPlanOut &pf,
-                  hipStream_t st, const KnnRider *rider, const KnnAffine *affine)
+                  hipStream_t st, const KnnRider *rider, const BnAffine *affine)
 {
     const int slots = simds * kF2WavesPerSimd;   // filter wavefronts per SIMD
     if (affine) {
         if constexpr (NH == 1)
             hipLaunchKernelGGL((knn_prep_kernel<1, true>), dim3((unsigned)((w.nrec * kWave + 255) / 256 + 2)), dim3(256), 0, st, f.x,
                                f.ptr, f.B, f.N, w.nrm, w.rec, w.nrec, reinterpret_cast<uint32_t *>(w.flags), w.zero_bytes, px,
-                               pf, f.form2, *affine);
+                               pf, f.form2, *affine, 0);
     } else {
         hipLaunchKernelGGL((knn_prep_kernel<NH>), dim3((unsigned)((w.nrec * kWave + 255) / 256 + 2)), dim3(256), 0, st, f.x,
                            f.ptr, f.B, f.N, w.nrm, w.rec, w.nrec, reinterpret_cast<uint32_t *>(w.flags), w.zero_bytes, px, pf,
-                           f.form2, KnnAffine{});
+                           f.form2, BnAffine{}, 0);
     }
     DMET_LAUNCH_CHECK("knn_prep_kernel");
     const int64_t ftiles_max = (f.N + kFQ - 1) / kFQ + f.B;
@@ -1151,7 +1151,7 @@ KnnOutcome launch_knn(const KnnBuild &r, const KnnWorkspace &w)
         f.no_rerank = (f.form2 && r.hint.min_nodes >= kF2MinNodes && r.hint.max_nodes >= r.hint.min_nodes &&
                        r.hint.max_nodes <= kF2MaxNodes) ? 1 : 0;
         // the affine rides in the prep launch and the rider in the second filter form, both at 32 features only
-        const KnnAffine *affine = (NH == 1 && r.affine.raw) ? &r.affine : nullptr;
+        const BnAffine *affine = (NH == 1 && r.affine.raw) ? &r.affine : nullptr;
         const KnnRider *rider = (NH == 1 && f.form2 && r.rider.P) ? &r.rider : nullptr;
         int rc = 0;
         if constexpr (DP == 32 || DP == 64) {
@@ -1252,7 +1252,7 @@ static KnnBuild local_request(const float *x, const int64_t *ptr, int B, int64_t
                               uint16_t *nbr16, void *ws, size_t ws_bytes, dmet_stream_t stream)
 {
     return KnnBuild{x, ptr, N, KnnQuerySet{nullptr, nullptr}, nullptr, B, D, k, nbr, dist, nbr16, ws, ws_bytes,
-                    as_stream(stream), KnnRider{}, KnnAffine{}, KnnSizeHint{}};
+                    as_stream(stream), KnnRider{}, BnAffine{}, KnnSizeHint{}};
 }
 
 // 0: build it; 1: an empty problem, nothing to do; < 0: refused
@@ -1353,16 +1353,14 @@ extern "C" int dmet_bn_knn_local_dense_f32(const float *raw, const float *residu
     DMET_REQUIRE(raw && gamma && beta && mean && invstd && y, "dmet_bn_knn_local_dense_f32: null pointer");
     // only the matrix-core path has the prep launch the transform rides in: any other build leaves everything to the
     // caller, the size hint included (the unfused build that the caller then runs needs it)
-    const bool eligible = D == 32 && k >= 1 && k <= 20 && N > 0 && B > 0 && filter_mode() != 0 && aligned16(raw) && aligned16(y) &&
-                          aligned16(gamma) && aligned16(beta) && aligned16(mean) && aligned16(invstd) &&
-                          (!residual || aligned16(residual));
-    if (!eligible) return 0;
+    const BnAffine affine{raw, residual, gamma, beta, mean, invstd};
+    if (!(D == 32 && k >= 1 && k <= 20 && N > 0 && B > 0 && filter_mode() != 0 && bn_affine_aligned16(affine, y))) return 0;
     if (W) {
         if (const int rc = rider_checks(W, layout, P, Q)) return rc;
     }
     KnnBuild r = local_request(y, ptr, B, N, D, k, nbr, dist, nbr16, ws, ws_bytes, stream);
     r.hint = take_size_hint();
-    r.affine = KnnAffine{raw, residual, gamma, beta, mean, invstd};
+    r.affine = affine;
     if (W) r.rider = make_rider(r, W, bias, layout, P, Q);
     const KnnOutcome o = local_build(r);
     *dense_done = (o.rc == 0 && o.rider_done) ? 1 : 0;
@@ -1449,5 +1447,5 @@ extern "C" int dmet_knn_xy_f32(const float *x, const int64_t *ptr_x, int64_t Nx,
     DMET_REQUIRE((x || Nx == 0) && ptr_x && y && ptr_y && nbr && dist && ws, "dmet_knn_xy_f32: null pointer");
     DMET_REQUIRE(ws_bytes >= dmet_knn_xy_workspace_bytes(Nx, Ny, B, D, k), "dmet_knn_xy_f32: workspace too small");
     return knn_build(KnnBuild{x, ptr_x, Ny, KnnQuerySet{y, ptr_y}, any ? &per : nullptr, B, D, k, nbr, dist, nullptr, ws,
-                              ws_bytes, as_stream(stream), KnnRider{}, KnnAffine{}, KnnSizeHint{}}).rc;
+                              ws_bytes, as_stream(stream), KnnRider{}, BnAffine{}, KnnSizeHint{}}).rc;
 }

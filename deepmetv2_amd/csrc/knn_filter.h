@@ -86,15 +86,13 @@ struct KnnRider {
 
 // BatchNorm transform + residual fused into the prep launch (dmet_bn_knn_local_dense_f32): the build's input y is not
 // there yet -- the prep kernel reads the rows it is made of, raw (the BatchNorm's input) and res, writes
-//   y = (raw - mean) * (gamma * invstd) + beta + res      (the expression of bn_apply_kernel, same bits)
+//   y = (raw - mean) * (gamma * invstd) + beta + res      (bn_affine4 of bn_affine.h, as in bn_apply_kernel: same bits)
 // and cuts its tile records from the values it just formed: one pass over the rows instead of two, one launch less.
-struct KnnAffine {
-    const float *raw = nullptr, *res = nullptr, *gamma = nullptr, *beta = nullptr, *mean = nullptr, *invstd = nullptr;
-    int kernarg_pad = 0;   // never read: see the static_assert
-};
-// knn_prep_kernel takes a KnnAffine as its last argument and the hidden kernel arguments follow it: a change of this size
-// moves them and with them the s_load offsets of every instance, so the device code would no longer be the verified one
-static_assert(sizeof(KnnAffine) == 56, "KnnAffine is the tail of knn_prep_kernel's argument block: keep its size");
+// knn_prep_kernel takes the BnAffine and a never-read int kernarg_pad as its last arguments and the hidden kernel
+// arguments follow them at the next multiple of 8: a change of this size moves them and with them the s_load offsets of
+// every instance, so the device code would no longer be the verified one
+static_assert(sizeof(BnAffine) == 48 && alignof(BnAffine) == 8,
+              "BnAffine + the padded kernarg_pad are the 56-byte tail of knn_prep_kernel's argument block: keep its size");
 
 // rider workgroups per launch (DMET_KNN_RIDER_GROUPS: experiments; 128..1024 measured within 1 % of each other at
 // 64 x 4500 nodes: the last round leaves ~1150 of the 2048 wavefront slots empty)
@@ -175,7 +173,7 @@ __global__ __launch_bounds__(256) void knn_prep_kernel(const float *__restrict__
                                                         int B, int64_t N, float *__restrict__ nrm,
                                                         uint8_t *__restrict__ rec, int64_t nrec,
                                                         uint32_t *__restrict__ zero, size_t zero_bytes, KnnPlanOut o0,
-                                                        KnnPlanOut o1, int form2, KnnAffine af = KnnAffine{})
+                                                        KnnPlanOut o1, int form2, BnAffine af, int /*kernarg_pad*/)
 {
     static_assert(!AFFINE || NH == 1, "the fused BatchNorm transform is built for 32 features");
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -233,13 +231,8 @@ __global__ __launch_bounds__(256) void knn_prep_kernel(const float *__restrict__
         __shared__ __attribute__((aligned(16))) float prep_tile[4][32 * 36];
         float *T = prep_tile[threadIdx.x >> 6];
         const int fg = lane & 7;
-        float4 mu4, sc4, be4;
-        if constexpr (AFFINE) {
-            mu4 = reinterpret_cast<const float4 *>(af.mean)[fg];
-            const float4 is4 = reinterpret_cast<const float4 *>(af.invstd)[fg], ga4 = reinterpret_cast<const float4 *>(af.gamma)[fg];
-            be4 = reinterpret_cast<const float4 *>(af.beta)[fg];
-            sc4 = make_float4(ga4.x * is4.x, ga4.y * is4.y, ga4.z * is4.z, ga4.w * is4.w);
-        }
+        BnAffine4 c4;
+        if constexpr (AFFINE) c4 = bn_affine_load4(af, fg);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
             const int rowj = 8 * jj + (lane >> 3);
@@ -248,13 +241,8 @@ __global__ __launch_bounds__(256) void knn_prep_kernel(const float *__restrict__
             float4 v;
             if constexpr (AFFINE) {
                 // x is the OUTPUT here: y = (raw - mean) * (gamma * invstd) + beta (+ res), written for the live rows
-                const float4 a = reinterpret_cast<const float4 *>(af.raw + rj * 32)[fg];
-                v.x = (a.x - mu4.x) * sc4.x + be4.x; v.y = (a.y - mu4.y) * sc4.y + be4.y;
-                v.z = (a.z - mu4.z) * sc4.z + be4.z; v.w = (a.w - mu4.w) * sc4.w + be4.w;
-                if (af.res) {
-                    const float4 q = reinterpret_cast<const float4 *>(af.res + rj * 32)[fg];
-                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
-                }
+                v = bn_affine4(reinterpret_cast<const float4 *>(af.raw + rj * 32)[fg], c4.mu, c4.scale, c4.beta);
+                if (af.res) v = bn_add4(v, reinterpret_cast<const float4 *>(af.res + rj * 32)[fg]);
                 if (livej) reinterpret_cast<float4 *>(const_cast<float *>(x) + rj * 32)[fg] = v;
             } else {
                 v = reinterpret_cast<const float4 *>(x + rj * 32)[fg];

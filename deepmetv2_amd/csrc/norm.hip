@@ -6,6 +6,7 @@
 // Here: forward = column statistics (fixed row ranges per workgroup, partials combined in order in double: bitwise
 // reproducible) + one streaming kernel y = (x - mean) * (gamma * invstd) + beta (+ residual); backward = the two
 // column sums (sum g, sum g * xhat) + one streaming kernel.  H (channels) is a multiple of 4, at most 64.
+#include "bn_affine.h"
 #include "common.h"
 
 namespace dmet {
@@ -127,26 +128,21 @@ __global__ __launch_bounds__(64) void bn_eval_stats_kernel(const float *__restri
     save_invstd[c] = (float)(1.0 / sqrt((double)running_var[c] + (double)eps));
 }
 
-// y = (x - mean) * (gamma * invstd) + beta (+ residual); with mean = running_mean, invstd from running_var in eval mode
+// y = (x - mean) * (gamma * invstd) + beta (+ residual): bn_affine4 of bn_affine.h, which the kernels that carry this
+// transform call too; with mean = running_mean, invstd from running_var in eval mode
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float *__restrict__ x, const float *__restrict__ res,
                                                        int64_t N, int H, const float *__restrict__ gamma,
                                                        const float *__restrict__ beta, const float *__restrict__ mean,
                                                        const float *__restrict__ invstd, float *__restrict__ y)
 {
+    const BnAffine a{x, res, gamma, beta, mean, invstd};
     const int h4 = H / 4;
     const int64_t total = N * h4;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int c4 = (int)(t % h4);
         const float4 v = reinterpret_cast<const float4 *>(x)[t];
-        const float4 mu = reinterpret_cast<const float4 *>(mean)[c4], is = reinterpret_cast<const float4 *>(invstd)[c4];
-        const float4 ga = reinterpret_cast<const float4 *>(gamma)[c4], be = reinterpret_cast<const float4 *>(beta)[c4];
-        float4 o;
-        o.x = (v.x - mu.x) * (ga.x * is.x) + be.x; o.y = (v.y - mu.y) * (ga.y * is.y) + be.y;
-        o.z = (v.z - mu.z) * (ga.z * is.z) + be.z; o.w = (v.w - mu.w) * (ga.w * is.w) + be.w;
-        if (res) {
-            const float4 r = reinterpret_cast<const float4 *>(res)[t];
-            o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-        }
+        const BnAffine4 c = bn_affine_load4(a, (int)(t % h4));
+        float4 o = bn_affine4(v, c.mu, c.scale, c.beta);
+        if (res) o = bn_add4(o, reinterpret_cast<const float4 *>(res)[t]);
         reinterpret_cast<float4 *>(y)[t] = o;
     }
 }
@@ -167,7 +163,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float *__re
     mean_gx[c] = (float)(s1 / (double)N);
 }
 
-// g_x = gamma * invstd * (g - mean_g - xhat * mean_gx)      (training-mode batch statistics)
+// g_x = gamma * invstd * (g - mean_g - xhat * mean_gx)      (training-mode batch statistics): bn_bwd4 of bn_affine.h
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *__restrict__ x, const float *__restrict__ g,
                                                            int64_t N, int H, const float *__restrict__ gamma,
                                                            const float *__restrict__ mean,
@@ -183,12 +179,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *__restri
         const float4 mu = reinterpret_cast<const float4 *>(mean)[c4], is = reinterpret_cast<const float4 *>(invstd)[c4];
         const float4 ga = reinterpret_cast<const float4 *>(gamma)[c4];
         const float4 mg = reinterpret_cast<const float4 *>(mean_g)[c4], mx = reinterpret_cast<const float4 *>(mean_gx)[c4];
-        float4 o;
-        o.x = ga.x * is.x * (gv.x - mg.x - (v.x - mu.x) * is.x * mx.x);
-        o.y = ga.y * is.y * (gv.y - mg.y - (v.y - mu.y) * is.y * mx.y);
-        o.z = ga.z * is.z * (gv.z - mg.z - (v.z - mu.z) * is.z * mx.z);
-        o.w = ga.w * is.w * (gv.w - mg.w - (v.w - mu.w) * is.w * mx.w);
-        reinterpret_cast<float4 *>(gx)[t] = o;
+        reinterpret_cast<float4 *>(gx)[t] = bn_bwd4(gv, v, ga, mu, is, mg, mx);
     }
 }
 
@@ -224,8 +215,7 @@ extern "C" int dmet_bn_fwd_tracked_f32(const float *x, const float *residual, in
     DMET_REQUIRE(N >= 0, "dmet_bn_fwd_f32: N=%lld", (long long)N);
     if (N == 0) return 0;
     DMET_REQUIRE(x && gamma && beta && y && save_mean && save_invstd && ws, "dmet_bn_fwd_f32: null pointer");
-    DMET_REQUIRE(aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta) && aligned16(save_mean) &&
-                     aligned16(save_invstd) && (!residual || aligned16(residual)),
+    DMET_REQUIRE(bn_affine_aligned16(BnAffine{x, residual, gamma, beta, save_mean, save_invstd}, y),
                  "dmet_bn_fwd_f32: pointers must be 16-byte aligned");
     DMET_REQUIRE(ws_bytes >= dmet_bn_workspace_bytes(N, H), "dmet_bn_fwd_f32: workspace too small");
     DMET_REQUIRE(training || (running_mean && running_var), "dmet_bn_fwd_f32: eval mode needs running statistics");
@@ -246,13 +236,7 @@ extern "C" int dmet_bn_fwd_tracked_f32(const float *x, const float *residual, in
                            (const float *)running_var, H, eps, save_mean, save_invstd);
         DMET_LAUNCH_CHECK("bn_eval_stats_kernel");
     }
-    const int64_t total = N * (H / 4);
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, residual, N, H, gamma, beta,
-                       (const float *)save_mean, (const float *)save_invstd, y);
-    DMET_LAUNCH_CHECK("bn_apply_kernel");
-    return 0;
+    return dmet_bn_apply_f32(x, residual, N, H, gamma, beta, save_mean, save_invstd, y, stream);   // the transform's one launch
 }
 
 extern "C" int dmet_bn_stats_f32(const float *x, int64_t N, int H, float eps, float momentum, float *running_mean,
@@ -351,8 +335,7 @@ extern "C" int dmet_bn_apply_f32(const float *x, const float *residual, int64_t 
     DMET_REQUIRE(N >= 0, "dmet_bn_apply_f32: N=%lld", (long long)N);
     if (N == 0) return 0;
     DMET_REQUIRE(x && gamma && beta && mean && invstd && y, "dmet_bn_apply_f32: null pointer");
-    DMET_REQUIRE(aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta) && aligned16(mean) &&
-                     aligned16(invstd) && (!residual || aligned16(residual)),
+    DMET_REQUIRE(bn_affine_aligned16(BnAffine{x, residual, gamma, beta, mean, invstd}, y),
                  "dmet_bn_apply_f32: pointers must be 16-byte aligned");
     const int64_t total = N * (H / 4);
     int64_t blocks = (total + 255) / 256;

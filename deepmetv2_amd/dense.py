@@ -83,27 +83,33 @@ def encode(x_cont: torch.Tensor, x_cat: torch.Tensor, *params: torch.Tensor) -> 
     return _Encode.apply(x_cont, x_cat, *params)
 
 
+def _bn_forward(x, residual, gamma, beta, running_mean, running_var, training, momentum, eps, tracked, next_build):
+    """(y, mean, invstd) of y = residual + BatchNorm(x).  Without `next_build` bn_fwd: statistics and transform in one call.
+    With it the transform rides in the launch that consumes y (the next layer's graph build or dense layer, the head's
+    forward): statistics here (eval mode: the running ones), then y = next_build(x, residual, gamma, beta, mean, invstd), or,
+    when that launch takes another path after all and returns None, the transform alone (bn_apply: bn_fwd's kernel and bits)."""
+    if next_build is None:
+        return _native.bn_fwd(x, residual, gamma, beta, eps, momentum, running_mean, running_var, training,
+                              num_batches_tracked=tracked)
+    if training:
+        mean, invstd = _native.bn_stats(x, eps, momentum, running_mean, running_var, tracked)
+    else:
+        mean, invstd = _native.bn_eval_stats(running_mean, running_var, eps)
+    y = next_build(x, residual, gamma, beta, mean, invstd)
+    if y is None:
+        y = _native.bn_apply(x, residual, gamma, beta, mean, invstd)
+    return y, mean, invstd
+
+
 class _BatchNorm(torch.autograd.Function):
     """BatchNorm1d over the rows of x[N,H] (+ residual) on the HIP kernels of csrc/norm.hip."""
 
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var, training, momentum, eps, tracked=None,
                 next_build=None):
-        y = None
-        if next_build is not None and x.is_cuda and x.shape[1] == 32 and (training or running_mean is not None):
-            # the transform rides in the prep launch of the NEXT layer's graph build (which consumes y): statistics here
-            # (eval mode: the running ones), then one pass that writes y and cuts the build's tile records from it
-            # (dmet_bn_knn_local_dense_f32; before the head: dmet_bn_head_fwd_f32)
-            if training:
-                mean, invstd = _native.bn_stats(x, eps, momentum, running_mean, running_var, tracked)
-            else:
-                mean, invstd = _native.bn_eval_stats(running_mean, running_var, eps)
-            y = next_build(x, residual, weight.detach(), bias.detach(), mean, invstd)
-            if y is None:   # that build takes another path after all: the transform alone (the statistics are done),
-                y = _native.bn_apply(x, residual, weight.detach(), bias.detach(), mean, invstd)   # bn_fwd's kernel and bits
-        if y is None:
-            y, mean, invstd = _native.bn_fwd(x, residual, weight.detach(), bias.detach(), eps, momentum,
-                                             running_mean, running_var, training, num_batches_tracked=tracked)
+        fused = next_build is not None and x.is_cuda and x.shape[1] == 32 and (training or running_mean is not None)
+        y, mean, invstd = _bn_forward(x, residual, weight.detach(), bias.detach(), running_mean, running_var, training,
+                                      momentum, eps, tracked, next_build if fused else None)
         ctx.save_for_backward(x, weight, mean, invstd)
         ctx.training = training
         ctx.has_residual = residual is not None
@@ -135,15 +141,8 @@ class _EncodeBN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_cont, x_cat, weight, bias, running_mean, running_var, momentum, eps, tracked, next_build, *params):
         h = _native.encode_fwd(x_cont, x_cat, [p.detach() for p in params])
-        y = None
-        if next_build is not None:
-            mean, invstd = _native.bn_stats(h, eps, momentum, running_mean, running_var, tracked)
-            y = next_build(h, None, weight.detach(), bias.detach(), mean, invstd)
-            if y is None:
-                y = _native.bn_apply(h, None, weight.detach(), bias.detach(), mean, invstd)
-        if y is None:
-            y, mean, invstd = _native.bn_fwd(h, None, weight.detach(), bias.detach(), eps, momentum, running_mean,
-                                             running_var, True, num_batches_tracked=tracked)
+        y, mean, invstd = _bn_forward(h, None, weight.detach(), bias.detach(), running_mean, running_var, True, momentum, eps,
+                                      tracked, next_build)
         ctx.save_for_backward(x_cont, x_cat, h, weight, mean, invstd, *params)
         return y
 
