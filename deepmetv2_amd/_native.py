@@ -373,106 +373,75 @@ def knn_xy(x: torch.Tensor, ptr_x: torch.Tensor, y: torch.Tensor, ptr_y: torch.T
     return _knn_run(dev, Ny, k, False, L.dmet_knn_xy_workspace_bytes(Nx, Ny, B, D, k), call)[:2]
 
 
+def _radius_build(x: torch.Tensor, ptr: torch.Tensor, r: float, max_nbr: int, skip_self: bool, pad: bool, local: bool,
+                  int32_rows: bool, period, query=None):
+    """One radius build: (nbr[N,max_nbr] int32 or None, cnt[N] int32, rows16 or None) over the N query rows -- the rows
+    of x, or of y for query = (y, ptr_y) with x / ptr the candidates.  Picks the form and the one C entry of the request."""
+    if query is None:
+        dev, x, N, D, B = _knn_operands(x, ptr)
+    else:
+        dev, x, y, ptr, ptr_y = _xy_operands(x, ptr, *query)
+        (Nx, D), N, B = x.shape, y.shape[0], ptr_y.numel() - 1
+    L = _lib.load()
+    per, per_p = _period_array(period, D)
+    # the window runs on coordinate 0 of one point set; everything else is all pairs of an event (A/B and fallback)
+    windowed = RADIUS_FORM != "sweep" and query is None and (per is None or per[0] == 0.0)
+    skip32 = local and windowed and not int32_rows and not pad
+    nbr = None if skip32 else torch.empty((N, max_nbr), dtype=torch.int32, device=dev)
+    cnt = torch.empty((N,), dtype=torch.int32, device=dev)
+    stride16 = (max_nbr + 7) // 8 * 8 if local and windowed else 0
+    rows16 = torch.empty((N, stride16), dtype=torch.int16, device=dev) if stride16 else None
+    ws = _ws(L.dmet_radius_workspace_bytes(N), dev) if windowed else None
+    head = (x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr, 1 if skip_self else 0)
+    fill, st = 1 if pad else 0, _stream(dev)
+    out = (None if nbr is None else nbr.data_ptr(), cnt.data_ptr())
+    rows = (None if rows16 is None else rows16.data_ptr(), stride16)
+    if query is not None:
+        name, args = "dmet_radius_xy_f32", (x.data_ptr(), ptr.data_ptr(), Nx, y.data_ptr(), ptr_y.data_ptr(), N, B, D,
+                                            float(r), max_nbr, per_p, fill, *out, st)
+    elif windowed:
+        tail = (ws.data_ptr(), ws.numel(), st)
+        if per is not None:
+            name, args = "dmet_radius_windowed_periodic_f32", (*head, fill, per_p, *out, *rows, *tail)
+        elif local:
+            name, args = "dmet_radius_windowed_local_f32", (*head, fill, *out, *rows, *tail)
+        else:
+            name, args = "dmet_radius_windowed_f32", (*head, fill, *out, *tail)
+    elif per is not None:
+        name, args = "dmet_radius_periodic_f32", (*head, fill, per_p, *out, st)
+    else:
+        name, args = ("dmet_radius_f32" if pad else "dmet_radius_counted_f32"), (*head, *out, st)
+    with _on(dev):
+        _lib.check(getattr(L, name)(*args), name)
+    return nbr, cnt, rows16
+
+
 def radius_xy(x: torch.Tensor, ptr_x: torch.Tensor, y: torch.Tensor, ptr_y: torch.Tensor, r: float, max_nbr: int,
               period=None, pad: bool = True):
     """Two point sets (dmet_radius_xy_f32): for every row of y the first max_nbr rows of x (ascending id) of the same
     event within r.  (nbr[Ny,max_nbr] int32, cnt[Ny] int32); pad=False leaves the slots >= cnt[i] unwritten."""
-    dev, x, y, ptr_x, ptr_y = _xy_operands(x, ptr_x, y, ptr_y)
-    L = _lib.load()
-    (Nx, D), Ny, B = x.shape, y.shape[0], ptr_y.numel() - 1
-    _per, per_p = _period_array(period, D)
-    nbr = torch.empty((Ny, max_nbr), dtype=torch.int32, device=dev)
-    cnt = torch.empty((Ny,), dtype=torch.int32, device=dev)
-    with _on(dev):
-        _lib.check(L.dmet_radius_xy_f32(x.data_ptr(), ptr_x.data_ptr(), Nx, y.data_ptr(), ptr_y.data_ptr(), Ny, B, D,
-                                        float(r), max_nbr, per_p, 1 if pad else 0, nbr.data_ptr(), cnt.data_ptr(),
-                                        _stream(dev)), "dmet_radius_xy_f32")
-    return nbr, cnt
+    return _radius_build(x, ptr_x, r, max_nbr, False, pad, False, True, period, (y, ptr_y))[:2]
 
 
 def radius(x: torch.Tensor, ptr: torch.Tensor, r: float, max_nbr: int, skip_self: bool = False,
-           pad: bool = True, local: bool = False, int32_rows: bool = True):
+           pad: bool = True, local: bool = False, int32_rows: bool = True, period=None):
     """(nbr[N,max_nbr] int32, cnt[N] int32).  pad=False leaves the slots >= cnt[i] unwritten instead of filling them
     with -1 (the fill is most of a 255-wide table's bytes); only for consumers that go by cnt.
     local=True: a third result, the rows again as event-local uint16 ids (int16-typed [N, roundup8(max_nbr)], slots
     cnt[i] .. roundup8(cnt[i]) - 1 = 0xFFFF, the rest unwritten) for gather_max_local_j16; None when the all-pairs
     form is selected.  int32_rows=False (with local=True, pad=False, windowed form): the int32 table is not written at all
-    and comes back as None -- for callers whose consumers read the uint16 rows (graph.NeighborTable expands them on demand)."""
-    dev = _require_device(x, ptr)
-    L = _lib.load()
-    x = _f32c(x.detach(), "x")
-    N, D = x.shape
-    B = ptr.numel() - 1
-    skip32 = bool(local and not int32_rows and not pad and RADIUS_FORM != "sweep")
-    nbr = None if skip32 else torch.empty((N, max_nbr), dtype=torch.int32, device=dev)
-    cnt = torch.empty((N,), dtype=torch.int32, device=dev)
-    if local:
-        rows16 = None
-        if RADIUS_FORM != "sweep":
-            stride16 = (max_nbr + 7) // 8 * 8
-            rows16 = torch.empty((N, stride16), dtype=torch.int16, device=dev)
-            ws = _ws(L.dmet_radius_workspace_bytes(N), dev)
-            with _on(dev):
-                _lib.check(L.dmet_radius_windowed_local_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr,
-                                                            1 if skip_self else 0, 1 if pad else 0, _ptr(nbr),
-                                                            cnt.data_ptr(), rows16.data_ptr(), stride16, ws.data_ptr(),
-                                                            ws.numel(), _stream(dev)), "dmet_radius_windowed_local_f32")
-            return nbr, cnt, rows16
-        nbr, cnt = radius(x, ptr, r, max_nbr, skip_self, pad)
-        return nbr, cnt, None
-    with _on(dev):
-        if RADIUS_FORM == "sweep":      # all pairs of an event (A/B and fallback)
-            fn = L.dmet_radius_f32 if pad else L.dmet_radius_counted_f32
-            _lib.check(fn(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr, 1 if skip_self else 0,
-                          nbr.data_ptr(), cnt.data_ptr(), _stream(dev)), "dmet_radius_f32")
-        else:                            # same table, candidates windowed by the first coordinate
-            ws = _ws(L.dmet_radius_workspace_bytes(N), dev)
-            _lib.check(L.dmet_radius_windowed_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr,
-                                                  1 if skip_self else 0, 1 if pad else 0, nbr.data_ptr(),
-                                                  cnt.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
-                       "dmet_radius_windowed_f32")
-    return nbr, cnt
+    and comes back as None -- for callers whose consumers read the uint16 rows (graph.NeighborTable expands them on demand).
+    period: None, or D floats, period[c] > 0 the circumference of coordinate c, 0 a plain coordinate
+    (dmet_radius_periodic_f32 / dmet_radius_windowed_periodic_f32).  The window runs on coordinate 0, so period[0] > 0
+    takes the all-pairs form (rows16 = None, as RADIUS_FORM == "sweep" does)."""
+    out = _radius_build(x, ptr, r, max_nbr, skip_self, pad, local, int32_rows, period)
+    return out if local else out[:2]
 
 
 def radius_periodic(x: torch.Tensor, ptr: torch.Tensor, r: float, max_nbr: int, period, skip_self: bool = False,
                     pad: bool = True, local: bool = False, int32_rows: bool = True):
-    """radius() with periodic coordinates: period = D floats, period[c] > 0 the circumference of coordinate c, 0 a plain
-    coordinate (dmet_radius_periodic_f32 / dmet_radius_windowed_periodic_f32).  Same outputs as radius().  The window
-    runs on coordinate 0, so period[0] > 0 takes the all-pairs form (rows16 = None, as RADIUS_FORM == "sweep" does)."""
-    dev = _require_device(x, ptr)
-    L = _lib.load()
-    x = _f32c(x.detach(), "x")
-    N, D = x.shape
-    B = ptr.numel() - 1
-    per, per_p = _period_array(period, D)
-    windowed = RADIUS_FORM != "sweep" and per[0] == 0.0
-    if local and windowed:
-        stride16 = (max_nbr + 7) // 8 * 8
-        nbr = None if (not int32_rows and not pad) else torch.empty((N, max_nbr), dtype=torch.int32, device=dev)
-        cnt = torch.empty((N,), dtype=torch.int32, device=dev)
-        rows16 = torch.empty((N, stride16), dtype=torch.int16, device=dev)
-        ws = _ws(L.dmet_radius_workspace_bytes(N), dev)
-        with _on(dev):
-            _lib.check(L.dmet_radius_windowed_periodic_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr,
-                                                           1 if skip_self else 0, 1 if pad else 0, per_p,
-                                                           _ptr(nbr), cnt.data_ptr(),
-                                                           rows16.data_ptr(), stride16, ws.data_ptr(), ws.numel(),
-                                                           _stream(dev)), "dmet_radius_windowed_periodic_f32")
-        return nbr, cnt, rows16
-    nbr = torch.empty((N, max_nbr), dtype=torch.int32, device=dev)
-    cnt = torch.empty((N,), dtype=torch.int32, device=dev)
-    with _on(dev):
-        if windowed:
-            ws = _ws(L.dmet_radius_workspace_bytes(N), dev)
-            _lib.check(L.dmet_radius_windowed_periodic_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr,
-                                                           1 if skip_self else 0, 1 if pad else 0, per_p,
-                                                           nbr.data_ptr(), cnt.data_ptr(), None, 0, ws.data_ptr(),
-                                                           ws.numel(), _stream(dev)), "dmet_radius_windowed_periodic_f32")
-        else:                            # all pairs of an event
-            _lib.check(L.dmet_radius_periodic_f32(x.data_ptr(), ptr.data_ptr(), B, N, D, float(r), max_nbr,
-                                                  1 if skip_self else 0, 1 if pad else 0, per_p, nbr.data_ptr(),
-                                                  cnt.data_ptr(), _stream(dev)), "dmet_radius_periodic_f32")
-    return (nbr, cnt, None) if local else (nbr, cnt)
+    """radius(..., period=period)."""
+    return radius(x, ptr, r, max_nbr, skip_self, pad, local, int32_rows, period)
 
 
 # ---- K2+K3 fused -----------------------------------------------------------------------------------------------

@@ -268,11 +268,10 @@ def radius_table(x: torch.Tensor, r: float, batch: Optional[torch.Tensor] = None
     if int32_rows is None:
         int32_rows = not (info.max_nodes is not None and info.max_nodes <= 65534
                           and os.environ.get("DMET_RADIUS_INT32", "lazy") == "lazy")
-    if per is None:
-        nbr, _cnt, rows16 = _native.radius(x, info.ptr, r, m, skip_self=not loop, pad=False, local=True, int32_rows=int32_rows)
-    else:
-        nbr, _cnt, rows16 = _native.radius_periodic(x, info.ptr, r, m, per, skip_self=not loop, pad=False, local=True,
-                                                    int32_rows=int32_rows)
+    # a plain build is called exactly as it is without the keyword (stand-ins of _native.radius need not know `period`)
+    periodic = {} if per is None else {"period": per}
+    nbr, _cnt, rows16 = _native.radius(x, info.ptr, r, m, skip_self=not loop, pad=False, local=True, int32_rows=int32_rows,
+                                       **periodic)
     # with self loops every node finds at least itself (the cap counts hits in index order, but a full row is not empty)
     return NeighborTable(nbr, info.ptr, dense=False, max_nodes=info.max_nodes, cnt=_cnt, nonempty=bool(loop),
                          rows16=rows16, shape=(x.shape[0], m))

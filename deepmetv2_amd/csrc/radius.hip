@@ -349,110 +349,108 @@ __global__ __launch_bounds__(kWave * 4) void radius_window_kernel(const float *_
 
 using namespace dmet;
 
-// the per x query-set ladder of radius_kernel
-template <int DP>
-static void launch_radius(int64_t blocks, hipStream_t st, const float *x, const int64_t *ptr, int B, int64_t N, int D,
-                          float r2, int max_nbr, int skip_self, int32_t *nbr, int32_t *cnt, const RadPeriod *per,
-                          const KnnQuerySet *qs)
-{
-    with_pack<true, true>(per, qs, [&](auto... pack) {
-        hipLaunchKernelGGL((radius_kernel<DP, decltype(pack)...>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x, ptr, B,
-                           N, D, r2, max_nbr, skip_self, nbr, cnt, pack...);
-    });
-}
+enum class RadiusForm { AllPairs, Windowed };
 
-// x / ptr: the candidates; qs == nullptr: they are the N queries too; otherwise the N queries are the rows of qs (whose
-// entry has checked x and skip_self is 0)
-static int radius_impl(const char *who, const float *x, const int64_t *ptr, int B, int64_t N, int D, float r, int max_nbr,
-                       int skip_self, bool fill, int32_t *nbr, int32_t *cnt, dmet_stream_t stream, const RadPeriod *per,
-                       const KnnQuerySet *qs = nullptr)
-{
-    DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647, "%s: N out of range", who);
-    DMET_REQUIRE(D >= 1 && D <= 8, "%s: D=%d not in [1,8]", who, D);
-    DMET_REQUIRE(max_nbr >= 1, "%s: max_nbr=%d", who, max_nbr);
-    if (N == 0 || B == 0) return 0;
-    DMET_REQUIRE((qs ? qs->qx && qs->qptr : x != nullptr) && ptr && nbr && cnt, "%s: null pointer", who);
-    const float r2 = r * r;
-    const int64_t blocks = (N + 4 * kWave - 1) / (4 * kWave);
-    hipStream_t st = as_stream(stream);
-    // empty slots are -1: one coalesced fill instead of per-lane tail stores (294 MB for 288 000 x 255: the counted
-    // form leaves them unwritten, its consumers go by cnt)
-    if (fill) {
-        hipError_t me = hipMemsetAsync(nbr, 0xff, sizeof(int32_t) * (size_t)N * (size_t)max_nbr, st);
-        if (me != hipSuccess) return hip_fail(me, "hipMemsetAsync(nbr)");
-    }
-    if (D <= 2)
-        launch_radius<2>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, nbr, cnt, per, qs);
-    else if (D <= 4)
-        launch_radius<4>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, nbr, cnt, per, qs);
-    else
-        launch_radius<8>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, nbr, cnt, per, qs);
-    DMET_LAUNCH_CHECK(qs ? "radius_kernel (two sets)" : "radius_kernel");
-    return 0;
-}
-
-extern "C" int dmet_radius_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r, int max_nbr,
-                               int skip_self, int32_t *nbr, int32_t *cnt, dmet_stream_t stream)
-{
-    return radius_impl("dmet_radius_f32", x, ptr, B, N, D, r, max_nbr, skip_self, true, nbr, cnt, stream, nullptr);
-}
-
-extern "C" int dmet_radius_counted_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r,
-                                       int max_nbr, int skip_self, int32_t *nbr, int32_t *cnt, dmet_stream_t stream)
-{
-    return radius_impl("dmet_radius_f32", x, ptr, B, N, D, r, max_nbr, skip_self, false, nbr, cnt, stream, nullptr);
-}
+// One radius build, as its entry asks for it.  radius_build works from this request alone.
+struct RadiusBuild {
+    const char *who;            // the entry that was called, for messages
+    const float *x;             // candidate rows, cut into B events by ptr; the queries too unless qs is set
+    const int64_t *ptr;
+    int B;
+    int64_t N;                  // number of QUERY rows: the rows of x, or of qs->qx when that is set
+    int D;
+    float r;
+    int max_nbr, skip_self;
+    bool fill;                  // slots from cnt on are -1 (one memset); false: left unwritten, consumers go by cnt
+    int32_t *nbr, *cnt;
+    hipStream_t st;
+    RadiusForm form = RadiusForm::AllPairs;   // Windowed: candidates windowed by coordinate 0 (one point set, needs ws)
+    void *ws = nullptr;
+    size_t ws_bytes = 0;
+    uint16_t *nbr16 = nullptr;                // Windowed: optional event-local copy of the rows, stride16 ids apart
+    int stride16 = 0;
+    const float *period = nullptr;            // D circumferences, 0 = a plain coordinate
+    bool need_period = false;                 // a null period is an error
+    const KnnQuerySet *qs = nullptr;          // non-null: two point sets (its entry has checked x; skip_self is 0)
+};
 
 extern "C" size_t dmet_radius_workspace_bytes(int64_t N)
 {
     return N > 0 ? sizeof(int32_t) * (size_t)N + 512 : 0;
 }
 
-// the per ladder of radius_window_kernel (it has no two-set instance)
-template <int DP>
-static void launch_radius_window(int64_t blocks, hipStream_t st, const float *x, const int64_t *ptr, int B, int64_t N,
-                                 int D, float r2, int max_nbr, int skip_self, const int32_t *order, int32_t *nbr,
-                                 int32_t *cnt, uint16_t *nbr16, int stride16, const RadPeriod *per)
+static int radius_build(const RadiusBuild &b)
 {
-    with_pack<true, false>(per, nullptr, [&](auto... pack) {
-        hipLaunchKernelGGL((radius_window_kernel<DP, decltype(pack)...>), dim3((unsigned)blocks), dim3(kWave * 4), 0, st, x,
-                           ptr, B, N, D, r2, max_nbr, skip_self, order, nbr, cnt, nbr16, stride16, pack...);
-    });
-}
-
-static int radius_windowed_impl(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r, int max_nbr,
-                                int skip_self, int fill, int32_t *nbr, int32_t *cnt, uint16_t *nbr16, int stride16,
-                                void *ws, size_t ws_bytes, dmet_stream_t stream, const RadPeriod *per)
-{
-    DMET_REQUIRE(!nbr16 || (stride16 >= max_nbr && stride16 % 8 == 0 && aligned16(nbr16)),
-                 "dmet_radius_windowed_local_f32: nbr16 rows need a 16-byte aligned stride of >= max_nbr ids (stride16=%d)",
-                 stride16);
-    DMET_REQUIRE(N >= 0 && N < (int64_t)2147483647, "dmet_radius_windowed_f32: N out of range");
-    DMET_REQUIRE(D >= 1 && D <= 8, "dmet_radius_windowed_f32: D=%d not in [1,8]", D);
-    DMET_REQUIRE(max_nbr >= 1, "dmet_radius_windowed_f32: max_nbr=%d", max_nbr);
-    if (N == 0 || B == 0) return 0;
+    const bool windowed = b.form == RadiusForm::Windowed;
+    RadPeriod per;
+    bool any = false;
+    if (b.period || b.need_period) {
+        const int rc = radius_periods(b.who, b.D, b.period, &per, &any);
+        if (rc) return rc;
+        DMET_REQUIRE(!windowed || b.period[0] == 0.0f, "%s: coordinate 0 is periodic (period[0]=%g): the window runs on "
+                     "coordinate 0; use dmet_radius_periodic_f32", b.who, (double)b.period[0]);
+    }
+    // all periods 0: the plain kernel (bit-identical to the entries without periods by construction)
+    const RadPeriod *pp = any ? &per : nullptr;
+    DMET_REQUIRE(!b.nbr16 || (b.stride16 >= b.max_nbr && b.stride16 % 8 == 0 && aligned16(b.nbr16)),
+                 "%s: nbr16 rows need a 16-byte aligned stride of >= max_nbr ids (stride16=%d)", b.who, b.stride16);
+    DMET_REQUIRE(b.N >= 0 && b.N < (int64_t)2147483647, "%s: N out of range", b.who);
+    DMET_REQUIRE(b.D >= 1 && b.D <= 8, "%s: D=%d not in [1,8]", b.who, b.D);
+    DMET_REQUIRE(b.max_nbr >= 1, "%s: max_nbr=%d", b.who, b.max_nbr);
+    if (b.N == 0 || b.B == 0) return 0;
     // nbr == NULL: only the uint16 rows are written (a caller whose consumers read those: the 255-wide int32 table is 294 MB
     // of address space at 288 000 nodes, its ~36 used slots per row 41 MB of 16-byte pieces: 12 of the kernel's 130 us)
-    DMET_REQUIRE(x && ptr && cnt && ws && (nbr || (nbr16 && !fill)), "dmet_radius_windowed_f32: null pointer");
-    DMET_REQUIRE(ws_bytes >= dmet_radius_workspace_bytes(N), "dmet_radius_windowed_f32: workspace too small");
-    int32_t *order = reinterpret_cast<int32_t *>((reinterpret_cast<uintptr_t>(ws) + 255u) & ~(uintptr_t)255u);
-    const float r2 = r * r;
-    const int64_t blocks = (N / kWave + B + 1 + 3) / 4;   // event-aligned wavefront ids, four per workgroup
-    hipStream_t st = as_stream(stream);
-    if (fill) {
-        hipError_t me = hipMemsetAsync(nbr, 0xff, sizeof(int32_t) * (size_t)N * (size_t)max_nbr, st);
+    DMET_REQUIRE((b.qs ? b.qs->qx && b.qs->qptr : b.x != nullptr) && b.ptr && b.cnt && (b.nbr || (b.nbr16 && !b.fill)) &&
+                 (b.ws || !windowed), "%s: null pointer", b.who);
+    int32_t *order = nullptr;
+    if (windowed) {
+        DMET_REQUIRE(b.ws_bytes >= dmet_radius_workspace_bytes(b.N), "%s: workspace too small", b.who);
+        order = reinterpret_cast<int32_t *>((reinterpret_cast<uintptr_t>(b.ws) + 255u) & ~(uintptr_t)255u);
+    }
+    // empty slots are -1: one coalesced fill instead of per-lane tail stores (294 MB for 288 000 x 255: the counted
+    // form leaves them unwritten, its consumers go by cnt)
+    if (b.fill) {
+        hipError_t me = hipMemsetAsync(b.nbr, 0xff, sizeof(int32_t) * (size_t)b.N * (size_t)b.max_nbr, b.st);
         if (me != hipSuccess) return hip_fail(me, "hipMemsetAsync(nbr)");
     }
-    hipLaunchKernelGGL(radius_order_kernel, dim3((unsigned)B), dim3(kRadBins), 0, st, x, ptr, B, D, order);
-    DMET_LAUNCH_CHECK("radius_order_kernel");
-    if (D <= 2)
-        launch_radius_window<2>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, order, nbr, cnt, nbr16, stride16, per);
-    else if (D <= 4)
-        launch_radius_window<4>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, order, nbr, cnt, nbr16, stride16, per);
-    else
-        launch_radius_window<8>(blocks, st, x, ptr, B, N, D, r2, max_nbr, skip_self, order, nbr, cnt, nbr16, stride16, per);
-    DMET_LAUNCH_CHECK("radius_window_kernel");
+    if (windowed) {
+        hipLaunchKernelGGL(radius_order_kernel, dim3((unsigned)b.B), dim3(kRadBins), 0, b.st, b.x, b.ptr, b.B, b.D, order);
+        DMET_LAUNCH_CHECK("radius_order_kernel");
+    }
+    const float r2 = b.r * b.r;
+    // four wavefronts per workgroup: 64 queries each, or (windowed) event-aligned wavefront ids
+    const int64_t blocks = windowed ? (b.N / kWave + b.B + 1 + 3) / 4 : (b.N + 4 * kWave - 1) / (4 * kWave);
+    // the D ladder, then the per x query-set ladder of each kernel (the window kernel has no two-set instance)
+    with_int<2, 4, 8>(b.D <= 2 ? 2 : b.D <= 4 ? 4 : 8, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        if (windowed)
+            with_pack<true, false>(pp, nullptr, [&](auto... pack) {
+                hipLaunchKernelGGL((radius_window_kernel<DP, decltype(pack)...>), dim3((unsigned)blocks), dim3(kWave * 4), 0,
+                                   b.st, b.x, b.ptr, b.B, b.N, b.D, r2, b.max_nbr, b.skip_self, order, b.nbr, b.cnt, b.nbr16,
+                                   b.stride16, pack...);
+            });
+        else
+            with_pack<true, true>(pp, b.qs, [&](auto... pack) {
+                hipLaunchKernelGGL((radius_kernel<DP, decltype(pack)...>), dim3((unsigned)blocks), dim3(kWave * 4), 0, b.st,
+                                   b.x, b.ptr, b.B, b.N, b.D, r2, b.max_nbr, b.skip_self, b.nbr, b.cnt, pack...);
+            });
+    });
+    DMET_LAUNCH_CHECK(windowed ? "radius_window_kernel" : b.qs ? "radius_kernel (two sets)" : "radius_kernel");
     return 0;
+}
+
+// ---- entries: each fills a RadiusBuild and calls radius_build once --------------------------------------------------
+extern "C" int dmet_radius_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r, int max_nbr,
+                               int skip_self, int32_t *nbr, int32_t *cnt, dmet_stream_t stream)
+{
+    return radius_build({"dmet_radius_f32", x, ptr, B, N, D, r, max_nbr, skip_self, true, nbr, cnt, as_stream(stream)});
+}
+
+extern "C" int dmet_radius_counted_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r,
+                                       int max_nbr, int skip_self, int32_t *nbr, int32_t *cnt, dmet_stream_t stream)
+{
+    return radius_build({"dmet_radius_counted_f32", x, ptr, B, N, D, r, max_nbr, skip_self, false, nbr, cnt,
+                         as_stream(stream)});
 }
 
 extern "C" int dmet_radius_windowed_local_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r,
@@ -460,16 +458,16 @@ extern "C" int dmet_radius_windowed_local_f32(const float *x, const int64_t *ptr
                                               uint16_t *nbr16, int stride16, void *ws, size_t ws_bytes,
                                               dmet_stream_t stream)
 {
-    return radius_windowed_impl(x, ptr, B, N, D, r, max_nbr, skip_self, fill, nbr, cnt, nbr16, stride16, ws, ws_bytes,
-                                stream, nullptr);
+    return radius_build({"dmet_radius_windowed_local_f32", x, ptr, B, N, D, r, max_nbr, skip_self, fill != 0, nbr, cnt,
+                         as_stream(stream), RadiusForm::Windowed, ws, ws_bytes, nbr16, stride16});
 }
 
 extern "C" int dmet_radius_windowed_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r,
                                         int max_nbr, int skip_self, int fill, int32_t *nbr, int32_t *cnt, void *ws,
                                         size_t ws_bytes, dmet_stream_t stream)
 {
-    return radius_windowed_impl(x, ptr, B, N, D, r, max_nbr, skip_self, fill, nbr, cnt, nullptr, 0, ws, ws_bytes, stream,
-                                nullptr);
+    return radius_build({"dmet_radius_windowed_f32", x, ptr, B, N, D, r, max_nbr, skip_self, fill != 0, nbr, cnt,
+                         as_stream(stream), RadiusForm::Windowed, ws, ws_bytes});
 }
 
 // Periodic coordinates (train.py:47-48: phi wraps at +-pi).  period[c] > 0: circumference of coordinate c; 0: plain.
@@ -477,13 +475,8 @@ extern "C" int dmet_radius_periodic_f32(const float *x, const int64_t *ptr, int 
                                         int max_nbr, int skip_self, int fill, const float *period, int32_t *nbr,
                                         int32_t *cnt, dmet_stream_t stream)
 {
-    RadPeriod per;
-    bool any = false;
-    const int rc = radius_periods("dmet_radius_periodic_f32", D, period, &per, &any);
-    if (rc) return rc;
-    // all periods 0: the plain kernel (bit-identical to dmet_radius_f32 / dmet_radius_counted_f32 by construction)
-    return radius_impl("dmet_radius_f32", x, ptr, B, N, D, r, max_nbr, skip_self, fill != 0, nbr, cnt, stream,
-                       any ? &per : nullptr);
+    return radius_build({"dmet_radius_periodic_f32", x, ptr, B, N, D, r, max_nbr, skip_self, fill != 0, nbr, cnt,
+                         as_stream(stream), RadiusForm::AllPairs, nullptr, 0, nullptr, 0, period, true});
 }
 
 extern "C" int dmet_radius_windowed_periodic_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, float r,
@@ -491,14 +484,8 @@ extern "C" int dmet_radius_windowed_periodic_f32(const float *x, const int64_t *
                                                  int32_t *nbr, int32_t *cnt, uint16_t *nbr16, int stride16, void *ws,
                                                  size_t ws_bytes, dmet_stream_t stream)
 {
-    RadPeriod per;
-    bool any = false;
-    const int rc = radius_periods("dmet_radius_windowed_periodic_f32", D, period, &per, &any);
-    if (rc) return rc;
-    DMET_REQUIRE(period[0] == 0.0f, "dmet_radius_windowed_periodic_f32: coordinate 0 is periodic (period[0]=%g): the "
-                 "window runs on coordinate 0; use dmet_radius_periodic_f32", (double)period[0]);
-    return radius_windowed_impl(x, ptr, B, N, D, r, max_nbr, skip_self, fill, nbr, cnt, nbr16, stride16, ws, ws_bytes,
-                                stream, any ? &per : nullptr);
+    return radius_build({"dmet_radius_windowed_periodic_f32", x, ptr, B, N, D, r, max_nbr, skip_self, fill != 0, nbr, cnt,
+                         as_stream(stream), RadiusForm::Windowed, ws, ws_bytes, nbr16, stride16, period, true});
 }
 
 // ---- two point sets: queries y against candidates x of the same events (torch_cluster.radius) -----------------------
@@ -510,16 +497,17 @@ extern "C" int dmet_radius_xy_f32(const float *x, const int64_t *ptr_x, int64_t 
     DMET_REQUIRE(Nx >= 0 && Nx < (int64_t)2147483647 && Ny >= 0 && Ny < (int64_t)2147483647,
                  "%s: Nx=%lld / Ny=%lld out of range", who, (long long)Nx, (long long)Ny);
     DMET_REQUIRE(B >= 0, "%s: B=%d", who, B);
-    RadPeriod per;
-    bool any = false;
-    if (period) {
+    if (period) {   // a bad period is reported ahead of the two checks below; radius_build reads it again for the kernel
+        RadPeriod per;
+        bool any = false;
         const int rc = radius_periods(who, D, period, &per, &any);
         if (rc) return rc;
     }
-    if (Ny > 0) {   // (an empty query set still gets radius_impl's checks of D and max_nbr)
+    if (Ny > 0) {   // (an empty query set still gets radius_build's checks of D and max_nbr)
         DMET_REQUIRE(B >= 1, "%s: %lld queries but no event", who, (long long)Ny);
         DMET_REQUIRE((x || Nx == 0) && ptr_x && y && ptr_y && nbr && cnt, "%s: null pointer", who);
     }
     const KnnQuerySet qs{y, ptr_y};
-    return radius_impl(who, x, ptr_x, B, Ny, D, r, max_nbr, 0, fill != 0, nbr, cnt, stream, any ? &per : nullptr, &qs);
+    return radius_build({who, x, ptr_x, B, Ny, D, r, max_nbr, 0, fill != 0, nbr, cnt, as_stream(stream),
+                         RadiusForm::AllPairs, nullptr, 0, nullptr, 0, period, false, &qs});
 }

@@ -108,12 +108,12 @@ def test_periodic_call_reaches_radius_periodic(monkeypatch):
     fake_native.install(monkeypatch)
     seen = {}
 
-    def spy(x, ptr, r, m, period, skip_self=False, pad=True, local=False, int32_rows=True):
+    def spy(x, ptr, r, m, skip_self=False, pad=True, local=False, int32_rows=True, period=None):
         seen.update(period=period, skip_self=skip_self, pad=pad, local=local, m=m)
         nbr, cnt = rp.radius_table(x.numpy(), ptr.numpy(), r, m, period, skip_self)
         return torch.from_numpy(nbr), torch.from_numpy(cnt), None
 
-    monkeypatch.setattr(_native, "radius_periodic", spy)
+    monkeypatch.setattr(_native, "radius", spy)     # radius_table hands the periods to the one entry, as period=
     x, batch = _events(2)
     ei = dm.radius_graph(x, 0.4, batch, loop=False, max_num_neighbors=8, period=[None, 2 * math.pi])
     assert seen == dict(period=[0.0, TWO_PI_F32], skip_self=True, pad=False, local=True, m=9)
