@@ -1194,7 +1194,8 @@ def reverse_index(keys: torch.Tensor, num_keys: int) -> Tuple[torch.Tensor, torc
         raise TypeError("keys must be a contiguous int32 tensor")
     M = keys.numel()
     rev_ptr = torch.empty((num_keys + 1,), dtype=torch.int32, device=dev)
-    rev_pos = torch.empty((max(M, 1),), dtype=torch.int32, device=dev)
+    # M == 0: no position exists; one element, zero, so that callers hold a tensor with an address (no output of the entry)
+    rev_pos = torch.empty((M,), dtype=torch.int32, device=dev) if M else torch.zeros((1,), dtype=torch.int32, device=dev)
     _t = timer.record('reverse_index', dev)
     with _on(dev):
         ws = _ws(L.dmet_reverse_index_workspace_bytes(M, num_keys), dev)

@@ -290,7 +290,10 @@ int dmet_gather_max_counted_lds_f32(const float *P, const float *Q, const int32_
  * (argj[N,H] uint16, 0xFFFF = no neighbour; events of at most 65534 nodes), so that the backward scatter
  * (dmet_gather_max_bwd_j16_f32) needs no look-up in the wide table; `order` (optional, from dmet_table_order_by_count:
  * the event's local node indices grouped by slot count) makes the lane pairs of a wavefront walk rows of similar depth.
- * out is identical to dmet_gather_max_counted_f32. */
+ * out is identical to dmet_gather_max_counted_f32.
+ * dmet_table_order_by_count writes all of order[N]: per event a permutation of its local indices, deepest rows first.
+ * The order inside a group of equal count is unspecified and may differ between runs (a counting sort with integer
+ * atomics in LDS); it influences no result, every node is computed independently. */
 int dmet_table_order_by_count(const int32_t *cnt, const int64_t *ptr, int B, int64_t N, int32_t *order,
                               dmet_stream_t stream);
 int dmet_gather_max_counted_lds_j16_f32(const float *P, const float *Q, const int32_t *nbr, const int32_t *cnt,
@@ -366,6 +369,8 @@ int dmet_edge_mlp2_bn_bf16(const float *x, int64_t N, int Hin, const int32_t *nb
  *   x W1b^T], agg[2 N H2] (sum, or max then min), win[2 N H2] int32 (max only: grouped position of the winning edge of
  *   the max, then of the min, lowest on ties; defined only for nodes with in-edges), bnstat[4 H2] = (a, b, mean,
  *   invstd) of the per-channel map m -> a m + b.  A node without in-edges gives 0 (R3).  bn == 1 needs E >= 1.
+ *   agg, like win, is defined only for nodes with in-edges: the rows of a node without one are left unwritten (every
+ *   reader -- the apply launch, the BatchNorm backward sums -- skips a node whose rowptr says it has no in-edge).
  * dmet_edge_mlp_bwd_f32 takes g_out[N, H2] and writes gx[N, Hin] (may be NULL), gpq[N, 2 H1] = [gP | gQ] (the
  *   gradients of P and Q; the caller forms gW1 = [gP^T x | (gQ - gP)^T x] and gb1 = sum gP), gW2, gb2, and with a
  *   BatchNorm ggamma, gbeta (each may be NULL).  Every gradient is written, not accumulated.
