@@ -104,6 +104,8 @@ SIGNATURES = {
     "dmet_attention_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dmet_attention_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i,
                                     _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmet_interpolate_fwd_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp]),
+    "dmet_interpolate_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp]),
     "dmet_reverse_index_workspace_bytes": (_sz, [_i64, _i64]),
     "dmet_reverse_index": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dmet_edge_features_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),

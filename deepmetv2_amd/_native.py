@@ -1079,6 +1079,71 @@ def gravnet_bwd(g_out: torch.Tensor, h: torch.Tensor, s_src: torch.Tensor, s_tgt
     return g_h, g_s_src, g_s_tgt
 
 
+INTERPOLATE_MAX_F = 256           # features per row (include/dmet.h, "Interpolation")
+INTERPOLATE_MAX_K = GRAVNET_MAX_K   # DMET_MAX_K
+
+
+def _interpolate_limits(F: int, k: int) -> None:
+    if not 1 <= F <= INTERPOLATE_MAX_F:
+        raise ValueError(f"interpolate: F={F} features, supported 1..{INTERPOLATE_MAX_F}")
+    if not 1 <= k <= INTERPOLATE_MAX_K:
+        raise ValueError(f"interpolate: k={k}, supported 1..{INTERPOLATE_MAX_K}")
+
+
+def interpolate_check_shapes(x: torch.Tensor, nbr: torch.Tensor, dist: torch.Tensor) -> None:
+    """The argument errors of the interpolation entries, raised from shapes alone (before any device is asked for)."""
+    if x.dim() != 2 or nbr.dim() != 2 or dist.dim() != 2:
+        raise ValueError(f"interpolate: x [Ns, F], nbr [Nt, k] and dist [Nt, k] must be 2-D, got {tuple(x.shape)}, "
+                         f"{tuple(nbr.shape)}, {tuple(dist.shape)}")
+    _interpolate_limits(x.shape[1], nbr.shape[1])
+    if tuple(dist.shape) != tuple(nbr.shape):
+        raise ValueError(f"interpolate: the table is {tuple(nbr.shape)}, its distances {tuple(dist.shape)}")
+
+
+def interpolate_fwd(x: torch.Tensor, nbr: torch.Tensor, dist: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(out[Nt, F] = sum over row i of nbr of r_t x[j], r_t = w_t / W_i, w_t = 1 / max(dist[i,t], 1e-16); wsum[Nt] = W_i);
+    see include/dmet.h, dmet_interpolate_fwd_f32.  The outputs are zero-filled allocations: the entry writes all of them."""
+    interpolate_check_shapes(x, nbr, dist)
+    dev = _require_device(x, nbr, dist)
+    L = _lib.load()
+    x = _f32c(x, "x"); nbr = _i32c(nbr, "nbr"); dist = _f32c(dist, "dist")
+    (Ns, F), (Nt, k) = x.shape, nbr.shape
+    out = torch.zeros((Nt, F), dtype=torch.float32, device=dev)
+    wsum = torch.zeros((Nt,), dtype=torch.float32, device=dev)
+    _t = timer.record('interpolate_fwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_interpolate_fwd_f32(_ptr(x), nbr.data_ptr(), dist.data_ptr(), Nt, Ns, k, F, out.data_ptr(),
+                                              wsum.data_ptr(), _stream(dev)), "dmet_interpolate_fwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, wsum
+
+
+def interpolate_bwd(g_out: torch.Tensor, dist: torch.Tensor, wsum: torch.Tensor, rev_ptr: torch.Tensor,
+                    rev_pos: torch.Tensor, Ns: int) -> torch.Tensor:
+    """g_x[Ns, F] of interpolate_fwd; (rev_ptr, rev_pos) = the table's reverse index over the Ns sources.  See
+    include/dmet.h, dmet_interpolate_bwd_f32."""
+    if g_out.dim() != 2 or dist.dim() != 2 or g_out.shape[0] != dist.shape[0]:
+        raise ValueError(f"interpolate_bwd: g_out [Nt, F] and dist [Nt, k] must be 2-D over the same rows, got "
+                         f"{tuple(g_out.shape)} and {tuple(dist.shape)}")
+    (Nt, F), k, Ns = g_out.shape, dist.shape[1], int(Ns)
+    _interpolate_limits(F, k)
+    if Ns < 0 or wsum.numel() != Nt or rev_ptr.numel() != Ns + 1 or rev_pos.numel() < Nt * k:
+        raise ValueError(f"interpolate_bwd: wsum / reverse index do not fit a [{Nt}, {k}] table over {Ns} sources")
+    dev = _require_device(g_out, dist, wsum, rev_ptr, rev_pos)
+    L = _lib.load()
+    g_out = _f32c(g_out, "g_out"); dist = _f32c(dist, "dist"); wsum = _f32c(wsum, "wsum")
+    rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_pos = _i32c(rev_pos, "rev_pos")
+    g_x = torch.zeros((Ns, F), dtype=torch.float32, device=dev)
+    _t = timer.record('interpolate_bwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_interpolate_bwd_f32(_ptr(g_out), _ptr(dist), _ptr(wsum), rev_ptr.data_ptr(), rev_pos.data_ptr(),
+                                              Nt, Ns, k, F, _ptr(g_x), _stream(dev)), "dmet_interpolate_bwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return g_x
+
+
 ATTENTION_MAX_C = 64     # channels per head (include/dmet.h, "Attention aggregation")
 ATTENTION_MAX_H = 16     # heads
 ATTENTION_MAX_HC = 256   # heads * channels

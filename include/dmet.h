@@ -593,6 +593,38 @@ int dmet_attention_bwd_f32(const float *q, const float *k, const float *v, const
                            const int32_t *rev_ptr, const int32_t *rev_pos, int64_t Nt, int64_t Ns, int64_t E, int width,
                            int H, int C, float *alpha_w, float *gs_w, float *g_q, float *g_k, float *g_v,
                            dmet_stream_t stream);
+/* ---- Interpolation: inverse-distance feature propagation ------------------------------------------------------------
+ * replaces the body of torch_geometric.nn.unpool.knn_interpolate(x, pos_x, pos_y, batch_x, batch_y, k) after its kNN
+ * search (squared_distance = (pos_x[x_idx] - pos_y[y_idx]).pow(2).sum(-1), weights = 1 / clamp(squared_distance,
+ * min=1e-16), y = scatter(x[x_idx] * weights, y_idx, 'sum') / scatter(weights, y_idx, 'sum')) and its autograd graph: a
+ * [2, E] edge index sized by a host sync, two index_selects, the [E, F] messages and two scatters with float atomics
+ * (csrc/interpolate.hip).
+ * Inputs: a fixed-width table nbr[Nt, k] int32 of ids into the SOURCE set (-1 = empty slot, anywhere in a row; an id
+ *   outside [0, Ns) is treated as empty), dist[Nt, k] fp32 the table's own R1 squared distances (dmet_knn_xy_f32 /
+ *   dmet_knn_f32, periodic or not; the value in an empty slot is ignored), x[Ns, F] fp32 the source features.
+ *   1 <= k <= DMET_MAX_K, 1 <= F <= 256.
+ * dmet_interpolate_fwd_f32, for target i and every valid slot t, j = nbr[i,t]:
+ *   w_t = 1.0f / fmaxf(dist[i,t], 1e-16f)
+ *   W_i = sum_t w_t                         valid slots in ascending t, fp32
+ *   r_t = w_t / W_i
+ *   out[i,f] = fmaf(r_t, x[j,f], acc)       valid slots in ascending t, acc from 0
+ *   wsum[Nt] fp32: wsum[i] = W_i.  A row without a valid slot gives out[i,:] = 0 exactly (R3) and wsum[i] = 0.
+ *   The weights are normalised before the sum (upstream divides the sum): nothing overflows at w = 1e16, the backward
+ *   needs r anyway, and the two forms differ by rounding only.  Nothing per edge is written.
+ * dmet_interpolate_bwd_f32, by source j over the reverse index rev_ptr[Ns+1], rev_pos[] of
+ *   dmet_reverse_index(nbr, Nt*k, Ns), positions p = i*k + t in ascending order:
+ *   g_x[j,f] = fmaf(r_p, g_out[i,f], acc)   r_p = (1.0f / fmaxf(dist[p], 1e-16f)) / wsum[i]: the forward's expression, the
+ *   same bits.  A source nobody lists gets g_x[j,:] = 0.  A long list is walked by its one owner.
+ *   There is no gradient into dist (upstream forms the weights under no_grad).
+ * No float atomics: sums run in a fixed order, two runs give identical bits.  Every element of out, wsum and g_x is
+ * written, not accumulated.  Rows are read and written 16 bytes at a time where F % 4 == 0 and x / out (g_out / g_x)
+ * start on a 16-byte boundary, element by element otherwise, with the same bits.
+ * Both return -EINVAL on bad arguments (NULL pointers, negative sizes, k or F out of range) before any device work.
+ * Nt == 0: the forward returns 0 at once; the backward zero-fills g_x (Ns > 0) and returns. */
+int dmet_interpolate_fwd_f32(const float *x, const int32_t *nbr, const float *dist, int64_t Nt, int64_t Ns, int k, int F,
+                             float *out, float *wsum, dmet_stream_t stream);
+int dmet_interpolate_bwd_f32(const float *g_out, const float *dist, const float *wsum, const int32_t *rev_ptr,
+                             const int32_t *rev_pos, int64_t Nt, int64_t Ns, int k, int F, float *g_x, dmet_stream_t stream);
 /* Reverse index: a stable sort of the positions 0..M-1 of an int32 key array by key value.
  *   rev_ptr[num_keys+1]: rev_pos[rev_ptr[j] .. rev_ptr[j+1]-1] = the positions holding key j, ascending.
  * Keys outside [0, num_keys) (the -1 "no neighbour" entries) sort last and are not indexed.
