@@ -1040,6 +1040,11 @@ inline float knn_cut_scale()
     return (end != e && *end == '\0' && v >= 0.0f && v <= 1e6f) ? v : kF2CutScale;
 }
 
+// DMET_KNN_RUNCUT=0: the second form's main sweep records its hit masks against tk[M-1] alone and the cut is applied after
+// the sweep only, as before the running cut (f2_running_tau): same tables and counters, A/B timing in one library.  Read
+// per call.
+inline int knn_run_cut() { return env_is("DMET_KNN_RUNCUT", "0") ? 0 : 1; }
+
 // prep + filter (+ in-place re-rank) + re-rank of the split tail tiles, for result capacity KF >= k.  affine (32 features
 // only): the transform the prep launch applies; rider (32 features, second form only): the dense layer the filter launch
 // carries; nullptr: none.
@@ -1146,7 +1151,7 @@ KnnOutcome launch_knn(const KnnBuild &r, const KnnWorkspace &w)
                         w.psd, w.psj, r.nbr, r.dist, r.nbr16, w.flags, w.any, w.qflag, w.qlist, w.tile_ptr, QT, filter_form2(),
                         NH == 1 ? 1.0f : 1.5f, nullptr, nullptr, nullptr, nullptr, 0, 0,
                         (aligned16(r.nbr) && aligned16(r.dist) && aligned16(r.nbr16) && !env_is("DMET_KNN_EMIT", "lanes")) ? 1 : 0, 0,
-                        knn_cut_scale(), w.any + 1};
+                        knn_cut_scale(), w.any + 1, knn_run_cut()};
         // every event is a second-form event (the caller says so): the first form's tail merge has nothing to do
         f.no_rerank = (f.form2 && r.hint.min_nodes >= kF2MinNodes && r.hint.max_nodes >= r.hint.min_nodes &&
                        r.hint.max_nodes <= kF2MaxNodes) ? 1 : 0;

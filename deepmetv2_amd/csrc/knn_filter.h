@@ -75,6 +75,8 @@ struct KnnFilterArgs {
     float cut_scale;            // second form, final threshold min(tk[M-1], tk[k-1] + cut_scale x (what certifies the bound
                                 // d_k <= tk[k-1] + |x|^2 + slack)): see f2_cut; < 0: no cut (DMET_KNN_CUT, knn_cut_scale)
     int32_t *retries;           // [2] second attempts of the second form: wavefronts that swept again, queries they carried
+    int run_cut;                // second form: 1: the main sweep records its masks against the running cut (f2_tile, F2Lane::
+                                // margin); 0: against tk[M-1] alone, the cut comes after the sweep only (DMET_KNN_RUNCUT=0)
 };
 
 // The dense layer a build may carry (dmet_knn_local_dense_f32); P == nullptr: none.
@@ -823,7 +825,8 @@ static_assert(sizeof(F2Wave) * 12 <= 163840, "three workgroups of four wavefront
 template <int M>
 struct F2Lane {
     float tk[M];     // the M smallest tile minima, sorted
-    float tau;       // admission threshold (= tk[M-1]; -inf for idle lanes / after an overflow)
+    float tau;       // admission threshold (= min(tk[M-1], tk[k-1] + margin); -inf for idle lanes / after an overflow)
+    float margin;    // the running cut's distance above tk[k-1] (filter2_wave sets it before the main sweep); +inf: no cut
     unsigned tq;     // tau as the query side of the fold (f2_tau16; 0 while no mask is recorded)
     float rep;       // the threshold tq stands for (>= tau, or kF2TauRepMax)
     int cnt;         // entries in the lane's queue
@@ -1058,6 +1061,45 @@ __device__ __forceinline__ float f2_cut(float tkk, float nx, float scale)
 // than the split form did (measured on the model's embeddings at k = 16: uncertified queries per 4500-node event
 // ~10 at KP + 4, ~2 at KP + 5, ~0.1 at KP + 6); a lane keeps kF2Slots = 30 entries, so the widest list stays at 24
 constexpr int f2_list_len(int KP) { return KP <= 16 ? KP + 6 : KP + 4; }
+// the result capacity KP a list of M belongs to (the instances are KP = 8, 16, 20: filter2_wave asserts the round trip)
+constexpr int f2_list_cap(int M) { return M <= 22 ? M - 6 : M - 4; }
+
+// The running cut.  The main sweep used to record its hit masks against tk[M-1] alone ("the parent" below), with the
+// cut above tk[k-1] (f2_cut) applied once it was over: the cut drops whole entries, but every bit that was set
+// between the final threshold and tk[M-1] inside a surviving entry still went through a re-rank round.  The main sweep
+// therefore records against  tau = min(tk[M-1], tk[KP-1] + margin)  with `margin` = f2_cut(tk[k-1]) - tk[k-1] taken
+// once per first attempt and lane after the deferred pass, padded upward by 1 % (filter2_wave).  Tables and counters
+// stay the parent's:
+//   * tk[] does not depend on the masks, so the lists are the parent's;
+//   * fp addition of a constant is monotone and both tk[M-1] and tk[KP-1] only fall, so the thresholds the masks are
+//     taken against (f2_tile: what a CONV tile converts at 32 features, tau in every tile at 64) are non-increasing over
+//     the sweep, and the sweep leaves tau at min(tk[M-1], tk[k-1] + margin) of the final list, or at its tk[M-1];
+//   * margin was taken at a larger tk[k-1]; f2_cut's margin grows with tk[k-1] (the slack grows with sqrt(tk[k-1] +
+//     |x|^2)) up to its few-ulp nudges, which the pad covers: tk[k-1] + margin >= f2_cut(final tk[k-1]);
+//   * so the final threshold, min(tau, f2_cut(final tk[k-1])), is the parent's min(tk[M-1], cut) bit for bit;
+//   * every threshold applied on the way is at least that value: every dropped candidate had a key at or above it,
+//     which is all the certificate asks -- same outcomes, same flagged queries, same second attempts.  Only stray bits
+//     and entries disappear; a lane can only overflow more rarely;
+//   * should the pad ever be too small, the final min() hands the certificate the smallest threshold that was applied:
+//     that costs a second attempt, never a wrong row.
+// "Same outcomes" holds for every certificate that passes, and for WHICH queries fail: a stray candidate has a key at
+// or above the final threshold T, so where the certificate passes it is farther than d_k and never entered the list,
+// and where it fails, it fails without the strays as well (the k-th distance of fewer candidates is no smaller).  A
+// query that fails may see a larger k-th distance than it did with its strays, and starts its second attempt from a
+// larger T*: still exact, admits more.  It also needs a margin > 0: k tiles hold a key <= tk[k-1] < T, so the first
+// attempt always has its k candidates; at a margin of exactly zero (DMET_KNN_CUT=0.0: T = tk[k-1]) that count rested on
+// the stray bits, and queries that used to retry were flagged instead (measured, one 2000-node event at 32 features,
+// k = 16: 49 flagged / 616 retried against 20 / 649).  The running cut is therefore off at a zero margin.
+// The slot is the compile-time KP - 1 (a runtime k would cost a KP-long select chain per tile): with k != KP the margin
+// stays +inf, as it does without a cut (DMET_KNN_CUT=off), with DMET_KNN_RUNCUT=0, while tk[k-1] is the sentinel, and
+// when the margin is not a finite number > 0.
+template <int M>
+__device__ __forceinline__ float f2_running_tau(const F2Lane<M> &L)
+{
+    float t = L.tk[f2_list_cap(M) - 1] + L.margin;     // (sentinel + inf = inf; no operand is a NaN)
+    asm("v_min_f32 %0, %0, %1" : "+v"(t) : "v"(L.tk[M - 1]));
+    return t;
+}
 
 // candidate row (0..31) of hit-mask position p (counted from the most significant bit), see f2_tile
 __device__ __forceinline__ int f2_mask_row(int p) { return (p & 3) + 8 * ((p & 15) >> 2) + 4 * (p >> 4); }
@@ -1170,7 +1212,15 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
 #pragma unroll
             for (int p = M - 1; p >= 1; --p) L.tk[p] = __builtin_amdgcn_fmed3f(L.tk[p - 1], v, L.tk[p]);
             asm("v_min_f32 %0, %0, %1" : "+v"(L.tk[0]) : "v"(v));
-            if (alive && !L.overflow) L.tau = L.tk[M - 1];
+            // The running cut where a mask threshold is taken from tau: every tile at 64 features, the CONV tiles at 32
+            // (the tile between two conversions keeps tk[M-1], which only a compaction reads before the next CONV tile
+            // lowers it again: it then drops less, never more; if that tile ends the sweep, the final cut is still
+            // applied to tk[M-1], as it was before the running cut).  The deferred pass records nothing: tk[M-1].
+            // Formed outside the condition: an asm statement under an `if` becomes an exec-masked branch in every tile,
+            // not a select.
+            constexpr bool kRun = kRec && (NH != 1 || CONV);
+            const float tau = kRun ? f2_running_tau<M>(L) : L.tk[M - 1];
+            if (alive && !L.overflow) L.tau = tau;
             if (NH == 1 && kRec && CONV) {   // (every second tile: see f2_sweep)
                 L.tq = f2_tau16(L.tau, L.rep);
                 f2_fold_tau(fq, L.tq);
@@ -1268,6 +1318,7 @@ template <int KP, int NH = 1>
 __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, int *tickets, int group, int wv, int lane)
 {
     constexpr int M = f2_list_len(KP);
+    static_assert(f2_list_cap(M) == KP, "f2_running_tau reads slot KP - 1 of the list");
     constexpr int D = 32 * NH;
     constexpr int MS = (M + 1 + 3) & ~3;
     const int col = lane & 31, hh = lane >> 5;
@@ -1334,6 +1385,7 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
 #pragma unroll
     for (int p = 0; p < M; ++p) L.tk[p] = kKnnSentinel;
     L.tau = attempt == 0 ? -__builtin_inff() : t_fix;     // first attempt: nothing is recorded before tk is full
+    L.margin = __builtin_inff();
     L.tq = 0u;
     L.rep = 0.0f;
     L.cnt = 0;
@@ -1351,6 +1403,18 @@ __device__ __forceinline__ void filter2_wave(const KnnFilterArgs &a, F2Wave &S, 
         if (attempt == 0) {
             const int t_def = min(t_hi, t_lo + kF2Defer);
             f2_sweep<M, true, false, NH>(L, S, rec, rbase, t_lo, t_def, bq, lane, hh, valid);     // tau only
+            // The running cut's margin (see f2_running_tau), from the list as the deferred pass left it; the main sweep
+            // starts from the threshold it gives.  The norm is loaded here and again at the final cut: one more load
+            // per item, no register held across the main sweep.
+            if (a.run_cut && a.cut_scale >= 0.0f && a.k == KP && t_def < t_hi) {
+                const float tkk = L.tk[KP - 1];
+                int qi = valid ? myq : ev_lo;
+                asm volatile("" : "+v"(qi));
+                const float m = f2_cut<NH>(tkk, a.nrm[qi], a.cut_scale) - tkk;
+                // (a NaN fails both comparisons; a zero margin, DMET_KNN_CUT=0.0, leaves the running cut off: see above)
+                if (tkk < kKnnSentinel && m > 0.0f && m < __builtin_inff()) L.margin = __builtin_fmaf(m, 0.01f, m);
+                L.tau = fminf(L.tau, tkk + L.margin);
+            }
             f2_sweep<M, true, true, NH>(L, S, rec, rbase, t_def, t_hi, bq, lane, hh, valid);
             // The final threshold: tk[M-1], or the cut above tk[k-1] where that is lower (f2_cut).  The revisit below,
             // the compaction, the re-rank and the certificate all see the threshold that is applied here.  Lanes whose
