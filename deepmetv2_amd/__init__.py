@@ -12,6 +12,7 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import GravNetConv                    # torch_geometric.nn
     from deepmetv2_amd import TransformerConv                # torch_geometric.nn (attention_aggregate: utils.softmax + sum)
     from deepmetv2_amd import knn_interpolate                # torch_geometric.nn.unpool (interpolate_aggregate: its sums)
+    from deepmetv2_amd import PointNetConv, PointConv        # torch_geometric.nn (pointnet_aggregate: message + max)
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -31,6 +32,7 @@ from .drn import DynamicReductionNetwork
 from .gravnet import GravNetConv, gravnet_aggregate
 from .attention import TransformerConv, attention_aggregate
 from .interpolate import interpolate_aggregate, knn_interpolate
+from .pointnet import PointConv, PointNetConv, pointnet_aggregate
 
 __all__ = [
     "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "knn_xy_table", "radius", "radius_graph", "radius_table",
@@ -40,6 +42,6 @@ __all__ = [
     "graclus", "normalized_cut", "normalized_cut_2d", "max_pool", "max_pool_x", "avg_pool", "avg_pool_x",
     "global_max_pool", "global_mean_pool", "global_add_pool", "DynamicReductionNetwork",
     "GravNetConv", "gravnet_aggregate", "TransformerConv", "attention_aggregate", "fps", "nearest",
-    "knn_interpolate", "interpolate_aggregate",
+    "knn_interpolate", "interpolate_aggregate", "PointNetConv", "PointConv", "pointnet_aggregate",
 ]
 __version__ = "0.1.0"

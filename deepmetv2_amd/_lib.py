@@ -106,6 +106,11 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmet_interpolate_fwd_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp]),
     "dmet_interpolate_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp]),
+    "dmet_pointnet_supported": (_i, [_i, _i, _i, _i]),
+    "dmet_pointnet_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "dmet_pointnet_fwd_f32": (_i, [_vp] * 6 + [_i64] * 3 + [_i] * 3 + [_vp, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp] * 6 +
+                              [_sz, _vp]),
+    "dmet_pointnet_bwd_f32": (_i, [_vp] * 12 + [_i64] * 3 + [_i] * 3 + [_vp, _i, _vp] + [_i] * 4 + [_vp] * 9 + [_sz, _vp]),
     "dmet_reverse_index_workspace_bytes": (_sz, [_i64, _i64]),
     "dmet_reverse_index": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dmet_edge_features_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),

@@ -1251,6 +1251,175 @@ def attention_bwd(g_out: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torc
     return g_q, g_kv[0], g_kv[1]
 
 
+POINTNET_MAX_F = 128       # include/dmet.h, "PointNet convolution"
+POINTNET_MAX_D = 8
+POINTNET_MAX_H1 = 128
+POINTNET_H2 = (16, 32, 64, 128)
+POINTNET_MAX_WIDTH = 1024  # DMET_POINTNET_MAX_WIDTH
+POINTNET_ACT = {"relu": 0, "elu": 1}
+
+
+def pointnet_widths_supported(F: int, D: int, H1: int, H2: int) -> bool:
+    """What dmet_pointnet_supported answers, from the widths alone (no library, no device)."""
+    return 0 <= F <= POINTNET_MAX_F and 1 <= D <= POINTNET_MAX_D and 1 <= H1 <= POINTNET_MAX_H1 and H2 in POINTNET_H2
+
+
+def pointnet_check_shapes(x_src: Optional[torch.Tensor], pos_src: torch.Tensor, pos_dst: torch.Tensor, W1: torch.Tensor,
+                          b1: Optional[torch.Tensor], W2: torch.Tensor, b2: Optional[torch.Tensor], act: str,
+                          num_targets: int, num_sources: int, width: Optional[int], self_loop: bool) -> None:
+    """The argument errors of the PointNet entries, raised from shapes alone (before any device is asked for).  The graph
+    has num_targets rows over num_sources sources; width: the table form's (None: an edge list)."""
+    if pos_src.dim() != 2 or pos_dst.dim() != 2 or pos_src.shape[1] != pos_dst.shape[1]:
+        raise ValueError(f"pointnet: pos_src [Ns, D] and pos_dst [Nt, D] must be 2-D with one D, got {tuple(pos_src.shape)} "
+                         f"and {tuple(pos_dst.shape)}")
+    if x_src is not None and (x_src.dim() != 2 or x_src.shape[0] != pos_src.shape[0]):
+        raise ValueError(f"pointnet: x_src must be [{pos_src.shape[0]}, F], got {tuple(x_src.shape)}")
+    F, D = (0 if x_src is None else x_src.shape[1]), pos_src.shape[1]
+    if W1.dim() != 2 or W2.dim() != 2 or W1.shape[1] != F + D or W2.shape[1] != W1.shape[0]:
+        raise ValueError(f"pointnet: W1 must be [H1, F + D = {F + D}] and W2 [H2, H1], got {tuple(W1.shape)} and "
+                         f"{tuple(W2.shape)}")
+    H1, H2 = W1.shape[0], W2.shape[0]
+    if not pointnet_widths_supported(F, D, H1, H2):
+        raise ValueError(f"pointnet: unsupported widths F={F}, D={D}, H1={H1}, H2={H2}: 0 <= F <= {POINTNET_MAX_F}, "
+                         f"1 <= D <= {POINTNET_MAX_D}, 1 <= H1 <= {POINTNET_MAX_H1}, H2 in {POINTNET_H2}")
+    if (b1 is not None and b1.numel() != H1) or (b2 is not None and b2.numel() != H2):
+        raise ValueError(f"pointnet: b1 must hold H1 = {H1} and b2 H2 = {H2} elements")
+    if act not in POINTNET_ACT:
+        raise ValueError(f"pointnet: act must be one of {sorted(POINTNET_ACT)}, got {act!r}")
+    if width is not None and not 1 <= width <= POINTNET_MAX_WIDTH:
+        raise ValueError(f"pointnet: table width {width}, supported 1..{POINTNET_MAX_WIDTH}")
+    if pos_dst.shape[0] != num_targets:
+        raise ValueError(f"pointnet: the graph has {num_targets} target rows, pos_dst has {pos_dst.shape[0]}")
+    if pos_src.shape[0] != num_sources:
+        raise ValueError(f"pointnet: the graph indexes {num_sources} sources, pos_src has {pos_src.shape[0]} rows")
+    if self_loop and num_targets != num_sources:
+        raise ValueError(f"pointnet: self loops need one node set, got {num_sources} sources and {num_targets} targets")
+
+
+def _pointnet_graph(idx: torch.Tensor, rowptr: Optional[torch.Tensor], cnt: Optional[torch.Tensor], Nt: int):
+    """(idx, rowptr, cnt, E, width, positions) of a table (rowptr None, idx = nbr[Nt, width]) or a list (idx = src[E])."""
+    idx = _i32c(idx, "nbr" if rowptr is None else "src")
+    if rowptr is None:
+        if idx.dim() != 2 or idx.shape[0] != Nt:
+            raise ValueError(f"pointnet: nbr must be [{Nt}, width], got {tuple(idx.shape)}")
+        if cnt is not None:
+            cnt = _i32c(cnt, "cnt")
+            if cnt.numel() != Nt:
+                raise ValueError(f"pointnet: cnt must hold {Nt} entries, got {cnt.numel()}")
+        return idx, None, cnt, 0, int(idx.shape[1]), Nt * int(idx.shape[1])
+    rowptr = _i32c(rowptr, "rowptr")
+    if idx.dim() != 1 or rowptr.numel() != Nt + 1:
+        raise ValueError(f"pointnet: src must be [E] and rowptr [{Nt + 1}], got {tuple(idx.shape)} and {tuple(rowptr.shape)}")
+    return idx, rowptr, None, int(idx.numel()), 0, int(idx.numel())
+
+
+def _pointnet_fwd(x_src: Optional[torch.Tensor], pos_src: torch.Tensor, pos_dst: torch.Tensor, idx: torch.Tensor,
+                  rowptr: Optional[torch.Tensor], cnt: Optional[torch.Tensor], W1: torch.Tensor, b1: Optional[torch.Tensor],
+                  W2: torch.Tensor, b2: Optional[torch.Tensor], act: str, act2: bool, self_loop: bool):
+    """(out[Nt, H2], win[Nt, H2] int32, state) of the fused PointNet aggregation over a table (idx = nbr[Nt, width], rowptr
+    None, cnt optional) or a grouped edge list (idx = src[E], rowptr[Nt+1]); see include/dmet.h, dmet_pointnet_fwd_f32.
+    `state` = (a, b, s or None) is what _pointnet_bwd needs beside out and win.  Not public: the closed table of
+    allocating wrappers names the public ones; pointnet.py is the caller."""
+    Nt, Ns = pos_dst.shape[0], pos_src.shape[0]
+    width = idx.shape[1] if rowptr is None and idx.dim() == 2 else None
+    pointnet_check_shapes(x_src, pos_src, pos_dst, W1, b1, W2, b2, act, Nt, Ns, width, self_loop)
+    dev = _require_device(x_src, pos_src, pos_dst, idx, rowptr, cnt, W1, b1, W2, b2)
+    L = _lib.load()
+    same = pos_src is pos_dst
+    pos_src = _f32c(pos_src, "pos_src")
+    pos_dst = pos_src if same else _f32c(pos_dst, "pos_dst")
+    if x_src is not None:
+        x_src = _f32c(x_src, "x_src")
+    W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2")
+    b1 = None if b1 is None else _f32c(b1, "b1")
+    b2 = None if b2 is None else _f32c(b2, "b2")
+    idx, rowptr, cnt, E, width, _M = _pointnet_graph(idx, rowptr, cnt, Nt)
+    F, D = (0 if x_src is None else x_src.shape[1]), pos_src.shape[1]
+    H1, H2 = W1.shape[0], W2.shape[0]
+    out = torch.empty((Nt, H2), dtype=torch.float32, device=dev)
+    win = torch.empty((Nt, H2), dtype=torch.int32, device=dev)
+    a = torch.empty((Ns, H1), dtype=torch.float32, device=dev)
+    b = torch.empty((Nt, H1), dtype=torch.float32, device=dev)
+    s = torch.empty((Nt, H1), dtype=torch.float32, device=dev) if self_loop else None
+    _t = timer.record('pointnet_fwd', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_pointnet_workspace_bytes(F, D, H1, H2), dev)
+        _lib.check(L.dmet_pointnet_fwd_f32(_ptr(x_src), _ptr(pos_src), _ptr(pos_dst), _ptr(idx),
+                                           None if rowptr is None else rowptr.data_ptr(), _ptr(cnt), Nt, Ns, E, width, F, D,
+                                           W1.data_ptr(), _ptr(b1), H1, W2.data_ptr(), _ptr(b2), H2, POINTNET_ACT[act],
+                                           1 if act2 else 0, 1 if self_loop else 0, _ptr(a), _ptr(b), _ptr(s), _ptr(out),
+                                           _ptr(win), ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_pointnet_fwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, win, (a, b, s)
+
+
+def _pointnet_bwd(g_out: torch.Tensor, out: torch.Tensor, win: torch.Tensor, state, x_src: Optional[torch.Tensor],
+                  pos_src: torch.Tensor, pos_dst: torch.Tensor, idx: torch.Tensor, rev_ptr: torch.Tensor,
+                  rev_pos: torch.Tensor, rowptr: Optional[torch.Tensor], tgt: Optional[torch.Tensor],
+                  cnt: Optional[torch.Tensor], W1: torch.Tensor, W2: torch.Tensor, act: str, act2: bool, self_loop: bool,
+                  want=(True, True, True, True, True, True, True)):
+    """(g_x, g_pos_src, g_pos_dst, g_W1, g_b1, g_W2, g_b2) of _pointnet_fwd, None where `want` says so (g_x also for
+    F == 0); (rev_ptr, rev_pos) = the graph's by-source index (table.reverse() / EdgeList.by_source()), tgt = EdgeList.tgt
+    for a list.  See include/dmet.h, dmet_pointnet_bwd_f32.  g_W1 and g_b1 are formed here through dmet_xty_f32."""
+    a, b, s = state
+    Nt, Ns = b.shape[0], a.shape[0]
+    dev = _require_device(g_out, out, win, a, b, s, idx, rev_ptr, rev_pos, rowptr, tgt, cnt, W1, W2)
+    L = _lib.load()
+    g_out = _f32c(g_out, "g_out"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2")
+    idx, rowptr, cnt, E, width, M = _pointnet_graph(idx, rowptr, cnt, Nt)
+    rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_pos = _i32c(rev_pos, "rev_pos")
+    H1, H2 = W1.shape[0], W2.shape[0]
+    D = pos_src.shape[1]
+    F = W1.shape[1] - D
+    if tuple(g_out.shape) != (Nt, H2) or tuple(out.shape) != (Nt, H2) or tuple(win.shape) != (Nt, H2):
+        raise ValueError(f"pointnet_bwd: g_out, out and win must be [{Nt}, {H2}]")
+    if rev_ptr.numel() != Ns + 1:
+        raise ValueError(f"pointnet_bwd: the by-source index must cover {Ns} sources")
+    if rowptr is not None:
+        if tgt is None or tgt.numel() != E:
+            raise ValueError(f"pointnet_bwd: an edge list needs tgt [{E}]")
+        tgt = _i32c(tgt, "tgt")
+    want_x, want_ps, want_pd, want_w1, want_b1, want_w2, want_b2 = want
+    g_a = torch.empty((Ns, H1), dtype=torch.float32, device=dev)
+    g_b = torch.empty((Nt, H1), dtype=torch.float32, device=dev)
+    g_s = torch.empty((Nt, H1), dtype=torch.float32, device=dev) if self_loop else None
+    g_x = torch.empty((Ns, F), dtype=torch.float32, device=dev) if want_x and F > 0 else None
+    g_ps = torch.empty((Ns, D), dtype=torch.float32, device=dev) if want_ps else None
+    g_pd = torch.empty((Nt, D), dtype=torch.float32, device=dev) if want_pd else None
+    g_W2 = torch.empty((H2, H1), dtype=torch.float32, device=dev) if want_w2 else None
+    g_b2 = torch.empty((H2,), dtype=torch.float32, device=dev) if want_b2 else None
+    _t = timer.record('pointnet_bwd', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_pointnet_workspace_bytes(F, D, H1, H2), dev)
+        _lib.check(L.dmet_pointnet_bwd_f32(_ptr(a), _ptr(b), _ptr(s), _ptr(out), _ptr(win), _ptr(g_out), _ptr(idx),
+                                           None if rowptr is None else rowptr.data_ptr(), _ptr(tgt), _ptr(cnt),
+                                           rev_ptr.data_ptr(), rev_pos.data_ptr(), Nt, Ns, E, width, F, D, W1.data_ptr(), H1,
+                                           W2.data_ptr(), H2, POINTNET_ACT[act], 1 if act2 else 0, 1 if self_loop else 0,
+                                           _ptr(g_a), _ptr(g_b), _ptr(g_s), _ptr(g_x), _ptr(g_ps), _ptr(g_pd), _ptr(g_W2),
+                                           _ptr(g_b2), ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_pointnet_bwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    g_W1 = g_b1 = None
+    if want_w1 or want_b1:
+        g_as = g_a + g_s if self_loop else g_a        # what reaches x and b1: the implicit entry reads no position
+        if want_b1:
+            g_b1 = xty_wide_ones(g_as) if Ns else torch.zeros((H1,), dtype=torch.float32, device=dev)
+        if want_w1:
+            parts = []
+            if F > 0:
+                parts.append(_xty_wide(g_as, _f32c(x_src, "x_src")) if Ns else torch.zeros((H1, F), dtype=torch.float32,
+                                                                                          device=dev))
+            gp = torch.zeros((H1, D), dtype=torch.float32, device=dev)
+            if Ns:
+                gp = gp + _xty_wide(g_a, _f32c(pos_src, "pos_src"))
+            if Nt:
+                gp = gp + _xty_wide(g_b, _f32c(pos_dst, "pos_dst"))
+            parts.append(gp)
+            g_W1 = torch.cat(parts, dim=1)
+    return g_x, g_ps, g_pd, g_W1, g_b1, g_W2, g_b2
+
+
 def reverse_index(keys: torch.Tensor, num_keys: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Stable sort of positions by int32 key: rev_ptr[num_keys+1] int32, rev_pos[M] int32 (see include/dmet.h)."""
     dev = _require_device(keys)

@@ -625,6 +625,68 @@ int dmet_interpolate_fwd_f32(const float *x, const int32_t *nbr, const float *di
                              float *out, float *wsum, dmet_stream_t stream);
 int dmet_interpolate_bwd_f32(const float *g_out, const float *dist, const float *wsum, const int32_t *rev_ptr,
                              const int32_t *rev_pos, int64_t Nt, int64_t Ns, int k, int F, float *g_x, dmet_stream_t stream);
+/* ---- PointNet convolution: fused set abstraction -------------------------------------------------------------------
+ * replaces torch_geometric.nn.PointNetConv.forward for local_nn = Sequential(Linear(F + D, H1), act, Linear(H1, H2)
+ * [, act]) and aggr = 'max': remove_self_loops + add_self_loops on the edge index, message
+ * (msg = pos_j - pos_i; msg = torch.cat([x_j, msg], dim=1); return self.local_nn(msg)) and the scatter max, with their
+ * autograd graph: the [E, F + D] features, the [E, H1] and [E, H2] activations and a host read of E
+ * (csrc/pointnet.hip).
+ * Inputs: x_src[Ns, F] (NULL when F == 0), pos_src[Ns, D], pos_dst[Nt, D], W1[H1, F + D] = [W1x | W1p], b1[H1] or NULL,
+ *   W2[H2, H1], b2[H2] or NULL; fp32, contiguous, row-major as torch.nn.Linear.weight.  0 <= F <= 128, 1 <= D <= 8,
+ *   1 <= H1 <= 128, H2 in {16, 32, 64, 128}: dmet_pointnet_supported(F, D, H1, H2) returns 1 for these, 0 otherwise.
+ *   act: 0 ReLU, 1 ELU (alpha 1; expm1f below 0), used in both places; act2: 1 applies it after the second Linear too.
+ * The graph in one of two forms:
+ *   table (rowptr == NULL): idx = nbr[Nt, width] int32, 1 <= width <= DMET_POINTNET_MAX_WIDTH; an id outside [0, Ns) is
+ *     an empty slot, anywhere in a row; with cnt[Nt] (may be NULL) the slots at or beyond cnt[i] are never read; E is
+ *     ignored.
+ *   list  (rowptr != NULL): rowptr[Nt+1], idx = src[E], tgt[E] int32 grouped by target, any in-degree; width and cnt are
+ *     ignored; src / tgt may be NULL when E == 0.
+ *   self_loop = 1 (legal only with Ns == Nt, one node set): entries with src == i are skipped and one implicit entry
+ *     i -> i is taken after the row's own entries -- remove_self_loops + add_self_loops without rewriting the graph.
+ * dmet_pointnet_fwd_f32, in evaluation order:
+ *   s[j,c] = fmaf chain over f ascending from b1[c] of x_src[j,f] W1[c,f]            (written only with self_loop)
+ *   p[n,c] = fmaf chain over d ascending from 0 of pos[n,d] W1[c,F+d]
+ *   a[Ns,H1] = s + p over the sources,  b[Nt,H1] = p over the targets            (the caller's buffers, kept for backward)
+ *   h1_e = act(a[src(e)] - b[i]) for an entry e of target i;  h1 = act(s[i]) for the implicit entry: a position
+ *     difference of exactly 0
+ *   z2_e[o] = b2[o] + sum_c h1_e[c] W2[o,c]   on v_mfma_f32_16x16x4_f32, c in the order 16 B + 4 q + t for B, then t = 0..3,
+ *     then the matrix core's own q = 0..3;  m_e = act(z2_e) when act2 else z2_e
+ *   out[i,o] = max_e m_e[o] over the row's entries in entry order, strict compares: the earliest entry wins a tie (R4)
+ *   win[Nt,H2] int32: the winning table slot t (table) or grouped list position (list), -2 for the implicit entry, -1
+ *     for a target without an entry, whose out row is exactly 0 (R3).  Nothing per edge is written.
+ * dmet_pointnet_bwd_f32, with g_z2[i,o] = g_out[i,o] act'(out[i,o]) (act2; else g_out[i,o]) routed to entry win[i,o]:
+ *   g_pre1_e = (sum_o g_z2_e[o] W2[o,:]) act'(h1_e), h1_e formed again as above.
+ *   by target: g_b[i] = -sum_e g_pre1_e over the row's own entries, g_s[i] = g_pre1 of the implicit entry (self_loop),
+ *     g_W2 = sum g_z2_e^T h1_e and g_b2 = sum g_z2 as one partial per workgroup, added in workgroup order in double.
+ *   by source, over the by-source index rev_ptr[Ns+1], rev_pos[] in ascending order -- dmet_reverse_index(nbr, Nt*width,
+ *     Ns) for a table (i = pos / width), dmet_reverse_index(src, E, Ns) for a list (i = tgt[pos]):  g_a[j] = sum g_pre1_e.
+ *     Four consecutive sources share a wavefront and its tiles of 16 positions; a long list is walked by its one owner.
+ *   node level: g_x = (g_a + g_s) W1x, g_pos_src = g_a W1p, g_pos_dst = g_b W1p (g_x, g_pos_src, g_pos_dst, g_W2, g_b2
+ *     may each be NULL: not wanted).  g_a[Ns,H1], g_b[Nt,H1], g_s[Nt,H1] are the caller's buffers and outputs:
+ *     g_W1 = [(g_a + g_s)^T x_src | g_a^T pos_src + g_b^T pos_dst] and g_b1 = column sums of g_a + g_s follow through
+ *     dmet_xty_f32 on the caller's side.
+ *   Every gradient element is written, not accumulated; the backward zero-fills the source-side gradients (g_a, g_x,
+ *   g_pos_src) first, so a source nobody lists gets exact zeros.  No float atomics: two runs give identical bits, and a
+ *   table and a list holding the same entries in the same order give identical bits (the tiles of 16 are cut from the
+ *   entry numbers of a row: a table's valid slots come first, as in every table this library builds).
+ * ws: dmet_pointnet_workspace_bytes(F, D, H1, H2) bytes (0 for unsupported widths).
+ * Both return -EINVAL before any device work on NULL or negative arguments, unsupported widths, a width outside the
+ * limit and self_loop with Ns != Nt.  Nt == 0: the forward returns 0 at once; the backward zero-fills the source-side
+ * gradients, g_W2 and g_b2 and returns. */
+#define DMET_POINTNET_MAX_WIDTH 1024
+int dmet_pointnet_supported(int F, int D, int H1, int H2);
+size_t dmet_pointnet_workspace_bytes(int F, int D, int H1, int H2);
+int dmet_pointnet_fwd_f32(const float *x_src, const float *pos_src, const float *pos_dst, const int32_t *idx,
+                          const int32_t *rowptr, const int32_t *cnt, int64_t Nt, int64_t Ns, int64_t E, int width, int F,
+                          int D, const float *W1, const float *b1, int H1, const float *W2, const float *b2, int H2, int act,
+                          int act2, int self_loop, float *a, float *b, float *s, float *out, int32_t *win, void *ws,
+                          size_t ws_bytes, dmet_stream_t stream);
+int dmet_pointnet_bwd_f32(const float *a, const float *b, const float *s, const float *out, const int32_t *win,
+                          const float *g_out, const int32_t *idx, const int32_t *rowptr, const int32_t *tgt,
+                          const int32_t *cnt, const int32_t *rev_ptr, const int32_t *rev_pos, int64_t Nt, int64_t Ns,
+                          int64_t E, int width, int F, int D, const float *W1, int H1, const float *W2, int H2, int act,
+                          int act2, int self_loop, float *g_a, float *g_b, float *g_s, float *g_x, float *g_pos_src,
+                          float *g_pos_dst, float *g_W2, float *g_b2, void *ws, size_t ws_bytes, dmet_stream_t stream);
 /* Reverse index: a stable sort of the positions 0..M-1 of an int32 key array by key value.
  *   rev_ptr[num_keys+1]: rev_pos[rev_ptr[j] .. rev_ptr[j+1]-1] = the positions holding key j, ascending.
  * Keys outside [0, num_keys) (the -1 "no neighbour" entries) sort last and are not indexed.
