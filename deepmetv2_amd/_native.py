@@ -182,20 +182,29 @@ def _note_gather(name: str) -> None:
 # ---- K1 ------------------------------------------------------------------------------------------------------
 # ---- the weight-gradient sums of a backward pass in one launch (dmet_finalize_defer_begin / dmet_finalize_flush) --------
 DEFER_FINALIZE = os.environ.get("DMET_DEFER_FINALIZE", "1") != "0"
-_DEFER = {"active": False, "keep": [], "dev": None}
+_DEFER = {"active": False, "keep": [], "dev": None, "seen": set()}
 
 
 def finalize_defer_begin() -> bool:
     """From here to finalize_flush() (process-wide: autograd runs backward on a thread of its own) edgeconv_linear_bwd, encode_bwd / encode_bn_bwd and head_bwd leave
     the small second launch that sums their weight-gradient partials to ONE launch at the flush: their parameter
-    gradients hold garbage until then (the harness flushes right after loss.backward()), and their workspaces are kept
-    alive here.  DMET_DEFER_FINALIZE=0: a no-op (every call sums its own partials at once, as without this call)."""
+    gradients hold garbage until then (the harness flushes right after loss.backward()).  Kept alive here until the flush:
+    the calls' workspaces AND the memory of the gradients they returned -- autograd drops the gradient of a parameter
+    with requires_grad=False during the pass, and the flush would write into whoever got the block next.  The queue of
+    the library holds 8 sums; a call beyond them sums at once.  DMET_DEFER_FINALIZE=0: a no-op (every call sums its own
+    partials at once, as without this call).
+
+    What the caller still has to hold to: nothing may READ one of those gradients before the flush.  Autograd itself
+    does when a parameter is used twice in the pass (it adds the two gradients): the second call on the same
+    parameters therefore forms the sums queued so far and its own at once (_defer_second_use).  Not covered: a weight that
+    is no leaf (its gradient flows on into other backward nodes), tensor hooks on these parameters, a backward pass
+    that accumulates into a .grad that is already there (train_step drops every .grad first)."""
     if not DEFER_FINALIZE:
         return False
     if _DEFER["active"]:
         finalize_flush()     # a deferral somebody left open (an exception between begin and flush): its sums are formed first
     _lib.check(_lib.load().dmet_finalize_defer_begin(), "dmet_finalize_defer_begin")
-    _DEFER["active"], _DEFER["keep"], _DEFER["dev"] = True, [], None
+    _DEFER["active"], _DEFER["keep"], _DEFER["dev"], _DEFER["seen"] = True, [], None, set()
     return True
 
 
@@ -213,14 +222,43 @@ def finalize_flush() -> None:
         else:
             _lib.check(L.dmet_finalize_flush(None), "dmet_finalize_flush")
     finally:
-        _DEFER["active"], _DEFER["keep"], _DEFER["dev"] = False, [], None
+        _DEFER["active"], _DEFER["keep"], _DEFER["dev"], _DEFER["seen"] = False, [], None, set()
 
 
-def _defer_keep(dev: torch.device, *workspaces: torch.Tensor) -> None:
-    # a queued sum reads its partials from the call's workspace at the flush: the workspace must not go back to the allocator
+def _defer_keep(dev: torch.device, ws: torch.Tensor, *outs: Optional[torch.Tensor]) -> None:
+    """A queued sum reads its partials from the call's workspace `ws` at the flush and writes the gradients `outs` there:
+    neither may go back to the allocator before.  Of the gradients the STORAGE is kept, not the tensor: a second
+    reference to the tensor itself would make autograd copy it (unwritten) into .grad instead of taking it over."""
     if _DEFER["active"]:
         _DEFER["dev"] = dev
-        _DEFER["keep"].extend(workspaces)
+        _DEFER["keep"].append(ws)
+        _DEFER["keep"].extend(t.untyped_storage() for t in outs if t is not None)
+
+
+def _defer_second_use(dev: torch.device, *params: Optional[torch.Tensor]) -> bool:
+    """Before a call that would queue the gradient sums of `params`: False when none of them was seen in this deferral
+    (they are now).  A module applied twice comes here a second time: autograd adds the two gradients of a parameter as
+    soon as it has both, so neither may be unwritten then.  The sums queued so far are formed now, in their queue order,
+    and the library's queue is closed, so that the call sums at once; True -- the caller reopens it after the call
+    (_defer_resume) for what the pass has left.  The bits are those of the per-call sums either way."""
+    if not _DEFER["active"]:
+        return False
+    keys = {p.data_ptr() for p in params if p is not None}
+    if _DEFER["seen"].isdisjoint(keys):
+        _DEFER["seen"] |= keys
+        return False
+    L = _lib.load()
+    qdev = _DEFER["dev"] if _DEFER["dev"] is not None else dev
+    if L.dmet_finalize_pending() > 0:
+        with _on(qdev):
+            _lib.check(L.dmet_finalize_flush(_stream(qdev)), "dmet_finalize_flush")
+    else:
+        _lib.check(L.dmet_finalize_flush(None), "dmet_finalize_flush")
+    return True
+
+
+def _defer_resume() -> None:
+    _lib.check(_lib.load().dmet_finalize_defer_begin(), "dmet_finalize_defer_begin")
 
 
 def knn_size_hint(min_nodes: Optional[int], max_nodes: Optional[int]) -> None:
@@ -1702,10 +1740,15 @@ def encode_bwd(x_cont: torch.Tensor, x_cat: torch.Tensor, params, h: torch.Tenso
         return [g.zero_() for g in grads]
     with _on(dev):
         ws = _ws(L.dmet_encode_bwd_workspace_bytes(N), dev)
-        _lib.check(L.dmet_encode_bwd_f32(x.data_ptr(), x.stride(0), _ptr(xc), N, *[t.data_ptr() for t in ps],
-                                         h.data_ptr(), g_h.data_ptr(), *[g.data_ptr() for g in grads], ws.data_ptr(),
-                                         ws.numel(), _stream(dev)), "dmet_encode_bwd_f32")
-        _defer_keep(dev, ws)
+        again = _defer_second_use(dev, *params)
+        try:
+            _lib.check(L.dmet_encode_bwd_f32(x.data_ptr(), x.stride(0), _ptr(xc), N, *[t.data_ptr() for t in ps],
+                                             h.data_ptr(), g_h.data_ptr(), *[g.data_ptr() for g in grads], ws.data_ptr(),
+                                             ws.numel(), _stream(dev)), "dmet_encode_bwd_f32")
+        finally:
+            if again:
+                _defer_resume()
+        _defer_keep(dev, ws, *grads)
     return grads
 
 
@@ -1735,13 +1778,21 @@ def encode_bn_bwd(x_cont: torch.Tensor, x_cat: torch.Tensor, params, h: torch.Te
                                            st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr(), st[3].data_ptr(),
                                            ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_bn_bwd_stats_f32")
         ws2 = _ws(L.dmet_encode_bwd_workspace_bytes(N), dev)
-        _lib.check(L.dmet_encode_bn_bwd_f32(x.data_ptr(), x.stride(0), _ptr(xc), N,
-                                            *[t.data_ptr() for t in ps], h.data_ptr(), g_y.data_ptr(), gamma.data_ptr(),
-                                            mean.data_ptr(), invstd.data_ptr(), st[2].data_ptr(), st[3].data_ptr(),
-                                            *[g.data_ptr() for g in grads],
-                                            ctypes.cast(ctypes.pointer(fused), ctypes.c_void_p), ws2.data_ptr(), ws2.numel(),
-                                            _stream(dev)), "dmet_encode_bn_bwd_f32")
-        _defer_keep(dev, ws2)
+        again = _defer_second_use(dev, *params)
+        try:
+            _lib.check(L.dmet_encode_bn_bwd_f32(x.data_ptr(), x.stride(0), _ptr(xc), N,
+                                                *[t.data_ptr() for t in ps], h.data_ptr(), g_y.data_ptr(), gamma.data_ptr(),
+                                                mean.data_ptr(), invstd.data_ptr(), st[2].data_ptr(), st[3].data_ptr(),
+                                                *[g.data_ptr() for g in grads],
+                                                ctypes.cast(ctypes.pointer(fused), ctypes.c_void_p), ws2.data_ptr(), ws2.numel(),
+                                                _stream(dev)), "dmet_encode_bn_bwd_f32")
+        finally:
+            if again:
+                _defer_resume()
+        if fused.value:
+            _defer_keep(dev, ws2, *grads)
+        elif not again:     # nothing was launched or queued: the caller's encode_bwd is these parameters' first use
+            _DEFER["seen"].difference_update(p.data_ptr() for p in params)
     if not fused.value:
         return None
     return grads, st[0], st[1]
@@ -1893,6 +1944,7 @@ def edgeconv_linear_bwd(x: torch.Tensor, weight: torch.Tensor, g_out: torch.Tens
     (255 = none) or uint16 winner ids (0xFFFF = none): g_out is masked to 0 there (R3: such a node produced 0)."""
     dev = _require_device(x, weight, g_out, gQ)
     L = _lib.load()
+    weight_key = weight      # the caller's tensor, before any contiguous copy: what tells a second use of the layer
     x = _f32c(x, "x"); weight = _f32c(weight, "weight"); g_out = _f32c(g_out, "g_out"); gQ = _f32c(gQ, "gQ")
     N, H = x.shape
     if H != 32 or tuple(weight.shape) != (32, 64) or g_out.shape != x.shape or (
@@ -1911,18 +1963,23 @@ def edgeconv_linear_bwd(x: torch.Tensor, weight: torch.Tensor, g_out: torch.Tens
             g_add = _f32c(g_add, "g_add")
             if g_add.shape != x.shape:
                 raise ValueError("edgeconv_linear_bwd: g_add must have the shape of x")
-        if gq_sliced:
-            _lib.check(L.dmet_edgeconv_linear_bwd_sliced_f32(x.data_ptr(), weight.data_ptr(), g_out.data_ptr(),
-                                                             _ptr(arg), int(j16), gQ.data_ptr(), _ptr(g_add), N, H,
-                                                             gx.data_ptr(), gW.data_ptr(), _ptr(gb),
-                                                             ws.data_ptr(), ws.numel(), _stream(dev)),
-                       "dmet_edgeconv_linear_bwd_sliced_f32")
-        else:
-            entry = L.dmet_edgeconv_linear_bwd_add_j16_f32 if j16 else L.dmet_edgeconv_linear_bwd_add_f32
-            _lib.check(entry(x.data_ptr(), weight.data_ptr(), g_out.data_ptr(), _ptr(arg), gQ.data_ptr(), _ptr(g_add), N, H,
-                             gx.data_ptr(), gW.data_ptr(), _ptr(gb), ws.data_ptr(), ws.numel(), _stream(dev)),
-                       "dmet_edgeconv_linear_bwd_add_j16_f32" if j16 else "dmet_edgeconv_linear_bwd_add_f32")
-        _defer_keep(dev, ws)
+        again = _defer_second_use(dev, weight_key)
+        try:
+            if gq_sliced:
+                _lib.check(L.dmet_edgeconv_linear_bwd_sliced_f32(x.data_ptr(), weight.data_ptr(), g_out.data_ptr(),
+                                                                 _ptr(arg), int(j16), gQ.data_ptr(), _ptr(g_add), N, H,
+                                                                 gx.data_ptr(), gW.data_ptr(), _ptr(gb),
+                                                                 ws.data_ptr(), ws.numel(), _stream(dev)),
+                           "dmet_edgeconv_linear_bwd_sliced_f32")
+            else:
+                entry = L.dmet_edgeconv_linear_bwd_add_j16_f32 if j16 else L.dmet_edgeconv_linear_bwd_add_f32
+                _lib.check(entry(x.data_ptr(), weight.data_ptr(), g_out.data_ptr(), _ptr(arg), gQ.data_ptr(), _ptr(g_add), N, H,
+                                 gx.data_ptr(), gW.data_ptr(), _ptr(gb), ws.data_ptr(), ws.numel(), _stream(dev)),
+                           "dmet_edgeconv_linear_bwd_add_j16_f32" if j16 else "dmet_edgeconv_linear_bwd_add_f32")
+        finally:
+            if again:
+                _defer_resume()
+        _defer_keep(dev, ws, gW, gb)
     return gx, gW, gb
 
 
@@ -2026,11 +2083,16 @@ def head_bwd(emb: torch.Tensor, params, out: torch.Tensor, g_out: torch.Tensor):
         return [g_emb] + [g.zero_() for g in grads]
     with _on(dev):
         ws = _ws(L.dmet_head_bwd_workspace_bytes(N), dev)
-        _lib.check(L.dmet_head_bwd_f32(emb.data_ptr(), N, ps[0].data_ptr(), ps[1].data_ptr(), ps[2].data_ptr(),
-                                       out.data_ptr(), g_out.data_ptr(), g_emb.data_ptr(),
-                                       *[g.data_ptr() for g in grads], ws.data_ptr(), ws.numel(), _stream(dev)),
-                   "dmet_head_bwd_f32")
-        _defer_keep(dev, ws)
+        again = _defer_second_use(dev, *params)
+        try:
+            _lib.check(L.dmet_head_bwd_f32(emb.data_ptr(), N, ps[0].data_ptr(), ps[1].data_ptr(), ps[2].data_ptr(),
+                                           out.data_ptr(), g_out.data_ptr(), g_emb.data_ptr(),
+                                           *[g.data_ptr() for g in grads], ws.data_ptr(), ws.numel(), _stream(dev)),
+                       "dmet_head_bwd_f32")
+        finally:
+            if again:
+                _defer_resume()
+        _defer_keep(dev, ws, *grads)
     return [g_emb] + grads
 
 
