@@ -13,6 +13,7 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import TransformerConv                # torch_geometric.nn (attention_aggregate: utils.softmax + sum)
     from deepmetv2_amd import knn_interpolate                # torch_geometric.nn.unpool (interpolate_aggregate: its sums)
     from deepmetv2_amd import PointNetConv, PointConv        # torch_geometric.nn (pointnet_aggregate: message + max)
+    from deepmetv2_amd import GATConv, GATv2Conv             # torch_geometric.nn (gat_v1_aggregate / gat_aggregate)
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -33,6 +34,7 @@ from .gravnet import GravNetConv, gravnet_aggregate
 from .attention import TransformerConv, attention_aggregate
 from .interpolate import interpolate_aggregate, knn_interpolate
 from .pointnet import PointConv, PointNetConv, pointnet_aggregate
+from .gat import GATConv, GATv2Conv, gat_aggregate, gat_v1_aggregate
 
 __all__ = [
     "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "knn_xy_table", "radius", "radius_graph", "radius_table",
@@ -43,5 +45,6 @@ __all__ = [
     "global_max_pool", "global_mean_pool", "global_add_pool", "DynamicReductionNetwork",
     "GravNetConv", "gravnet_aggregate", "TransformerConv", "attention_aggregate", "fps", "nearest",
     "knn_interpolate", "interpolate_aggregate", "PointNetConv", "PointConv", "pointnet_aggregate",
+    "GATConv", "GATv2Conv", "gat_aggregate", "gat_v1_aggregate",
 ]
 __version__ = "0.1.0"

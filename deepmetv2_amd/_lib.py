@@ -104,6 +104,9 @@ SIGNATURES = {
     "dmet_attention_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dmet_attention_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i,
                                     _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dmet_gat_supported": (_i, [_i, _i]),
+    "dmet_gat_fwd_f32": (_i, [_i] + [_vp] * 5 + [_f, _i, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dmet_gat_bwd_f32": (_i, [_i] + [_vp] * 5 + [_f, _i] + [_vp] * 8 + [_i64, _i64, _i64, _i, _i, _i] + [_vp] * 9 + [_vp]),
     "dmet_interpolate_fwd_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp]),
     "dmet_interpolate_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp]),
     "dmet_pointnet_supported": (_i, [_i, _i, _i, _i]),

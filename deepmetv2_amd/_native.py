@@ -8,6 +8,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import inspect
+import math
 import os
 from typing import Optional, Tuple
 
@@ -1287,6 +1288,146 @@ def attention_bwd(g_out: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torc
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
     return g_q, g_kv[0], g_kv[1]
+
+
+GAT_MAX_C = ATTENTION_MAX_C      # include/dmet.h, "GAT aggregation": the attention section's limits
+GAT_MAX_H = ATTENTION_MAX_H
+GAT_MAX_HC = ATTENTION_MAX_HC
+GAT_MAX_K = ATTENTION_MAX_K
+GAT_V1, GAT_V2 = 1, 2            # the ABI's mode: GATConv / GATv2Conv
+
+
+def gat_check_shapes(mode: int, xl: torch.Tensor, a: torch.Tensor, b: torch.Tensor, num_targets: int, num_sources: int,
+                     width: Optional[int] = None, negative_slope: float = 0.2, self_loops: bool = False) -> None:
+    """The argument errors of the GAT entries, raised from shapes alone (before any device is asked for).  mode GAT_V2:
+    (a, b) = (xr[Nt, H, C], att[H, C]); mode GAT_V1: (a, b) = (s_src[Ns, H], s_dst[Nt, H]).  The graph has num_targets
+    rows over num_sources sources; width: the table form's k (None: an edge list)."""
+    if mode not in (GAT_V1, GAT_V2):
+        raise ValueError(f"gat: mode={mode!r}, {GAT_V1} (GATConv) or {GAT_V2} (GATv2Conv)")
+    if xl.dim() != 3:
+        raise ValueError(f"gat: xl must be [Ns, H, C], got {tuple(xl.shape)}")
+    H, C = xl.shape[1], xl.shape[2]
+    if not 1 <= C <= GAT_MAX_C:
+        raise ValueError(f"gat: C={C} channels per head, supported 1..{GAT_MAX_C}")
+    if not 1 <= H <= GAT_MAX_H:
+        raise ValueError(f"gat: H={H} heads, supported 1..{GAT_MAX_H}")
+    if H * C > GAT_MAX_HC:
+        raise ValueError(f"gat: H*C={H * C}, supported up to {GAT_MAX_HC}")
+    if width is not None and not 1 <= width <= GAT_MAX_K:
+        raise ValueError(f"gat: k={width}, supported 1..{GAT_MAX_K}")
+    slope = float(negative_slope)
+    if not (math.isfinite(slope) and slope >= 0.0):
+        raise ValueError(f"gat: negative_slope={negative_slope!r} must be finite and >= 0")
+    if mode == GAT_V2:
+        if a.dim() != 3 or tuple(a.shape[1:]) != (H, C):
+            raise ValueError(f"gat: xl has {H} heads of {C} channels, xr must be [Nt, {H}, {C}], got {tuple(a.shape)}")
+        if tuple(b.shape) not in ((H, C), (1, H, C)):
+            raise ValueError(f"gat: att must be [{H}, {C}] (or [1, {H}, {C}]), got {tuple(b.shape)}")
+        nt = a.shape[0]
+    else:
+        if a.dim() != 2 or a.shape[1] != H or a.shape[0] != xl.shape[0]:
+            raise ValueError(f"gat: s_src must be [{xl.shape[0]}, {H}], got {tuple(a.shape)}")
+        if b.dim() != 2 or b.shape[1] != H:
+            raise ValueError(f"gat: s_dst must be [Nt, {H}], got {tuple(b.shape)}")
+        nt = b.shape[0]
+    if nt != num_targets:
+        raise ValueError(f"gat: the graph has {num_targets} target rows, {'xr' if mode == GAT_V2 else 's_dst'} has {nt}")
+    if xl.shape[0] != num_sources:
+        raise ValueError(f"gat: the graph indexes {num_sources} sources, xl has {xl.shape[0]} rows")
+    if self_loops and num_targets != num_sources:
+        raise ValueError(f"gat: self_loops needs one node set, the graph has {num_targets} targets over {num_sources} "
+                         "sources; pass self_loops=False")
+
+
+def _gat_operands(mode, xl, a, b):
+    """(xr, att, s_src, s_dst) as the ABI takes them, fp32 contiguous; the other mode's pair is None."""
+    if mode == GAT_V2:
+        return _f32c(a, "xr"), _f32c(b.reshape(xl.shape[1], xl.shape[2]), "att"), None, None
+    return None, None, _f32c(a, "s_src"), _f32c(b, "s_dst")
+
+
+def _gat_fwd(mode: int, xl: torch.Tensor, a: torch.Tensor, b: torch.Tensor, idx: torch.Tensor,
+              rowptr: Optional[torch.Tensor] = None, negative_slope: float = 0.2, self_loops: bool = False,
+             want_alpha: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """(out[Nt, H, C], lse[Nt, H], alpha[Nt*k or E, H] or None) of additive attention over a table (idx = nbr[Nt, k],
+    rowptr None) or a grouped edge list (idx = src[E], rowptr[Nt+1]).  mode GAT_V2: (a, b) = (xr, att); GAT_V1: (a, b) =
+    (s_src, s_dst).  See include/dmet.h, dmet_gat_fwd_f32.  Not public, like _pointnet_fwd: the closed table of allocating
+    wrappers names the public ones; gat.py is the caller."""
+    Ns = xl.shape[0]
+    Nt = (a if mode == GAT_V2 else b).shape[0]
+    gat_check_shapes(mode, xl, a, b, Nt, Ns, idx.shape[1] if rowptr is None and idx.dim() == 2 else None, negative_slope,
+                     self_loops)
+    dev = _require_device(xl, a, b, idx, rowptr)
+    L = _lib.load()
+    xl = _f32c(xl, "xl")
+    xr, att, s_src, s_dst = _gat_operands(mode, xl, a, b)
+    idx, rowptr, E, width, M = _attention_graph(idx, rowptr, Nt)
+    _n, H, C = xl.shape
+    out = torch.empty((Nt, H, C), dtype=torch.float32, device=dev)
+    lse = torch.empty((Nt, H), dtype=torch.float32, device=dev)
+    alpha = torch.empty((M, H), dtype=torch.float32, device=dev) if want_alpha else None
+    _t = timer.record('gat_fwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_gat_fwd_f32(mode, _ptr(xl), _ptr(xr), _ptr(att), _ptr(s_src), _ptr(s_dst), float(negative_slope),
+                                      int(bool(self_loops)), _ptr(idx), None if rowptr is None else rowptr.data_ptr(),
+                                      Nt, Ns, E, width, H, C, out.data_ptr(), lse.data_ptr(), _ptr(alpha), _stream(dev)),
+                   "dmet_gat_fwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, lse, alpha
+
+
+def _gat_bwd(mode: int, g_out: torch.Tensor, xl: torch.Tensor, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor,
+             lse: torch.Tensor, idx: torch.Tensor, rev_ptr: torch.Tensor, rev_pos: torch.Tensor,
+             rowptr: Optional[torch.Tensor] = None, tgt: Optional[torch.Tensor] = None, negative_slope: float = 0.2,
+             self_loops: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Gradients of _gat_fwd.  mode GAT_V2: (g_xl[Ns, H, C], g_xr[Nt, H, C], g_att[H, C]); mode GAT_V1: (g_xl[Ns, H, C],
+    g_s_src[Ns, H], g_s_dst[Nt, H]).  (rev_ptr, rev_pos) = the graph's by-source index (table.reverse() /
+    EdgeList.by_source()), tgt = EdgeList.tgt for a list.  g_att is the sum over the targets of the kernel's per-target
+    rows, one torch.sum.  See include/dmet.h, dmet_gat_bwd_f32."""
+    Ns = xl.shape[0]
+    Nt = (a if mode == GAT_V2 else b).shape[0]
+    gat_check_shapes(mode, xl, a, b, Nt, Ns, idx.shape[1] if rowptr is None and idx.dim() == 2 else None, negative_slope,
+                     self_loops)
+    dev = _require_device(g_out, xl, a, b, out, lse, idx, rev_ptr, rev_pos, rowptr, tgt)
+    L = _lib.load()
+    xl = _f32c(xl, "xl"); out = _f32c(out, "out"); lse = _f32c(lse, "lse"); g_out = _f32c(g_out, "g_out")
+    xr, att, s_src, s_dst = _gat_operands(mode, xl, a, b)
+    idx, rowptr, E, width, M = _attention_graph(idx, rowptr, Nt)
+    rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_pos = _i32c(rev_pos, "rev_pos")
+    _n, H, C = xl.shape
+    if g_out.shape != (Nt, H, C) or out.shape != (Nt, H, C) or lse.shape != (Nt, H):
+        raise ValueError(f"gat_bwd: g_out and out must be [{Nt}, {H}, {C}] and lse [{Nt}, {H}]")
+    if rev_ptr.numel() != Ns + 1 or rev_pos.numel() < M:
+        raise ValueError(f"gat_bwd: the by-source index does not fit {M} positions over {Ns} sources")
+    if rowptr is not None:
+        if tgt is None or tgt.numel() != E:
+            raise ValueError(f"gat_bwd: an edge list needs tgt [{E}]")
+        tgt = _i32c(tgt, "tgt")
+    g_xl = torch.empty((Ns, H, C), dtype=torch.float32, device=dev)
+    work = torch.empty((2, M, H), dtype=torch.float32, device=dev)     # alpha and g_score: the per-edge buffers, 8 B per head
+    work_self = torch.empty((2, Nt, H), dtype=torch.float32, device=dev) if self_loops else None
+    g_xr = g_rows = g_ssrc = g_sdst = None
+    if mode == GAT_V2:
+        g_t = torch.empty((2, Nt, H, C), dtype=torch.float32, device=dev)      # g_xr and the per-target rows of g_att
+        g_xr, g_rows = g_t[0], g_t[1]
+    else:
+        g_ssrc = torch.empty((Ns, H), dtype=torch.float32, device=dev)
+        g_sdst = torch.empty((Nt, H), dtype=torch.float32, device=dev)
+    _t = timer.record('gat_bwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_gat_bwd_f32(mode, _ptr(xl), _ptr(xr), _ptr(att), _ptr(s_src), _ptr(s_dst), float(negative_slope),
+                                      int(bool(self_loops)), out.data_ptr(), lse.data_ptr(), g_out.data_ptr(), _ptr(idx),
+                                      None if rowptr is None else rowptr.data_ptr(), _ptr(tgt), rev_ptr.data_ptr(),
+                                      rev_pos.data_ptr(), Nt, Ns, E, width, H, C, _ptr(work[0]), _ptr(work[1]),
+                                      None if work_self is None else _ptr(work_self[0]),
+                                      None if work_self is None else _ptr(work_self[1]), _ptr(g_xl), _ptr(g_xr),
+                                      _ptr(g_rows), _ptr(g_ssrc), _ptr(g_sdst), _stream(dev)), "dmet_gat_bwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    if mode == GAT_V2:
+        return g_xl, g_xr, g_rows.sum(0)
+    return g_xl, g_ssrc, g_sdst
 
 
 POINTNET_MAX_F = 128       # include/dmet.h, "PointNet convolution"

@@ -593,6 +593,61 @@ int dmet_attention_bwd_f32(const float *q, const float *k, const float *v, const
                            const int32_t *rev_ptr, const int32_t *rev_pos, int64_t Nt, int64_t Ns, int64_t E, int width,
                            int H, int C, float *alpha_w, float *gs_w, float *g_q, float *g_k, float *g_v,
                            dmet_stream_t stream);
+/* ---- GAT aggregation: additive attention ---------------------------------------------------------------------------
+ * replaces torch_geometric.nn.GATv2Conv.edge_update (x = x_i + x_j; x = F.leaky_relu(x, negative_slope);
+ * alpha = (x * self.att).sum(dim=-1); alpha = softmax(alpha, index, ptr, dim_size)) and GATConv.edge_update
+ * (alpha = alpha_j + alpha_i; alpha = F.leaky_relu(alpha, negative_slope); alpha = softmax(...)), the message
+ * x_j * alpha.unsqueeze(-1) of both, the 'add' aggregation, remove_self_loops + add_self_loops on the edge index, and
+ * their autograd graph: two [E, H*C] gathers and their sum, two scatters for the softmax and one for the sum
+ * (csrc/gat.hip).
+ * mode 2 (GATv2Conv): xl[Ns, H, C] of the sources, xr[Nt, H, C] of the targets, att[H, C]; s_src / s_dst are ignored.
+ * mode 1 (GATConv):   xl[Ns, H, C], s_src[Ns, H], s_dst[Nt, H] (the caller's (x * att_src).sum(-1) and
+ *   (x * att_dst).sum(-1)); xr / att are ignored.  fp32, contiguous.  slope: the LeakyReLU's, finite and >= 0.
+ * The graph is the attention section's: a table (rowptr == NULL, idx = nbr[Nt, width], 1 <= width <= DMET_MAX_K, an id
+ * outside [0, Ns) = an empty slot) or a grouped list (rowptr[Nt+1], idx = src[E], tgt[E]; any in-degree).
+ * self_loops = 1 (legal only with Nt == Ns, one node set): a written entry with src == i is skipped and one implicit
+ *   entry i -> i is taken after the row's own entries -- remove_self_loops + add_self_loops without rewriting the graph.
+ * 1 <= C <= 64, 1 <= H <= 16, H*C <= 256: dmet_gat_supported(H, C) returns 1 for these and 0 otherwise.
+ * dmet_gat_fwd_f32, for target i, head h and every valid entry e of row i, j = src(e), lrelu(t) = t > 0 ? t : slope t:
+ *   mode 2: score_e = sum_c att[h,c] lrelu(xl[j,h,c] + xr[i,h,c])        mode 1: score_e = lrelu(s_src[j,h] + s_dst[i,h])
+ *   m = max_e score_e,  l = sum_e expf(score_e - m),  alpha_e = expf(score_e - m) / l
+ *   out[i,h,:] = sum_e alpha_e xl[j,h,:]                 lse[Nt, H]: lse[i,h] = m + logf(l)
+ *   PyG's softmax divides by l + 1e-16; l >= 1 (the maximum's own term), so the 1e-16 is below fp32 rounding and is
+ *   omitted, as in the attention section.  A row is taken in chunks of 16 (C <= 32) or 32 entries with a running
+ *   (m, l, acc) rescaled once per chunk; the terms of l and acc are added in ascending entry order, the implicit self
+ *   entry last, and out = acc / l.  A sum over channels is each lane's channels c = lane, lane + 16|32 in ascending
+ *   order, then an xor butterfly over the lanes.  The bits depend on that chunking, never on the launch or on the run; a
+ *   table and a list that hold the same entries in the same order give the same bits.  A row with no valid entry gives
+ *   out = 0 (R3) and lse = 0; with self_loops a row with no other entry gives out[i,h,:] = xl[i,h,:] exactly.
+ *   alpha[E or Nt*width, H] (may be NULL): the weights of the written entries, 0 in an empty slot and in a skipped
+ *   written self loop; the implicit entry's weight is not returned.  Nothing else per edge is written.
+ * dmet_gat_bwd_f32, two launches.  By target, with delta[i,h] = sum_c g_out[i,h,c] out[i,h,c] and the score recomputed
+ *   with the forward's chain:  alpha_e = expf(score_e - lse[i,h]),  g_s_e = alpha_e (sum_c g_out[i,h,c] xl[j,h,c] - delta).
+ *   mode 2, t_e[c] = xl[j,h,c] + xr[i,h,c], d_e[c] = (g_s_e att[h,c]) (t_e[c] > 0 ? 1 : slope) (the slope at t == 0, as
+ *     torch's leaky_relu backward):  g_xr[i,h,:] = sum_e d_e,  g_att_rows[Nt, H, C]: g_att_rows[i,h,c] = sum_e g_s_e
+ *     lrelu(t_e[c]), both in ascending e; the caller sums g_att_rows over i in a fixed order for g_att.  gs_w = g_s_e.
+ *   mode 1, d_e = g_s_e (s_src[j,h] + s_dst[i,h] > 0 ? 1 : slope):  g_sdst[i,h] = sum_e d_e, ascending e.  gs_w = d_e.
+ *   alpha_w, gs_w [E or Nt*width, H] fp32: the caller's scratch, every position written (0 in an empty slot); they are
+ *   the only per-edge buffers.  alpha_self, gs_self [Nt, H]: the same pair for the implicit entry (self_loops; may be
+ *   NULL otherwise).  By source, over the by-source index rev_ptr[Ns+1], rev_pos[] in ascending order (as in the
+ *   attention section), then the implicit entry j -> j; a written self loop is skipped here too:
+ *   mode 2: g_xl[j,h,:] = sum (alpha_e g_out[i,h,:] + d_e)        mode 1: g_xl[j,h,:] = sum alpha_e g_out[i,h,:],
+ *                                                                          g_ssrc[j,h] = sum gs_w
+ *   A hub's list is walked by its one owner.  Every gradient is written, not accumulated; rows and sources without
+ *   entries get zeros.  No float atomics: two runs give identical bits.  Pointers of the other mode may be NULL.
+ * Both return -EINVAL on anything outside these limits, on NULL or negative arguments, on self_loops with Nt != Ns and on
+ * a non-finite or negative slope, before any device work.  Nt == 0: the forward returns 0 at once; the backward
+ * zero-fills g_xl (and g_ssrc in mode 1) when Ns > 0 and returns. */
+int dmet_gat_supported(int H, int C);
+int dmet_gat_fwd_f32(int mode, const float *xl, const float *xr, const float *att, const float *s_src, const float *s_dst,
+                     float slope, int self_loops, const int32_t *idx, const int32_t *rowptr, int64_t Nt, int64_t Ns,
+                     int64_t E, int width, int H, int C, float *out, float *lse, float *alpha, dmet_stream_t stream);
+int dmet_gat_bwd_f32(int mode, const float *xl, const float *xr, const float *att, const float *s_src, const float *s_dst,
+                     float slope, int self_loops, const float *out, const float *lse, const float *g_out,
+                     const int32_t *idx, const int32_t *rowptr, const int32_t *tgt, const int32_t *rev_ptr,
+                     const int32_t *rev_pos, int64_t Nt, int64_t Ns, int64_t E, int width, int H, int C, float *alpha_w,
+                     float *gs_w, float *alpha_self, float *gs_self, float *g_xl, float *g_xr, float *g_att_rows,
+                     float *g_ssrc, float *g_sdst, dmet_stream_t stream);
 /* ---- Interpolation: inverse-distance feature propagation ------------------------------------------------------------
  * replaces the body of torch_geometric.nn.unpool.knn_interpolate(x, pos_x, pos_y, batch_x, batch_y, k) after its kNN
  * search (squared_distance = (pos_x[x_idx] - pos_y[y_idx]).pow(2).sum(-1), weights = 1 / clamp(squared_distance,
