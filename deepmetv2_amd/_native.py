@@ -1189,6 +1189,18 @@ ATTENTION_MAX_HC = 256   # heads * channels
 ATTENTION_MAX_K = GRAVNET_MAX_K   # DMET_MAX_K: the width of a table, as for GravNet
 
 
+def _row_softmax_limits(who: str, H: int, C: int, width: Optional[int]) -> None:
+    """The ranges csrc/row_softmax.h's kernels take, for attention and GAT alike; width: a table's k (None: a list)."""
+    if not 1 <= C <= ATTENTION_MAX_C:
+        raise ValueError(f"{who}: C={C} channels per head, supported 1..{ATTENTION_MAX_C}")
+    if not 1 <= H <= ATTENTION_MAX_H:
+        raise ValueError(f"{who}: H={H} heads, supported 1..{ATTENTION_MAX_H}")
+    if H * C > ATTENTION_MAX_HC:
+        raise ValueError(f"{who}: H*C={H * C}, supported up to {ATTENTION_MAX_HC}")
+    if width is not None and not 1 <= width <= ATTENTION_MAX_K:
+        raise ValueError(f"{who}: k={width}, supported 1..{ATTENTION_MAX_K}")
+
+
 def attention_check_shapes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_targets: int, num_sources: int,
                            width: Optional[int] = None) -> None:
     """The argument errors of the attention entries, raised from shapes alone (before any device is asked for).  The graph
@@ -1197,14 +1209,7 @@ def attention_check_shapes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, nu
         raise ValueError(f"attention: q [Nt, H, C], k and v [Ns, H, C] must be 3-D, got {tuple(q.shape)}, {tuple(k.shape)}, "
                          f"{tuple(v.shape)}")
     H, C = q.shape[1], q.shape[2]
-    if not 1 <= C <= ATTENTION_MAX_C:
-        raise ValueError(f"attention: C={C} channels per head, supported 1..{ATTENTION_MAX_C}")
-    if not 1 <= H <= ATTENTION_MAX_H:
-        raise ValueError(f"attention: H={H} heads, supported 1..{ATTENTION_MAX_H}")
-    if H * C > ATTENTION_MAX_HC:
-        raise ValueError(f"attention: H*C={H * C}, supported up to {ATTENTION_MAX_HC}")
-    if width is not None and not 1 <= width <= ATTENTION_MAX_K:
-        raise ValueError(f"attention: k={width}, supported 1..{ATTENTION_MAX_K}")
+    _row_softmax_limits("attention", H, C, width)
     if tuple(k.shape[1:]) != (H, C) or tuple(v.shape[1:]) != (H, C):
         raise ValueError(f"attention: q has {H} heads of {C} channels, k {tuple(k.shape[1:])}, v {tuple(v.shape[1:])}")
     if k.shape[0] != v.shape[0]:
@@ -1215,17 +1220,34 @@ def attention_check_shapes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, nu
         raise ValueError(f"attention: the graph indexes {num_sources} sources, k and v have {k.shape[0]} rows")
 
 
-def _attention_graph(idx: torch.Tensor, rowptr: Optional[torch.Tensor], Nt: int):
+def _row_graph(who: str, idx: torch.Tensor, rowptr: Optional[torch.Tensor], Nt: int):
     """(idx, rowptr, E, width, positions) of a table (rowptr None, idx = nbr[Nt, k]) or a list (idx = src[E])."""
     idx = _i32c(idx, "nbr" if rowptr is None else "src")
     if rowptr is None:
         if idx.dim() != 2 or idx.shape[0] != Nt:
-            raise ValueError(f"attention: nbr must be [{Nt}, k], got {tuple(idx.shape)}")
+            raise ValueError(f"{who}: nbr must be [{Nt}, k], got {tuple(idx.shape)}")
         return idx, None, 0, int(idx.shape[1]), Nt * int(idx.shape[1])
     rowptr = _i32c(rowptr, "rowptr")
     if idx.dim() != 1 or rowptr.numel() != Nt + 1:
-        raise ValueError(f"attention: src must be [E] and rowptr [{Nt + 1}], got {tuple(idx.shape)} and {tuple(rowptr.shape)}")
+        raise ValueError(f"{who}: src must be [E] and rowptr [{Nt + 1}], got {tuple(idx.shape)} and {tuple(rowptr.shape)}")
     return idx, rowptr, int(idx.numel()), 0, int(idx.numel())
+
+
+def _row_softmax_bwd_args(who: str, g_out: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, rev_ptr: torch.Tensor,
+                          rev_pos: torch.Tensor, rowptr: Optional[torch.Tensor], tgt: Optional[torch.Tensor], Nt: int,
+                          Ns: int, H: int, C: int, E: int, M: int):
+    """(rev_ptr, rev_pos, tgt) as the backward entries take them, once the row tensors, the by-source index and a list's
+    tgt fit the graph."""
+    rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_pos = _i32c(rev_pos, "rev_pos")
+    if g_out.shape != (Nt, H, C) or out.shape != (Nt, H, C) or lse.shape != (Nt, H):
+        raise ValueError(f"{who}: g_out and out must be [{Nt}, {H}, {C}] and lse [{Nt}, {H}]")
+    if rev_ptr.numel() != Ns + 1 or rev_pos.numel() < M:
+        raise ValueError(f"{who}: the by-source index does not fit {M} positions over {Ns} sources")
+    if rowptr is not None:
+        if tgt is None or tgt.numel() != E:
+            raise ValueError(f"{who}: an edge list needs tgt [{E}]")
+        tgt = _i32c(tgt, "tgt")
+    return rev_ptr, rev_pos, tgt
 
 
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx: torch.Tensor, rowptr: Optional[torch.Tensor] = None,
@@ -1237,7 +1259,7 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx: torch.
     dev = _require_device(q, k, v, idx, rowptr)
     L = _lib.load()
     q = _f32c(q, "q"); k = _f32c(k, "k"); v = _f32c(v, "v")
-    idx, rowptr, E, width, M = _attention_graph(idx, rowptr, Nt)
+    idx, rowptr, E, width, M = _row_graph("attention", idx, rowptr, Nt)
     _n, H, C = q.shape
     out = torch.empty((Nt, H, C), dtype=torch.float32, device=dev)
     lse = torch.empty((Nt, H), dtype=torch.float32, device=dev)
@@ -1264,17 +1286,10 @@ def attention_bwd(g_out: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torc
     L = _lib.load()
     q = _f32c(q, "q"); k = _f32c(k, "k"); v = _f32c(v, "v"); out = _f32c(out, "out"); lse = _f32c(lse, "lse")
     g_out = _f32c(g_out, "g_out")
-    idx, rowptr, E, width, M = _attention_graph(idx, rowptr, Nt)
-    rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_pos = _i32c(rev_pos, "rev_pos")
+    idx, rowptr, E, width, M = _row_graph("attention", idx, rowptr, Nt)
     _n, H, C = q.shape
-    if g_out.shape != (Nt, H, C) or out.shape != (Nt, H, C) or lse.shape != (Nt, H):
-        raise ValueError(f"attention_bwd: g_out and out must be [{Nt}, {H}, {C}] and lse [{Nt}, {H}]")
-    if rev_ptr.numel() != Ns + 1 or rev_pos.numel() < M:
-        raise ValueError(f"attention_bwd: the by-source index does not fit {M} positions over {Ns} sources")
-    if rowptr is not None:
-        if tgt is None or tgt.numel() != E:
-            raise ValueError(f"attention_bwd: an edge list needs tgt [{E}]")
-        tgt = _i32c(tgt, "tgt")
+    rev_ptr, rev_pos, tgt = _row_softmax_bwd_args("attention_bwd", g_out, out, lse, rev_ptr, rev_pos, rowptr, tgt, Nt, Ns, H,
+                                                  C, E, M)
     g_q = torch.empty((Nt, H, C), dtype=torch.float32, device=dev)
     g_kv = torch.empty((2, Ns, H, C), dtype=torch.float32, device=dev)
     work = torch.empty((2, M, H), dtype=torch.float32, device=dev)     # alpha and g_score: the per-edge buffers, 8 B per head
@@ -1307,14 +1322,7 @@ def gat_check_shapes(mode: int, xl: torch.Tensor, a: torch.Tensor, b: torch.Tens
     if xl.dim() != 3:
         raise ValueError(f"gat: xl must be [Ns, H, C], got {tuple(xl.shape)}")
     H, C = xl.shape[1], xl.shape[2]
-    if not 1 <= C <= GAT_MAX_C:
-        raise ValueError(f"gat: C={C} channels per head, supported 1..{GAT_MAX_C}")
-    if not 1 <= H <= GAT_MAX_H:
-        raise ValueError(f"gat: H={H} heads, supported 1..{GAT_MAX_H}")
-    if H * C > GAT_MAX_HC:
-        raise ValueError(f"gat: H*C={H * C}, supported up to {GAT_MAX_HC}")
-    if width is not None and not 1 <= width <= GAT_MAX_K:
-        raise ValueError(f"gat: k={width}, supported 1..{GAT_MAX_K}")
+    _row_softmax_limits("gat", H, C, width)
     slope = float(negative_slope)
     if not (math.isfinite(slope) and slope >= 0.0):
         raise ValueError(f"gat: negative_slope={negative_slope!r} must be finite and >= 0")
@@ -1361,7 +1369,7 @@ def _gat_fwd(mode: int, xl: torch.Tensor, a: torch.Tensor, b: torch.Tensor, idx:
     L = _lib.load()
     xl = _f32c(xl, "xl")
     xr, att, s_src, s_dst = _gat_operands(mode, xl, a, b)
-    idx, rowptr, E, width, M = _attention_graph(idx, rowptr, Nt)
+    idx, rowptr, E, width, M = _row_graph("gat", idx, rowptr, Nt)
     _n, H, C = xl.shape
     out = torch.empty((Nt, H, C), dtype=torch.float32, device=dev)
     lse = torch.empty((Nt, H), dtype=torch.float32, device=dev)
@@ -1393,17 +1401,9 @@ def _gat_bwd(mode: int, g_out: torch.Tensor, xl: torch.Tensor, a: torch.Tensor, 
     L = _lib.load()
     xl = _f32c(xl, "xl"); out = _f32c(out, "out"); lse = _f32c(lse, "lse"); g_out = _f32c(g_out, "g_out")
     xr, att, s_src, s_dst = _gat_operands(mode, xl, a, b)
-    idx, rowptr, E, width, M = _attention_graph(idx, rowptr, Nt)
-    rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_pos = _i32c(rev_pos, "rev_pos")
+    idx, rowptr, E, width, M = _row_graph("gat", idx, rowptr, Nt)
     _n, H, C = xl.shape
-    if g_out.shape != (Nt, H, C) or out.shape != (Nt, H, C) or lse.shape != (Nt, H):
-        raise ValueError(f"gat_bwd: g_out and out must be [{Nt}, {H}, {C}] and lse [{Nt}, {H}]")
-    if rev_ptr.numel() != Ns + 1 or rev_pos.numel() < M:
-        raise ValueError(f"gat_bwd: the by-source index does not fit {M} positions over {Ns} sources")
-    if rowptr is not None:
-        if tgt is None or tgt.numel() != E:
-            raise ValueError(f"gat_bwd: an edge list needs tgt [{E}]")
-        tgt = _i32c(tgt, "tgt")
+    rev_ptr, rev_pos, tgt = _row_softmax_bwd_args("gat_bwd", g_out, out, lse, rev_ptr, rev_pos, rowptr, tgt, Nt, Ns, H, C, E, M)
     g_xl = torch.empty((Ns, H, C), dtype=torch.float32, device=dev)
     work = torch.empty((2, M, H), dtype=torch.float32, device=dev)     # alpha and g_score: the per-edge buffers, 8 B per head
     work_self = torch.empty((2, Nt, H), dtype=torch.float32, device=dev) if self_loops else None

@@ -13,21 +13,15 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native
+from ._softmax_conv import SoftmaxConv, by_source_index, check_graph, graph_args, shape_alpha
 from .gravnet import _upcast
-from .graph import BipartiteTable, EdgeList, GraphFuture, NeighborTable, edge_list_from_edge_index, lookup_graph
+from .graph import BipartiteTable, EdgeList, NeighborTable
 
 MAX_HEADS = _native.ATTENTION_MAX_H
 MAX_HEAD_CHANNELS = _native.ATTENTION_MAX_C
 MAX_HEADS_TIMES_CHANNELS = _native.ATTENTION_MAX_HC
 
 Graph = Union[NeighborTable, BipartiteTable, EdgeList]
-
-
-def _graph_args(graph):
-    """(idx, rowptr, tgt) as the kernels take them: a table's nbr, or a list's src, rowptr and tgt."""
-    if isinstance(graph, EdgeList):
-        return graph.src, graph.rowptr, graph.tgt
-    return graph.nbr, None, None
 
 
 class _AttentionAggregate(torch.autograd.Function):
@@ -37,7 +31,7 @@ class _AttentionAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, graph, want_alpha: bool):
         qf, kf, vf = _upcast(q, "q"), _upcast(k, "k"), _upcast(v, "v")
-        idx, rowptr, _tgt = _graph_args(graph)
+        idx, rowptr, _tgt = graph_args(graph)
         out, lse, alpha = _native.attention_fwd(qf, kf, vf, idx, rowptr, want_alpha)
         ctx.save_for_backward(qf, kf, vf, out, lse)
         ctx.graph = graph
@@ -52,8 +46,8 @@ class _AttentionAggregate(torch.autograd.Function):
     def backward(ctx, g_out, _g_alpha):
         qf, kf, vf, out, lse = ctx.saved_tensors
         graph = ctx.graph
-        idx, rowptr, tgt = _graph_args(graph)
-        rev_ptr, rev_pos = graph.by_source() if isinstance(graph, EdgeList) else graph.reverse()
+        idx, rowptr, tgt = graph_args(graph)
+        rev_ptr, rev_pos = by_source_index(graph)
         g_q, g_k, g_v = _native.attention_bwd(g_out.float(), qf, kf, vf, out, lse, idx, rev_ptr, rev_pos, rowptr, tgt)
         dq, dk, dv = ctx.dtypes
         return g_q.to(dq), g_k.to(dk), g_v.to(dv), None, None
@@ -61,24 +55,10 @@ class _AttentionAggregate(torch.autograd.Function):
 
 def _aggregate(q, k, v, graph, want_alpha):
     """(out, alpha or None); alpha [Nt, k, H] for a table, [E, H] in the list's grouped order for an EdgeList."""
-    if isinstance(graph, NeighborTable):
-        if graph.cnt is not None:
-            raise ValueError("attention_aggregate needs a -1-padded table (knn_table), not a counted radius table")
-        _native.attention_check_shapes(q, k, v, graph.num_nodes, graph.num_nodes, graph.k)
-        graph.join()
-    elif isinstance(graph, BipartiteTable):
-        if graph.cnt is not None:
-            raise ValueError("attention_aggregate needs a -1-padded table (knn_xy_table), not a counted radius table")
-        _native.attention_check_shapes(q, k, v, graph.num_queries, graph.num_candidates, graph.k)
-    elif isinstance(graph, EdgeList):
-        _native.attention_check_shapes(q, k, v, graph.num_nodes, graph.num_src)
-    else:
-        raise TypeError("attention_aggregate: graph must be a NeighborTable, a BipartiteTable or an EdgeList, got "
-                        f"{type(graph).__name__}")
+    check_graph("attention_aggregate", graph,
+                lambda nt, ns, width, _loops: _native.attention_check_shapes(q, k, v, nt, ns, width))
     out, alpha = _AttentionAggregate.apply(q, k, v, graph, bool(want_alpha))
-    if not want_alpha:
-        return out, None
-    return out, (alpha if isinstance(graph, EdgeList) else alpha.view(q.shape[0], graph.k, q.shape[1]))
+    return out, (shape_alpha(alpha, graph, q.shape[0], q.shape[1]) if want_alpha else None)
 
 
 def attention_aggregate(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, graph: Graph, return_alpha: bool = False):
@@ -98,7 +78,7 @@ def attention_aggregate(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, graph
     return (out, alpha) if return_alpha else out
 
 
-class TransformerConv(torch.nn.Module):
+class TransformerConv(SoftmaxConv):
     """torch_geometric.nn.TransformerConv(in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0,
     edge_dim=None, bias=True, root_weight=True), flow source_to_target:
 
@@ -123,15 +103,7 @@ class TransformerConv(torch.nn.Module):
                  beta: bool = False, dropout: float = 0.0, edge_dim: Optional[int] = None, bias: bool = True,
                  root_weight: bool = True):
         super().__init__()
-        if dropout != 0.0:
-            raise ValueError("TransformerConv: dropout on the attention weights is not supported (no RNG kernel); use 0.0")
-        if edge_dim is not None:
-            raise ValueError("TransformerConv: edge features (edge_dim) are not supported")
-        for name, val, top in (("heads", heads, MAX_HEADS), ("out_channels", out_channels, MAX_HEAD_CHANNELS)):
-            if not isinstance(val, int) or isinstance(val, bool) or not 1 <= val <= top:
-                raise ValueError(f"{name}={val!r}, supported 1..{top}")
-        if heads * out_channels > MAX_HEADS_TIMES_CHANNELS:
-            raise ValueError(f"heads * out_channels = {heads * out_channels}, supported up to {MAX_HEADS_TIMES_CHANNELS}")
+        self._check_options(heads, out_channels, dropout, edge_dim, size_prefix="")
         self.in_channels = in_channels
         self.out_channels = out_channels
         self.heads = heads
@@ -160,40 +132,9 @@ class TransformerConv(torch.nn.Module):
             if lin is not None:
                 lin.reset_parameters()
 
-    def _resolve(self, edge_index, num_src: int, num_dst: int, pair: bool, want_alpha: bool):
-        """(graph for attention_aggregate, how to hand alpha back: 'table', 'flat', or the list itself)."""
-        if isinstance(edge_index, GraphFuture):
-            edge_index = edge_index.peek() if isinstance(edge_index.peek(), NeighborTable) else edge_index.result()
-        if isinstance(edge_index, (NeighborTable, BipartiteTable)):
-            if isinstance(edge_index, NeighborTable) and pair:
-                raise ValueError("TransformerConv: an (x_src, x_dst) pair goes with a BipartiteTable or an edge_index tensor")
-            if isinstance(edge_index, BipartiteTable) and not pair:
-                raise ValueError("TransformerConv: a BipartiteTable needs an (x_src, x_dst) pair")
-            if edge_index.cnt is not None:       # a counted radius table: its valid slots as a list (one host read)
-                return edge_index.edge_list(), "list"
-            return edge_index, "table"
-        if not torch.is_tensor(edge_index):
-            raise TypeError(f"TransformerConv: edge_index must be a graph object or an int64 [2, E] tensor, got "
-                            f"{type(edge_index).__name__}")
-        hit = None if pair else lookup_graph(edge_index)
-        if hit is not None and hit[1] == "source_to_target" and hit[0].num_nodes == num_dst and hit[0].cnt is None:
-            table = hit[0]
-            # the tensor lists the table's slots in position order when it is sized Nt*k: alpha goes back flat
-            if not want_alpha or edge_index.shape[1] == table.num_nodes * table.k:
-                return table, "flat"
-        return edge_list_from_edge_index(edge_index, num_dst, "source_to_target", num_src=num_src if pair else None), "list"
-
     def forward(self, x: Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]], edge_index,
                 return_attention_weights: Optional[bool] = None):
-        pair = isinstance(x, (tuple, list))
-        if pair:
-            if len(x) != 2:
-                raise ValueError("TransformerConv: x must be a tensor or an (x_src, x_dst) pair")
-            x_src, x_dst = x
-        else:
-            x_src = x_dst = x
-        if x_src.dim() != 2 or x_dst.dim() != 2:
-            raise ValueError(f"TransformerConv: x must be [N, F], got {tuple(x_src.shape)} and {tuple(x_dst.shape)}")
+        pair, x_src, x_dst = self._split(x)
         want = bool(return_attention_weights)
         graph, how = self._resolve(edge_index, x_src.shape[0], x_dst.shape[0], pair, want)
         H, C = self.heads, self.out_channels
@@ -209,15 +150,4 @@ class TransformerConv(torch.nn.Module):
                 out = b * x_r + (1 - b) * out
             else:
                 out = out + x_r
-        if not want:
-            return out
-        if how == "table":
-            return out, (edge_index.peek() if isinstance(edge_index, GraphFuture) else edge_index, alpha)
-        if how == "flat":
-            return out, (edge_index, alpha.reshape(-1, H))
-        if graph.perm is not None:       # back from the grouped order to the caller's
-            alpha = torch.empty_like(alpha).index_copy_(0, graph.perm.long(), alpha)
-        return out, (edge_index, alpha)
-
-    def __repr__(self) -> str:
-        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"
+        return self._with_alpha(out, edge_index, graph, how, alpha) if want else out

@@ -16,7 +16,7 @@ SOURCES = ["knn.hip", "radius.hip", "edgeconv.hip", "edgemlp.hip", "misc.hip", "
            "edgemlp_f32.hip", "edgemlp_bf16.hip", "edgeconv_sum.hip", "gravnet.hip", "attention.hip", "fps.hip", "interpolate.hip",
            "pointnet.hip", "gat.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "bn_affine.h", "knn_common.h", "knn_filter.h", "knn_key64.h", "nls_body.h",
-                                           "edgemlp_fused.h")] + \
+                                           "edgemlp_fused.h", "row_softmax.h")] + \
           [os.path.join(PKG_DIR, "..", "include", "dmet.h")]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=off", "-Wall",

@@ -14,224 +14,70 @@
 // row's own entries -- remove_self_loops + add_self_loops without rewriting the graph (the csrc/pointnet.hip
 // convention).  The by-source pass adds the same entry for source i after its reverse list.
 //
-// Lane layout, all three kernels, is attention.hip's: a group of LPT lanes (16 for C <= 32, 32 beyond; inside one
-// wavefront) owns one (row, head) pair, a row of any length is taken in chunks of LPT entries, lane l reads the id of
-// entry l once, the group walks the chunk kGatInFlight gathers at a time over the channels c = lane, lane + LPT, a
-// channel sum is each lane's partial sum in ascending c followed by the xor butterfly of the group, and lane e keeps
-// the scalars of entry e.  The running (m, l, acc) is rescaled once per chunk that holds a valid entry; l and acc add
-// their terms in ascending entry order, the implicit self entry last.  No LDS, no __syncthreads, no float atomics: the
-// bits depend on LPT, never on the launch or the run, and a table and the edge list of the same entries in the same
-// order give the same bits.  Every loop is bounded by a row length or a reverse-list length read once and clamped.
-#include <math.h>
-
-#include "common.h"
+// The lane layout, the running softmax of a row and the walks of the two backward passes are row_softmax.h's; here are
+// the two scores, the per-entry arithmetic of the backward and the entry points.
+#include "row_softmax.h"
 
 namespace dmet {
 namespace {
 
-constexpr int kGatMaxC = 64;
-constexpr int kGatMaxH = 16;
-constexpr int kGatMaxHC = 256;
-constexpr int kGatBlock = 256;
-constexpr int kGatInFlight = 4;    // head-row gathers in flight per group
 constexpr int kGatV1 = 1, kGatV2 = 2;
-
-template <int LPT>
-__device__ __forceinline__ float gat_group_sum(float v)
-{
-    // xor butterfly inside the group: a fixed order, and every lane of the group ends with the same bits
-#pragma unroll
-    for (int off = LPT / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, LPT);
-    return v;
-}
-
-template <int LPT>
-__device__ __forceinline__ float gat_group_max(float v)
-{
-#pragma unroll
-    for (int off = LPT / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, LPT));
-    return v;
-}
-
-template <int LPT, int ITER>
-__device__ __forceinline__ float gat_group_dot(const float (&a)[ITER], const float (&b)[ITER])
-{
-    float part = 0.f;
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) part += a[it] * b[it];
-    return gat_group_sum<LPT>(part);
-}
 
 __device__ __forceinline__ float gat_lrelu(float t, float slope) { return t > 0.f ? t : slope * t; }
 __device__ __forceinline__ float gat_dlrelu(float t, float slope) { return t > 0.f ? 1.f : slope; }   // slope at t == 0, as torch
 
-// the v2 score: the one chain the forward and the backward form it with (channels past C hold zeros in all three rows)
-template <int LPT, int ITER>
-__device__ __forceinline__ float gat_score_v2(const float (&at)[ITER], const float (&xl)[ITER], const float (&xr)[ITER],
-                                              float slope)
-{
-    float part = 0.f;
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) part += at[it] * gat_lrelu(xl[it] + xr[it], slope);
-    return gat_group_sum<LPT>(part);
-}
-
-// channels lane, lane + LPT, ... of the head row at p (zeros past C, and for a missing row)
-template <int LPT, int ITER>
-__device__ __forceinline__ void gat_load_row(float (&r)[ITER], const float *__restrict__ p, bool on, int lane, int C)
-{
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        const int c = lane + it * LPT;
-        r[it] = (on && c < C) ? p[c] : 0.f;
-    }
-}
-
-struct GatGraph {
-    const int32_t *idx;       // nbr[Nt, k] (table) or src[E] (list)
-    const int32_t *rowptr;    // NULL: table
-    const int32_t *tgt;       // list, backward only
-    const int32_t *rev_ptr, *rev_pos;
-    int64_t Nt, Ns, M;        // M = Nt*k or E: the number of positions
-    int k;
-    int self_loops;
-};
-
-// positions [lo, lo + n) of row i, clamped to [0, M]
-__device__ __forceinline__ void gat_row(const GatGraph &g, int64_t i, int64_t &lo, int &n)
-{
-    if (g.rowptr == nullptr) {
-        lo = i * g.k;
-        n = g.k;
-    } else {
-        lo = min(max((int64_t)g.rowptr[i], (int64_t)0), g.M);
-        const int64_t hi = min(max((int64_t)g.rowptr[i + 1], lo), g.M);
-        n = (int)(hi - lo);
-    }
-}
-
-// the id of logical entry t of row i: the written entries [0, n), then (self_loops) the entry i -> i at t == n; -1 for
-// an empty slot, an id outside [0, Ns), a written self loop under self_loops, and anything past the row
-__device__ __forceinline__ int32_t gat_entry(const GatGraph &g, int64_t i, int64_t lo, int n, int t)
-{
-    if (t < n) {
-        const int32_t j = g.idx[lo + t];
-        if (j < 0 || (int64_t)j >= g.Ns) return -1;
-        if (g.self_loops && (int64_t)j == i) return -1;
-        return j;
-    }
-    return (g.self_loops && t == n) ? (int32_t)i : -1;
-}
-
 struct GatArgs {
     const float *xl, *xr, *att, *s_src, *s_dst, *out, *lse, *g_out;
     float slope;
-    GatGraph g;
+    RowGraph g;
     int H, C;
     float *o, *l, *alpha, *alpha_w, *gs_w, *alpha_self, *gs_self, *g_xl, *g_xr, *g_att_rows, *g_ssrc, *g_sdst;
 };
 
-template <int LPT, int ITER, int MODE>
-__global__ __launch_bounds__(kGatBlock) void gat_fwd_kernel(GatArgs a)
-{
-    constexpr int TPB = kGatBlock / LPT;
-    const GatGraph &g = a.g;
-    const int H = a.H, C = a.C;
-    const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int64_t unit = (int64_t)bid * TPB + threadIdx.x / LPT;
-    const int lane = threadIdx.x % LPT;
-    if (unit >= g.Nt * H) return;        // whole groups leave: the shuffles below stay inside a group
-    const int64_t i = unit / H;
-    const int h = (int)(unit - i * H);
-    const int HC = H * C;
-    const float slope = a.slope;
-    int64_t lo;
-    int n;
-    gat_row(g, i, lo, n);
-    const int ne = n + (g.self_loops ? 1 : 0);      // logical entries: the self entry after the row's own
+// the v2 score of an xl row: the one chain the forward and the backward form it with (channels past C hold zeros in all
+// three rows)
+template <int LPT, int ITER>
+struct GatScoreV2 {
+    static constexpr bool kGather = true;
+    const float *rows;      // xl
+    float xr[ITER], at[ITER], slope;
+    __device__ __forceinline__ GatScoreV2(const GatArgs &a, const Unit &u) : rows(a.xl), slope(a.slope)
+    {
+        load_row<LPT, ITER>(xr, a.xr + u.row * a.H * a.C + u.h * a.C, true, u.lane, a.C);
+        load_row<LPT, ITER>(at, a.att + u.h * a.C, true, u.lane, a.C);
+    }
+    __device__ __forceinline__ float operator()(const float (&xl)[ITER]) const
+    {
+        float part = 0.f;
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) part += at[it] * gat_lrelu(xl[it] + xr[it], slope);
+        return group_sum<LPT>(part);
+    }
+};
 
-    float xr[ITER], at[ITER], acc[ITER];
-    float sd = 0.f;
-    if constexpr (MODE == kGatV2) {
-        gat_load_row<LPT, ITER>(xr, a.xr + i * HC + h * C, true, lane, C);
-        gat_load_row<LPT, ITER>(at, a.att + h * C, true, lane, C);
-    } else {
-        sd = a.s_dst[unit];
+// the v1 score: a scalar per entry, each lane forms its own
+struct GatScoreV1 {
+    static constexpr bool kGather = false;
+    const float *s_src;
+    float sd, slope;
+    int H, h;
+    __device__ __forceinline__ GatScoreV1(const GatArgs &a, const Unit &u)
+        : s_src(a.s_src), sd(a.s_dst[u.unit]), slope(a.slope), H(a.H), h(u.h)
+    {
     }
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) acc[it] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    int cnt = 0;
-    for (int base = 0; base < ne; base += LPT) {
-        const int32_t jl = gat_entry(g, i, lo, n, base + lane);      // lane l: the id of entry base + l
-        const int mch = min(LPT, ne - base);
-        float sl = -INFINITY;           // lane e keeps the score of entry base + e
-        if constexpr (MODE == kGatV2) {
-            for (int e0 = 0; e0 < mch; e0 += kGatInFlight) {
-                int32_t j[kGatInFlight];
-                float xj[kGatInFlight][ITER];
-#pragma unroll
-                for (int u = 0; u < kGatInFlight; ++u) {
-                    j[u] = __shfl(jl, (e0 + u) & (LPT - 1), LPT);
-                    if (e0 + u >= mch) j[u] = -1;
-                }
-#pragma unroll
-                for (int u = 0; u < kGatInFlight; ++u)
-                    gat_load_row<LPT, ITER>(xj[u], a.xl + (int64_t)max(j[u], 0) * HC + h * C, j[u] >= 0, lane, C);
-#pragma unroll
-                for (int u = 0; u < kGatInFlight; ++u) {
-                    if (j[u] < 0) continue;        // the same for every lane of the group
-                    const float s = gat_score_v2<LPT, ITER>(at, xj[u], xr, slope);
-                    if (lane == e0 + u) sl = s;
-                }
-            }
-        } else if (jl >= 0) {
-            sl = gat_lrelu(a.s_src[(int64_t)jl * H + h] + sd, slope);      // a scalar per entry: each lane forms its own
-        }
-        if (a.alpha != nullptr && base + lane < n) a.alpha[(lo + base + lane) * H + h] = sl;     // the score, until (m, l) is known
-        if (gat_group_max<LPT>(jl >= 0 ? 1.f : 0.f) == 0.f) continue;      // a chunk of empty slots: the running state stays
-        const float m_new = fmaxf(m, gat_group_max<LPT>(sl));
-        const float scale = (cnt == 0) ? 0.f : expf(m - m_new);
-        const float pl = jl >= 0 ? expf(sl - m_new) : 0.f;
-        m = m_new;
-        l *= scale;
-#pragma unroll
-        for (int it = 0; it < ITER; ++it) acc[it] *= scale;
-        for (int e0 = 0; e0 < mch; e0 += kGatInFlight) {
-            int32_t j[kGatInFlight];
-            float p[kGatInFlight], xj[kGatInFlight][ITER];
-#pragma unroll
-            for (int u = 0; u < kGatInFlight; ++u) {
-                j[u] = __shfl(jl, (e0 + u) & (LPT - 1), LPT);
-                p[u] = __shfl(pl, (e0 + u) & (LPT - 1), LPT);
-                if (e0 + u >= mch) j[u] = -1;
-            }
-#pragma unroll
-            for (int u = 0; u < kGatInFlight; ++u)
-                gat_load_row<LPT, ITER>(xj[u], a.xl + (int64_t)max(j[u], 0) * HC + h * C, j[u] >= 0, lane, C);
-#pragma unroll
-            for (int u = 0; u < kGatInFlight; ++u) {
-                if (j[u] < 0) continue;
-                l += p[u];
-#pragma unroll
-                for (int it = 0; it < ITER; ++it) acc[it] += p[u] * xj[u][it];
-                ++cnt;
-            }
-        }
-    }
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        const int c = lane + it * LPT;
-        if (c < C) a.o[i * HC + h * C + c] = cnt > 0 ? acc[it] / l : 0.f;     // a row without a valid entry: zeros (R3)
-    }
-    if (lane == 0) a.l[unit] = cnt > 0 ? m + logf(l) : 0.f;
-    if (a.alpha != nullptr) {
-        // each lane turns the scores it stored itself into weights; an empty slot is told by its id, not by the value
-        for (int t = lane; t < n; t += LPT) {
-            const int64_t pos = (lo + t) * H + h;
-            a.alpha[pos] = gat_entry(g, i, lo, n, t) >= 0 ? expf(a.alpha[pos] - m) / l : 0.f;
-        }
-    }
+    __device__ __forceinline__ float sum(int32_t j) const { return s_src[(int64_t)j * H + h] + sd; }
+    __device__ __forceinline__ float operator()(int32_t j) const { return gat_lrelu(sum(j), slope); }
+};
+
+template <int LPT, int ITER, int MODE>
+__global__ __launch_bounds__(kBlock) void gat_fwd_kernel(GatArgs a)
+{
+    Unit u;
+    if (!take_unit<LPT>(a.g.Nt, a.H, u)) return;
+    if constexpr (MODE == kGatV2)
+        softmax_row_fwd<LPT, ITER>(a.g, u, a.H, a.C, GatScoreV2<LPT, ITER>(a, u), a.xl, a.o, a.l, a.alpha);
+    else
+        softmax_row_fwd<LPT, ITER>(a.g, u, a.H, a.C, GatScoreV1(a, u), a.xl, a.o, a.l, a.alpha);
 }
 
 // By-target pass: alpha and g_s of every position (0 in an empty slot; the self entry's pair goes to alpha_self / gs_self)
@@ -240,273 +86,124 @@ __global__ __launch_bounds__(kGatBlock) void gat_fwd_kernel(GatArgs a)
 //   v2: g_xr[i,h,c] = sum_e (g_s_e att[h,c]) lrelu'(t_e[c]),  g_att_rows[i,h,c] = sum_e g_s_e lrelu(t_e[c]);  gs_w = g_s_e
 //   v1: g_sdst[i,h] = sum_e g_s_e lrelu'(s_src[j,h] + s_dst[i,h]);  gs_w holds that product, the by-source pass sums it
 template <int LPT, int ITER, int MODE>
-__global__ __launch_bounds__(kGatBlock) void gat_bwd_target_kernel(GatArgs a)
+__global__ __launch_bounds__(kBlock) void gat_bwd_target_kernel(GatArgs a)
 {
-    constexpr int TPB = kGatBlock / LPT;
-    const GatGraph &g = a.g;
-    const int H = a.H, C = a.C;
-    const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int64_t unit = (int64_t)bid * TPB + threadIdx.x / LPT;
-    const int lane = threadIdx.x % LPT;
-    if (unit >= g.Nt * H) return;
-    const int64_t i = unit / H;
-    const int h = (int)(unit - i * H);
-    const int HC = H * C;
+    Unit u;
+    if (!take_unit<LPT>(a.g.Nt, a.H, u)) return;
+    const int C = a.C;
     const float slope = a.slope;
-    int64_t lo;
-    int n;
-    gat_row(g, i, lo, n);
-    const int ne = n + (g.self_loops ? 1 : 0);
-
-    float xr[ITER], at[ITER], go[ITER], o[ITER], gxr[ITER], gat[ITER];
-    float sd = 0.f, gsd = 0.f;
+    float go[ITER], delta, ls;
+    target_row<LPT, ITER>(a.g_out, a.out, a.lse, u, a.H, C, go, delta, ls);
+    const float *const rows[1] = {a.xl};
     if constexpr (MODE == kGatV2) {
-        gat_load_row<LPT, ITER>(xr, a.xr + i * HC + h * C, true, lane, C);
-        gat_load_row<LPT, ITER>(at, a.att + h * C, true, lane, C);
-    } else {
-        sd = a.s_dst[unit];
-    }
-    gat_load_row<LPT, ITER>(go, a.g_out + i * HC + h * C, true, lane, C);
-    gat_load_row<LPT, ITER>(o, a.out + i * HC + h * C, true, lane, C);
+        const GatScoreV2<LPT, ITER> score(a, u);
+        float gxr[ITER], gat[ITER];
 #pragma unroll
-    for (int it = 0; it < ITER; ++it) gxr[it] = gat[it] = 0.f;
-    const float delta = gat_group_dot<LPT, ITER>(go, o);
-    const float ls = a.lse[unit];
-    for (int base = 0; base < ne; base += LPT) {
-        const int32_t jl = gat_entry(g, i, lo, n, base + lane);
-        const int mch = min(LPT, ne - base);
-        float al = 0.f, gl = 0.f;        // lane e keeps alpha and g_s of entry base + e for one store
-        float dl = 0.f;                  // v1: lane e's lrelu' (and alpha in al) before the walk
-        if (MODE == kGatV1 && jl >= 0) {
-            const float t = a.s_src[(int64_t)jl * H + h] + sd;
-            al = expf(gat_lrelu(t, slope) - ls);       // the forward's bits
-            dl = gat_dlrelu(t, slope);
-        }
-        for (int e0 = 0; e0 < mch; e0 += kGatInFlight) {
-            int32_t j[kGatInFlight];
-            float av[kGatInFlight], dv[kGatInFlight], xj[kGatInFlight][ITER];
+        for (int it = 0; it < ITER; ++it) gxr[it] = gat[it] = 0.f;
+        target_walk<LPT, ITER, 1>(
+            a.g, u, a.H, C, rows, a.alpha_w, a.gs_w, a.alpha_self, a.gs_self, [](int32_t, float &, float &) {},
+            [&](const float (&r)[1][ITER], float, float, float &al, float &gs) {
+                al = expf(score(r[0]) - ls);       // the forward's bits
+                gs = al * (group_dot<LPT, ITER>(go, r[0]) - delta);
 #pragma unroll
-            for (int u = 0; u < kGatInFlight; ++u) {
-                const int from = (e0 + u) & (LPT - 1);
-                j[u] = __shfl(jl, from, LPT);
-                if (MODE == kGatV1) {
-                    av[u] = __shfl(al, from, LPT);
-                    dv[u] = __shfl(dl, from, LPT);
+                for (int it = 0; it < ITER; ++it) {
+                    const float t = r[0][it] + score.xr[it];
+                    gxr[it] += (gs * score.at[it]) * gat_dlrelu(t, slope);
+                    gat[it] += gs * gat_lrelu(t, slope);
                 }
-                if (e0 + u >= mch) j[u] = -1;
-            }
-#pragma unroll
-            for (int u = 0; u < kGatInFlight; ++u)
-                gat_load_row<LPT, ITER>(xj[u], a.xl + (int64_t)max(j[u], 0) * HC + h * C, j[u] >= 0, lane, C);
-#pragma unroll
-            for (int u = 0; u < kGatInFlight; ++u) {
-                if (j[u] < 0) continue;        // the same for every lane of the group
-                if constexpr (MODE == kGatV2) {
-                    const float s = gat_score_v2<LPT, ITER>(at, xj[u], xr, slope);       // the forward's bits
-                    const float al_e = expf(s - ls);
-                    const float gs = al_e * (gat_group_dot<LPT, ITER>(go, xj[u]) - delta);
-                    if (lane == e0 + u) {
-                        al = al_e;
-                        gl = gs;
-                    }
-#pragma unroll
-                    for (int it = 0; it < ITER; ++it) {
-                        const float t = xj[u][it] + xr[it];
-                        gxr[it] += (gs * at[it]) * gat_dlrelu(t, slope);
-                        gat[it] += gs * gat_lrelu(t, slope);
-                    }
-                } else {
-                    const float gs = av[u] * (gat_group_dot<LPT, ITER>(go, xj[u]) - delta);
-                    const float gp = gs * dv[u];
-                    if (lane == e0 + u) gl = gp;
-                    gsd += gp;
-                }
-            }
-        }
-        const int t = base + lane;
-        if (t < n) {
-            const int64_t pos = (lo + t) * H + h;
-            a.alpha_w[pos] = al;
-            a.gs_w[pos] = gl;
-        } else if (t == n && g.self_loops) {
-            a.alpha_self[unit] = al;
-            a.gs_self[unit] = gl;
-        }
-    }
-    if constexpr (MODE == kGatV2) {
+            });
 #pragma unroll
         for (int it = 0; it < ITER; ++it) {
-            const int c = lane + it * LPT;
+            const int c = u.lane + it * LPT;
             if (c < C) {
-                a.g_xr[i * HC + h * C + c] = gxr[it];
-                a.g_att_rows[i * HC + h * C + c] = gat[it];
+                a.g_xr[u.row * a.H * C + u.h * C + c] = gxr[it];
+                a.g_att_rows[u.row * a.H * C + u.h * C + c] = gat[it];
             }
         }
-    } else if (lane == 0) {
-        a.g_sdst[unit] = gsd;
+    } else {
+        const GatScoreV1 score(a, u);
+        float gsd = 0.f;
+        target_walk<LPT, ITER, 1>(
+            a.g, u, a.H, C, rows, a.alpha_w, a.gs_w, a.alpha_self, a.gs_self,
+            [&](int32_t j, float &al, float &dl) {      // lane e's alpha and lrelu' of entry e, before the walk
+                if (j < 0) return;
+                const float t = score.sum(j);
+                al = expf(gat_lrelu(t, slope) - ls);       // the forward's bits
+                dl = gat_dlrelu(t, slope);
+            },
+            [&](const float (&r)[1][ITER], float av, float dv, float &al, float &gp) {
+                const float gs = av * (group_dot<LPT, ITER>(go, r[0]) - delta);
+                al = av;
+                gp = gs * dv;
+                gsd += gp;
+            });
+        if (u.lane == 0) a.g_sdst[u.unit] = gsd;
     }
 }
 
-// By-source pass: for source j and head h, over the positions that hold j (rev_pos, ascending), i = the position's row,
-// then (self_loops) the implicit entry j -> j:
+// By-source pass: for source j and head h, over the positions that hold j, i = the position's row, then (self_loops) the
+// implicit entry j -> j:
 //   v2: g_xl[j,h,c] = sum alpha_e g_out[i,h,c] + (g_s_e att[h,c]) lrelu'(xl[j,h,c] + xr[i,h,c])
 //   v1: g_xl[j,h,:] = sum alpha_e g_out[i,h,:]      g_ssrc[j,h] = sum gs_w
-// A hub's list is walked by its one group, however long it is.
 template <int LPT, int ITER, int MODE>
-__global__ __launch_bounds__(kGatBlock) void gat_bwd_source_kernel(GatArgs a)
+__global__ __launch_bounds__(kBlock) void gat_bwd_source_kernel(GatArgs a)
 {
-    constexpr int TPB = kGatBlock / LPT;
-    const GatGraph &g = a.g;
-    const int H = a.H, C = a.C;
-    const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int64_t unit = (int64_t)bid * TPB + threadIdx.x / LPT;
-    const int lane = threadIdx.x % LPT;
-    if (unit >= g.Ns * H) return;
-    const int64_t j = unit / H;
-    const int h = (int)(unit - j * H);
-    const int HC = H * C;
+    Unit u;
+    if (!take_unit<LPT>(a.g.Ns, a.H, u)) return;
+    const int C = a.C;
     const float slope = a.slope;
-    const int64_t lo = min(max((int64_t)g.rev_ptr[j], (int64_t)0), g.M);
-    const int64_t hi = min(max((int64_t)g.rev_ptr[j + 1], lo), g.M);
-
-    float xj[ITER], at[ITER], gx[ITER];
-    float gss = 0.f;
-    if constexpr (MODE == kGatV2) {
-        gat_load_row<LPT, ITER>(xj, a.xl + j * HC + h * C, true, lane, C);
-        gat_load_row<LPT, ITER>(at, a.att + h * C, true, lane, C);
-    }
+    float gx[ITER];
 #pragma unroll
     for (int it = 0; it < ITER; ++it) gx[it] = 0.f;
-    for (int64_t base = lo; base < hi; base += LPT) {
-        // lane l: target, alpha and g_s of entry base + l
-        int32_t il = -1;
-        float al = 0.f, gl = 0.f;
-        if (base + lane < hi) {
-            const int64_t pos = g.rev_pos[base + lane];
-            if (pos >= 0 && pos < g.M) {
-                const int64_t i = g.rowptr == nullptr ? pos / g.k : (int64_t)g.tgt[pos];
-                if (i >= 0 && i < g.Nt && !(g.self_loops && i == j)) {      // a written self loop was skipped by target too
-                    il = (int32_t)i;
-                    al = a.alpha_w[pos * H + h];
-                    gl = a.gs_w[pos * H + h];
-                }
-            }
-        }
-        const int mch = (int)min((int64_t)LPT, hi - base);
-        for (int e0 = 0; e0 < mch; e0 += kGatInFlight) {
-            int32_t i[kGatInFlight];
-            float av[kGatInFlight], gs[kGatInFlight], gr[kGatInFlight][ITER], xi[kGatInFlight][ITER];
+    if constexpr (MODE == kGatV2) {
+        float xj[ITER], at[ITER];
+        load_row<LPT, ITER>(xj, a.xl + u.row * a.H * C + u.h * C, true, u.lane, C);
+        load_row<LPT, ITER>(at, a.att + u.h * C, true, u.lane, C);
+        const float *const rows[2] = {a.g_out, a.xr};
+        source_walk<LPT, ITER, 2>(a.g, u, a.H, C, rows, a.alpha_w, a.gs_w, a.alpha_self, a.gs_self,
+                                  [&](const float (&r)[2][ITER], float av, float gs) {
 #pragma unroll
-            for (int u = 0; u < kGatInFlight; ++u) {
-                const int from = (e0 + u) & (LPT - 1);
-                i[u] = __shfl(il, from, LPT);
-                av[u] = __shfl(al, from, LPT);
-                gs[u] = __shfl(gl, from, LPT);
-                if (e0 + u >= mch) i[u] = -1;
-            }
+                                      for (int it = 0; it < ITER; ++it)
+                                          gx[it] += av * r[0][it] + (gs * at[it]) * gat_dlrelu(xj[it] + r[1][it], slope);
+                                  });
+    } else {
+        float gss = 0.f;
+        const float *const rows[1] = {a.g_out};
+        source_walk<LPT, ITER, 1>(a.g, u, a.H, C, rows, a.alpha_w, a.gs_w, a.alpha_self, a.gs_self,
+                                  [&](const float (&r)[1][ITER], float av, float gs) {
 #pragma unroll
-            for (int u = 0; u < kGatInFlight; ++u) {
-                const int64_t row = (int64_t)max(i[u], 0) * HC + h * C;
-                gat_load_row<LPT, ITER>(gr[u], a.g_out + row, i[u] >= 0, lane, C);
-                if constexpr (MODE == kGatV2) gat_load_row<LPT, ITER>(xi[u], a.xr + row, i[u] >= 0, lane, C);
-            }
-#pragma unroll
-            for (int u = 0; u < kGatInFlight; ++u) {
-                if (i[u] < 0) continue;        // the same for every lane of the group
-                if constexpr (MODE == kGatV2) {
-#pragma unroll
-                    for (int it = 0; it < ITER; ++it)
-                        gx[it] += av[u] * gr[u][it] + (gs[u] * at[it]) * gat_dlrelu(xj[it] + xi[u][it], slope);
-                } else {
-#pragma unroll
-                    for (int it = 0; it < ITER; ++it) gx[it] += av[u] * gr[u][it];
-                    gss += gs[u];
-                }
-            }
-        }
-    }
-    if (g.self_loops) {      // the implicit entry j -> j, after the reverse list (Nt == Ns)
-        const float av = a.alpha_self[unit], gs = a.gs_self[unit];
-        float gr[ITER], xi[ITER];
-        gat_load_row<LPT, ITER>(gr, a.g_out + j * HC + h * C, true, lane, C);
-        if constexpr (MODE == kGatV2) {
-            gat_load_row<LPT, ITER>(xi, a.xr + j * HC + h * C, true, lane, C);
-#pragma unroll
-            for (int it = 0; it < ITER; ++it) gx[it] += av * gr[it] + (gs * at[it]) * gat_dlrelu(xj[it] + xi[it], slope);
-        } else {
-#pragma unroll
-            for (int it = 0; it < ITER; ++it) gx[it] += av * gr[it];
-            gss += gs;
-        }
+                                      for (int it = 0; it < ITER; ++it) gx[it] += av * r[0][it];
+                                      gss += gs;
+                                  });
+        if (u.lane == 0) a.g_ssrc[u.unit] = gss;
     }
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
-        const int c = lane + it * LPT;
-        if (c < C) a.g_xl[j * HC + h * C + c] = gx[it];
+        const int c = u.lane + it * LPT;
+        if (c < C) a.g_xl[u.row * a.H * C + u.h * C + c] = gx[it];
     }
-    if (MODE == kGatV1 && lane == 0) a.g_ssrc[unit] = gss;
 }
 
-template <int LPT, int ITER, int MODE>
-int launch_fwd(const GatArgs &a, hipStream_t st)
-{
-    constexpr int TPB = kGatBlock / LPT;
-    const int64_t blocks = (a.g.Nt * a.H + TPB - 1) / TPB;
-    hipLaunchKernelGGL((gat_fwd_kernel<LPT, ITER, MODE>), dim3((unsigned)blocks), dim3(kGatBlock), 0, st, a);
-    DMET_LAUNCH_CHECK("gat_fwd_kernel");
-    return 0;
-}
-
-template <int LPT, int ITER, int MODE>
-int launch_bwd(const GatArgs &a, hipStream_t st)
-{
-    constexpr int TPB = kGatBlock / LPT;
-    const int64_t tb = (a.g.Nt * a.H + TPB - 1) / TPB, sb = (a.g.Ns * a.H + TPB - 1) / TPB;    // sb = 0: empty rows only
-    hipLaunchKernelGGL((gat_bwd_target_kernel<LPT, ITER, MODE>), dim3((unsigned)tb), dim3(kGatBlock), 0, st, a);
-    DMET_LAUNCH_CHECK("gat_bwd_target_kernel");
-    if (sb == 0) return 0;
-    hipLaunchKernelGGL((gat_bwd_source_kernel<LPT, ITER, MODE>), dim3((unsigned)sb), dim3(kGatBlock), 0, st, a);
-    DMET_LAUNCH_CHECK("gat_bwd_source_kernel");
-    return 0;
-}
-
-// lanes per (row, head) pair and channels per lane for a head width C: 16 lanes up to 32 channels, 32 beyond
 template <bool FWD, int MODE>
-int dispatch_width(const GatArgs &a, hipStream_t st)
+int run(const GatArgs &a, hipStream_t st)
 {
-    if (a.C <= 16) return FWD ? launch_fwd<16, 1, MODE>(a, st) : launch_bwd<16, 1, MODE>(a, st);
-    if (a.C <= 32) return FWD ? launch_fwd<16, 2, MODE>(a, st) : launch_bwd<16, 2, MODE>(a, st);
-    return FWD ? launch_fwd<32, 2, MODE>(a, st) : launch_bwd<32, 2, MODE>(a, st);
+    return dispatch_width(a.C, [&](auto lpt, auto iter) {
+        constexpr int LPT = decltype(lpt)::value, ITER = decltype(iter)::value;
+        if constexpr (FWD) return launch<LPT>("gat_fwd_kernel", gat_fwd_kernel<LPT, ITER, MODE>, a.g.Nt, a.H, st, a);
+        if (int rc = launch<LPT>("gat_bwd_target_kernel", gat_bwd_target_kernel<LPT, ITER, MODE>, a.g.Nt, a.H, st, a)) return rc;
+        return launch<LPT>("gat_bwd_source_kernel", gat_bwd_source_kernel<LPT, ITER, MODE>, a.g.Ns, a.H, st, a);   // Ns == 0: no launch
+    });
 }
-
-template <bool FWD>
-int dispatch(int mode, const GatArgs &a, hipStream_t st)
-{
-    return mode == kGatV2 ? dispatch_width<FWD, kGatV2>(a, st) : dispatch_width<FWD, kGatV1>(a, st);
-}
-
-bool supported(int H, int C) { return C >= 1 && C <= kGatMaxC && H >= 1 && H <= kGatMaxH && H * C <= kGatMaxHC; }
 
 int check_shape(const char *who, int mode, bool list, int64_t Nt, int64_t Ns, int64_t E, int k, int H, int C, float slope,
                 int self_loops)
 {
     DMET_REQUIRE(mode == kGatV1 || mode == kGatV2, "%s: mode=%d, 1 (GATConv) or 2 (GATv2Conv)", who, mode);
-    DMET_REQUIRE(Nt >= 0 && Ns >= 0 && Nt < (int64_t)2147483647 && Ns < (int64_t)2147483647,
-                 "%s: Nt=%lld, Ns=%lld out of range", who, (long long)Nt, (long long)Ns);
-    DMET_REQUIRE(supported(H, C), "%s: H=%d, C=%d not in 1 <= C <= %d, 1 <= H <= %d, H*C <= %d", who, H, C, kGatMaxC,
-                 kGatMaxH, kGatMaxHC);
+    if (int rc = check_graph_shape(who, list, Nt, Ns, E, k, H, C)) return rc;
     DMET_REQUIRE(isfinite(slope) && slope >= 0.f, "%s: slope=%g must be finite and >= 0", who, (double)slope);
     DMET_REQUIRE(self_loops == 0 || self_loops == 1, "%s: self_loops=%d, 0 or 1", who, self_loops);
     DMET_REQUIRE(!self_loops || Nt == Ns, "%s: self_loops needs one node set, Nt=%lld Ns=%lld", who, (long long)Nt,
                  (long long)Ns);
-    if (list)
-        DMET_REQUIRE(E >= 0 && E < (int64_t)2147483647, "%s: E=%lld out of range", who, (long long)E);
-    else
-        DMET_REQUIRE(k >= 1 && k <= DMET_MAX_K, "%s: k=%d not in [1,%d] (table form: rowptr NULL)", who, k, DMET_MAX_K);
-    DMET_REQUIRE(list || Nt * (int64_t)k < (int64_t)2147483647, "%s: Nt*k out of range", who);
-    // a launch covers Nt*H (Ns*H) lane groups, at least 8 to a workgroup
-    DMET_REQUIRE(Nt * (int64_t)H < (int64_t)2147483647 * 4 && Ns * (int64_t)H < (int64_t)2147483647 * 4,
-                 "%s: Nt*H or Ns*H out of range", who);
     return 0;
 }
 
@@ -536,9 +233,8 @@ extern "C" int dmet_gat_fwd_f32(int mode, const float *xl, const float *xr, cons
     GatArgs a{};
     a.xl = xl; a.xr = xr; a.att = att; a.s_src = s_src; a.s_dst = s_dst; a.slope = slope; a.H = H; a.C = C;
     a.o = out; a.l = lse; a.alpha = alpha;
-    a.g.idx = idx; a.g.rowptr = rowptr; a.g.Nt = Nt; a.g.Ns = Ns; a.g.k = list ? 0 : width;
-    a.g.M = list ? E : Nt * (int64_t)width; a.g.self_loops = self_loops;
-    return dispatch<true>(mode, a, as_stream(stream));
+    a.g = make_graph(idx, rowptr, nullptr, nullptr, nullptr, Nt, Ns, E, width, self_loops);
+    return mode == kGatV2 ? run<true, kGatV2>(a, as_stream(stream)) : run<true, kGatV1>(a, as_stream(stream));
 }
 
 extern "C" int dmet_gat_bwd_f32(int mode, const float *xl, const float *xr, const float *att, const float *s_src,
@@ -576,8 +272,6 @@ extern "C" int dmet_gat_bwd_f32(int mode, const float *xl, const float *xr, cons
     a.out = out; a.lse = lse; a.g_out = g_out;
     a.alpha_w = alpha_w; a.gs_w = gs_w; a.alpha_self = alpha_self; a.gs_self = gs_self;
     a.g_xl = g_xl; a.g_xr = g_xr; a.g_att_rows = g_att_rows; a.g_ssrc = g_ssrc; a.g_sdst = g_sdst;
-    a.g.idx = idx; a.g.rowptr = rowptr; a.g.tgt = tgt; a.g.rev_ptr = rev_ptr; a.g.rev_pos = rev_pos;
-    a.g.Nt = Nt; a.g.Ns = Ns; a.g.k = list ? 0 : width; a.g.M = list ? E : Nt * (int64_t)width;
-    a.g.self_loops = self_loops;
-    return dispatch<false>(mode, a, st);
+    a.g = make_graph(idx, rowptr, tgt, rev_ptr, rev_pos, Nt, Ns, E, width, self_loops);
+    return mode == kGatV2 ? run<false, kGatV2>(a, st) : run<false, kGatV1>(a, st);
 }

@@ -15,9 +15,9 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from .attention import _graph_args
+from ._softmax_conv import SoftmaxConv, by_source_index, check_graph, graph_args, shape_alpha
 from .gravnet import _upcast
-from .graph import BipartiteTable, EdgeList, GraphFuture, NeighborTable, edge_list_from_edge_index, lookup_graph
+from .graph import BipartiteTable, EdgeList, GraphFuture, NeighborTable
 
 MAX_HEADS = _native.GAT_MAX_H
 MAX_HEAD_CHANNELS = _native.GAT_MAX_C
@@ -35,7 +35,7 @@ class _GatAggregate(torch.autograd.Function):
     def forward(ctx, mode, xl, a, b, graph, slope, self_loops, want_alpha):
         names = ("xr", "att") if mode == _native.GAT_V2 else ("s_src", "s_dst")
         xf, af, bf = _upcast(xl, "xl"), _upcast(a, names[0]), _upcast(b, names[1])
-        idx, rowptr, _tgt = _graph_args(graph)
+        idx, rowptr, _tgt = graph_args(graph)
         out, lse, alpha = _native._gat_fwd(mode, xf, af, bf, idx, rowptr, slope, self_loops, want_alpha)
         ctx.save_for_backward(xf, af, bf, out, lse)
         ctx.graph, ctx.mode, ctx.slope, ctx.self_loops = graph, mode, slope, self_loops
@@ -51,8 +51,8 @@ class _GatAggregate(torch.autograd.Function):
     def backward(ctx, g_out, _g_alpha):
         xf, af, bf, out, lse = ctx.saved_tensors
         graph = ctx.graph
-        idx, rowptr, tgt = _graph_args(graph)
-        rev_ptr, rev_pos = graph.by_source() if isinstance(graph, EdgeList) else graph.reverse()
+        idx, rowptr, tgt = graph_args(graph)
+        rev_ptr, rev_pos = by_source_index(graph)
         g_xl, g_a, g_b = _native._gat_bwd(ctx.mode, g_out.float(), xf, af, bf, out, lse, idx, rev_ptr, rev_pos, rowptr, tgt,
                                          ctx.slope, ctx.self_loops)
         dx, da, db = ctx.dtypes
@@ -64,26 +64,10 @@ def _aggregate(who, mode, xl, a, b, graph, slope, self_loops, want_alpha):
     for t in (xl, a, b):
         if not torch.is_tensor(t):
             raise TypeError(f"{who}: the inputs must be tensors, got {type(t).__name__}")
-    if isinstance(graph, NeighborTable):
-        if graph.cnt is not None:
-            raise ValueError(f"{who} needs a -1-padded table (knn_table), not a counted radius table")
-        _native.gat_check_shapes(mode, xl, a, b, graph.num_nodes, graph.num_nodes, graph.k, slope, self_loops)
-        graph.join()
-    elif isinstance(graph, BipartiteTable):
-        if graph.cnt is not None:
-            raise ValueError(f"{who} needs a -1-padded table (knn_xy_table), not a counted radius table")
-        if self_loops:
-            raise ValueError(f"{who}: a BipartiteTable has two node sets and no self loops; pass self_loops=False")
-        _native.gat_check_shapes(mode, xl, a, b, graph.num_queries, graph.num_candidates, graph.k, slope, False)
-    elif isinstance(graph, EdgeList):
-        _native.gat_check_shapes(mode, xl, a, b, graph.num_nodes, graph.num_src, None, slope, self_loops)
-    else:
-        raise TypeError(f"{who}: graph must be a NeighborTable, a BipartiteTable or an EdgeList, got "
-                        f"{type(graph).__name__}")
+    check_graph(who, graph, lambda nt, ns, width, loops: _native.gat_check_shapes(mode, xl, a, b, nt, ns, width, slope, loops),
+                self_loops)
     out, alpha = _GatAggregate.apply(mode, xl, a, b, graph, float(slope), bool(self_loops), bool(want_alpha))
-    if not want_alpha:
-        return out, None
-    return out, (alpha if isinstance(graph, EdgeList) else alpha.view(out.shape[0], graph.k, xl.shape[1]))
+    return out, (shape_alpha(alpha, graph, out.shape[0], xl.shape[1]) if want_alpha else None)
 
 
 def gat_aggregate(xl: torch.Tensor, xr: torch.Tensor, att: torch.Tensor, graph: Graph, negative_slope: float = 0.2,
@@ -130,24 +114,15 @@ def _linear(n_in: int, n_out: int, bias: bool) -> torch.nn.Linear:
     return torch.nn.Linear(n_in, n_out, bias=bias)
 
 
-class _GatBase(torch.nn.Module):
-    """What GATConv and GATv2Conv share: the argument checks, the graph forms, the residual, the bias and the way the
-    attention weights go back."""
+class _GatBase(SoftmaxConv):
+    """What GATConv and GATv2Conv share beyond SoftmaxConv: the slope, the self loops and their refusals, the residual
+    and the bias."""
 
     def __init__(self, in_channels, out_channels, heads, concat, negative_slope, dropout, add_self_loops, edge_dim,
                  fill_value, bias, residual):
         super().__init__()
         who = self.__class__.__name__
-        if dropout != 0.0:
-            raise ValueError(f"{who}: dropout on the attention weights is not supported (no RNG kernel); use 0.0")
-        if edge_dim is not None:
-            raise ValueError(f"{who}: edge features (edge_dim) are not supported")
-        for name, val, top in (("heads", heads, MAX_HEADS), ("out_channels", out_channels, MAX_HEAD_CHANNELS)):
-            if not isinstance(val, int) or isinstance(val, bool) or not 1 <= val <= top:
-                raise ValueError(f"{who}: {name}={val!r}, supported 1..{top}")
-        if heads * out_channels > MAX_HEADS_TIMES_CHANNELS:
-            raise ValueError(f"{who}: heads * out_channels = {heads * out_channels}, supported up to "
-                             f"{MAX_HEADS_TIMES_CHANNELS}")
+        self._check_options(heads, out_channels, dropout, edge_dim, size_prefix=f"{who}: ")
         slope = float(negative_slope)
         if not (math.isfinite(slope) and slope >= 0.0):
             raise ValueError(f"{who}: negative_slope={negative_slope!r} must be finite and >= 0")
@@ -185,52 +160,23 @@ class _GatBase(torch.nn.Module):
             torch.nn.init.zeros_(self.bias)
 
     def _split(self, x):
-        who = self.__class__.__name__
-        pair = isinstance(x, (tuple, list))
-        if pair:
-            if len(x) != 2:
-                raise ValueError(f"{who}: x must be a tensor or an (x_src, x_dst) pair")
-            x_src, x_dst = x
-        else:
-            x_src = x_dst = x
-        if not torch.is_tensor(x_src) or not torch.is_tensor(x_dst):
-            raise TypeError(f"{who}: x must be a tensor or an (x_src, x_dst) pair of tensors")
-        if x_src.dim() != 2 or x_dst.dim() != 2:
-            raise ValueError(f"{who}: x must be [N, F], got {tuple(x_src.shape)} and {tuple(x_dst.shape)}")
+        pair, x_src, x_dst = super()._split(x)
         if pair and self.add_self_loops:
-            raise ValueError(f"{who}: an (x_src, x_dst) pair has no self loops; construct the layer with add_self_loops=False")
+            raise ValueError(f"{self.__class__.__name__}: an (x_src, x_dst) pair has no self loops; construct the layer with "
+                             "add_self_loops=False")
         return pair, x_src, x_dst
 
     def _resolve(self, edge_index, num_src: int, num_dst: int, pair: bool, want_alpha: bool):
-        """(graph for the aggregate, how to hand alpha back: 'table', 'flat' or 'list'); TransformerConv._resolve's rules."""
+        """SoftmaxConv._resolve's rules, after what add_self_loops=True cannot go with."""
         who = self.__class__.__name__
-        if want_alpha and self.add_self_loops:
-            raise ValueError(f"{who}: return_attention_weights needs the self loops in the graph itself: build it with "
-                             "them, e.g. knn_table(..., loop=True), and pass add_self_loops=False")
-        if isinstance(edge_index, GraphFuture):
-            edge_index = edge_index.peek() if isinstance(edge_index.peek(), NeighborTable) else edge_index.result()
-        if isinstance(edge_index, (NeighborTable, BipartiteTable)):
-            if isinstance(edge_index, NeighborTable) and pair:
-                raise ValueError(f"{who}: an (x_src, x_dst) pair goes with a BipartiteTable or an edge_index tensor")
-            if isinstance(edge_index, BipartiteTable):
-                if self.add_self_loops:
-                    raise ValueError(f"{who}: a BipartiteTable has two node sets and no self loops; construct the layer "
-                                     "with add_self_loops=False")
-                if not pair:
-                    raise ValueError(f"{who}: a BipartiteTable needs an (x_src, x_dst) pair")
-            if edge_index.cnt is not None:       # a counted radius table: its valid slots as a list (one host read)
-                return edge_index.edge_list(), "list"
-            return edge_index, "table"
-        if not torch.is_tensor(edge_index):
-            raise TypeError(f"{who}: edge_index must be a graph object or an int64 [2, E] tensor, got "
-                            f"{type(edge_index).__name__}")
-        hit = None if pair else lookup_graph(edge_index)
-        if hit is not None and hit[1] == "source_to_target" and hit[0].num_nodes == num_dst and hit[0].cnt is None:
-            table = hit[0]
-            # the tensor lists the table's slots in position order when it is sized Nt*k: alpha goes back flat
-            if not want_alpha or edge_index.shape[1] == table.num_nodes * table.k:
-                return table, "flat"
-        return edge_list_from_edge_index(edge_index, num_dst, "source_to_target", num_src=num_src if pair else None), "list"
+        if self.add_self_loops:
+            if want_alpha:
+                raise ValueError(f"{who}: return_attention_weights needs the self loops in the graph itself: build it with "
+                                 "them, e.g. knn_table(..., loop=True), and pass add_self_loops=False")
+            if isinstance(edge_index.peek() if isinstance(edge_index, GraphFuture) else edge_index, BipartiteTable):
+                raise ValueError(f"{who}: a BipartiteTable has two node sets and no self loops; construct the layer with "
+                                 "add_self_loops=False")
+        return super()._resolve(edge_index, num_src, num_dst, pair, want_alpha)
 
     def _finish(self, out, x_dst, edge_index, graph, how, alpha, want):
         H, C = self.heads, self.out_channels
@@ -239,18 +185,7 @@ class _GatBase(torch.nn.Module):
             out = out + self.res(x_dst)
         if self.bias is not None:
             out = out + self.bias
-        if not want:
-            return out
-        if how == "table":
-            return out, (edge_index.peek() if isinstance(edge_index, GraphFuture) else edge_index, alpha)
-        if how == "flat":
-            return out, (edge_index, alpha.reshape(-1, H))
-        if graph.perm is not None:       # back from the grouped order to the caller's
-            alpha = torch.zeros_like(alpha).index_copy_(0, graph.perm.long(), alpha)
-        return out, (edge_index, alpha)
-
-    def __repr__(self) -> str:
-        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"
+        return self._with_alpha(out, edge_index, graph, how, alpha) if want else out
 
 
 class GATv2Conv(_GatBase):
