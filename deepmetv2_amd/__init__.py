@@ -14,6 +14,10 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import knn_interpolate                # torch_geometric.nn.unpool (interpolate_aggregate: its sums)
     from deepmetv2_amd import PointNetConv, PointConv        # torch_geometric.nn (pointnet_aggregate: message + max)
     from deepmetv2_amd import GATConv, GATv2Conv             # torch_geometric.nn (gat_v1_aggregate / gat_aggregate)
+    from deepmetv2_amd import scatter, scatter_sum, scatter_mean, scatter_min, segment_csr      # torch_scatter
+    from deepmetv2_amd import scatter_softmax, scatter_log_softmax, scatter_logsumexp           # torch_scatter.composite
+    from deepmetv2_amd import softmax                        # torch_geometric.utils
+    from deepmetv2_amd import AttentionalAggregation         # torch_geometric.nn.aggr (GlobalAttention)
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -25,7 +29,10 @@ from .conv import DynamicEdgeConv, EdgeConv
 from .data import Batch, DeviceLoader, EventLoader, collate, events_from_padded
 from .graph import BipartiteTable, GraphFuture, NeighborTable, build_async, raise_deferred_errors, register_batch, to_undirected
 from .metrics import metrics, resolution, u_perp_par_loss
-from .scatter import met_reduce, scatter_add, scatter_max
+from . import scatter        # the module, callable as torch_scatter.scatter (see its last lines)
+from .scatter import (met_reduce, scatter_add, scatter_log_softmax, scatter_logsumexp, scatter_max, scatter_mean,
+                      scatter_min, scatter_softmax, scatter_sum, segment_csr, softmax)
+from .aggr import AttentionalAggregation
 from .nn import accelerate
 from .pool import (avg_pool, avg_pool_x, global_add_pool, global_max_pool, global_mean_pool, graclus, max_pool,
                    max_pool_x, normalized_cut, normalized_cut_2d)
@@ -46,5 +53,7 @@ __all__ = [
     "GravNetConv", "gravnet_aggregate", "TransformerConv", "attention_aggregate", "fps", "nearest",
     "knn_interpolate", "interpolate_aggregate", "PointNetConv", "PointConv", "pointnet_aggregate",
     "GATConv", "GATv2Conv", "gat_aggregate", "gat_v1_aggregate",
+    "scatter", "scatter_sum", "scatter_mean", "scatter_min", "scatter_softmax", "scatter_log_softmax", "scatter_logsumexp",
+    "segment_csr", "softmax", "AttentionalAggregation",
 ]
 __version__ = "0.1.0"

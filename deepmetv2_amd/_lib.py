@@ -122,6 +122,13 @@ SIGNATURES = {
     "dmet_segment_max_bwd_f32": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
     "dmet_segment_sum_bwd_f32": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "dmet_edge_features_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    "dmet_segment_mean_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp, _vp]),
+    "dmet_segment_mean_bwd_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp, _vp]),
+    "dmet_segment_min_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp]),
+    "dmet_segment_softmax_fwd_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp]),
+    "dmet_segment_softmax_bwd_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp]),
+    "dmet_segment_logsumexp_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp, _vp]),
+    "dmet_segment_logsumexp_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp]),
     "dmet_met_reduce_f32": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp]),
     "dmet_met_reduce_bwd_f32": (_i, [_vp, _vp, _i64, _vp, _i, _i64, _vp, _vp]),
     "dmet_met_loss_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

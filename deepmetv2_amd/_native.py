@@ -1726,6 +1726,105 @@ def segment_sum_bwd(g_out: torch.Tensor, rowptr: torch.Tensor, E: int) -> torch.
     return g_msg
 
 
+# ---- csrc/segment.hip: rows of any length; `max_len` is the hint of the longest row (0: unknown) ------------------------------
+def _segment_args(src: torch.Tensor, rowptr: torch.Tensor, name: str):
+    dev = _require_device(src, rowptr)
+    src = _f32c(src, name)
+    if src.dim() != 2:
+        raise ValueError(f"{name} must be [E, H], got {tuple(src.shape)}")
+    if rowptr.dtype != torch.int32 or not rowptr.is_contiguous():
+        raise TypeError("rowptr must be contiguous int32")
+    return dev, src, rowptr.numel() - 1
+
+
+def _segment_mean(src: torch.Tensor, rowptr: torch.Tensor, max_len: int = 0) -> torch.Tensor:
+    dev, src, n = _segment_args(src, rowptr, "src")
+    E, H = src.shape
+    out = torch.empty((n, H), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_segment_mean_f32(src.data_ptr(), rowptr.data_ptr(), n, E, H, int(max_len), out.data_ptr(),
+                                                     _stream(dev)), "dmet_segment_mean_f32")
+    return out
+
+
+def _segment_mean_bwd(g_out: torch.Tensor, rowptr: torch.Tensor, E: int, max_len: int = 0) -> torch.Tensor:
+    dev, g_out, n = _segment_args(g_out, rowptr, "g_out")
+    H = g_out.shape[1]
+    g_src = torch.empty((E, H), dtype=torch.float32, device=dev) if n > 0 else torch.zeros((E, H), dtype=torch.float32,
+                                                                                          device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_segment_mean_bwd_f32(g_out.data_ptr(), rowptr.data_ptr(), n, E, H, int(max_len),
+                                                         g_src.data_ptr(), _stream(dev)), "dmet_segment_mean_bwd_f32")
+    return g_src
+
+
+def _segment_min(src: torch.Tensor, rowptr: torch.Tensor, max_len: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    dev, src, n = _segment_args(src, rowptr, "src")
+    E, H = src.shape
+    out = torch.empty((n, H), dtype=torch.float32, device=dev)
+    arg = torch.empty((n, H), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_segment_min_f32(src.data_ptr(), rowptr.data_ptr(), n, E, H, int(max_len), out.data_ptr(),
+                                                    arg.data_ptr(), _stream(dev)), "dmet_segment_min_f32")
+    return out, arg
+
+
+def _segment_softmax_fwd(src: torch.Tensor, rowptr: torch.Tensor, log: bool = False,
+                         max_len: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(y[E,H], lse[n,H]): the softmax (log: the log_softmax) of every row, and m + logf(l) per row."""
+    dev, src, n = _segment_args(src, rowptr, "src")
+    E, H = src.shape
+    y = torch.empty((E, H), dtype=torch.float32, device=dev) if n > 0 else torch.zeros((E, H), dtype=torch.float32, device=dev)
+    lse = torch.empty((n, H), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_segment_softmax_fwd_f32(src.data_ptr(), rowptr.data_ptr(), n, E, H, int(bool(log)),
+                                                            int(max_len), y.data_ptr(), lse.data_ptr(), _stream(dev)),
+                   "dmet_segment_softmax_fwd_f32")
+    return y, lse
+
+
+def _segment_softmax_bwd(y: torch.Tensor, g: torch.Tensor, rowptr: torch.Tensor, log: bool = False,
+                         max_len: int = 0) -> torch.Tensor:
+    dev, y, n = _segment_args(y, rowptr, "y")
+    g = _f32c(g, "g")
+    if g.shape != y.shape or g.device != dev:
+        raise ValueError(f"g must be {tuple(y.shape)} on {dev}, got {tuple(g.shape)} on {g.device}")
+    E, H = y.shape
+    g_src = torch.empty((E, H), dtype=torch.float32, device=dev) if n > 0 else torch.zeros((E, H), dtype=torch.float32,
+                                                                                          device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_segment_softmax_bwd_f32(y.data_ptr(), g.data_ptr(), rowptr.data_ptr(), n, E, H,
+                                                            int(bool(log)), int(max_len), g_src.data_ptr(), _stream(dev)),
+                   "dmet_segment_softmax_bwd_f32")
+    return g_src
+
+
+def _segment_logsumexp(src: torch.Tensor, rowptr: torch.Tensor, max_len: int = 0) -> torch.Tensor:
+    dev, src, n = _segment_args(src, rowptr, "src")
+    E, H = src.shape
+    out = torch.empty((n, H), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_segment_logsumexp_f32(src.data_ptr(), rowptr.data_ptr(), n, E, H, int(max_len),
+                                                          out.data_ptr(), _stream(dev)), "dmet_segment_logsumexp_f32")
+    return out
+
+
+def _segment_logsumexp_bwd(src: torch.Tensor, out: torch.Tensor, g_out: torch.Tensor, rowptr: torch.Tensor,
+                           max_len: int = 0) -> torch.Tensor:
+    dev, src, n = _segment_args(src, rowptr, "src")
+    out, g_out = _f32c(out, "out"), _f32c(g_out, "g_out")
+    E, H = src.shape
+    if out.shape != (n, H) or g_out.shape != (n, H) or out.device != dev or g_out.device != dev:
+        raise ValueError(f"out and g_out must be [{n}, {H}] on {dev}")
+    g_src = torch.empty((E, H), dtype=torch.float32, device=dev) if n > 0 else torch.zeros((E, H), dtype=torch.float32,
+                                                                                          device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_segment_logsumexp_bwd_f32(src.data_ptr(), out.data_ptr(), g_out.data_ptr(),
+                                                              rowptr.data_ptr(), n, E, H, int(max_len), g_src.data_ptr(),
+                                                              _stream(dev)), "dmet_segment_logsumexp_bwd_f32")
+    return g_src
+
+
 # ---- K4 --------------------------------------------------------------------------------------------------------
 def met_reduce(w: torch.Tensor, x: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
     dev = _require_device(w, x, ptr)

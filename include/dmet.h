@@ -776,6 +776,40 @@ int dmet_segment_sum_bwd_f32(const float *g_out, const int32_t *rowptr, int64_t 
 int dmet_edge_features_bwd_f32(const float *g_feat, const int32_t *rowptr, const int32_t *srcptr,
                                const int32_t *srcperm, int64_t N, int H, float *gx,
                                dmet_stream_t stream);
+
+/* ---- segment reductions over long and short rows (csrc/segment.hip) -------------------------------------
+ * The rest of the scatter family over fp32 rows src[E,H] (a 1-D src: H = 1) grouped by rowptr[rows+1] int32: row i owns
+ * the positions [rowptr[i], rowptr[i+1]), each span clamped to [0, E].  A wavefront owns a (row, block of channels) pair;
+ * max_len is a hint of the longest row: from 1024 on a 256-thread workgroup owns the pair instead, 0 means unknown and
+ * selects the wavefront form.  Either form takes rows of any length; the two agree to rounding, not in bits.  No float
+ * atomics, every output element written once, sums in an order fixed by H and the form: same bits run to run.
+ *   mean         : out[i,c] = (sum_e src[e,c]) / max(n_i, 1)                              (empty -> 0)
+ *   mean_bwd     : g_src[e,c] = g_out[i,c] / max(n_i, 1)
+ *   min          : out[i,c] = min_e src[e,c] (empty -> 0), arg[i,c] = winning e (lowest on ties), -1 if empty; the
+ *                  backward is dmet_segment_max_bwd_f32 (the same arg convention)
+ *   softmax_fwd  : m = max_e s, l = sum_e expf(s - m) in one online pass; then y[e,c] = expf(s - m) / l, or with log != 0
+ *                  y = (s - m) - logf(l); lse[i,c] = m + logf(l) (empty -> 0).  A row of -inf alone gives NaN, a -inf
+ *                  beside finite scores exactly 0 (softmax).
+ *   softmax_bwd  : g_src = y * (g - sum_row y*g), or with log != 0 g_src = g - expf(y) * sum_row g     (g is [E,H])
+ *   logsumexp    : out[i,c] = m + logf(l)                                                  (empty -> 0)
+ *   logsumexp_bwd: g_src[e,c] = g_out[i,c] * expf(src[e,c] - out[i,c])
+ * The per-entry outputs (y, g_src) are zero at positions before rowptr[0] and from rowptr[rows] on.  rowptr must be
+ * non-decreasing for them to be fully written: where it is not, positions in a gap between two rows are left as the
+ * caller allocated them and positions two rows share are written by both (in bounds; not defined, not reproducible). */
+int dmet_segment_mean_f32(const float *src, const int32_t *rowptr, int64_t rows, int64_t E, int H, int max_len,
+                          float *out, dmet_stream_t stream);
+int dmet_segment_mean_bwd_f32(const float *g_out, const int32_t *rowptr, int64_t rows, int64_t E, int H, int max_len,
+                              float *g_src, dmet_stream_t stream);
+int dmet_segment_min_f32(const float *src, const int32_t *rowptr, int64_t rows, int64_t E, int H, int max_len,
+                         float *out, int32_t *arg, dmet_stream_t stream);
+int dmet_segment_softmax_fwd_f32(const float *src, const int32_t *rowptr, int64_t rows, int64_t E, int H, int log,
+                                 int max_len, float *y, float *lse, dmet_stream_t stream);
+int dmet_segment_softmax_bwd_f32(const float *y, const float *g, const int32_t *rowptr, int64_t rows, int64_t E, int H,
+                                 int log, int max_len, float *g_src, dmet_stream_t stream);
+int dmet_segment_logsumexp_f32(const float *src, const int32_t *rowptr, int64_t rows, int64_t E, int H, int max_len,
+                               float *out, dmet_stream_t stream);
+int dmet_segment_logsumexp_bwd_f32(const float *src, const float *out, const float *g_out, const int32_t *rowptr,
+                                   int64_t rows, int64_t E, int H, int max_len, float *g_src, dmet_stream_t stream);
 /* The same two pieces for TWO node sets (EdgeConv((x_src, x_dst), edge_index)): src[e] indexes x_src[N_src,H], tgt[e]
  * indexes x_dst[N_dst,H], edges grouped by target (rowptr[N_dst+1]); both ids unchecked, so 0 <= src[e] < N_src and
  * 0 <= tgt[e] < N_dst must hold for every e (a table's -1 slots are dropped before, dmet_table_degree).  Any H > 0.
