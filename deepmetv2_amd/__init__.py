@@ -18,6 +18,8 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import scatter_softmax, scatter_log_softmax, scatter_logsumexp           # torch_scatter.composite
     from deepmetv2_amd import softmax                        # torch_geometric.utils
     from deepmetv2_amd import AttentionalAggregation         # torch_geometric.nn.aggr (GlobalAttention)
+    from deepmetv2_amd import PNAConv, DegreeScalerAggregation   # torch_geometric.nn (multi_aggregate: its statistics)
+    from deepmetv2_amd import scatter_std                    # torch_scatter.composite
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -31,7 +33,7 @@ from .graph import BipartiteTable, GraphFuture, NeighborTable, build_async, rais
 from .metrics import metrics, resolution, u_perp_par_loss
 from . import scatter        # the module, callable as torch_scatter.scatter (see its last lines)
 from .scatter import (met_reduce, scatter_add, scatter_log_softmax, scatter_logsumexp, scatter_max, scatter_mean,
-                      scatter_min, scatter_softmax, scatter_sum, segment_csr, softmax)
+                      scatter_min, scatter_softmax, scatter_std, scatter_sum, segment_csr, softmax)
 from .aggr import AttentionalAggregation
 from .nn import accelerate
 from .pool import (avg_pool, avg_pool_x, global_add_pool, global_max_pool, global_mean_pool, graclus, max_pool,
@@ -42,6 +44,7 @@ from .attention import TransformerConv, attention_aggregate
 from .interpolate import interpolate_aggregate, knn_interpolate
 from .pointnet import PointConv, PointNetConv, pointnet_aggregate
 from .gat import GATConv, GATv2Conv, gat_aggregate, gat_v1_aggregate
+from .pna import DegreeScalerAggregation, PNAConv, multi_aggregate
 
 __all__ = [
     "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "knn_xy_table", "radius", "radius_graph", "radius_table",
@@ -55,5 +58,6 @@ __all__ = [
     "GATConv", "GATv2Conv", "gat_aggregate", "gat_v1_aggregate",
     "scatter", "scatter_sum", "scatter_mean", "scatter_min", "scatter_softmax", "scatter_log_softmax", "scatter_logsumexp",
     "segment_csr", "softmax", "AttentionalAggregation",
+    "PNAConv", "DegreeScalerAggregation", "multi_aggregate", "scatter_std",
 ]
 __version__ = "0.1.0"

@@ -1183,6 +1183,118 @@ def interpolate_bwd(g_out: torch.Tensor, dist: torch.Tensor, wsum: torch.Tensor,
     return g_x
 
 
+MULTI_AGGR_MAX_F = 256            # features per row (include/dmet.h, "Multi-aggregation")
+MULTI_AGGR_MAX_K = GRAVNET_MAX_K    # DMET_MAX_K: the width of a table
+MULTI_AGGR_KINDS = {"sum": 1, "mean": 2, "min": 3, "max": 4, "var": 5, "std": 6}     # the ABI's codes
+
+
+def multi_aggr_code(aggrs) -> int:
+    """The `aggrs` argument of the multi-aggregation entries: the requested statistics, four bits each from the lowest in
+    request order.  Unknown names, an empty request and a name given twice are ValueErrors."""
+    if isinstance(aggrs, str) or not aggrs:
+        raise ValueError(f"multi_aggr: aggrs must be a non-empty list of {sorted(MULTI_AGGR_KINDS)}, got {aggrs!r}")
+    names = list(aggrs)
+    for a in names:
+        if a not in MULTI_AGGR_KINDS:
+            raise ValueError(f"multi_aggr: unknown aggregator {a!r}, supported {sorted(MULTI_AGGR_KINDS)}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"multi_aggr: an aggregator may be requested once, got {names}")
+    return sum(MULTI_AGGR_KINDS[a] << (4 * s) for s, a in enumerate(names))
+
+
+def multi_aggr_check_shapes(x: torch.Tensor, aggrs, groups: int, num_targets: int, num_sources: int,
+                            width: Optional[int] = None) -> None:
+    """The argument errors of the multi-aggregation entries, raised from shapes alone (before any device is asked for).
+    The graph has num_targets rows over num_sources sources; width: the table form's k (None: an edge list)."""
+    multi_aggr_code(aggrs)
+    if x.dim() != 2:
+        raise ValueError(f"multi_aggr: x must be [Ns, F], got {tuple(x.shape)}")
+    F = x.shape[1]
+    if not 1 <= F <= MULTI_AGGR_MAX_F:
+        raise ValueError(f"multi_aggr: F={F} features, supported 1..{MULTI_AGGR_MAX_F}")
+    if not isinstance(groups, int) or isinstance(groups, bool) or groups < 1 or F % groups:
+        raise ValueError(f"multi_aggr: groups={groups!r} must be a positive int that divides F={F}")
+    if width is not None and not 1 <= width <= MULTI_AGGR_MAX_K:
+        raise ValueError(f"multi_aggr: k={width}, supported 1..{MULTI_AGGR_MAX_K}")
+    if x.shape[0] != num_sources:
+        raise ValueError(f"multi_aggr: the graph indexes {num_sources} sources, x has {x.shape[0]} rows")
+    if num_targets < 0:
+        raise ValueError(f"multi_aggr: {num_targets} target rows")
+
+
+def _multi_aggr_fwd(x: torch.Tensor, idx: torch.Tensor, rowptr: Optional[torch.Tensor], num_targets: int, aggrs,
+                    groups: int = 1):
+    """(out[Nt, G, A, F/G], count[Nt] int32, saved) of the requested statistics over a table (idx = nbr[Nt, k], rowptr
+    None) or a grouped edge list (idx = src[E], rowptr[Nt+1]); saved = (mean, var, argmin, argmax), each [Nt, F] or None
+    when the request does not need it.  See include/dmet.h, dmet_multi_aggr_fwd_f32.  Not public, like _gat_fwd: pna.py and
+    scatter.py are the callers."""
+    Nt = int(num_targets)
+    multi_aggr_check_shapes(x, aggrs, groups, Nt, x.shape[0], idx.shape[1] if rowptr is None and idx.dim() == 2 else None)
+    code = multi_aggr_code(aggrs)
+    dev = _require_device(x, idx, rowptr)
+    L = _lib.load()
+    x = _f32c(x, "x")
+    idx, rowptr, E, width, _M = _row_graph("multi_aggr", idx, rowptr, Nt)
+    Ns, F = x.shape
+    A = len(aggrs)
+    second = "var" in aggrs or "std" in aggrs
+    out = torch.empty((Nt, groups, A, F // groups), dtype=torch.float32, device=dev)
+    count = torch.empty((Nt,), dtype=torch.int32, device=dev)
+    stats = torch.empty((2, Nt, F), dtype=torch.float32, device=dev) if second else None
+    args = torch.empty((2, Nt, F), dtype=torch.int32, device=dev) if ("min" in aggrs or "max" in aggrs) else None
+    mean, var = (stats[0], stats[1]) if second else (None, None)
+    amin = args[0] if "min" in aggrs else None
+    amax = args[1] if "max" in aggrs else None
+    _t = timer.record('multi_aggr_fwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_multi_aggr_fwd_f32(_ptr(x), _ptr(idx), None if rowptr is None else rowptr.data_ptr(), Nt, Ns, E,
+                                             width, F, groups, code, _ptr(out), _ptr(count), _ptr(mean), _ptr(var),
+                                             _ptr(amin), _ptr(amax), _stream(dev)), "dmet_multi_aggr_fwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, count, (mean, var, amin, amax)
+
+
+def _multi_aggr_bwd(g_out: torch.Tensor, x: torch.Tensor, count: torch.Tensor, saved, rev_ptr: torch.Tensor,
+                    rev_pos: torch.Tensor, tgt: Optional[torch.Tensor], width: Optional[int], aggrs,
+                    groups: int = 1) -> torch.Tensor:
+    """g_x[Ns, F] of _multi_aggr_fwd; (rev_ptr, rev_pos) = the graph's by-source index, width = the table's k or None for
+    a list, whose tgt[E] names the row of every position.  See include/dmet.h, dmet_multi_aggr_bwd_f32."""
+    Nt = int(count.numel())
+    multi_aggr_check_shapes(x, aggrs, groups, Nt, x.shape[0], width)
+    code = multi_aggr_code(aggrs)
+    Ns, F = x.shape
+    A = len(aggrs)
+    mean, var, amin, amax = saved
+    if tuple(g_out.shape) != (Nt, groups, A, F // groups):
+        raise ValueError(f"multi_aggr_bwd: g_out must be [{Nt}, {groups}, {A}, {F // groups}], got {tuple(g_out.shape)}")
+    dev = _require_device(g_out, x, count, mean, var, amin, amax, rev_ptr, rev_pos, tgt)
+    L = _lib.load()
+    x = _f32c(x, "x"); g_out = _f32c(g_out, "g_out")
+    rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_pos = _i32c(rev_pos, "rev_pos")
+    if width is None:
+        if tgt is None:
+            raise ValueError("multi_aggr_bwd: an edge list needs tgt")
+        tgt = _i32c(tgt, "tgt")
+        E, M, width = int(tgt.numel()), int(tgt.numel()), 0
+    else:
+        E, M, tgt = 0, Nt * int(width), None
+    if rev_ptr.numel() != Ns + 1 or rev_pos.numel() < M:
+        raise ValueError(f"multi_aggr_bwd: the by-source index does not fit {M} positions over {Ns} sources")
+    second = "var" in aggrs or "std" in aggrs
+    coef = torch.empty((2 if second else 1, Nt, F), dtype=torch.float32, device=dev)      # c0 and c1: two floats per target row
+    g_x = torch.empty((Ns, F), dtype=torch.float32, device=dev)
+    _t = timer.record('multi_aggr_bwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_multi_aggr_bwd_f32(_ptr(x), _ptr(g_out), _ptr(count), _ptr(mean), _ptr(var), _ptr(amin),
+                                             _ptr(amax), _ptr(tgt), rev_ptr.data_ptr(), _ptr(rev_pos), Nt, Ns, E, width, F,
+                                             groups, code, _ptr(coef[0]), _ptr(coef[1]) if second else None, _ptr(g_x),
+                                             _stream(dev)), "dmet_multi_aggr_bwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return g_x
+
+
 ATTENTION_MAX_C = 64     # channels per head (include/dmet.h, "Attention aggregation")
 ATTENTION_MAX_H = 16     # heads
 ATTENTION_MAX_HC = 256   # heads * channels

@@ -6,7 +6,8 @@ csrc/edgeconv.hip (segment_reduce_kernel).  Sums are deterministic: a fixed-shap
 
 The rest of the torch_scatter family -- scatter, scatter_sum, scatter_mean, scatter_min, scatter_softmax,
 scatter_log_softmax, scatter_logsumexp, segment_csr -- and torch_geometric.utils.softmax run on csrc/segment.hip, whose
-kernels put a wavefront or a workgroup along a row of any length.
+kernels put a wavefront or a workgroup along a row of any length.  scatter_std takes its centred variance from
+csrc/multi_aggr.hip.
 """
 from __future__ import annotations
 
@@ -176,7 +177,7 @@ def scatter_max(src: torch.Tensor, index: torch.Tensor, dim: int = 0, out=None,
 # The rest of the family over csrc/segment.hip: mean, min, softmax, log_softmax, logsumexp, segment_csr
 #
 # Call shapes, as scatter_add: a 1-D `src` with an index of the same shape, or `src` [E,H] along dim 0 with an index of
-# [E], [E,1] or [E,H] with equal columns.  Out of scope: scatter_std, scatter_mul, segment_coo, any other `dim`, and an
+# [E], [E,1] or [E,H] with equal columns.  Out of scope: scatter_mul, segment_coo, any other `dim`, and an
 # integer `src`.  (The global pools keep their own kernels: a faster pool would change bits that tests pin.)
 # ---------------------------------------------------------------------------------------------------------------
 scatter_sum = scatter_add
@@ -303,11 +304,36 @@ def scatter_min(src: torch.Tensor, index: torch.Tensor, dim: int = -1, out=None,
     return res, torch.where(arg64 < 0, torch.full_like(arg64, E), arg64)
 
 
+def scatter_std(src: torch.Tensor, index: torch.Tensor, dim: int = -1, out: Optional[torch.Tensor] = None,
+                dim_size: Optional[int] = None, unbiased: bool = True) -> torch.Tensor:
+    """torch_scatter.scatter_std for the call shapes of scatter_mean (rows of up to 256 features): with n the number of
+    entries of a row and var = (1/n) sum (x - mean)^2,
+
+        sqrt(n var / (max(n - 1, 1) + 1e-6))    unbiased        sqrt(n var / (n + 1e-6))    otherwise
+
+    which is torch_scatter's published formula (sum of squared deviations over count + 1e-6; **unpinned**: torch_scatter
+    is not installed next to this package).  var is csrc/multi_aggr.hip's: centred on the row's own mean in a second
+    walk, never a difference of two fp32 means, and gathered through the grouping permutation, so an unsorted index
+    costs no grouped copy of src.  An empty row and a row of one entry give 0.  Differentiable; the gradient at zero
+    variance is infinite (the derivative of sqrt at 0), as upstream.  bf16 / fp16 are computed in fp32 and returned in
+    src.dtype.  `out` is not implemented."""
+    from .pna import _aggregate_rows
+    _no_out("scatter_std", out)
+    rows = _rows_of_src("scatter_std", src, index, dim)
+    E, H = rows.shape
+    n, rowptr, perm = _group_rows(index, E, H, dim_size)
+    var, count = _aggregate_rows(rows.float(), rowptr, perm, n, ("var",))
+    cnt = count.to(torch.float32).view(-1, 1)
+    denom = ((cnt - 1).clamp(min=1) if unbiased else cnt) + 1e-6
+    res = (cnt * var.view(n, H) / denom).sqrt().to(src.dtype)
+    return res.view(-1) if src.dim() == 1 else res
+
+
 def scatter(src: torch.Tensor, index: torch.Tensor, dim: int = -1, out: Optional[torch.Tensor] = None,
             dim_size: Optional[int] = None, reduce: str = "sum") -> torch.Tensor:
     """torch_scatter.scatter: 'sum' / 'add' and 'max' are scatter_add and scatter_max themselves (their bits), 'mean' and
-    'min' the functions above; 'min' and 'max' return the values only.  'mul' (scatter_mul) is not implemented, nor are
-    scatter_std and segment_coo, a `dim` other than the two call shapes of scatter_add, and an integer `src`."""
+    'min' the functions above; 'min' and 'max' return the values only.  'mul' (scatter_mul) is not implemented, nor is
+    segment_coo, a `dim` other than the two call shapes of scatter_add, and an integer `src`."""
     if reduce in ("sum", "add"):
         return scatter_add(src, index, dim, out, dim_size)
     if reduce == "mean":

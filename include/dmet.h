@@ -680,6 +680,44 @@ int dmet_interpolate_fwd_f32(const float *x, const int32_t *nbr, const float *di
                              float *out, float *wsum, dmet_stream_t stream);
 int dmet_interpolate_bwd_f32(const float *g_out, const float *dist, const float *wsum, const int32_t *rev_ptr,
                              const int32_t *rev_pos, int64_t Nt, int64_t Ns, int k, int F, float *g_x, dmet_stream_t stream);
+/* ---- Multi-aggregation: sum, mean, min, max, var and std of the same neighbour rows ----------------------------------
+ * replaces the aggregators of torch_geometric.nn.PNAConv (aggr.SumAggregation ... aggr.StdAggregation under
+ * aggr.DegreeScalerAggregation), one scatter each over the same [E, F] messages, and supplies the variance of
+ * torch_scatter.scatter_std (csrc/multi_aggr.hip): every source row is gathered once per walk and all requested
+ * statistics are formed from it in registers.
+ * The graph: width >= 1 is a table idx = nbr[Nt, width] (1 <= width <= DMET_MAX_K, position p = i*width + t belongs to
+ *   target i, E and rowptr are ignored); width == 0 is an edge list grouped by target, idx = src[E], rowptr[Nt+1]
+ *   (clamped to [0, E]), any in-degree.  -1 and an id outside [0, Ns) are no entry; a duplicate id counts once per slot.
+ * x[Ns, F] fp32, 1 <= F <= 256; G >= 1 feature groups with F % G == 0.
+ * aggrs: the A requested statistics in request order, four bits each from the lowest: 1 sum, 2 mean, 3 min, 4 max,
+ *   5 var, 6 std; the first zero nibble ends the list; 1 <= A <= 6, each statistic at most once.
+ * dmet_multi_aggr_fwd_f32, for target i with valid entries j_1..j_n in ascending position order, per feature f:
+ *   sum  = ((0 + x[j_1,f]) + x[j_2,f]) + ...          mean = sum / (float)n
+ *   min, max: the first strictly smaller / larger value wins, so the lowest position keeps a tie (R4)
+ *   var  = (((0 + d_1*d_1) + d_2*d_2) + ...) / (float)n with d_e = x[j_e,f] - mean: a second walk over the row, centred
+ *          on the row's own mean (error at most (2n+8) u var + ((n+2) u mean|x|)^2, u = 2^-24)
+ *   std  = s = sqrtf(fmaxf(var, 1e-5f)), 0 where s <= sqrtf(1e-5f)
+ *   out[Nt, G, A, F/G]: statistic a of feature f at out[i, f / (F/G), a, f % (F/G)].  count[Nt] int32 = n.  n == 0: every
+ *   statistic 0 exactly (R3).  mean[Nt, F], var[Nt, F] (required with var or std, optional else), argmin[Nt, F] int32
+ *   (required with min), argmax[Nt, F] (required with max): the winner's position, -1 in an empty row.
+ * dmet_multi_aggr_bwd_f32: one launch per target forms c1[i,f] = (2 g_v) / n and c0[i,f] = (g_sum + g_mean / n) -
+ *   c1 mean, g_v = g_var + g_std / (2 std) where var > 1e-5 and std > 0, g_v = g_var otherwise, 0 and 0 for n == 0 (c0,
+ *   c1: caller's work rows [Nt, F]; c1 only with var or std); then by source j over the positions p of the by-source
+ *   index rev_ptr[Ns+1], rev_pos[] (dmet_reverse_index over idx) in ascending order, i = p / width or tgt[p]:
+ *   g_x[j,f] = acc + ((((c1[i,f] * x[j,f]) + c0[i,f]) + [argmin[i,f] == p] g_min[i,f]) + [argmax[i,f] == p] g_max[i,f])
+ *   g_out has out's layout.  A source nobody lists gets 0.  A long list is walked by its one owner.
+ * No float atomics; sums run in a fixed order, two runs give identical bits; every element of every output is written.
+ * Rows are read and written 16 bytes at a time where F % 4 == 0, (F/G) % 4 == 0 and every row tensor starts on a 16-byte
+ * boundary, element by element otherwise, with the same bits.
+ * Both return -EINVAL on bad arguments before any device work.  Nt == 0: the forward returns 0 at once; the backward
+ * zero-fills g_x (Ns > 0) and returns. */
+int dmet_multi_aggr_fwd_f32(const float *x, const int32_t *idx, const int32_t *rowptr, int64_t Nt, int64_t Ns, int64_t E,
+                            int width, int F, int G, int aggrs, float *out, int32_t *count, float *mean, float *var,
+                            int32_t *argmin, int32_t *argmax, dmet_stream_t stream);
+int dmet_multi_aggr_bwd_f32(const float *x, const float *g_out, const int32_t *count, const float *mean, const float *var,
+                            const int32_t *argmin, const int32_t *argmax, const int32_t *tgt, const int32_t *rev_ptr,
+                            const int32_t *rev_pos, int64_t Nt, int64_t Ns, int64_t E, int width, int F, int G, int aggrs,
+                            float *c0, float *c1, float *g_x, dmet_stream_t stream);
 /* ---- PointNet convolution: fused set abstraction -------------------------------------------------------------------
  * replaces torch_geometric.nn.PointNetConv.forward for local_nn = Sequential(Linear(F + D, H1), act, Linear(H1, H2)
  * [, act]) and aggr = 'max': remove_self_loops + add_self_loops on the edge index, message

@@ -1,0 +1,372 @@
+"""Float64 restatements for csrc/multi_aggr.hip and deepmetv2_amd/pna.py, the error bounds the GPU tests hold the kernels
+to, an fp32 numpy emulation of the kernels' own chains (for the host tests: it must stay under half of every bound, and
+it stands in for the kernels where the layers' host logic is tested without a GPU), and PyG's PNAConv /
+DegreeScalerAggregation composed exactly as their published source composes them.
+
+A graph is given as positions: tgt[P], src[P] and valid[P] (position p belongs to row tgt[p] and holds source src[p];
+valid: an id in [0, Ns)), in ascending position order -- `positions_of_table` and `positions_of_list` make them.
+
+Bounds, u = 2^-24, n the row length, mean|x| and var the reference's (the issue's):
+  count, min, max and their positions   equal
+  sum    (n + 2) u sum|x|
+  mean   (n + 3) u mean|x|
+  var    (2n + 8) u var + ((n + 2) u mean|x|)^2 + 1e-45
+  std    where var > 4e-5: var_bound / (2 std) + 2 u std
+  g_x    see `grad_bound`
+"""
+import math
+
+import numpy as np
+import torch
+
+U = 2.0 ** -24
+KINDS = ("sum", "mean", "min", "max", "var", "std")
+VAR_FLOOR = 1e-5
+
+
+def positions_of_table(nbr, Ns):
+    nbr = nbr.cpu().long()
+    Nt, k = nbr.shape
+    tgt = torch.arange(Nt).view(-1, 1).expand(Nt, k).reshape(-1)
+    src = nbr.reshape(-1)
+    return tgt, src, (src >= 0) & (src < Ns)
+
+
+def positions_of_list(src, rowptr, Ns):
+    src, rowptr = src.cpu().long(), rowptr.cpu().long()
+    Nt = rowptr.numel() - 1
+    tgt = torch.repeat_interleave(torch.arange(Nt), rowptr.diff())
+    return tgt, src, (src >= 0) & (src < Ns)
+
+
+def stats(x, tgt, src, valid, Nt):
+    """Per row, in float64 and row by row: dict of sum, mean, min, max, var, std [Nt, F], abs_sum, abs_mean [Nt, F],
+    count [Nt], argmin, argmax [Nt, F] (positions, the lowest on ties, -1 in an empty row)."""
+    x = x.double()
+    F = x.shape[1]
+    out = {k: torch.zeros(Nt, F, dtype=torch.float64) for k in KINDS + ("abs_sum", "abs_mean")}
+    out["count"] = torch.zeros(Nt, dtype=torch.int64)
+    out["argmin"] = torch.full((Nt, F), -1, dtype=torch.int64)
+    out["argmax"] = torch.full((Nt, F), -1, dtype=torch.int64)
+    pos = torch.nonzero(valid).view(-1)
+    rows = tgt[pos]
+    for i in range(Nt):
+        ps = pos[rows == i]
+        n = ps.numel()
+        if n == 0:
+            continue
+        xs = x[src[ps]]
+        out["count"][i] = n
+        out["sum"][i] = xs.sum(0)
+        out["abs_sum"][i] = xs.abs().sum(0)
+        mean = xs.sum(0) / n
+        out["mean"][i] = mean
+        out["abs_mean"][i] = xs.abs().sum(0) / n
+        var = ((xs - mean) ** 2).sum(0) / n
+        out["var"][i] = var
+        s = var.clamp(min=VAR_FLOOR).sqrt()
+        out["std"][i] = torch.where(s <= math.sqrt(VAR_FLOOR), torch.zeros_like(s), s)
+        mn, mx = xs.amin(0), xs.amax(0)
+        out["min"][i], out["max"][i] = mn, mx
+        out["argmin"][i] = ps[(xs == mn).to(torch.int8).argmax(0)]      # argmax: the first of equal values
+        out["argmax"][i] = ps[(xs == mx).to(torch.int8).argmax(0)]
+    return out
+
+
+def bounds(ref):
+    """{kind: the per-element error bound [Nt, F]} of the module docstring; std's holds where var > 4e-5."""
+    n = ref["count"].double().view(-1, 1)
+    var_b = (2 * n + 8) * U * ref["var"] + ((n + 2) * U * ref["abs_mean"]) ** 2 + 1e-45
+    std = ref["std"]
+    std_b = torch.where(ref["var"] > 4e-5, var_b / (2 * std.clamp(min=1e-30)) + 2 * U * std, torch.zeros_like(std))
+    return {"sum": (n + 2) * U * ref["abs_sum"], "mean": (n + 3) * U * ref["abs_mean"], "var": var_b, "std": std_b}
+
+
+def clamp_is_clear(ref) -> bool:
+    """The condition on the inputs: every reference variance is exactly 0 or outside [2.5e-6, 4e-5]."""
+    v = ref["var"][ref["count"] > 0]
+    return bool(((v == 0) | (v < 2.5e-6) | (v > 4e-5)).all())
+
+
+def layout(t, aggrs, groups):
+    """{kind: [Nt, F]} of a result or gradient tensor [Nt, G, A, F/G] (or [Nt, A, F])."""
+    Nt = t.shape[0]
+    t = t.reshape(Nt, groups, len(aggrs), -1)
+    return {a: t[:, :, s, :].reshape(Nt, -1) for s, a in enumerate(aggrs)}
+
+
+def pack(per_kind, aggrs, groups):
+    """The inverse of layout: [Nt, G, A, F/G]."""
+    Nt = per_kind[aggrs[0]].shape[0]
+    return torch.stack([per_kind[a].reshape(Nt, groups, -1) for a in aggrs], dim=2)
+
+
+def _coefficients(ref, g):
+    """(c0 parts, c1, g_v, uses_std) in float64 from the reference statistics and {kind: g [Nt, F]}."""
+    n = ref["count"].double().view(-1, 1).clamp(min=1)
+    has = (ref["count"] > 0).view(-1, 1)
+    zero = torch.zeros_like(ref["mean"])
+    g_sum, g_mean, g_var, g_std = (g.get(k, zero) for k in ("sum", "mean", "var", "std"))
+    on = (ref["var"] > VAR_FLOOR) & (ref["std"] > 0)
+    g_v = g_var + torch.where(on, g_std / (2 * ref["std"].clamp(min=1e-30)), zero)
+    c1 = torch.where(has, 2 * g_v / n, zero)
+    return torch.where(has, g_sum, zero), torch.where(has, g_mean / n, zero), c1, on
+
+
+def grad(x, tgt, src, valid, ref, g):
+    """(g_x [Ns, F], n_j [Ns]) in float64: g_x[j] = sum over the valid positions p that hold j, i = tgt[p], of
+    c0_i + c1_i x_j + [argmin_i == p] g_min_i + [argmax_i == p] g_max_i."""
+    x = x.double()
+    a, b, c1, _on = _coefficients(ref, g)
+    pos = torch.nonzero(valid).view(-1)
+    i, j = tgt[pos], src[pos]
+    term = a[i] + b[i] + c1[i] * (x[j] - ref["mean"][i])
+    if "min" in g:
+        term = term + torch.where(ref["argmin"][i] == pos.view(-1, 1), g["min"][i], torch.zeros_like(term))
+    if "max" in g:
+        term = term + torch.where(ref["argmax"][i] == pos.view(-1, 1), g["max"][i], torch.zeros_like(term))
+    g_x = torch.zeros_like(x).index_add_(0, j, term)
+    return g_x, torch.bincount(j, minlength=x.shape[0])
+
+
+def grad_bound(x, tgt, src, valid, ref, g):
+    """The bound on |g_x - reference| per element, derived from the kernels' chain (csrc/multi_aggr.hip):
+
+      per target:   s = sqrtf(var)   g_v = g_var + g_std / (2 s)   c1 = (2 g_v) / n   c0 = (g_sum + g_mean / n) - c1 mean
+      per position: t = ((c1 x_j + c0) + [..] g_min) + [..] g_max      acc = acc + t         (n_j positions, in order)
+
+    Every rounding is relative to a partial result that is at most the sum of the magnitudes of the terms met so far,
+      M_p = |g_sum| + |g_mean| / n + |c1| |mean| + |c1| |x_j| + [..] |g_min| + [..] |g_max|.
+    A component passes through at most 3 roundings in g_v (divide, add; 2 s is exact; one spare for sqrtf's own),
+    1 in c1, 3 in c0 (divide, add, product, subtract: 4 for the mean part), 4 per position (product, add, two
+    conditional adds) and n_j - 1 in the accumulation: fewer than n_j + 12, so the first term is
+      (n_j + 12) u sum_p M_p.
+    The statistics the coefficients are formed from carry the forward's error: the mean enters c0 as c1 mean, so
+      sum_p |c1_i| (n_i + 2) u mean|x|_i,
+    and the standard deviation enters g_v as g_std / (2 std), whose error (std's bound b_std) moves c1 by
+    |g_std| b_std / (n std^2) and the term by that times |x_j - mean_i| (c1 is one value in both products):
+      sum_p |g_std_i| b_std_i |x_j - mean_i| / (n_i std_i^2).
+    Second-order terms are covered by the slack between the true count of roundings and n_j + 12."""
+    x = x.double()
+    a, b, c1, on = _coefficients(ref, g)
+    n = ref["count"].double().view(-1, 1).clamp(min=1)
+    pos = torch.nonzero(valid).view(-1)
+    i, j = tgt[pos], src[pos]
+    mag = a[i].abs() + b[i].abs() + c1[i].abs() * (ref["mean"][i].abs() + x[j].abs())
+    if "min" in g:
+        mag = mag + torch.where(ref["argmin"][i] == pos.view(-1, 1), g["min"][i].abs(), torch.zeros_like(mag))
+    if "max" in g:
+        mag = mag + torch.where(ref["argmax"][i] == pos.view(-1, 1), g["max"][i].abs(), torch.zeros_like(mag))
+    prop = c1[i].abs() * ((n + 2) * U * ref["abs_mean"])[i]
+    if "std" in g:
+        b_std = bounds(ref)["std"]
+        dc1 = torch.where(on, g["std"].abs() * b_std / (n * ref["std"].clamp(min=1e-30) ** 2), torch.zeros_like(b_std))
+        prop = prop + dc1[i] * (x[j] - ref["mean"][i]).abs()
+    n_j = torch.bincount(j, minlength=x.shape[0]).double().view(-1, 1)
+    total = torch.zeros_like(x).index_add_(0, j, mag)
+    return (n_j + 12) * U * total + torch.zeros_like(x).index_add_(0, j, prop) + 1e-45
+
+
+# ---- the kernels' chains in fp32 numpy ----------------------------------------------------------------------------------
+def emulate_fwd(x, tgt, src, valid, Nt, one_pass=False):
+    """The forward's chain element by element in numpy float32, in position order.  one_pass=True forms the variance as
+    mean(x^2) - mean(x)^2 instead (the form the kernel must not use).  Returns the dict of `stats` in float32 / int64."""
+    x = np.asarray(x, dtype=np.float32)
+    tgt, src, valid = (np.asarray(t) for t in (tgt, src, valid))
+    F = x.shape[1]
+    f32 = np.float32
+    out = {k: np.zeros((Nt, F), dtype=f32) for k in KINDS}
+    out["count"] = np.zeros(Nt, dtype=np.int64)
+    out["argmin"] = np.full((Nt, F), -1, dtype=np.int64)
+    out["argmax"] = np.full((Nt, F), -1, dtype=np.int64)
+    rows = [[] for _ in range(Nt)]
+    for p in np.nonzero(valid)[0]:
+        rows[tgt[p]].append(p)
+    for i, ps in enumerate(rows):
+        n = len(ps)
+        if n == 0:
+            continue
+        s, sq = np.zeros(F, dtype=f32), np.zeros(F, dtype=f32)
+        mn, mx = np.full(F, np.inf, dtype=f32), np.full(F, -np.inf, dtype=f32)
+        pmn, pmx = np.full(F, -1, dtype=np.int64), np.full(F, -1, dtype=np.int64)
+        for p in ps:
+            v = x[src[p]]
+            s = s + v
+            sq = sq + v * v
+            lo, hi = v < mn, v > mx
+            mn, pmn = np.where(lo, v, mn), np.where(lo, p, pmn)
+            mx, pmx = np.where(hi, v, mx), np.where(hi, p, pmx)
+        mean = s / f32(n)
+        if one_pass:
+            var = sq / f32(n) - mean * mean
+        else:
+            acc = np.zeros(F, dtype=f32)
+            for p in ps:
+                d = x[src[p]] - mean
+                acc = acc + d * d
+            var = acc / f32(n)
+        sd = np.sqrt(np.maximum(var, f32(VAR_FLOOR)))
+        out["count"][i] = n
+        out["sum"][i], out["mean"][i], out["min"][i], out["max"][i], out["var"][i] = s, mean, mn, mx, var
+        out["std"][i] = np.where(sd <= np.sqrt(f32(VAR_FLOOR)), f32(0), sd)
+        out["argmin"][i], out["argmax"][i] = pmn, pmx
+    return out
+
+
+def emulate_bwd(x, tgt, src, valid, fwd, g):
+    """The backward's chain in numpy float32 from the emulated forward `fwd` and {kind: g [Nt, F]}: g_x [Ns, F]."""
+    f32 = np.float32
+    x = np.asarray(x, dtype=f32)
+    tgt, src, valid = (np.asarray(t) for t in (tgt, src, valid))
+    Nt, F = fwd["mean"].shape
+    g = {k: np.asarray(v, dtype=f32) for k, v in g.items()}
+    zero = np.zeros((Nt, F), dtype=f32)
+    n = np.maximum(fwd["count"], 1).astype(f32).reshape(-1, 1)
+    has = (fwd["count"] > 0).reshape(-1, 1)
+    c0 = g.get("sum", zero) + g.get("mean", zero) / n
+    second = "var" in g or "std" in g
+    c1 = zero
+    if second:
+        gv = g.get("var", zero)
+        if "std" in g:
+            s = fwd["std"]
+            on = (fwd["var"] > f32(VAR_FLOOR)) & (s > 0)
+            gv = gv + np.where(on, g["std"] / (f32(2) * np.where(on, s, f32(1))), f32(0))
+        c1 = (f32(2) * gv) / n
+        c0 = c0 - c1 * fwd["mean"]
+    c0, c1 = np.where(has, c0, f32(0)), np.where(has, c1, f32(0)) if second else zero
+    g_x = np.zeros_like(x)
+    for p in np.nonzero(valid)[0]:       # ascending positions: every source's own order
+        i, j = tgt[p], src[p]
+        t = c0[i]
+        if second:
+            t = c1[i] * x[j] + t
+        if "min" in g:
+            t = np.where(fwd["argmin"][i] == p, t + g["min"][i], t)
+        if "max" in g:
+            t = np.where(fwd["argmax"][i] == p, t + g["max"][i], t)
+        g_x[j] = g_x[j] + t
+    return g_x
+
+
+class FakeKernels:
+    """Stand-ins for deepmetv2_amd._native._multi_aggr_fwd / _multi_aggr_bwd on CPU tensors over the emulation above."""
+
+    @staticmethod
+    def _positions(idx, rowptr, Ns):
+        return positions_of_table(idx, Ns) if rowptr is None else positions_of_list(idx, rowptr, Ns)
+
+    def fwd(self, x, idx, rowptr, num_targets, aggrs, groups=1):
+        self.pos = self._positions(idx, rowptr, x.shape[0])
+        f = emulate_fwd(x.detach().numpy(), *self.pos, num_targets)
+        self.last = f
+        out = pack({a: torch.from_numpy(f[a]) for a in aggrs}, tuple(aggrs), groups)
+        saved = tuple(torch.from_numpy(f[k]) for k in ("mean", "var")) + \
+            tuple(torch.from_numpy(f[k]).int() for k in ("argmin", "argmax"))
+        return out, torch.from_numpy(f["count"]).int(), saved
+
+    def bwd(self, g_out, x, count, saved, rev_ptr, rev_pos, tgt, width, aggrs, groups=1):
+        g = {a: t.numpy() for a, t in layout(g_out.detach(), tuple(aggrs), groups).items()}
+        return torch.from_numpy(emulate_bwd(x.detach().numpy(), *self.pos, self.last, g))
+
+    def install(self, monkeypatch):
+        import deepmetv2_amd._native as nat
+        monkeypatch.setattr(nat, "_multi_aggr_fwd", self.fwd)
+        monkeypatch.setattr(nat, "_multi_aggr_bwd", self.bwd)
+
+
+# ---- PyG's modules as published ------------------------------------------------------------------------------------------
+def _reduce(msg, tgt, N, how):
+    if how in ("sum", "mean"):
+        s = torch.zeros((N,) + msg.shape[1:], dtype=msg.dtype).index_add(0, tgt, msg)
+        if how == "sum":
+            return s
+        cnt = torch.bincount(tgt, minlength=N).clamp(min=1).to(msg.dtype)
+        return s / cnt.view(-1, *([1] * (msg.dim() - 1)))
+    idx = tgt.view(-1, *([1] * (msg.dim() - 1))).expand_as(msg)
+    return torch.zeros((N,) + msg.shape[1:], dtype=msg.dtype).scatter_reduce(0, idx, msg, "amin" if how == "min" else "amax",
+                                                                            include_self=False)
+
+
+def upstream_aggregate(msg, tgt, N, how):
+    """One of PyG's aggregations over dim 0 of msg: Sum / Mean / Min / Max, VarAggregation (mean(x^2) - mean(x)^2) and
+    StdAggregation (clamp(min=1e-5).sqrt(), masked to 0 where <= sqrt(1e-5))."""
+    if how in ("var", "std"):
+        mean = _reduce(msg, tgt, N, "mean")
+        var = _reduce(msg * msg, tgt, N, "mean") - mean * mean
+        if how == "var":
+            return var
+        out = var.clamp(min=VAR_FLOOR).sqrt()
+        return out.masked_fill(out <= math.sqrt(VAR_FLOOR), 0.0)
+    return _reduce(msg, tgt, N, how)
+
+
+def avg_degrees(deg):
+    deg = deg.to(torch.float)
+    N = int(deg.sum())
+    bins = torch.arange(deg.numel())
+    return float((bins * deg).sum()) / N, float(((bins + 1).log() * deg).sum()) / N
+
+
+def upstream_degree_scaler(msg, tgt, N, aggrs, scalers, avg_lin, avg_log):
+    """DegreeScalerAggregation.forward over dim 0 of msg [E, ..., F]: the aggregators side by side in the last dim, then
+    the scalers side by side; the degree clamped to at least 1."""
+    out = torch.cat([upstream_aggregate(msg, tgt, N, a) for a in aggrs], dim=-1)
+    deg = torch.bincount(tgt, minlength=N).to(out.dtype).clamp(min=1).view(-1, *([1] * (out.dim() - 1)))
+    outs = []
+    for s in scalers:
+        if s == "identity":
+            outs.append(out)
+        elif s == "amplification":
+            outs.append(out * (torch.log(deg + 1) / avg_log))
+        elif s == "attenuation":
+            outs.append(out * (avg_log / torch.log(deg + 1)))
+        elif s == "linear":
+            outs.append(out * (deg / avg_lin))
+        elif s == "inverse_linear":
+            outs.append(out * (avg_lin / deg))
+        else:
+            raise ValueError(s)
+    return torch.cat(outs, dim=-1)
+
+
+class UpstreamPNAConv(torch.nn.Module):
+    """PNAConv as PyG's published source composes it, with the same parameter names: per-edge cat([x_i, x_j]), pre_nn per
+    tower, DegreeScalerAggregation, cat with x, post_nn per tower, lin."""
+
+    def __init__(self, in_channels, out_channels, aggregators, scalers, deg, towers=1, pre_layers=1, post_layers=1,
+                 divide_input=False, train_norm=False):
+        super().__init__()
+        self.aggregators, self.scalers, self.towers, self.divide_input = list(aggregators), list(scalers), towers, divide_input
+        self.F_in = in_channels // towers if divide_input else in_channels
+        self.F_out = out_channels // towers
+        self.aggr_module = torch.nn.Module()
+        lin_, log_ = avg_degrees(deg)
+        for name, val in (("avg_deg_lin", lin_), ("avg_deg_log", log_)):
+            if train_norm:
+                setattr(self.aggr_module, name, torch.nn.Parameter(torch.full((1,), val)))
+            else:
+                self.aggr_module.register_buffer(name, torch.full((1,), val))
+        self.pre_nns, self.post_nns = torch.nn.ModuleList(), torch.nn.ModuleList()
+        for _ in range(towers):
+            mods = [torch.nn.Linear(2 * self.F_in, self.F_in)]
+            for _ in range(pre_layers - 1):
+                mods += [torch.nn.ReLU(), torch.nn.Linear(self.F_in, self.F_in)]
+            self.pre_nns.append(torch.nn.Sequential(*mods))
+            mods = [torch.nn.Linear((len(aggregators) * len(scalers) + 1) * self.F_in, self.F_out)]
+            for _ in range(post_layers - 1):
+                mods += [torch.nn.ReLU(), torch.nn.Linear(self.F_out, self.F_out)]
+            self.post_nns.append(torch.nn.Sequential(*mods))
+        self.lin = torch.nn.Linear(out_channels, out_channels)
+
+    def forward(self, x, edge_index):
+        src, tgt = edge_index[0], edge_index[1]
+        N = x.shape[0]
+        x = x.view(N, self.towers, self.F_in) if self.divide_input else x.view(N, 1, self.F_in).repeat(1, self.towers, 1)
+        h = torch.cat([x[tgt], x[src]], dim=-1)
+        msg = torch.stack([nn(h[:, t]) for t, nn in enumerate(self.pre_nns)], dim=1)
+        out = upstream_degree_scaler(msg, tgt, N, self.aggregators, self.scalers, self.aggr_module.avg_deg_lin,
+                                     self.aggr_module.avg_deg_log)
+        out = torch.cat([x, out], dim=-1)
+        out = torch.cat([nn(out[:, t]) for t, nn in enumerate(self.post_nns)], dim=1)
+        return self.lin(out)
