@@ -20,6 +20,9 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import AttentionalAggregation         # torch_geometric.nn.aggr (GlobalAttention)
     from deepmetv2_amd import PNAConv, DegreeScalerAggregation   # torch_geometric.nn (multi_aggregate: its statistics)
     from deepmetv2_amd import scatter_std                    # torch_scatter.composite
+    from deepmetv2_amd import GCNConv, GraphConv, SAGEConv, GINConv   # torch_geometric.nn (weighted_aggregate: propagate)
+    from deepmetv2_amd import gcn_norm                       # torch_geometric.nn.conv.gcn_conv
+    from deepmetv2_amd import spmm                           # torch_sparse
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -45,6 +48,8 @@ from .interpolate import interpolate_aggregate, knn_interpolate
 from .pointnet import PointConv, PointNetConv, pointnet_aggregate
 from .gat import GATConv, GATv2Conv, gat_aggregate, gat_v1_aggregate
 from .pna import DegreeScalerAggregation, PNAConv, multi_aggregate
+from .propagate import spmm, weighted_aggregate
+from .gcn import GCNConv, GINConv, GraphConv, SAGEConv, gcn_norm
 
 __all__ = [
     "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "knn_xy_table", "radius", "radius_graph", "radius_table",
@@ -59,5 +64,6 @@ __all__ = [
     "scatter", "scatter_sum", "scatter_mean", "scatter_min", "scatter_softmax", "scatter_log_softmax", "scatter_logsumexp",
     "segment_csr", "softmax", "AttentionalAggregation",
     "PNAConv", "DegreeScalerAggregation", "multi_aggregate", "scatter_std",
+    "GCNConv", "GraphConv", "SAGEConv", "GINConv", "gcn_norm", "weighted_aggregate", "spmm",
 ]
 __version__ = "0.1.0"

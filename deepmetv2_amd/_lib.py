@@ -111,6 +111,8 @@ SIGNATURES = {
     "dmet_interpolate_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp]),
     "dmet_multi_aggr_fwd_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i] + [_vp] * 6 + [_vp]),
     "dmet_multi_aggr_bwd_f32": (_i, [_vp] * 10 + [_i64, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dmet_weighted_sum_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp]),
+    "dmet_weighted_sum_bwd_f32": (_i, [_vp] * 8 + [_i64, _i64, _i64, _i, _i, _vp, _vp, _vp]),
     "dmet_pointnet_supported": (_i, [_i, _i, _i, _i]),
     "dmet_pointnet_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "dmet_pointnet_fwd_f32": (_i, [_vp] * 6 + [_i64] * 3 + [_i] * 3 + [_vp, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp] * 6 +

@@ -1295,6 +1295,105 @@ def _multi_aggr_bwd(g_out: torch.Tensor, x: torch.Tensor, count: torch.Tensor, s
     return g_x
 
 
+WEIGHTED_SUM_MAX_F = 256            # features per row (include/dmet.h, "Weighted aggregation")
+WEIGHTED_SUM_MAX_K = GRAVNET_MAX_K    # DMET_MAX_K: the width of a table
+
+
+def weighted_sum_check_shapes(x: torch.Tensor, w: Optional[torch.Tensor], num_targets: int, num_sources: int,
+                              width: Optional[int] = None, num_edges: Optional[int] = None) -> None:
+    """The argument errors of the weighted-aggregation entries, raised from shapes alone (before any device is asked for).
+    The graph has num_targets rows over num_sources sources; width: the table form's k (None: an edge list of num_edges
+    entries, when that is known).  w: None, or one scalar per position."""
+    if x.dim() != 2:
+        raise ValueError(f"weighted_sum: x must be [Ns, F], got {tuple(x.shape)}")
+    F = x.shape[1]
+    if not 1 <= F <= WEIGHTED_SUM_MAX_F:
+        raise ValueError(f"weighted_sum: F={F} features, supported 1..{WEIGHTED_SUM_MAX_F}")
+    if width is not None and not 1 <= width <= WEIGHTED_SUM_MAX_K:
+        raise ValueError(f"weighted_sum: k={width}, supported 1..{WEIGHTED_SUM_MAX_K}")
+    if x.shape[0] != num_sources:
+        raise ValueError(f"weighted_sum: the graph indexes {num_sources} sources, x has {x.shape[0]} rows")
+    if num_targets < 0:
+        raise ValueError(f"weighted_sum: {num_targets} target rows")
+    if w is not None:
+        M = num_targets * width if width is not None else num_edges
+        if M is not None and w.numel() != M:
+            raise ValueError(f"weighted_sum: edge_weight must hold one scalar per position ({M}), got {tuple(w.shape)}")
+
+
+def _weighted_sum_fwd(x: torch.Tensor, w: Optional[torch.Tensor], idx: torch.Tensor, rowptr: Optional[torch.Tensor],
+                      num_targets: int):
+    """(out[Nt, F], count[Nt] int32): out_i = sum_e w_e x[src(e)] over a table (idx = nbr[Nt, k], rowptr None) or a
+    grouped edge list (idx = src[E], rowptr[Nt+1]); w [positions] or None (weight 1).  See include/dmet.h,
+    dmet_weighted_sum_fwd_f32.  Not public, like _multi_aggr_fwd: propagate.py is the caller."""
+    Nt = int(num_targets)
+    table = rowptr is None and idx.dim() == 2
+    weighted_sum_check_shapes(x, w, Nt, x.shape[0], idx.shape[1] if table else None, None if table else idx.numel())
+    dev = _require_device(x, w, idx, rowptr)
+    L = _lib.load()
+    x = _f32c(x, "x")
+    w = None if w is None else _f32c(w, "edge_weight").reshape(-1)
+    idx, rowptr, E, width, _M = _row_graph("weighted_sum", idx, rowptr, Nt)
+    Ns, F = x.shape
+    out = torch.empty((Nt, F), dtype=torch.float32, device=dev)
+    count = torch.empty((Nt,), dtype=torch.int32, device=dev)
+    _t = timer.record('weighted_sum_fwd', dev)
+    with _on(dev):
+        _lib.check(L.dmet_weighted_sum_fwd_f32(_ptr(x), _ptr(w), _ptr(idx), None if rowptr is None else rowptr.data_ptr(),
+                                               Nt, Ns, E, width, F, _ptr(out), _ptr(count), _stream(dev)),
+                   "dmet_weighted_sum_fwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, count
+
+
+def _weighted_sum_bwd(g_out: torch.Tensor, x: torch.Tensor, w: Optional[torch.Tensor], idx: torch.Tensor,
+                      rowptr: Optional[torch.Tensor], tgt: Optional[torch.Tensor], rev_ptr: Optional[torch.Tensor],
+                      rev_pos: Optional[torch.Tensor], need_x: bool = True, need_w: bool = True):
+    """(g_x[Ns, F] or None, g_w[positions] or None) of _weighted_sum_fwd; (rev_ptr, rev_pos) = the graph's by-source index
+    (read only for g_x), tgt[E] names the row of every position of a list.  A pass nobody needs is not launched.  See
+    include/dmet.h, dmet_weighted_sum_bwd_f32."""
+    if not need_x and not need_w:
+        return None, None
+    Nt = int(g_out.shape[0])
+    table = rowptr is None and idx.dim() == 2
+    weighted_sum_check_shapes(x, w, Nt, x.shape[0], idx.shape[1] if table else None, None if table else idx.numel())
+    Ns, F = x.shape
+    if tuple(g_out.shape) != (Nt, F):
+        raise ValueError(f"weighted_sum_bwd: g_out must be [{Nt}, {F}], got {tuple(g_out.shape)}")
+    dev = _require_device(g_out, x, w, idx, rowptr, tgt, rev_ptr, rev_pos)
+    L = _lib.load()
+    x = _f32c(x, "x"); g_out = _f32c(g_out, "g_out")
+    w = None if w is None else _f32c(w, "edge_weight").reshape(-1)
+    idx, rowptr, E, width, M = _row_graph("weighted_sum", idx, rowptr, Nt)
+    if rowptr is not None:
+        if tgt is None or tgt.numel() != E:
+            raise ValueError(f"weighted_sum_bwd: an edge list needs tgt [{E}]")
+        tgt = _i32c(tgt, "tgt")
+    else:
+        tgt = None
+    if need_x:
+        if rev_ptr is None or rev_pos is None:
+            raise ValueError("weighted_sum_bwd: g_x needs the by-source index")
+        rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_pos = _i32c(rev_pos, "rev_pos")
+        if rev_ptr.numel() != Ns + 1 or rev_pos.numel() < M:
+            raise ValueError(f"weighted_sum_bwd: the by-source index does not fit {M} positions over {Ns} sources")
+    else:
+        rev_ptr = rev_pos = None
+    g_x = torch.empty((Ns, F), dtype=torch.float32, device=dev) if need_x else None
+    g_w = torch.empty((M,), dtype=torch.float32, device=dev) if need_w else None
+    if (need_x and Ns > 0) or (need_w and M > 0):       # else both results are empty and a NULL pair is an argument error
+        _t = timer.record('weighted_sum_bwd', dev)
+        with _on(dev):
+            _lib.check(L.dmet_weighted_sum_bwd_f32(_ptr(x), _ptr(w), _ptr(g_out), _ptr(idx),
+                                                   None if rowptr is None else rowptr.data_ptr(), _ptr(tgt), _ptr(rev_ptr),
+                                                   _ptr(rev_pos), Nt, Ns, E, width, F, _ptr(g_x), _ptr(g_w), _stream(dev)),
+                       "dmet_weighted_sum_bwd_f32")
+        if _t is not None:
+            _t.record(torch.cuda.current_stream(dev))
+    return g_x, g_w
+
+
 ATTENTION_MAX_C = 64     # channels per head (include/dmet.h, "Attention aggregation")
 ATTENTION_MAX_H = 16     # heads
 ATTENTION_MAX_HC = 256   # heads * channels

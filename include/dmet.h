@@ -718,6 +718,41 @@ int dmet_multi_aggr_bwd_f32(const float *x, const float *g_out, const int32_t *c
                             const int32_t *argmin, const int32_t *argmax, const int32_t *tgt, const int32_t *rev_ptr,
                             const int32_t *rev_pos, int64_t Nt, int64_t Ns, int64_t E, int width, int F, int G, int aggrs,
                             float *c0, float *c1, float *g_x, dmet_stream_t stream);
+/* ---- Weighted aggregation: out_i = sum_e w_e x[src(e)] with a gradient into the edge weights ---------------------------
+ * replaces torch_geometric's propagate(edge_index, x=x, edge_weight=edge_weight) under aggr='add' -- message
+ * (return x_j if edge_weight is None else edge_weight.view(-1, 1) * x_j) and the scatter sum, in GCNConv, GraphConv,
+ * SAGEConv and GINConv -- and torch_sparse.spmm(index, value, m, n, matrix) (out = matrix[col] * value.unsqueeze(-1);
+ * scatter_add(out, row, dim=0, dim_size=m)), with their autograd graph: the index_select, the [E, F] product, an
+ * index_add_ with float atomics and a host read of E (csrc/weighted_sum.hip).
+ * The graph is the multi-aggregation section's: width >= 1 is a table idx = nbr[Nt, width] (1 <= width <= DMET_MAX_K,
+ *   position p = i*width + t belongs to target i, E and rowptr are ignored); width == 0 is an edge list grouped by
+ *   target, idx = src[E], rowptr[Nt+1] (clamped to [0, E]), any in-degree; the backward also takes tgt[E].  -1 and an id
+ *   outside [0, Ns) are no entry; a duplicate id counts once per slot.
+ * x[Ns, F] fp32, 1 <= F <= 256.  w[Nt*width] or w[E] fp32, one scalar per position, or NULL: weight 1.  The value of w in
+ *   an empty slot is never read into a result: a NaN there changes nothing.
+ * dmet_weighted_sum_fwd_f32, for target i with valid entries e_1..e_n in ascending position order, per feature f:
+ *   out[i,f] = fmaf(w_e, x[j_e,f], acc) from acc = 0; with w == NULL the step is acc + x[j_e,f], the bits of w all ones.
+ *   count[Nt] int32 = n (may be NULL).  n == 0: out[i,:] = 0 exactly (R3), count 0.
+ * dmet_weighted_sum_bwd_f32 runs up to two launches:
+ *   by source, when g_x != NULL: for source j over the positions p of the by-source index rev_ptr[Ns+1], rev_pos[]
+ *     (dmet_reverse_index over idx) in ascending order, i = p / width or tgt[p]:
+ *     g_x[j,f] = fmaf(w_p, g_out[i,f], acc).  A source nobody lists gets 0.  A long list is walked by its one owner.
+ *   by target, when g_w != NULL: for every position p of row i with j = src(p):  g_w[p] = sum_f g_out[i,f] x[j,f] -- a
+ *     lane adds the products of its four consecutive features in ascending order from 0, then an xor butterfly runs over
+ *     the row's 16, 32 or 64 lanes (F <= 64, <= 128, <= 256): one product rounding, at most 4 + 6 additions.  Every
+ *     position is written; an empty slot gets 0.
+ *   g_x and g_w are each optional (rev_ptr / rev_pos are read only for g_x, x only for g_w); both NULL is -EINVAL.
+ * No float atomics: sums run in a fixed order, two runs give identical bits.  Every element of out, count, g_x and g_w is
+ * written, not accumulated.  Rows are read and written 16 bytes at a time where F % 4 == 0 and every row tensor starts
+ * on a 16-byte boundary, element by element otherwise, with the same bits.
+ * Both return -EINVAL on bad arguments (NULL pointers, negative sizes, F or width out of range, a list without rowptr or,
+ * in the backward, without tgt) before any device work.  Nt == 0: the forward returns 0 at once; the backward zero-fills
+ * g_x (Ns > 0) and returns. */
+int dmet_weighted_sum_fwd_f32(const float *x, const float *w, const int32_t *idx, const int32_t *rowptr, int64_t Nt,
+                              int64_t Ns, int64_t E, int width, int F, float *out, int32_t *count, dmet_stream_t stream);
+int dmet_weighted_sum_bwd_f32(const float *x, const float *w, const float *g_out, const int32_t *idx, const int32_t *rowptr,
+                              const int32_t *tgt, const int32_t *rev_ptr, const int32_t *rev_pos, int64_t Nt, int64_t Ns,
+                              int64_t E, int width, int F, float *g_x, float *g_w, dmet_stream_t stream);
 /* ---- PointNet convolution: fused set abstraction -------------------------------------------------------------------
  * replaces torch_geometric.nn.PointNetConv.forward for local_nn = Sequential(Linear(F + D, H1), act, Linear(H1, H2)
  * [, act]) and aggr = 'max': remove_self_loops + add_self_loops on the edge index, message
