@@ -23,6 +23,8 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import GCNConv, GraphConv, SAGEConv, GINConv   # torch_geometric.nn (weighted_aggregate: propagate)
     from deepmetv2_amd import gcn_norm                       # torch_geometric.nn.conv.gcn_conv
     from deepmetv2_amd import spmm                           # torch_sparse
+    from deepmetv2_amd import GraphNorm, InstanceNorm, LayerNorm, PairNorm, GraphSizeNorm, MeanSubtractionNorm   # torch_geometric.nn
+                                                             # (event_moments / event_normalize: their statistics and pass)
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -50,6 +52,8 @@ from .gat import GATConv, GATv2Conv, gat_aggregate, gat_v1_aggregate
 from .pna import DegreeScalerAggregation, PNAConv, multi_aggregate
 from .propagate import spmm, weighted_aggregate
 from .gcn import GCNConv, GINConv, GraphConv, SAGEConv, gcn_norm
+from .event_norm import (GraphNorm, GraphSizeNorm, InstanceNorm, LayerNorm, MeanSubtractionNorm, PairNorm, event_moments,
+                         event_normalize)
 
 __all__ = [
     "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "knn_xy_table", "radius", "radius_graph", "radius_table",
@@ -65,5 +69,7 @@ __all__ = [
     "segment_csr", "softmax", "AttentionalAggregation",
     "PNAConv", "DegreeScalerAggregation", "multi_aggregate", "scatter_std",
     "GCNConv", "GraphConv", "SAGEConv", "GINConv", "gcn_norm", "weighted_aggregate", "spmm",
+    "GraphNorm", "InstanceNorm", "LayerNorm", "PairNorm", "GraphSizeNorm", "MeanSubtractionNorm", "event_moments",
+    "event_normalize",
 ]
 __version__ = "0.1.0"

@@ -133,6 +133,9 @@ SIGNATURES = {
     "dmet_segment_softmax_bwd_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp]),
     "dmet_segment_logsumexp_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp, _vp]),
     "dmet_segment_logsumexp_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp]),
+    "dmet_event_moments_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp]),
+    "dmet_event_dots_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dmet_event_affine_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dmet_met_reduce_f32": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp]),
     "dmet_met_reduce_bwd_f32": (_i, [_vp, _vp, _i64, _vp, _i, _i64, _vp, _vp]),
     "dmet_met_loss_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

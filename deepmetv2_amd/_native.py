@@ -2036,6 +2036,77 @@ def _segment_logsumexp_bwd(src: torch.Tensor, out: torch.Tensor, g_out: torch.Te
     return g_src
 
 
+# ---- csrc/event_norm.hip: per-event column statistics and the elementwise pass of the normalisation layers -----------------
+def _event_args(x: torch.Tensor, rowptr: torch.Tensor, name: str, *coef: Optional[torch.Tensor]):
+    """(device, x, B) for fp32 rows x[N, F] grouped by rowptr[B+1]; every given `coef` must be a contiguous fp32 [B, F]."""
+    dev, x, B = _segment_args(x, rowptr, name)
+    for t in coef:
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (B, x.shape[1]) or not t.is_contiguous()
+                              or t.device != dev):
+            raise ValueError(f"per-event operands must be contiguous float32 [{B}, {x.shape[1]}] on {dev}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    return dev, x, B
+
+
+def _event_moments(x: torch.Tensor, rowptr: torch.Tensor, max_len: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mean[B, F], var[B, F]) of the rows of every event; see include/dmet.h, dmet_event_moments_f32."""
+    dev, x, B = _event_args(x, rowptr, "x")
+    N, F = x.shape
+    mean = torch.empty((B, F), dtype=torch.float32, device=dev)
+    var = torch.empty((B, F), dtype=torch.float32, device=dev)
+    _t = timer.record('event_moments', dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_event_moments_f32(_ptr(x), rowptr.data_ptr(), B, N, F, int(max_len), _ptr(mean), _ptr(var),
+                                                      _stream(dev)), "dmet_event_moments_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return mean, var
+
+
+def _event_dots(g: torch.Tensor, x: Optional[torch.Tensor], rowptr: torch.Tensor, shift: Optional[torch.Tensor] = None,
+                scale: Optional[torch.Tensor] = None, max_len: int = 0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(s1[B, F], s2[B, F]): the sums of g and of g * ((x - shift) * scale) over every event; x None: (s1, None)."""
+    dev, g, B = _event_args(g, rowptr, "g", shift, scale)
+    N, F = g.shape
+    dots = x is not None
+    if dots:
+        x = _f32c(x, "x")
+        if x.shape != g.shape or x.device != dev or shift is None or scale is None:
+            raise ValueError(f"x must be {tuple(g.shape)} on {dev} and come with shift and scale")
+    s1 = torch.empty((B, F), dtype=torch.float32, device=dev)
+    s2 = torch.empty((B, F), dtype=torch.float32, device=dev) if dots else None
+    _t = timer.record('event_dots', dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_event_dots_f32(_ptr(g), _ptr(x) if dots else None, rowptr.data_ptr(), B, N, F, int(max_len),
+                                                   shift.data_ptr() if dots else None, scale.data_ptr() if dots else None,
+                                                   _ptr(s1), s2.data_ptr() if dots else None, _stream(dev)),
+                   "dmet_event_dots_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return s1, s2
+
+
+def _event_affine(x: torch.Tensor, rowptr: torch.Tensor, shift: torch.Tensor, k1: torch.Tensor, k0: torch.Tensor,
+                  g: Optional[torch.Tensor] = None, ka: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[N, F] = (x - shift[b]) * k1[b] + k0[b], with g and ka: g * ka[b] + that; rows no event owns are 0."""
+    dev, x, B = _event_args(x, rowptr, "x", shift, k1, k0, ka)
+    N, F = x.shape
+    if (g is None) != (ka is None):
+        raise ValueError("g and ka are given together or not at all")
+    if g is not None:
+        g = _f32c(g, "g")
+        if g.shape != x.shape or g.device != dev:
+            raise ValueError(f"g must be {tuple(x.shape)} on {dev}, got {tuple(g.shape)} on {g.device}")
+    out = torch.empty((N, F), dtype=torch.float32, device=dev) if B > 0 else torch.zeros((N, F), dtype=torch.float32, device=dev)
+    _t = timer.record('event_affine', dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_event_affine_f32(_ptr(x), _ptr(g), rowptr.data_ptr(), B, N, F, _ptr(shift), _ptr(k1),
+                                                     _ptr(k0), _ptr(ka), _ptr(out), _stream(dev)), "dmet_event_affine_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out
+
+
 # ---- K4 --------------------------------------------------------------------------------------------------------
 def met_reduce(w: torch.Tensor, x: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
     dev = _require_device(w, x, ptr)

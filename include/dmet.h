@@ -883,6 +883,33 @@ int dmet_segment_logsumexp_f32(const float *src, const int32_t *rowptr, int64_t 
                                float *out, dmet_stream_t stream);
 int dmet_segment_logsumexp_bwd_f32(const float *src, const float *out, const float *g_out, const int32_t *rowptr,
                                    int64_t rows, int64_t E, int H, int max_len, float *g_src, dmet_stream_t stream);
+/* ---- event normalisation: per-event column statistics and one elementwise pass (csrc/event_norm.hip) ----
+ * fp32 rows x[N,F] grouped by rowptr[B+1] int32: event b owns the rows [rowptr[b], rowptr[b+1]), each span clamped to
+ * [0, N]; n_b is its length.  Any F >= 1 and any event length.  moments and dots: a team owns an (event, block of
+ * channels) pair; it is one wavefront, and from a max_len hint (the longest event; 0 = unknown) of 1024 on a 1024-thread
+ * workgroup, for every event of the call.  Either form takes events of any length; the two agree to rounding, not in
+ * bits.  No float atomics, no scratch, every output element written once, sums in an order fixed by F and the form: same
+ * bits run to run and on unaligned pointers.
+ *   moments: mean[b,c] = (fp32 sum_n x[n,c]) / (float)n_b  (one division);
+ *            var[b,c] = (sum_n d*d) / (float)n_b with d = x[n,c] - mean[b,c], taken in a second walk over the event's rows
+ *            centred on its own rounded mean (never a difference of two means).  Empty event: mean = var = 0.
+ *   dots   : s1[b,c] = sum_n g[n,c];  s2[b,c] = sum_n g[n,c] * ((x[n,c] - shift[b,c]) * scale[b,c]), every operation
+ *            rounded once.  Empty event: 0.  x, shift, scale and s2 may be NULL together: s1 alone.
+ *   affine : out[n,c] = (x[n,c] - shift[b,c]) * k1[b,c] + k0[b,c]; with g and ka (NULL together or neither):
+ *            out[n,c] = g[n,c] * ka[b,c] + ((x[n,c] - shift[b,c]) * k1[b,c] + k0[b,c]); every operation rounded once, in
+ *            that order.  Rows before rowptr[0] and from rowptr[B] on are written as zeros.  A workgroup owns a run of
+ *            rows and finds the event of its first row by one search.
+ * B == 0 (all three) and N == 0 (affine) return without a launch; bad sizes and NULL pointers return -22 before any
+ * launch.  rowptr must be non-decreasing: a row whose end lies before its start is empty to moments and dots; affine leaves
+ * the rows in a gap between two events as the caller allocated them and writes rows two events share twice (in bounds; not
+ * defined, not reproducible).  A malformed rowptr never causes an access outside x, g or out. */
+int dmet_event_moments_f32(const float *x, const int32_t *rowptr, int64_t B, int64_t N, int F, int max_len, float *mean,
+                           float *var, dmet_stream_t stream);
+int dmet_event_dots_f32(const float *g, const float *x, const int32_t *rowptr, int64_t B, int64_t N, int F, int max_len,
+                        const float *shift, const float *scale, float *s1, float *s2, dmet_stream_t stream);
+int dmet_event_affine_f32(const float *x, const float *g, const int32_t *rowptr, int64_t B, int64_t N, int F,
+                          const float *shift, const float *k1, const float *k0, const float *ka, float *out,
+                          dmet_stream_t stream);
 /* The same two pieces for TWO node sets (EdgeConv((x_src, x_dst), edge_index)): src[e] indexes x_src[N_src,H], tgt[e]
  * indexes x_dst[N_dst,H], edges grouped by target (rowptr[N_dst+1]); both ids unchecked, so 0 <= src[e] < N_src and
  * 0 <= tgt[e] < N_dst must hold for every e (a table's -1 slots are dropped before, dmet_table_degree).  Any H > 0.
