@@ -25,6 +25,9 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import spmm                           # torch_sparse
     from deepmetv2_amd import GraphNorm, InstanceNorm, LayerNorm, PairNorm, GraphSizeNorm, MeanSubtractionNorm   # torch_geometric.nn
                                                              # (event_moments / event_normalize: their statistics and pass)
+    from deepmetv2_amd import TopKPooling, SAGPooling        # torch_geometric.nn
+    from deepmetv2_amd import topk, filter_adj               # torch_geometric.nn.pool.select / .connect (filter_table: tables)
+    from deepmetv2_amd import SortAggregation, global_sort_pool   # torch_geometric.nn.aggr / torch_geometric.nn
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -54,6 +57,7 @@ from .propagate import spmm, weighted_aggregate
 from .gcn import GCNConv, GINConv, GraphConv, SAGEConv, gcn_norm
 from .event_norm import (GraphNorm, GraphSizeNorm, InstanceNorm, LayerNorm, MeanSubtractionNorm, PairNorm, event_moments,
                          event_normalize)
+from .select import SAGPooling, SortAggregation, TopKPooling, filter_adj, filter_table, global_sort_pool, topk
 
 __all__ = [
     "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "knn_xy_table", "radius", "radius_graph", "radius_table",
@@ -71,5 +75,6 @@ __all__ = [
     "GCNConv", "GraphConv", "SAGEConv", "GINConv", "gcn_norm", "weighted_aggregate", "spmm",
     "GraphNorm", "InstanceNorm", "LayerNorm", "PairNorm", "GraphSizeNorm", "MeanSubtractionNorm", "event_moments",
     "event_normalize",
+    "TopKPooling", "SAGPooling", "SortAggregation", "global_sort_pool", "topk", "filter_adj", "filter_table",
 ]
 __version__ = "0.1.0"

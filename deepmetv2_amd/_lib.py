@@ -186,6 +186,14 @@ SIGNATURES = {
     "dmet_pool_pairs_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i64, _vp, _vp]),
     "dmet_fps_workspace_bytes": (_sz, [_i64, _i, _i]),
     "dmet_fps_f32": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "dmet_topk_workspace_bytes": (_sz, [_i64]),
+    "dmet_topk_f32": (_i, [_vp, _vp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dmet_select_rows_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp, _vp]),
+    "dmet_select_rows_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
+    "dmet_filter_table": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
+    "dmet_filter_edges_workspace_bytes": (_sz, [_i64]),
+    "dmet_filter_edges_count": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "dmet_filter_edges_write": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _sz, _i64, _vp, _vp, _vp]),
 }
 
 

@@ -2798,3 +2798,151 @@ def fps(x: torch.Tensor, ptr: torch.Tensor, out_ptr: torch.Tensor, start: Option
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
     return out
+
+
+# ---- selection pooling (csrc/select.hip) --------------------------------------------------------------------------------
+SELECT_LDS_NODES = 16384    # DMET_SELECT_LDS_NODES: the largest event whose keys are sorted in LDS
+SELECT_MAX_K = 1024         # DMET_SELECT_MAX_K
+
+
+def _sel_vec(t: torch.Tensor, name: str, dtype: torch.dtype, n: Optional[int] = None) -> torch.Tensor:
+    if t.dtype != dtype or t.dim() != 1 or (n is not None and t.numel() != n):
+        raise TypeError(f"{name} must be a 1-D {dtype} tensor" + (f" of {n} entries" if n is not None else "") +
+                        f", got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _topk(score: torch.Tensor, ptr: torch.Tensor, out_ptr: torch.Tensor, M: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(perm[M] int64, node_map[N] int32) of dmet_topk_f32: event b's best min(r_b, n_b) nodes by descending canonical
+    score (ties to the lower index) in its slots out_ptr[b] .. out_ptr[b+1], -1 in the slots left; node_map[i] = the
+    position of node i in perm or -1.  M: the size of perm as the caller knows it."""
+    dev = _require_device(score, ptr, out_ptr)
+    L = _lib.load()
+    score = _f32c(score.detach(), "score")
+    if score.dim() != 1:
+        raise ValueError(f"score must be [N], got {tuple(score.shape)}")
+    ptr = _sel_vec(ptr, "ptr", torch.int64)
+    out_ptr = _sel_vec(out_ptr, "out_ptr", torch.int64, ptr.numel())
+    if ptr.numel() < 1:
+        raise TypeError("topk: ptr and out_ptr must hold B + 1 entries")
+    N, B = score.numel(), ptr.numel() - 1
+    perm = torch.empty((int(M),), dtype=torch.int64, device=dev)
+    node_map = torch.empty((N,), dtype=torch.int32, device=dev) if B > 0 else torch.full((N,), -1, dtype=torch.int32, device=dev)
+    if B == 0 and M:
+        perm.fill_(-1)
+    _t = timer.record('topk', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_topk_workspace_bytes(N), dev)
+        _lib.check(L.dmet_topk_f32(_ptr(score), ptr.data_ptr(), B, N, out_ptr.data_ptr(), int(M), _ptr(perm), _ptr(node_map),
+                                   ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_topk_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return perm, node_map
+
+
+def _select_rows(x: torch.Tensor, s: Optional[torch.Tensor], perm: torch.Tensor) -> torch.Tensor:
+    """out[M, F] = x[perm] * s[perm][:, None] (s None: x[perm]); rows with perm < 0 are zeros (dmet_select_rows_f32)."""
+    dev = _require_device(x, s, perm)
+    x = _f32c(x.detach(), "x")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError(f"x must be [N, F] with F >= 1, got {tuple(x.shape)}")
+    N, F = x.shape
+    s = _sel_vec(_f32c(s.detach(), "s"), "s", torch.float32, N) if s is not None else None
+    perm = _sel_vec(perm, "perm", torch.int64)
+    M = perm.numel()
+    out = torch.empty((M, F), dtype=torch.float32, device=dev)
+    _t = timer.record('select_rows', dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_select_rows_f32(_ptr(x), s.data_ptr() if s is not None and N else None, _ptr(perm), N, M, F,
+                                                    _ptr(out), _stream(dev)), "dmet_select_rows_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out
+
+
+def _select_rows_bwd(g: torch.Tensor, x: Optional[torch.Tensor], s: Optional[torch.Tensor], node_map: torch.Tensor,
+                    need_gx: bool = True, need_gs: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(gx[N, F] or None, gs[N] or None) of dmet_select_rows_bwd_f32 for g[M, F]; x is needed for gs only."""
+    dev = _require_device(g, x, s, node_map)
+    g = _f32c(g.detach(), "g")
+    if g.dim() != 2 or g.shape[1] < 1:
+        raise ValueError(f"g must be [M, F] with F >= 1, got {tuple(g.shape)}")
+    M, F = g.shape
+    node_map = _sel_vec(node_map, "node_map", torch.int32)
+    N = node_map.numel()
+    if need_gs:
+        if x is None:
+            raise ValueError("select_rows_bwd: gs needs x")
+        x = _f32c(x.detach(), "x")
+        if tuple(x.shape) != (N, F):
+            raise ValueError(f"x must be [{N}, {F}], got {tuple(x.shape)}")
+    s = _sel_vec(_f32c(s.detach(), "s"), "s", torch.float32, N) if s is not None else None
+    gx = torch.empty((N, F), dtype=torch.float32, device=dev) if need_gx else None
+    gs = torch.empty((N,), dtype=torch.float32, device=dev) if need_gs else None
+    _t = timer.record('select_rows_bwd', dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_select_rows_bwd_f32(_ptr(g), _ptr(x) if need_gs else None,
+                                                        s.data_ptr() if s is not None and N else None, _ptr(node_map), N, M, F,
+                                                        _ptr(gx), _ptr(gs), _stream(dev)), "dmet_select_rows_bwd_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return gx, gs
+
+
+def _filter_table(nbr: torch.Tensor, cnt: Optional[torch.Tensor], perm: torch.Tensor,
+                 node_map: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(out_nbr[M, k] int32, out_cnt[M] int32) of dmet_filter_table: row perm[r] of nbr, its picked entries relabelled
+    through node_map and packed to the left, -1 behind them."""
+    dev = _require_device(nbr, cnt, perm, node_map)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2 or not 1 <= nbr.shape[1] <= SELECT_MAX_K:
+        raise ValueError(f"nbr must be int32 [N, k] with 1 <= k <= {SELECT_MAX_K}, got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    N, k = nbr.shape
+    cnt = _sel_vec(cnt, "cnt", torch.int32, N) if cnt is not None else None
+    perm = _sel_vec(perm, "perm", torch.int64)
+    node_map = _sel_vec(node_map, "node_map", torch.int32, N)
+    M = perm.numel()
+    out_nbr = torch.empty((M, k), dtype=torch.int32, device=dev)
+    out_cnt = torch.empty((M,), dtype=torch.int32, device=dev)
+    _t = timer.record('filter_table', dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_filter_table(_ptr(nbr), _ptr(cnt), _ptr(perm), _ptr(node_map), N, M, k, _ptr(out_nbr),
+                                                 _ptr(out_cnt), _stream(dev)), "dmet_filter_table")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out_nbr, out_cnt
+
+
+def _filter_edges(edge_index: torch.Tensor, node_map: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(edge_index'[2, E'] int64, kept[E'] int64, nbad int32 [1]) of dmet_filter_edges_count / _write: the edges whose ends
+    are both picked, relabelled through node_map, in the caller's order; kept = their positions in edge_index; nbad = the
+    number of edges with an end outside [0, N) (dropped; left on the device for a deferred check).  One host read: E'."""
+    dev = _require_device(edge_index, node_map)
+    L = _lib.load()
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError(f"edge_index must be [2, E], got {tuple(edge_index.shape)}")
+    if edge_index.dtype != torch.int64:
+        raise TypeError(f"edge_index must be int64 (torch.long), got {edge_index.dtype}")
+    node_map = _sel_vec(node_map, "node_map", torch.int32)
+    edge_index = edge_index.contiguous()
+    E, N = edge_index.shape[1], node_map.numel()
+    if E == 0:
+        return (torch.zeros((2, 0), dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.int64, device=dev),
+                torch.zeros((1,), dtype=torch.int32, device=dev))
+    row, col = edge_index[0], edge_index[1]
+    total = torch.empty((1,), dtype=torch.int64, device=dev)
+    nbad = torch.empty((1,), dtype=torch.int32, device=dev)
+    _t = timer.record('filter_edges', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_filter_edges_workspace_bytes(E), dev)
+        _lib.check(L.dmet_filter_edges_count(row.data_ptr(), col.data_ptr(), E, _ptr(node_map), N, total.data_ptr(),
+                                             nbad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+                   "dmet_filter_edges_count")
+        Eout = int(total.item())
+        out = torch.empty((2, Eout), dtype=torch.int64, device=dev)
+        kept = torch.empty((Eout,), dtype=torch.int64, device=dev)
+        _lib.check(L.dmet_filter_edges_write(row.data_ptr(), col.data_ptr(), E, _ptr(node_map), N, ws.data_ptr(), ws.numel(),
+                                             Eout, _ptr(out), _ptr(kept), _stream(dev)), "dmet_filter_edges_write")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return out, kept, nbad

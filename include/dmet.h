@@ -1205,6 +1205,71 @@ size_t dmet_fps_workspace_bytes(int64_t N, int B, int D);
 int dmet_fps_f32(const float *x, const int64_t *ptr, int B, int64_t N, int D, const int64_t *out_ptr,
                  const int64_t *start, int64_t M, int64_t *out, void *ws, size_t ws_bytes, dmet_stream_t stream);
 
+/* ---- Selection pooling: torch_geometric's topk / filter_adj under TopKPooling, SAGPooling, SortAggregation
+ *      (csrc/select.hip) ----------------------------------------------------------------------------------------------------
+ * dmet_topk_f32: the ranked selection of every event, one workgroup per event, all events in one launch.
+ *   Arguments: score[N] fp32; event b owns the nodes lo = ptr[b] .. ptr[b+1]-1 (n_b of them; ptr must be non-decreasing,
+ *   the caller's precondition as for every ptr of this header; its values are clamped to [0, N]) and
+ *   the slots out_ptr[b] .. out_ptr[b+1]-1 of perm (r_b of them, the caller's choice).  M = the size of perm: nothing is
+ *   written at or beyond perm[M] (a slot range is cut there).
+ *   Order within an event: descending canonical score, ties to the lower index.  Canonical score: -0.0 counts as +0.0,
+ *   every NaN (either sign, any payload) ranks above +inf -- where torch.sort(descending=True) puts it --, +-inf order
+ *   normally.  Realised as one unsigned 64-bit key per node: high word = the order-preserving map of the canonical fp32
+ *   bits (NaN -> 0xFFFFFFFF first; then sign set: ~bits, else bits | 0x80000000), low word = ~local index.  The keys of an
+ *   event are distinct and key 0, the padding to a power of two, lies below all of them, so the descending bitonic
+ *   network that sorts them has one answer.
+ *   Event b writes m_b = min(r_b, n_b) GLOBAL node ids, best first, to perm[out_ptr[b] ..), then -1 to the remaining
+ *   r_b - m_b slots.  node_map[i] (int32) = the position of node i in perm, -1 if it was not picked; it is written for
+ *   all N nodes, those of events that pick nothing and those before ptr[0] or from ptr[B] on included.
+ *   An event of up to DMET_SELECT_LDS_NODES nodes keeps its keys in LDS (128 KiB); a larger one keeps the same array in the
+ *   workspace, 2 N keys, at ws[2 lo ..) (the power of two above n_b is below 2 n_b), and runs the same code (same bits).
+ *   Limits: any n_b, 0 included; N, M <= 2^31-1.
+ *
+ * dmet_select_rows_f32: out[r, f] = x[perm[r], f] * s[perm[r]] for x[N,F], perm[M]; s == NULL: the plain gather; a row with
+ *   perm[r] outside [0, N) is zeros.  dmet_select_rows_bwd_f32, for g[M,F], by node through node_map, no memset and no
+ *   scatter: r = node_map[i] outside [0, M): gx[i,:] = 0, gs[i] = 0; else gx[i,f] = g[r,f] * s[i] (g[r,f] for s == NULL)
+ *   and gs[i] = sum_f g[r,f] * x[i,f], lane l of the node's wavefront adding f = l, l + 64, ... in that order, then the xor
+ *   butterfly over the 64 lanes.  gx or gs may be NULL: only the gradients somebody needs are formed (x may be NULL
+ *   without gs).  Any F >= 1.  No transcendental: the activation of the score is the caller's.
+ *
+ * dmet_filter_table: the induced subgraph of a neighbour table.  nbr[N,k] int32, cnt[N] or NULL (only the first cnt[i] slots
+ *   of row i are read), perm[M], node_map[N] -> out_nbr[M,k], out_cnt[M].  Row r = row perm[r] of nbr: its entries j with
+ *   0 <= j < N and node_map[j] >= 0, in slot order, relabelled to node_map[j] and packed to the left; every remaining slot
+ *   -1; out_cnt[r] = the number kept.  perm[r] outside [0, N): all -1, count 0.  1 <= k <= DMET_SELECT_MAX_K.
+ *
+ * dmet_filter_edges_count / dmet_filter_edges_write: the induced subgraph of an int64 edge index (row[E], col[E]), as a
+ *   stable compaction in two calls with one workspace.  An edge is kept when both ends lie in [0, N) -- compared before
+ *   node_map is read -- and both are picked.  _count leaves per-block counts (blocks of DMET_SELECT_EDGE_BLOCK edges) and
+ *   their exclusive scan in ws, total[0] (int64) = E' and nbad[0] (int32) = the number of edges with an out-of-range end
+ *   (those are dropped).  The caller reads E' (the one host read: upstream returns exact-size tensors too), sizes
+ *   out_index[2,E'] and kept[E'], and calls _write with the same operands and workspace: kept edge number q in the
+ *   caller's order gets out_index[0,q] = node_map[row[e]], out_index[1,q] = node_map[col[e]], kept[q] = e.  Nothing is
+ *   written at or beyond column Eout.
+ *
+ *   All entries: -EINVAL with a dmet_last_error() message naming the argument, before any HIP call, for a bad size, a
+ *   small workspace or a NULL operand of a non-empty problem; 0 at once for an empty problem (dmet_topk_f32: B == 0, or
+ *   N == 0 and M == 0; the others: no output element).  Asynchronous on `stream`, no allocation, no float atomics, no
+ *   global state; bit-identical from run to run. */
+#define DMET_SELECT_THREADS 1024        /* workgroup of an event */
+#define DMET_SELECT_LDS_NODES 16384     /* events up to this size sort their 64-bit keys in LDS (128 KiB) */
+#define DMET_SELECT_MAX_K 1024          /* widest table dmet_filter_table takes */
+#define DMET_SELECT_EDGE_BLOCK 1024     /* edges per block of the compaction */
+size_t dmet_topk_workspace_bytes(int64_t N);
+int dmet_topk_f32(const float *score, const int64_t *ptr, int B, int64_t N, const int64_t *out_ptr, int64_t M,
+                  int64_t *perm, int32_t *node_map, void *ws, size_t ws_bytes, dmet_stream_t stream);
+int dmet_select_rows_f32(const float *x, const float *s, const int64_t *perm, int64_t N, int64_t M, int F, float *out,
+                         dmet_stream_t stream);
+int dmet_select_rows_bwd_f32(const float *g, const float *x, const float *s, const int32_t *node_map, int64_t N, int64_t M,
+                             int F, float *gx, float *gs, dmet_stream_t stream);
+int dmet_filter_table(const int32_t *nbr, const int32_t *cnt, const int64_t *perm, const int32_t *node_map, int64_t N,
+                      int64_t M, int k, int32_t *out_nbr, int32_t *out_cnt, dmet_stream_t stream);
+size_t dmet_filter_edges_workspace_bytes(int64_t E);
+int dmet_filter_edges_count(const int64_t *row, const int64_t *col, int64_t E, const int32_t *node_map, int64_t N,
+                            int64_t *total, int32_t *nbad, void *ws, size_t ws_bytes, dmet_stream_t stream);
+int dmet_filter_edges_write(const int64_t *row, const int64_t *col, int64_t E, const int32_t *node_map, int64_t N,
+                            const void *ws, size_t ws_bytes, int64_t Eout, int64_t *out_index, int64_t *kept,
+                            dmet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
