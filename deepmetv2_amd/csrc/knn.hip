@@ -37,6 +37,7 @@
 #include "common.h"
 #include "knn_common.h"
 #include "knn_key64.h"
+#include "knn_tile_schedule.h"
 #include "nls_body.h"
 
 namespace dmet {

@@ -1106,17 +1106,17 @@ __device__ __forceinline__ int f2_mask_row(int p) { return (p & 3) + 8 * ((p & 1
 
 // One tile of a sweep, software-pipelined inside the wavefront: the 12 MFMAs of tile t + 1 (operands `use`) are
 // issued between the vector instructions that select from tile t's keys (c0, c1, computed one call earlier), and the
-// operands of tile t + 2 are loaded into `ld`.  On gfx950 independent VALU work of the same wavefront hides under an
-// MFMA (tools/mfma_overlap_micro.hip: 12 v_add per 32x32x16 MFMA interleaved cost 62 cycles per slot against 85 when
-// the two run in phases), but only if it is in program order between the MFMAs: the scheduler is told to emit
-// 1 MFMA + 11 VALU groups.  UPD: the tile minima feed tk / tau;  REC: hit masks are recorded.
+// operands of tile `t_load` -- two or four tiles ahead: f2_sweep, f2_sweep4 -- are loaded into `ld`.  On gfx950
+// independent VALU work of the same wavefront hides under an MFMA (tools/mfma_overlap_micro.hip: 12 v_add per
+// 32x32x16 MFMA interleaved cost 62 cycles per slot against 85 when the two run in phases), but only if it is in
+// program order between the MFMAs: the scheduler is told to emit 1 MFMA + 11 VALU groups.  UPD: the tile minima feed tk / tau;  REC: hit masks are recorded.
 // INS: this call inserts min(carry, its tile minimum) into the threshold list (every second tile: the list then holds the
 // M smallest minima of tile PAIRS -- still M groups that each contain a key <= tau); otherwise it only updates `carry`.
 // NH = 2 (64 features): `use` and `ld` are the SAME operand set (two sets of eight fragments next to the sixteen of
 // the queries do not fit the register file at two wavefronts per SIMD), reloaded right after its MFMAs were issued.
-template <int M, bool UPD, bool REC, bool INS, int NH = 1, bool CONV = true, int LEAD = 2>
+template <int M, bool UPD, bool REC, bool INS, int NH = 1, bool CONV = true>
 __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *__restrict__ rec, int64_t rbase, int t,
-                                        int t_hi, f32x16 &c0, f32x16 &c1, f32x16 &n0, f32x16 &n1, float &rc, float &rn,
+                                        int t_load, f32x16 &c0, f32x16 &c1, f32x16 &n0, f32x16 &n1, float &rc, float &rn,
                                         const F2Ops<NH> &use, F2Ops<NH> &ld, const f16x8 (&bq)[2][2 * NH], f16x8 (&fq)[2],
                                         int lane, int hh, bool alive, float &carry, unsigned &rofs)
 {
@@ -1136,7 +1136,7 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
 #if defined(DMET_F2_SAMEREC)
     f2_load<NH>(ld, rec, rbase + (t & 1), lane, hh, rofs);   // experiment: operands always cache-resident
 #else
-    f2_load<NH>(ld, rec, rbase + min(t + LEAD, t_hi - 1), lane, hh, rofs);   // clamped: the last calls re-read the last tile
+    f2_load<NH>(ld, rec, rbase + t_load, lane, hh, rofs);   // clamped: the last calls re-read the last tile
 #endif
     // the fold against the thresholds as they are now (tile t + 1's keys: stale by one update, i.e. larger -- a
     // superset): fq holds them since the last conversion (f2_sweep, or the CONV tile below).
@@ -1239,69 +1239,91 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
 #endif
 }
 
+// A recording sweep at 32 features (main sweep, revisit, second attempt): FOUR tiles of operands in flight.  What the
+// kernel's time per item holds beyond its own vector issue is waiting for operands (a loaded L2 round trip is ~2000
+// cycles, a revisit tile ~250 cycles of work), so call t issues tile t + 1's MFMAs and loads tile t + 4, and the sweep
+// requests its first four tiles at once instead of load, wait, MFMA, load.  Four calls per trip: the operand sets rotate
+// with period 4, the key blocks (c, n) and the threshold conversions with period 2 (knn_tile_schedule.h, shared with the
+// host test).  Only WHEN operands are loaded differs from a sweep with two sets: the order of MFMAs, conversions,
+// insertions and compactions does not.  (Three sets in the main sweep and two elsewhere until r09; the deferred pass
+// keeps two: four spill there.  profiles/r09_knn_operand_pipeline.md.)
+template <int M, bool UPD>
+__device__ __forceinline__ void f2_sweep4(F2Lane<M> &L, F2Wave &S, const uint8_t *__restrict__ rec, int64_t rbase, int t_lo,
+                                          int t_hi, const f16x8 (&bq)[2][2], int lane, int hh, bool alive)
+{
+    F2Ops<1> s[kF2Sets];
+    unsigned rofs = (unsigned)lane * 16u;
+#pragma unroll
+    for (int j = 0; j < kF2Sets; ++j) f2_load<1>(s[f2_tile_set(j)], rec, rbase + f2_load_tile(t_lo, j, t_hi), lane, hh, rofs);
+    // query side of the fold for both 32-query blocks, built here once per sweep -- from the threshold the sweep starts
+    // with (the running cut before the main sweep, the cut before the revisit, t_fix in a second attempt) -- and kept in
+    // registers: the tiles read them, a CONV tile rewrites their threshold dword.  Opaque, or hipcc rebuilds them (eight
+    // moves and the swap) in every tile rather than hold eight registers
+    f16x8 fq[2] = {f2_fold(0u), f2_fold(0u)};
+    L.tq = f2_tau16(L.tau, L.rep);
+    f2_fold_tau(fq, L.tq);
+    asm volatile("" : "+v"(fq[0]), "+v"(fq[1]));
+    float rc = L.rep, rn;
+    f32x16 c0 = f2_block<1>(s[0], bq[0], fq[0]);      // prologue: the first tile's keys
+    f32x16 c1 = f2_block<1>(s[0], bq[1], fq[1]);
+    f32x16 n0, n1;
+    float carry = kKnnSentinel;
+    // call Q of a trip selects from key block Q & 1, issues the MFMAs of set Q + 1 and loads into set Q, whose MFMAs the
+    // call before it issued
+    static_assert(f2_tile_set(4) == 0 && f2_tile_key_block(2) == 0 && f2_tile_key_block(3) == 1 && !f2_call_converts(2) &&
+                      f2_call_converts(3),
+                  "the trip below is the schedule's, written out");
+    for (int t = t_lo;;) {
+        f2_tile<M, UPD, true, true, 1, false>(L, S, rec, rbase, t, f2_load_tile(t, kF2Sets, t_hi), c0, c1, n0, n1, rc, rn, s[1],
+                                              s[0], bq, fq, lane, hh, alive, carry, rofs);
+        if (++t >= t_hi) break;
+        f2_tile<M, UPD, true, true, 1, true>(L, S, rec, rbase, t, f2_load_tile(t, kF2Sets, t_hi), n0, n1, c0, c1, rn, rc, s[2],
+                                             s[1], bq, fq, lane, hh, alive, carry, rofs);
+        if (++t >= t_hi) break;
+        f2_tile<M, UPD, true, true, 1, false>(L, S, rec, rbase, t, f2_load_tile(t, kF2Sets, t_hi), c0, c1, n0, n1, rc, rn, s[3],
+                                              s[2], bq, fq, lane, hh, alive, carry, rofs);
+        if (++t >= t_hi) break;
+        f2_tile<M, UPD, true, true, 1, true>(L, S, rec, rbase, t, f2_load_tile(t, kF2Sets, t_hi), n0, n1, c0, c1, rn, rc, s[0],
+                                             s[3], bq, fq, lane, hh, alive, carry, rofs);
+        if (++t >= t_hi) break;
+    }
+}
+
 // One pass over the tiles [t_lo, t_hi) of the event whose first record is rbase.
 template <int M, bool UPD, bool REC, int NH = 1>
 __device__ __forceinline__ void f2_sweep(F2Lane<M> &L, F2Wave &S, const uint8_t *__restrict__ rec, int64_t rbase,
                                          int t_lo, int t_hi, const f16x8 (&bq)[2][2 * NH], int lane, int hh, bool alive)
 {
     if (t_lo >= t_hi) return;
+    if constexpr (NH == 1 && REC) {
+        f2_sweep4<M, UPD>(L, S, rec, rbase, t_lo, t_hi, bq, lane, hh, alive);
+        return;
+    }
+    // two operand sets (the deferred pass; 64 features: two sets of eight fragments next to the sixteen of the queries
+    // are what fits): a cold start, and call t loads tile t + 2
     F2Ops<NH> A, B;
     unsigned rofs = (unsigned)lane * 16u;
     f2_load<NH>(A, rec, rbase + t_lo, lane, hh, rofs);
-    // query side of the fold for both 32-query blocks, built here once per sweep -- from the threshold the sweep starts
-    // with (the cut before the revisit, t_fix in a second attempt), 0 where no mask is recorded -- and kept in registers:
-    // the tiles read them, a CONV tile rewrites their threshold dword.  Opaque, or hipcc rebuilds them (eight moves and
-    // the swap) in every tile rather than hold eight registers
+    // query side of the fold: threshold 0 (32 features: the deferred pass records no mask, its results are the keys
+    // themselves; 64 features do not fold)
     f16x8 fq[2] = {f2_fold(0u), f2_fold(0u)};
-    if (NH == 1 && REC) {
-        L.tq = f2_tau16(L.tau, L.rep);
-        f2_fold_tau(fq, L.tq);
-        asm volatile("" : "+v"(fq[0]), "+v"(fq[1]));
-    }
     float rc = L.rep, rn;
     f32x16 c0 = f2_block<NH>(A, bq[0], fq[0]);      // prologue: the first tile's keys
     f32x16 c1 = f2_block<NH>(A, bq[1], fq[1]);
     f32x16 n0, n1;
-    f2_load<NH>(A, rec, rbase + min(t_lo + 1, t_hi - 1), lane, hh, rofs);
+    f2_load<NH>(A, rec, rbase + f2_load_tile(t_lo, 1, t_hi), lane, hh, rofs);
     float carry = kKnnSentinel;
-    if constexpr (NH == 1 && UPD && REC) {
-        // the main sweep keeps THREE tiles of operands in flight (the fold freed the seed registers): call t issues
-        // tile t + 1's MFMAs and loads tile t + 3.  Six calls per trip: the operand sets rotate with period 3, the key
-        // blocks (c, n) and the threshold conversions with period 2
-        F2Ops<NH> C;
-        f2_load<NH>(B, rec, rbase + min(t_lo + 2, t_hi - 1), lane, hh, rofs);
-        for (int t = t_lo; t < t_hi; t += 6) {
-            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t, t_hi, c0, c1, n0, n1, rc, rn, A, C, bq, fq, lane, hh,
-                                                     alive, carry, rofs);
-            if (t + 1 >= t_hi) break;
-            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 1, t_hi, n0, n1, c0, c1, rn, rc, B, A, bq, fq, lane,
-                                                    hh, alive, carry, rofs);
-            if (t + 2 >= t_hi) break;
-            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t + 2, t_hi, c0, c1, n0, n1, rc, rn, C, B, bq, fq, lane,
-                                                     hh, alive, carry, rofs);
-            if (t + 3 >= t_hi) break;
-            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 3, t_hi, n0, n1, c0, c1, rn, rc, A, C, bq, fq, lane,
-                                                    hh, alive, carry, rofs);
-            if (t + 4 >= t_hi) break;
-            f2_tile<M, UPD, REC, true, NH, false, 3>(L, S, rec, rbase, t + 4, t_hi, c0, c1, n0, n1, rc, rn, B, A, bq, fq, lane,
-                                                     hh, alive, carry, rofs);
-            if (t + 5 >= t_hi) break;
-            f2_tile<M, UPD, REC, true, NH, true, 3>(L, S, rec, rbase, t + 5, t_hi, n0, n1, c0, c1, rn, rc, C, B, bq, fq, lane,
-                                                    hh, alive, carry, rofs);
-        }
-        return;
-    }
     for (int t = t_lo; t < t_hi; t += 2) {
         // every tile inserts its own minimum (INS = true).  Inserting the minimum of tile PAIRS instead (half the
         // v_med3 chains) was tried: the threshold then admits up to 2M tiles, more than the 26 entries a lane can keep
         // -> 3 761 overflowed queries per launch and twice the kernel time
         // the fold's threshold is converted after every second tile only (f2_tau16 is ~15 VALU ops): the masks of
         // the next two tiles are taken against a threshold older by one more update -- larger, a superset
-        f2_tile<M, UPD, REC, true, NH, false>(L, S, rec, rbase, t, t_hi, c0, c1, n0, n1, rc, rn, A, B, bq, fq, lane, hh, alive,
-                                              carry, rofs);
+        f2_tile<M, UPD, REC, true, NH, false>(L, S, rec, rbase, t, f2_load_tile(t, kF2PlainLead, t_hi), c0, c1, n0, n1, rc, rn,
+                                              A, B, bq, fq, lane, hh, alive, carry, rofs);
         if (t + 1 < t_hi)
-            f2_tile<M, UPD, REC, true, NH, true>(L, S, rec, rbase, t + 1, t_hi, n0, n1, c0, c1, rn, rc, B, A, bq, fq, lane, hh,
-                                                 alive, carry, rofs);
+            f2_tile<M, UPD, REC, true, NH, true>(L, S, rec, rbase, t + 1, f2_load_tile(t + 1, kF2PlainLead, t_hi), n0, n1, c0,
+                                                 c1, rn, rc, B, A, bq, fq, lane, hh, alive, carry, rofs);
     }
 }
 
