@@ -73,6 +73,16 @@ def _f32a(t: torch.Tensor, name: str) -> torch.Tensor:
     return _aligned16(_f32c(t, name))
 
 
+def no_double_backward(who: str) -> None:
+    """First line of a backward that runs native kernels and is on the launch thread of the training step.  Grad mode is on
+    inside a backward only under create_graph=True; the gradients returned here would carry no grad_fn and a second
+    derivative through them would silently treat them as constants.  (`once_differentiable` does the same with one more
+    Python frame and a no_grad block per call.)"""
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"{who}: double backward is not supported: the backward runs native kernels and is "
+                           f"once_differentiable (differentiating it with create_graph=True would give constants)")
+
+
 def _ptr(t: Optional[torch.Tensor]):
     """The address of an optional tensor: None (a null pointer) for None and for an empty tensor."""
     return t.data_ptr() if t is not None and t.numel() else None
@@ -490,7 +500,7 @@ def node_linear_split(x: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor
     [Hout/8][N][8], for gather_max(..., sliced=True) only (the returned tensors then have shape [Hout/8, N, 8])."""
     dev = _require_device(x, W, b)
     L = _lib.load()
-    x = _f32c(x, "x"); W = _f32c(W, "W")
+    x = _f32a(x, "x"); W = _f32c(W, "W")
     N, Hin = x.shape
     Hout = W.shape[0]
     if W.shape[1] != 2 * Hin:
@@ -666,7 +676,7 @@ def gather_max_bwd_j16(g_out: torch.Tensor, argj: torch.Tensor, ptr: torch.Tenso
     sliced: gQ comes back slice-major, [8, N, 4] (for edgeconv_linear_bwd(..., gq_sliced=True): a scatter workgroup then
     writes one contiguous run instead of 16-byte pieces of 128-byte rows)."""
     dev = _require_device(g_out, argj, ptr)
-    g_out = _f32c(g_out, "g_out")
+    g_out = _f32a(g_out, "g_out")
     N, H = g_out.shape
     if argj.dtype != torch.int16 or argj.shape != g_out.shape or not argj.is_contiguous():
         raise TypeError("gather_max_bwd_j16: argj must be the contiguous int16 [N,H] tensor of gather_max_counted_j16")
@@ -682,7 +692,7 @@ def edgeconv_fused_lds(x: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tenso
     """EdgeConv(Linear(64->32), max) in one launch (LDS-resident Q slice per event); see include/dmet.h."""
     dev = _require_device(x, W, b, nbr, ptr)
     L = _lib.load()
-    x = _f32c(x, "x"); W = _f32c(W, "W")
+    x = _f32a(x, "x"); W = _f32c(W, "W")
     N, Hin = x.shape
     Hout = W.shape[0]
     k = nbr.shape[1]
@@ -711,7 +721,7 @@ def edge_mlp2_bf16(x: torch.Tensor, nbr: torch.Tensor, W1: torch.Tensor, b1: Opt
     fused with the max / add aggregation over the fixed-width table (include/dmet.h: dmet_edge_mlp2_bf16)."""
     dev = _require_device(x, nbr, W1, W2, b1, b2)
     L = _lib.load()
-    x = _f32c(x, "x"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2")
+    x = _f32a(x, "x"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2")
     N, Hin = x.shape
     H1, H2, k = W1.shape[0], W2.shape[0], nbr.shape[1]
     if W1.shape[1] != 2 * Hin or W2.shape[1] != H1:
@@ -739,7 +749,7 @@ def edge_mlp2_bn_bf16(x: torch.Tensor, nbr: torch.Tensor, W1: torch.Tensor, b1: 
     dmet_edge_mlp2_bn_bf16); the running statistics are updated in place in training mode."""
     dev = _require_device(x, nbr, W1, W2, b1, b2, gamma, beta)
     L = _lib.load()
-    x = _f32c(x, "x"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2")
+    x = _f32a(x, "x"); W1 = _f32c(W1, "W1"); W2 = _f32c(W2, "W2")
     N, Hin = x.shape
     H1, H2, k = W1.shape[0], W2.shape[0], nbr.shape[1]
     if W1.shape[1] != 2 * Hin or W2.shape[1] != H1:
@@ -920,7 +930,7 @@ def node_linear_split_bf16(x: torch.Tensor, W: torch.Tensor, b: Optional[torch.T
     """bf16-MFMA variant: P fp32 [N,H], Q as bf16 [N,H] (gathered table)."""
     dev = _require_device(x, W, b)
     L = _lib.load()
-    x = _f32c(x, "x"); W = _f32c(W, "W")
+    x = _f32a(x, "x"); W = _f32c(W, "W")
     N, Hin = x.shape
     Hout = W.shape[0]
     P = torch.empty((N, Hout), dtype=torch.float32, device=dev)
@@ -956,7 +966,7 @@ def gather_max_bwd(g_out: torch.Tensor, arg: torch.Tensor, rev_ptr: torch.Tensor
                    k: int) -> torch.Tensor:
     dev = _require_device(g_out, arg, rev_ptr, rev_slot)
     L = _lib.load()
-    g_out = _f32c(g_out, "g_out")
+    g_out = _f32a(g_out, "g_out")
     N, H = g_out.shape
     gQ = torch.empty((N, H), dtype=torch.float32, device=dev)
     _t = timer.record('gather_max_bwd', dev)
@@ -1022,7 +1032,7 @@ def gather_sum_bwd(g_out: torch.Tensor, deg: torch.Tensor, rev_ptr: torch.Tensor
     NeighborTable.reverse(); edge lists: (rev_ptr, rev_idx) = EdgeList.by_source() and tgt = EdgeList.tgt (k ignored)."""
     dev = _require_device(g_out, deg, rev_ptr, rev_idx, tgt)
     L = _lib.load()
-    g_out = _f32c(g_out, "g_out"); deg = _i32c(deg, "deg")
+    g_out = _f32a(g_out, "g_out"); deg = _i32c(deg, "deg")
     rev_ptr = _i32c(rev_ptr, "rev_ptr"); rev_idx = _i32c(rev_idx, "rev_idx")
     N, H = g_out.shape
     gPQ = torch.empty((2, N, H), dtype=torch.float32, device=dev)
@@ -1834,7 +1844,7 @@ def reverse_index(keys: torch.Tensor, num_keys: int) -> Tuple[torch.Tensor, torc
 def edge_features(x: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
     dev = _require_device(x, src, tgt)
     L = _lib.load()
-    x = _f32c(x, "x")
+    x = _f32a(x, "x")
     E = src.numel()
     H = x.shape[1]
     feat = torch.empty((E, 2 * H), dtype=torch.float32, device=dev)
@@ -2467,7 +2477,7 @@ def edgeconv_linear_bwd(x: torch.Tensor, weight: torch.Tensor, g_out: torch.Tens
     dev = _require_device(x, weight, g_out, gQ)
     L = _lib.load()
     weight_key = weight      # the caller's tensor, before any contiguous copy: what tells a second use of the layer
-    x = _f32c(x, "x"); weight = _f32c(weight, "weight"); g_out = _f32c(g_out, "g_out"); gQ = _f32c(gQ, "gQ")
+    x = _f32a(x, "x"); weight = _f32c(weight, "weight"); g_out = _f32a(g_out, "g_out"); gQ = _f32a(gQ, "gQ")
     N, H = x.shape
     if H != 32 or tuple(weight.shape) != (32, 64) or g_out.shape != x.shape or (
             tuple(gQ.shape) != ((8, N, 4) if gq_sliced else (N, H))):
@@ -2482,7 +2492,7 @@ def edgeconv_linear_bwd(x: torch.Tensor, weight: torch.Tensor, g_out: torch.Tens
     with _on(dev):
         ws = _ws(L.dmet_edgeconv_linear_bwd_workspace_bytes(N, H), dev)
         if g_add is not None:
-            g_add = _f32c(g_add, "g_add")
+            g_add = _f32a(g_add, "g_add")
             if g_add.shape != x.shape:
                 raise ValueError("edgeconv_linear_bwd: g_add must have the shape of x")
         again = _defer_second_use(dev, weight_key)
@@ -2512,7 +2522,7 @@ def gather_max_bwd_lds(g_out: torch.Tensor, arg: torch.Tensor, nbr: torch.Tensor
     max_nodes: the batch's largest event when the caller knows it (a hint: workgroups sized for small events).
     sliced: gQ comes back slice-major, [8, N, 4] (for edgeconv_linear_bwd(..., gq_sliced=True))."""
     dev = _require_device(g_out, arg, nbr, ptr)
-    g_out = _f32c(g_out, "g_out")
+    g_out = _f32a(g_out, "g_out")
     N, H = g_out.shape
     if arg.dtype != torch.uint8 or not arg.is_contiguous() or nbr.dtype != torch.int32 or not nbr.is_contiguous():
         raise TypeError("gather_max_bwd_lds: arg must be contiguous uint8, nbr contiguous int32")

@@ -79,7 +79,8 @@ def _pq_sliced(lds: bool) -> bool:
 
 
 class _EdgeConvLinearMax(torch.autograd.Function):
-    """out[i] = max_s (W.[x_i || x_j - x_i] + b), j = nbr[i,s], through P = x.(W1-W2)^T + b, Q = x.W2^T."""
+    """out[i] = max_s (W.[x_i || x_j - x_i] + b), j = nbr[i,s], through P = x.(W1-W2)^T + b, Q = x.W2^T.  Double backward
+    raises (_native.no_double_backward: the form that costs the launch thread least)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, table: NeighborTable, bf16: bool = False, passthrough: bool = False):
@@ -160,6 +161,7 @@ class _EdgeConvLinearMax(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_pass=None):
+        _native.no_double_backward("_EdgeConvLinearMax")
         x, weight, arg = ctx.saved_tensors
         table: NeighborTable = ctx.table
         H = x.shape[1]
@@ -227,8 +229,8 @@ class _EdgeConvLinearSum(torch.autograd.Function):
     neighbour table or a by-target edge list: no [E, 2F] edge features, no per-edge messages.  The backward walks a
     by-source index (NeighborTable.reverse() / EdgeList.by_source()) and hands gP, gQ to the node-level backward of
     _EdgeConvLinearMax.  No host sync, except in the backward over a counted radius table: its reverse index sorts the
-    valid slots only and learns their number with `torch.nonzero`.  `once_differentiable`: DMET_EDGE_LINEAR_SUM=0 gives
-    the generic route, e.g. for double backward."""
+    valid slots only and learns their number with `torch.nonzero`.  `once_differentiable`: double backward raises, here and on the
+    generic route (DMET_EDGE_LINEAR_SUM=0), whose edge features and segment reductions are kernels as well."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, graph, mean: bool, passthrough: bool = False):
@@ -290,7 +292,8 @@ def _as_mlp2(nn_module):
 class _EdgeMLP2Bf16(torch.autograd.Function):
     """aggr_s nn([x_i || x_j - x_i]) for a two-layer nn on the bf16 matrix cores (csrc/edgemlp.hip).  The backward
     recomputes the message passing through the fp32 operators (edge features -> nn -> segment max / sum) and
-    differentiates that: straight-through over the bf16 roundings, no per-edge tensor kept between the passes."""
+    differentiates that: straight-through over the bf16 roundings, no per-edge tensor kept between the passes.
+    `once_differentiable`: the recomputed graph is differentiated once, inside the backward; double backward raises."""
 
     @staticmethod
     def forward(ctx, x, W1, b1, W2, b2, table, act2, add, recompute, bn=None, gamma=None, beta=None):
@@ -308,6 +311,7 @@ class _EdgeMLP2Bf16(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_out):
         x, W1, b1, W2, b2, gamma, beta = ctx.saved_tensors
         bn = ctx.bn
@@ -332,6 +336,17 @@ class _EdgeMLP2Bf16(torch.autograd.Function):
         for (i, _), g in zip(wanted, grads):
             res[i] = g
         return tuple(res)
+
+
+def _to_fixed_binade(g: torch.Tensor):
+    """(g * 2^-s, 2^s) with max|g * 2^-s| in [8, 16): an exact power-of-two scaling, formed on the device (no host read).  A
+    zero or non-finite maximum leaves g as it is (s = 0): a non-finite gradient still comes out non-finite."""
+    top = g.detach().abs().max()
+    _m, e = torch.frexp(top)                                     # top = m 2^e, m in [0.5, 1)
+    ok = torch.isfinite(top) & (top > 0)
+    s = torch.where(ok, e - 4, torch.zeros_like(e)).clamp(-120, 120)
+    one = torch.ones_like(top)
+    return g * torch.ldexp(one, -s), torch.ldexp(one, s)
 
 
 def _edge_mlp2_function(route: str, name: str, doc: str):
@@ -359,9 +374,18 @@ def _edge_mlp2_function(route: str, name: str, doc: str):
         edges: EdgeList = ctx.edges
         srcptr, srcperm = edges.by_source()
         need = ctx.needs_input_grad
-        gx, gW1, gb1, gW2, gb2, gg, gbeta = getattr(_native, f"edge_mlp_bwd_{route}")(
+        # fp16 keeps 5 exponent bits: the kernel rounds the per-edge gradient g_z2 to fp16, so the route brings g_out to a
+        # fixed binade first and undoes that on the results (both exact): the backward is linear in g_out bit for bit
+        # under a power-of-two scale, and a small gradient does not meet fp16's subnormals
+        up = None
+        if route == "f16" and g_out.numel():
+            g_out, up = _to_fixed_binade(g_out)
+        grads = getattr(_native, f"edge_mlp_bwd_{route}")(
             g_out, x, edges.rowptr, edges.src, edges.tgt, srcptr, srcperm, W1, W2, b2, ctx.act2, ctx.aggr, ctx.mode,
             (pq, agg, win, bnstat), want_x=need[0], want_w1=need[1], want_b1=ctx.has_b1 and need[2])
+        if up is not None:
+            grads = [None if t is None else t * up for t in grads]
+        gx, gW1, gb1, gW2, gb2, gg, gbeta = grads
         return (gx, gW1 if need[1] else None, gb1, gW2 if need[3] else None, gb2 if (ctx.has_b2 and need[4]) else None,
                 gg if need[5] else None, gbeta if need[6] else None, None, None, None, None)
 
@@ -375,18 +399,21 @@ _EDGE_MLP2_DOCS = {
 aggr_e nn([x_tgt || x_src - x_tgt]) for nn = Linear - ELU - Linear [- ELU] [- BatchNorm1d] in fp32 over a grouped
     edge list (csrc/edgemlp_f32.hip): the first Linear split per node, the second one per edge, fused with the
     aggregation and the BatchNorm.  Nothing per edge is kept between the passes: the backward re-computes the messages
-    from the node-level state.  The backward is `once_differentiable`: double backward raises (DMET_EDGE_MLP_F32=0 gives
-    the generic route, which supports it).""",
+    from the node-level state.  The backward is `once_differentiable`: double backward raises (as it does on
+    the generic route, DMET_EDGE_MLP_F32=0).""",
     "bf16": """\
 The layer of _EdgeMLP2F32 with its per-edge products on the bf16 matrix cores (csrc/edgemlp_bf16.hip), forward
     and backward: the route taken when bf16 is requested (autocast or compute_dtype) over a grouped edge list.  fp32 in
-    and out; h1, W2 and g_z2 are rounded to bf16 inside the kernels only.  `once_differentiable`: DMET_EDGE_MLP_BF16=0
-    gives the generic route, e.g. for double backward.""",
+    and out; h1, W2 and g_z2 are rounded to bf16 inside the kernels only.  `once_differentiable`: double backward raises
+    (DMET_EDGE_MLP_BF16=0 gives the generic route).""",
     "f16": """\
 _EdgeMLP2Bf16Edges with fp16 operands on the fp16 matrix cores (csrc/edgemlp_bf16.hip, the same kernels): the
     route taken when fp16 is requested (torch.autocast("cuda") without a dtype, or compute_dtype) over a grouped edge
-    list.  fp32 in and out; h1, W2 and g_z2 are rounded to fp16 (RNE, overflow to inf) inside the kernels only.
-    `once_differentiable`: DMET_EDGE_MLP_F16=0 gives the generic route, e.g. for double backward.""",
+    list.  fp32 in and out; h1, W2 and g_z2 are rounded to fp16 (RNE, overflow to inf) inside the kernels only.  The
+    backward hands the kernel g_out scaled by a power of two to a largest magnitude in [8, 16) and scales the results back
+    (both exact), so a power-of-two scale of g_out passes through bit for bit and a small gradient is not lost to fp16's
+    subnormals; the kernel entry itself (_native.edge_mlp_bwd_f16) keeps fp16's range.
+    `once_differentiable`: double backward raises (DMET_EDGE_MLP_F16=0 gives the generic route).""",
 }
 _EdgeMLP2F32 = _edge_mlp2_function("f32", "_EdgeMLP2F32", _EDGE_MLP2_DOCS["f32"])
 _EdgeMLP2Bf16Edges = _edge_mlp2_function("bf16", "_EdgeMLP2Bf16Edges", _EDGE_MLP2_DOCS["bf16"])
@@ -398,7 +425,7 @@ _EDGE_MLP_ROUTES = {"bf16": (_EdgeMLP2Bf16Edges, torch.bfloat16), "f16": (_EdgeM
 
 
 class _EdgeFeatures(torch.autograd.Function):
-    """feat[e] = [x[tgt] || x[src] - x[tgt]] for a by-target grouped edge list."""
+    """feat[e] = [x[tgt] || x[src] - x[tgt]] for a by-target grouped edge list.  `once_differentiable`."""
 
     @staticmethod
     def forward(ctx, x, edges: EdgeList):
@@ -407,6 +434,7 @@ class _EdgeFeatures(torch.autograd.Function):
         return _native.edge_features(x, edges.src, edges.tgt)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_feat):
         edges: EdgeList = ctx.edges
         srcptr, srcperm = edges.by_source()
@@ -415,7 +443,8 @@ class _EdgeFeatures(torch.autograd.Function):
 
 
 class _EdgeFeaturesXY(torch.autograd.Function):
-    """feat[e] = [x_dst[tgt] || x_src[src] - x_dst[tgt]] for a by-target grouped edge list over two node sets."""
+    """feat[e] = [x_dst[tgt] || x_src[src] - x_dst[tgt]] for a by-target grouped edge list over two node sets.
+    `once_differentiable`."""
 
     @staticmethod
     def forward(ctx, x_src, x_dst, edges: EdgeList):
@@ -424,6 +453,7 @@ class _EdgeFeaturesXY(torch.autograd.Function):
         return _native.edge_features_xy(x_src, x_dst, edges.src, edges.tgt)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_feat):
         edges: EdgeList = ctx.edges
         srcptr, srcperm = edges.by_source()
@@ -446,10 +476,10 @@ class EdgeConv(torch.nn.Module):
     per-node split (csrc/edgeconv.hip); with add / sum / mean aggregation the same ``Linear`` runs through the split and a
     gather-sum over any graph, forward and backward, in fp32 when no 16 bits and no autocast are requested
     (csrc/edgeconv_sum.hip; no host sync over a table, except the one of a counted radius table's reverse index in the
-    backward; ``DMET_EDGE_LINEAR_SUM=0`` restores the generic route, e.g. for double backward); ``Sequential(Linear(2F, H1), ELU, Linear(H1, H2)[, ELU][, BatchNorm1d(H2)])``
+    backward; ``DMET_EDGE_LINEAR_SUM=0`` restores the generic route); ``Sequential(Linear(2F, H1), ELU, Linear(H1, H2)[, ELU][, BatchNorm1d(H2)])``
     (ELU alpha 1, fp32, BatchNorm momentum not None) runs fused in fp32 over any graph, forward and backward, for
     H2 in {16, 32, 64, 128}, H1 <= min(192, 2 H2), F <= 128 (csrc/edgemlp_f32.hip; ``DMET_EDGE_MLP_F32=0`` restores
-    the generic route, e.g. for double backward), or on the bf16 matrix cores when bf16 is requested (autocast or
+    the generic route), or on the bf16 matrix cores when bf16 is requested (autocast or
     ``compute_dtype``): over a fixed-width kNN table that csrc/edgemlp.hip takes, and otherwise over any graph, forward
     and backward, for H2 in {32, 64, 128}, H1 a multiple of 16 <= min(192, 2 H2), F <= 128 (csrc/edgemlp_bf16.hip,
     fp32 output; ``DMET_EDGE_MLP_BF16=0`` restores the generic route).  When fp16 is requested (``torch.autocast("cuda")``

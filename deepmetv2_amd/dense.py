@@ -4,6 +4,9 @@
 index_select -- plumbing); only the backward differs: the tall-skinny weight gradients go through csrc/dense.hip
 instead of a library GEMM / a sort-based scatter.  Modules keep their torch.nn.Linear / Embedding parameters (same
 state_dict); these functions are called with those parameters.
+
+The Functions are differentiable once: each backward opens with _native.no_double_backward (they are on the launch thread
+of the training step) and raises under create_graph=True.
 """
 from __future__ import annotations
 
@@ -25,6 +28,7 @@ class _Linear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        _native.no_double_backward("_Linear")
         x, weight = ctx.saved_tensors
         g = g.contiguous()
         gx = g @ weight if ctx.needs_input_grad[0] else None
@@ -42,6 +46,7 @@ class _Embedding(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        _native.no_double_backward("_Embedding")
         (index,) = ctx.saved_tensors
         return None, _native.onehot_xty(index, g.contiguous(), ctx.rows)
 
@@ -72,6 +77,7 @@ class _Encode(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_h):
+        _native.no_double_backward("_Encode")
         x_cont, x_cat, h, *params = ctx.saved_tensors
         grads = _native.encode_bwd(x_cont, x_cat, [p.detach() for p in params], h, g_h.contiguous())
         return (None, None, *grads)
@@ -117,6 +123,7 @@ class _BatchNorm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_y):
+        _native.no_double_backward("_BatchNorm")
         x, weight, mean, invstd = ctx.saved_tensors
         g_y = g_y.contiguous()
         if ctx.training:
@@ -148,6 +155,7 @@ class _EncodeBN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_y):
+        _native.no_double_backward("_EncodeBN")
         x_cont, x_cat, h, weight, mean, invstd, *params = ctx.saved_tensors
         g_y = g_y.contiguous()
         ps = [p.detach() for p in params]
@@ -235,6 +243,7 @@ class _Head(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
+        _native.no_double_backward("_Head")
         emb, W1, b1, W2, b2, out = ctx.saved_tensors
         g_emb, gW1, gb1, gW2, gb2 = _native.head_bwd(emb, [W1.detach(), b1.detach(), W2.detach(), b2.detach()], out,
                                                      g_out.contiguous())

@@ -8,6 +8,7 @@ event_moments gives the per-event column mean and (biased) variance; event_norma
 
 so the forward reads x twice (the second walk of the variance comes from L2) and writes y, and the backward makes two passes
 over [N, F] and allocates nothing of that size but g_x.  The [B, F] arithmetic is torch on the device: no host sync.
+The four Functions are `once_differentiable`: double backward raises.
 
 Modes of event_normalize, per event b and channel c, with mu and var from event_moments and alpha = mean_scale:
     channel   A = alpha mu,  q = var + (1 - alpha)^2 mu^2   (= mean((x - alpha mu)^2): a sum of non-negatives; (1 - alpha) mu
@@ -21,6 +22,7 @@ from __future__ import annotations
 from typing import Optional, Tuple
 
 import torch
+from torch.autograd.function import once_differentiable
 import torch.nn.functional as F_
 
 from . import _native
@@ -66,6 +68,7 @@ class _EventMoments(torch.autograd.Function):
         return mean, var
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_mean, g_var):
         x, rowptr, mean = ctx.saved_tensors
         inv_n = 1.0 / _counts(rowptr).clamp(min=1.0)
@@ -121,6 +124,7 @@ class _EventNormalize(torch.autograd.Function):
         return y, mean, var
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, _g_mean, _g_var):
         x, rowptr, mean, A, r, ka, *rest = ctx.saved_tensors
         max_len, mode, t_alpha, t_weight, alpha, weight = ctx.cfg
@@ -195,6 +199,7 @@ class _EventAffine(torch.autograd.Function):
         return _native._event_affine(x, rowptr, shift, k1, k0)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         x, rowptr, shift, k1 = ctx.saved_tensors
         need_x, _r, _m, need_shift, need_k1, need_k0 = ctx.needs_input_grad
@@ -220,6 +225,7 @@ class _Center(torch.autograd.Function):
         return _native._event_affine(x, rowptr, mean, torch.ones_like(mean), torch.zeros_like(mean))
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         (rowptr,) = ctx.saved_tensors
         g = g.float()

@@ -14,6 +14,7 @@ import copy
 from typing import Optional, Tuple
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native
 from .graph import BatchInfo, _registry_get, _registry_put, batch_info, coalesced_tag, lookup_graph, register_batch
@@ -111,7 +112,8 @@ def normalized_cut_2d(edge_index: torch.Tensor, pos: torch.Tensor) -> torch.Tens
 # cluster pooling
 # ---------------------------------------------------------------------------------------------------------------
 class _PairPool(torch.autograd.Function):
-    """Pooling of a graclus result: max (gradient to the winning member) or mean (split over the members)."""
+    """Pooling of a graclus result: max (gradient to the winning member) or mean (split over the members).
+    `once_differentiable`."""
 
     @staticmethod
     def forward(ctx, x, partner, cid, ptr, C, mode, want_batch):
@@ -125,6 +127,7 @@ class _PairPool(torch.autograd.Function):
         return out, pb
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, _g_pb):
         partner, cid, arg = ctx.saved_tensors
         gx = _native.pool_pairs_bwd(g if ctx.mode == "max" else None, arg, g if ctx.mode == "mean" else None,

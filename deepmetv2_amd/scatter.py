@@ -8,6 +8,9 @@ The rest of the torch_scatter family -- scatter, scatter_sum, scatter_mean, scat
 scatter_log_softmax, scatter_logsumexp, segment_csr -- and torch_geometric.utils.softmax run on csrc/segment.hip, whose
 kernels put a wavefront or a workgroup along a row of any length.  scatter_std takes its centred variance from
 csrc/multi_aggr.hip.
+
+Every autograd Function here is differentiable once: the segment Functions are `once_differentiable`, the MET Functions of
+the training step open their backward with _native.no_double_backward; under create_graph=True both raise.
 """
 from __future__ import annotations
 
@@ -16,6 +19,7 @@ import types
 from typing import Optional, Tuple
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native
 from .graph import _batch_info, _reverse_of_column, batch_info
@@ -28,6 +32,7 @@ class _SegmentSum1D(torch.autograd.Function):
         return _native.segment_sum_1d(src, ptr)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_out):
         (index,) = ctx.saved_tensors
         return g_out.index_select(0, index), None, None
@@ -41,6 +46,7 @@ class _SegmentSumRows(torch.autograd.Function):
         return _native.segment_sum(msg, rowptr, num_rows)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_out):
         (rowptr,) = ctx.saved_tensors
         return _native.segment_sum_bwd(g_out, rowptr, ctx.E), None, None
@@ -56,6 +62,7 @@ class _SegmentMaxRows(torch.autograd.Function):
         return out, arg
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_out, _g_arg):
         arg, rowptr = ctx.saved_tensors
         return _native.segment_max_bwd(g_out, arg, rowptr, ctx.E), None, None
@@ -191,6 +198,7 @@ class _SegmentMeanRows(torch.autograd.Function):
         return _native._segment_mean(src, rowptr, max_len)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_out):
         (rowptr,) = ctx.saved_tensors
         return _native._segment_mean_bwd(g_out, rowptr, ctx.E, ctx.max_len), None, None
@@ -206,6 +214,7 @@ class _SegmentMinRows(torch.autograd.Function):
         return out, arg
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_out, _g_arg):
         arg, rowptr = ctx.saved_tensors
         return _native.segment_max_bwd(g_out, arg, rowptr, ctx.E), None, None      # the same arg convention
@@ -220,6 +229,7 @@ class _SegmentSoftmaxRows(torch.autograd.Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         y, rowptr = ctx.saved_tensors
         return _native._segment_softmax_bwd(y, g, rowptr, ctx.log, ctx.max_len), None, None, None
@@ -234,6 +244,7 @@ class _SegmentLogSumExpRows(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_out):
         src, out, rowptr = ctx.saved_tensors
         return _native._segment_logsumexp_bwd(src, out, g_out, rowptr, ctx.max_len), None, None
@@ -456,6 +467,7 @@ class _MetReduce(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_met):
+        _native.no_double_backward("_MetReduce")
         x, ptr = ctx.saved_tensors
         return _native.met_reduce_bwd(g_met, x, ptr), None, None
 
@@ -477,10 +489,11 @@ class _MetLoss(torch.autograd.Function):
     def forward(ctx, met, truth):
         loss, g = _native.met_loss(met, truth)
         ctx.save_for_backward(g)
-        return loss.view(())
+        return loss.squeeze_(0)     # the [1] tensor itself as a scalar: a view made in here could not be written in place
 
     @staticmethod
     def backward(ctx, g_loss):
+        _native.no_double_backward("_MetLoss")
         (g,) = ctx.saved_tensors
         return g * g_loss, None
 
@@ -494,10 +507,11 @@ class _MetLossFromWeights(torch.autograd.Function):
         met = _native.met_reduce(w, x, ptr)
         loss, g = _native.met_loss(met, truth)
         ctx.save_for_backward(g, x, ptr)
-        return loss.view(())
+        return loss.squeeze_(0)     # the [1] tensor itself as a scalar: a view made in here could not be written in place
 
     @staticmethod
     def backward(ctx, g_loss):
+        _native.no_double_backward("_MetLossFromWeights")
         g, x, ptr = ctx.saved_tensors
         return _native.met_reduce_bwd(g, x, ptr, scale=g_loss.reshape(1).float()), None, None, None
 

@@ -15,6 +15,7 @@ import struct
 from typing import Callable, Optional, Tuple, Union
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native
 from .gcn import GraphConv
@@ -215,7 +216,7 @@ def filter_table(table: NeighborTable, perm: torch.Tensor, node_map: torch.Tenso
 
 
 class _SelectRows(torch.autograd.Function):
-    """out = x[perm] * s[perm][:, None] (s None: x[perm]); rows with perm < 0 are zeros.  fp32."""
+    """out = x[perm] * s[perm][:, None] (s None: x[perm]); rows with perm < 0 are zeros.  fp32.  `once_differentiable`."""
 
     @staticmethod
     def forward(ctx, x, s, perm, node_map):
@@ -224,6 +225,7 @@ class _SelectRows(torch.autograd.Function):
         return _native._select_rows(x, s, perm)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         x, s, node_map = ctx.saved_tensors
         need_gx = ctx.needs_input_grad[0]

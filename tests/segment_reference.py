@@ -75,6 +75,32 @@ def logsumexp_ref(src, rowptr):
     return torch.where(empty, torch.zeros_like(l), safe_m + torch.where(empty, torch.ones_like(l), l).log())
 
 
+# ---- the backward bounds of tests/test_gpu_segment_reduce.py, per entry of grouped rows ---------------------------------
+def _row_sum_of(t, rowptr):
+    ids = row_ids(rowptr)
+    return torch.zeros((rowptr.numel() - 1, t.shape[1]), dtype=t.dtype).index_add(0, ids, t)[ids]
+
+
+def softmax_bwd_bound(src, g, rowptr, n_of):
+    """test_softmax_backward: 4 (n + |s| + 8) u y (|g| + sum_row |y g|)."""
+    src, g = src.double(), g.double()
+    y = softmax_ref(src, rowptr)
+    return 4 * (n_of + src.abs() + 8) * U * y * (g.abs() + _row_sum_of((y * g).abs(), rowptr))
+
+
+def log_softmax_bwd_bound(src, g, rowptr, n_of, ref):
+    """test_log_softmax_backward: 2 u (|ref| + p (3 n + 4 |y| + 19) sum_row |g|), p = exp(y)."""
+    y = log_softmax_ref(src.double(), rowptr)
+    return 2 * U * (ref.abs() + y.exp() * (3 * n_of + 4 * y.abs() + 19) * _row_sum_of(g.double().abs(), rowptr))
+
+
+def logsumexp_bwd_bound(src, rowptr, n_of, ref):
+    """test_logsumexp_backward: 2 (2 n + 4 |out| + |s - out| + 19) u |ref|."""
+    src = src.double()
+    out_of = logsumexp_ref(src, rowptr)[row_ids(rowptr)]
+    return 2 * (2 * n_of + 4 * out_of.abs() + (src - out_of).abs() + 19) * U * ref.abs()
+
+
 # ---- CPU stand-ins of the _native entries (fp32 in and out, float64 inside) ---------------------------------------------
 def _segment_mean(src, rowptr, max_len=0):
     return mean_ref(src.detach(), rowptr).float()
