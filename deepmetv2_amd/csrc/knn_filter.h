@@ -1154,6 +1154,7 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
     // accumulators themselves (second session of round 2; a swap costs two issue slots and sat between the MFMA results
     // and everything else).
     unsigned mask = 0u;
+    unsigned ha = 0u, hb = 0u;     // the masks after element 0: see the v_min3 trees below
     if (kRec) {
         // One VALU op per key: the fold result is key - rep, v_alignbit shifts its sign bit into the mask (a -0 would
         // set a bit: admitted, never dropped).  Element e of a half ends up in bit 15 - e.
@@ -1164,6 +1165,7 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
             for (int e = 0; e < 16; ++e) {
                 ma = __builtin_amdgcn_alignbit(ma, __float_as_uint(c0[e]), 31);
                 mb = __builtin_amdgcn_alignbit(mb, __float_as_uint(c1[e]), 31);
+                if (e == 0) ha = ma, hb = mb;
             }
         } else {
             const auto tt = __builtin_amdgcn_permlane32_swap(__float_as_uint(L.tau), __float_as_uint(L.tau), false, false);
@@ -1172,6 +1174,7 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
             for (int e = 0; e < 16; ++e) {
                 ma = __builtin_amdgcn_alignbit(ma, __float_as_uint(c0[e] - t0), 31);
                 mb = __builtin_amdgcn_alignbit(mb, __float_as_uint(c1[e] - t1), 31);
+                if (e == 0) ha = ma, hb = mb;
             }
         }
         const auto mm = __builtin_amdgcn_permlane32_swap(ma, mb, false, false);
@@ -1183,9 +1186,26 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
         // the trees start from the sentinel (the first operand also keeps a NaN key out of the v_med3 chain), taken as
         // a scalar source: a VOP3 encoding has no literal, and a "+v" start value costs a v_mov per tree and tile
         // v_min3_f32 by hand: fminf() makes hipcc canonicalise every MFMA output with a v_max first (twice the ops)
+        // These statements read accumulators that MFMAs have just written, and hipcc pads the wait states an MFMA's
+        // result needs before its first reader (12 after an 8-pass one) only for readers it knows: an asm statement
+        // gets none, and one scheduled right behind its MFMA takes the minimum of stale registers -- a wrong threshold
+        // (other flagged-query and second-attempt counts, never a wrong table).  So each tree hangs on an instruction
+        // of hipcc's own that reads its accumulator block.  A recording call has one: the first v_alignbit of the
+        // block's hit mask, named as an unused operand of the tree's first statement (no instruction).  The other
+        // calls (deferred pass; the ablation builds) form the tree's sentinel with a v_med3 that reads a key and
+        // returns the sentinel whatever the key is (median of S, S, x): one instruction per tree.
+        // (profiles/r10_knn_counted_waits.md: the deferred pass as a four-call trip put a tree directly behind its
+        // MFMA; tools/knn_mfma_asm_distance.py lists the distances, tests/test_knn_wait_counts_asm.py holds them.)
         float na, nb;
-        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(na) : "s"(kKnnSentinel), "v"(c0[0]), "v"(c0[1]));
-        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(nb) : "s"(kKnnSentinel), "v"(c1[0]), "v"(c1[1]));
+        if (kRec) {
+            asm("v_min3_f32 %0, %1, %2, %3" : "=v"(na) : "s"(kKnnSentinel), "v"(c0[0]), "v"(c0[1]), "v"(ha));
+            asm("v_min3_f32 %0, %1, %2, %3" : "=v"(nb) : "s"(kKnnSentinel), "v"(c1[0]), "v"(c1[1]), "v"(hb));
+        } else {
+            const float sa = __builtin_amdgcn_fmed3f(kKnnSentinel, kKnnSentinel, c0[0]);
+            const float sb = __builtin_amdgcn_fmed3f(kKnnSentinel, kKnnSentinel, c1[0]);
+            asm("v_min3_f32 %0, %1, %2, %3" : "=v"(na) : "v"(sa), "v"(c0[0]), "v"(c0[1]));
+            asm("v_min3_f32 %0, %1, %2, %3" : "=v"(nb) : "v"(sb), "v"(c1[0]), "v"(c1[1]));
+        }
 #pragma unroll
         for (int e = 2; e < 16; e += 2) {
             asm("v_min3_f32 %0, %0, %1, %2" : "+v"(na) : "v"(c0[e]), "v"(c0[e + 1]));
@@ -1239,15 +1259,46 @@ __device__ __forceinline__ void f2_tile(F2Lane<M> &L, F2Wave &S, const uint8_t *
 #endif
 }
 
+// Call Q (0..3) of a four-set trip at tile t: it selects from key block Q & 1, issues the MFMAs of set Q + 1 and loads
+// tile t + 4 into set Q, whose MFMAs the call before it issued; the odd calls convert (knn_tile_schedule.h).
+template <int M, bool UPD, bool REC, int Q>
+__device__ __forceinline__ void f2_trip_call(F2Lane<M> &L, F2Wave &S, const uint8_t *__restrict__ rec, int64_t rbase, int t,
+                                             int t_hi, f32x16 &c0, f32x16 &c1, f32x16 &n0, f32x16 &n1, float &rc, float &rn,
+                                             F2Ops<1> (&s)[kF2Sets], const f16x8 (&bq)[2][2], f16x8 (&fq)[2], int lane, int hh,
+                                             bool alive, float &carry, unsigned &rofs)
+{
+    static_assert(f2_tile_set(4) == 0 && f2_tile_key_block(2) == 0 && f2_tile_key_block(3) == 1 && !f2_call_converts(2) &&
+                      f2_call_converts(3),
+                  "the trip below is the schedule's, written out");
+    static_assert(Q >= 0 && Q < kF2Sets && f2_remainder_trip_call(Q) == Q, "a remainder call is the same call of a trip");
+    constexpr bool kConv = f2_call_converts(Q);
+    if constexpr (f2_tile_key_block(Q) == 0)
+        f2_tile<M, UPD, REC, true, 1, kConv>(L, S, rec, rbase, t, f2_load_tile(t, kF2Sets, t_hi), c0, c1, n0, n1, rc, rn,
+                                             s[f2_trip_use_set(Q)], s[f2_trip_load_set(Q)], bq, fq, lane, hh, alive, carry, rofs);
+    else
+        f2_tile<M, UPD, REC, true, 1, kConv>(L, S, rec, rbase, t, f2_load_tile(t, kF2Sets, t_hi), n0, n1, c0, c1, rn, rc,
+                                             s[f2_trip_use_set(Q)], s[f2_trip_load_set(Q)], bq, fq, lane, hh, alive, carry, rofs);
+}
+
 // A recording sweep at 32 features (main sweep, revisit, second attempt): FOUR tiles of operands in flight.  What the
 // kernel's time per item holds beyond its own vector issue is waiting for operands (a loaded L2 round trip is ~2000
 // cycles, a revisit tile ~250 cycles of work), so call t issues tile t + 1's MFMAs and loads tile t + 4, and the sweep
 // requests its first four tiles at once instead of load, wait, MFMA, load.  Four calls per trip: the operand sets rotate
 // with period 4, the key blocks (c, n) and the threshold conversions with period 2 (knn_tile_schedule.h, shared with the
-// host test).  Only WHEN operands are loaded differs from a sweep with two sets: the order of MFMAs, conversions,
-// insertions and compactions does not.  (Three sets in the main sweep and two elsewhere until r09; the deferred pass
-// keeps two: four spill there.  profiles/r09_knn_operand_pipeline.md.)
-template <int M, bool UPD>
+// host tests).  Only WHEN operands are loaded differs from a sweep with two sets: the order of MFMAs, conversions,
+// insertions and compactions does not.
+// The sweep is a loop over WHOLE trips with no exit inside a trip, then its zero to three remaining calls written out.
+// With an exit after every call (`for (;;) { call; if (++t >= t_hi) break; ... }`, r09) the loop header joins four
+// paths that carry different numbers of loads in flight, and hipcc's wait insertion answers such a join with
+// s_waitcnt vmcnt(0): once per trip every outstanding load was drained, the three requested one tile earlier included.
+// In this form every tile block waits with a counted vmcnt(N) that leaves the three younger tiles in flight
+// (tools/knn_tile_counts.py lists the waits; tests/test_knn_wait_counts_asm.py holds them).  The loads are plain loads
+// that hipcc counts itself: no wait is placed by hand.  profiles/r10_knn_counted_waits.md.
+// REC = false is the deferred pass on this trip (-DDMET_F2_DEFER_FOUR only): it folds threshold 0 and converts nothing,
+// its results are the keys themselves.  As whole trips it does not spill (as a loop with exits it did, r09), its block
+// of four tiles waits with counted vmcnt only, the tables and counters are the parent's -- and every one of six
+// alternated runs was slower than with the two-set loop of f2_sweep (r10, -0.7 %): the deferred pass keeps two sets.
+template <int M, bool UPD, bool REC>
 __device__ __forceinline__ void f2_sweep4(F2Lane<M> &L, F2Wave &S, const uint8_t *__restrict__ rec, int64_t rbase, int t_lo,
                                           int t_hi, const f16x8 (&bq)[2][2], int lane, int hh, bool alive)
 {
@@ -1256,37 +1307,38 @@ __device__ __forceinline__ void f2_sweep4(F2Lane<M> &L, F2Wave &S, const uint8_t
 #pragma unroll
     for (int j = 0; j < kF2Sets; ++j) f2_load<1>(s[f2_tile_set(j)], rec, rbase + f2_load_tile(t_lo, j, t_hi), lane, hh, rofs);
     // query side of the fold for both 32-query blocks, built here once per sweep -- from the threshold the sweep starts
-    // with (the running cut before the main sweep, the cut before the revisit, t_fix in a second attempt) -- and kept in
-    // registers: the tiles read them, a CONV tile rewrites their threshold dword.  Opaque, or hipcc rebuilds them (eight
-    // moves and the swap) in every tile rather than hold eight registers
+    // with (the running cut before the main sweep, the cut before the revisit, t_fix in a second attempt; threshold 0
+    // in the deferred pass) -- and kept in registers: the tiles read them, a CONV tile rewrites their threshold dword.
+    // Opaque, or hipcc rebuilds them (eight moves and the swap) in every tile rather than hold eight registers
     f16x8 fq[2] = {f2_fold(0u), f2_fold(0u)};
-    L.tq = f2_tau16(L.tau, L.rep);
-    f2_fold_tau(fq, L.tq);
-    asm volatile("" : "+v"(fq[0]), "+v"(fq[1]));
+    if constexpr (REC) {
+        L.tq = f2_tau16(L.tau, L.rep);
+        f2_fold_tau(fq, L.tq);
+        asm volatile("" : "+v"(fq[0]), "+v"(fq[1]));
+    }
     float rc = L.rep, rn;
     f32x16 c0 = f2_block<1>(s[0], bq[0], fq[0]);      // prologue: the first tile's keys
     f32x16 c1 = f2_block<1>(s[0], bq[1], fq[1]);
     f32x16 n0, n1;
     float carry = kKnnSentinel;
-    // call Q of a trip selects from key block Q & 1, issues the MFMAs of set Q + 1 and loads into set Q, whose MFMAs the
-    // call before it issued
-    static_assert(f2_tile_set(4) == 0 && f2_tile_key_block(2) == 0 && f2_tile_key_block(3) == 1 && !f2_call_converts(2) &&
-                      f2_call_converts(3),
-                  "the trip below is the schedule's, written out");
-    for (int t = t_lo;;) {
-        f2_tile<M, UPD, true, true, 1, false>(L, S, rec, rbase, t, f2_load_tile(t, kF2Sets, t_hi), c0, c1, n0, n1, rc, rn, s[1],
-                                              s[0], bq, fq, lane, hh, alive, carry, rofs);
-        if (++t >= t_hi) break;
-        f2_tile<M, UPD, true, true, 1, true>(L, S, rec, rbase, t, f2_load_tile(t, kF2Sets, t_hi), n0, n1, c0, c1, rn, rc, s[2],
-                                             s[1], bq, fq, lane, hh, alive, carry, rofs);
-        if (++t >= t_hi) break;
-        f2_tile<M, UPD, true, true, 1, false>(L, S, rec, rbase, t, f2_load_tile(t, kF2Sets, t_hi), c0, c1, n0, n1, rc, rn, s[3],
-                                              s[2], bq, fq, lane, hh, alive, carry, rofs);
-        if (++t >= t_hi) break;
-        f2_tile<M, UPD, true, true, 1, true>(L, S, rec, rbase, t, f2_load_tile(t, kF2Sets, t_hi), n0, n1, c0, c1, rn, rc, s[0],
-                                             s[3], bq, fq, lane, hh, alive, carry, rofs);
-        if (++t >= t_hi) break;
+#define F2_TRIP_CALL(Q, T) \
+    f2_trip_call<M, UPD, REC, Q>(L, S, rec, rbase, T, t_hi, c0, c1, n0, n1, rc, rn, s, bq, fq, lane, hh, alive, carry, rofs)
+    int t = t_lo;
+    for (int n = f2_whole_trips(t_hi - t_lo); n > 0; --n, t += kF2Sets) {
+        F2_TRIP_CALL(0, t);
+        F2_TRIP_CALL(1, t + 1);
+        F2_TRIP_CALL(2, t + 2);
+        F2_TRIP_CALL(3, t + 3);
     }
+    const int rem = f2_remainder_calls(t_hi - t_lo);
+    if (rem > 0) {
+        F2_TRIP_CALL(0, t);
+        if (rem > 1) {
+            F2_TRIP_CALL(1, t + 1);
+            if (rem > 2) F2_TRIP_CALL(2, t + 2);
+        }
+    }
+#undef F2_TRIP_CALL
 }
 
 // One pass over the tiles [t_lo, t_hi) of the event whose first record is rbase.
@@ -1295,8 +1347,13 @@ __device__ __forceinline__ void f2_sweep(F2Lane<M> &L, F2Wave &S, const uint8_t 
                                          int t_lo, int t_hi, const f16x8 (&bq)[2][2 * NH], int lane, int hh, bool alive)
 {
     if (t_lo >= t_hi) return;
-    if constexpr (NH == 1 && REC) {
-        f2_sweep4<M, UPD>(L, S, rec, rbase, t_lo, t_hi, bq, lane, hh, alive);
+#ifdef DMET_F2_DEFER_FOUR
+    constexpr bool kFour = NH == 1;            // experiment: the deferred pass on four sets too (r10: slower in every run)
+#else
+    constexpr bool kFour = NH == 1 && REC;
+#endif
+    if constexpr (kFour) {
+        f2_sweep4<M, UPD, REC>(L, S, rec, rbase, t_lo, t_hi, bq, lane, hh, alive);
         return;
     }
     // two operand sets (the deferred pass; 64 features: two sets of eight fragments next to the sixteen of the queries
@@ -1313,12 +1370,15 @@ __device__ __forceinline__ void f2_sweep(F2Lane<M> &L, F2Wave &S, const uint8_t 
     f32x16 n0, n1;
     f2_load<NH>(A, rec, rbase + f2_load_tile(t_lo, 1, t_hi), lane, hh, rofs);
     float carry = kKnnSentinel;
+    // every tile inserts its own minimum (INS = true).  Inserting the minimum of tile PAIRS instead (half the
+    // v_med3 chains) was tried: the threshold then admits up to 2M tiles, more than the 26 entries a lane can keep
+    // -> 3 761 overflowed queries per launch and twice the kernel time
+    // the fold's threshold is converted after every second tile only (f2_tau16 is ~15 VALU ops): the masks of
+    // the next two tiles are taken against a threshold older by one more update -- larger, a superset
+    // (The same loop as whole pairs and an odd tile, without the exit between its two calls, was compiled in r10: its
+    // waits still count down to vmcnt(0) -- with two sets the loads of the next use are the youngest in flight -- and
+    // the 64-feature instances grow by 14 to 18 registers.  Not kept, not run.)
     for (int t = t_lo; t < t_hi; t += 2) {
-        // every tile inserts its own minimum (INS = true).  Inserting the minimum of tile PAIRS instead (half the
-        // v_med3 chains) was tried: the threshold then admits up to 2M tiles, more than the 26 entries a lane can keep
-        // -> 3 761 overflowed queries per launch and twice the kernel time
-        // the fold's threshold is converted after every second tile only (f2_tau16 is ~15 VALU ops): the masks of
-        // the next two tiles are taken against a threshold older by one more update -- larger, a superset
         f2_tile<M, UPD, REC, true, NH, false>(L, S, rec, rbase, t, f2_load_tile(t, kF2PlainLead, t_hi), c0, c1, n0, n1, rc, rn,
                                               A, B, bq, fq, lane, hh, alive, carry, rofs);
         if (t + 1 < t_hi)
