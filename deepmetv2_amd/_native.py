@@ -1150,7 +1150,7 @@ def interpolate_check_shapes(x: torch.Tensor, nbr: torch.Tensor, dist: torch.Ten
 
 
 def interpolate_fwd(x: torch.Tensor, nbr: torch.Tensor, dist: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(out[Nt, F] = sum over row i of nbr of r_t x[j], r_t = w_t / W_i, w_t = 1 / max(dist[i,t], 1e-16); wsum[Nt] = W_i);
+    """(out[Nt, F] = sum over row i of nbr of r_t x[j], r_t = w_t / W_i, w_t = 1 / clamp(dist[i,t], 1e-16); wsum[Nt] = W_i);
     see include/dmet.h, dmet_interpolate_fwd_f32.  The outputs are zero-filled allocations: the entry writes all of them."""
     interpolate_check_shapes(x, nbr, dist)
     dev = _require_device(x, nbr, dist)

@@ -4,6 +4,7 @@
 //   d = sum_c fmaf(a, a, acc), a = s_src[j,c] - s_tgt[i,c]   (the R1 chain: the bits of the kNN build's `dist`)
 //   w = expf(-10 d)
 //   out[i, 0:P] = (sum_t w h[j,:]) / cnt_i      out[i, P:2P] = max_t w h[j,:], arg = the winning slot (lowest on ties)
+// The max runs over the messages that are numbers: a NaN never wins and never blocks; all NaN: NaN, arg 255.
 // The [E, P] messages are never written: the forward gathers one h row per edge, the backward recomputes w.
 //
 // Lane layout, all three kernels: a group of LPT lanes (16 or 32, inside one wavefront) owns one row (a target in the
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(kGravBlock) void gravnet_fwd_kernel(
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         sum[it] = 0.f;
-        mx[it] = 0.f;
+        mx[it] = NAN;       // NaN: no number among the messages yet
         win[it] = kGravNoWinner;
     }
     int n = 0;
@@ -102,7 +103,10 @@ __global__ __launch_bounds__(kGravBlock) void gravnet_fwd_kernel(
                 for (int it = 0; it < ITER; ++it) {
                     const float m_ = w[u] * v[u][it];
                     sum[it] += m_;
-                    if (win[it] == kGravNoWinner || m_ > mx[it]) {      // strict: ties keep the lower slot (R4)
+                    // strict: ties keep the lower slot (R4).  While mx is NaN any message replaces it, so the first
+                    // number is taken whatever it is (+-inf too); once mx is a number a NaN fails the comparison: it
+                    // never wins and never blocks, in any slot
+                    if (m_ > mx[it] || mx[it] != mx[it]) {
                         mx[it] = m_;
                         win[it] = t;
                     }
@@ -117,8 +121,10 @@ __global__ __launch_bounds__(kGravBlock) void gravnet_fwd_kernel(
         const int p = lane + it * LPT;
         if (p < P) {
             out[i * 2 * P + p] = n > 0 ? sum[it] / fn : 0.f;         // a row without a valid slot: zeros (R3)
+            // no number among the messages of a non-empty row: mx is still NaN, and arg is 255 (the backward routes
+            // nothing)
             out[i * 2 * P + P + p] = n > 0 ? mx[it] : 0.f;
-            arg[i * P + p] = (uint8_t)win[it];
+            arg[i * P + p] = mx[it] != mx[it] ? kGravNoWinner : (uint8_t)win[it];
         }
     }
     if (lane == 0) cnt[i] = n;

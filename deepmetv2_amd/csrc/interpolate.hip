@@ -2,7 +2,7 @@
 // over a fixed-width table with the table's own distances.
 //
 // For target i and every valid slot t of its row, j = nbr[i,t]:
-//   w_t = 1 / max(dist[i,t], 1e-16)     W_i = sum_t w_t     r_t = w_t / W_i     out[i,:] = sum_t r_t x[j,:]   (fma chain)
+//   w_t = 1 / clamp(dist[i,t], 1e-16)   W_i = sum_t w_t     r_t = w_t / W_i     out[i,:] = sum_t r_t x[j,:]   (fma chain)
 // and by source j over the reverse index: g_x[j,:] = sum_p r_p g_out[i,:], r_p recomputed from dist[p] and wsum[i] = W_i.
 // The [E, F] messages are never written, there are no float atomics, both sums run in ascending slot / position order.
 //
@@ -22,7 +22,8 @@ constexpr int kInterpInFlight = 4;     // row gathers in flight per group
 constexpr int kInterpMaxF = 256;
 constexpr float kInterpMinD = 1e-16f;  // PyG: clamp(squared_distance, min=1e-16)
 
-__device__ __forceinline__ float interp_weight(float d) { return 1.0f / fmaxf(d, kInterpMinD); }
+// the clamp is a comparison, not fmaxf: a NaN distance gives a NaN weight (torch.clamp keeps NaN), never 1e16
+__device__ __forceinline__ float interp_weight(float d) { return 1.0f / (d < kInterpMinD ? kInterpMinD : d); }
 
 __device__ __forceinline__ void zero_unit(float &a) { a = 0.f; }
 __device__ __forceinline__ void zero_unit(float4 &a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }

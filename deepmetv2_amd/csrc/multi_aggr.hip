@@ -5,10 +5,13 @@
 // For target i with valid entries j_1..j_n (ascending slot / position order; -1 and ids outside [0, Ns) are skipped, a
 // duplicate id counts once per slot), per feature f, fp32:
 //   sum  = (((0 + x[j_1]) + x[j_2]) + ...)          mean = sum / (float)n
-//   min / max with the position (i*k + t, or the edge position) of the winner, the lowest on ties (R4)
+//   min / max over the candidates that are numbers (+-inf included), with the position (i*k + t, or the edge position)
+//          of the winner, the lowest on ties (R4); a NaN never wins and never blocks, in any slot; a feature whose
+//          candidates are all NaN gives NaN with position -1
 //   var  = (((0 + d_1 d_1) + d_2 d_2) + ...) / (float)n,  d_e = x[j_e] - mean      a second walk over the row, centred on
 //          the row's own mean: never a difference of two means
-//   std  = s = sqrtf(fmaxf(var, 1e-5f)), 0 where s <= sqrtf(1e-5f)                   (PyG's StdAggregation)
+//   std  = s = sqrtf(var < 1e-5f ? 1e-5f : var), 0 where s <= sqrtf(1e-5f)           (PyG's StdAggregation; the clamp
+//          keeps a NaN, as torch.clamp does: std is NaN where var is)
 // n == 0: zeros everywhere (R3), count 0, positions -1.  out is [Nt, G, A, F/G]: the A requested statistics in request
 // order inside each of G feature groups (PNA's towers).
 //
@@ -63,7 +66,7 @@ struct MaArgs {
 
 __device__ __forceinline__ float ma_std(float var)
 {
-    const float s = sqrtf(fmaxf(var, kMaVarFloor));
+    const float s = sqrtf(var < kMaVarFloor ? kMaVarFloor : var);      // a comparison, not fmaxf: NaN stays NaN
     return s <= sqrtf(kMaVarFloor) ? 0.f : s;
 }
 
@@ -113,8 +116,7 @@ __global__ __launch_bounds__(kMaBlock) void multi_aggr_fwd_kernel(MaArgs a)
 #pragma unroll
         for (int c = 0; c < W; ++c) {
             sum[it][c] = 0.f;
-            mn[it][c] = INFINITY;
-            mx[it][c] = -INFINITY;
+            mn[it][c] = mx[it][c] = NAN;        // NaN: no number among the candidates yet (min and max alike)
             pmn[it][c] = pmx[it][c] = -1;
         }
     int n = 0;
@@ -149,11 +151,15 @@ __global__ __launch_bounds__(kMaBlock) void multi_aggr_fwd_kernel(MaArgs a)
                         const float val = v[u][it].c[c];
                         sum[it][c] += val;
                         if (minmax) {
-                            if (val < mn[it][c]) {      // strict: the lowest position keeps a tie (R4)
+                            // strict: the lowest position keeps a tie (R4).  While the running value is NaN any
+                            // candidate replaces it, so the first number is taken whatever it is (+-inf too); once it
+                            // is a number a NaN fails the comparison: it never wins and never blocks, in any slot
+                            const bool none = mn[it][c] != mn[it][c];      // mx is NaN exactly when mn is
+                            if (val < mn[it][c] || none) {
                                 mn[it][c] = val;
                                 pmn[it][c] = pos;
                             }
-                            if (val > mx[it][c]) {
+                            if (val > mx[it][c] || none) {
                                 mx[it][c] = val;
                                 pmx[it][c] = pos;
                             }
@@ -227,12 +233,12 @@ __global__ __launch_bounds__(kMaBlock) void multi_aggr_fwd_kernel(MaArgs a)
         for (int c = 0; c < W; ++c) {       // a row without a valid entry: zeros (R3), positions -1
             s_sum.c[c] = sum[it][c];
             s_mean.c[c] = mean[it][c];
-            s_min.c[c] = n > 0 ? mn[it][c] : 0.f;
+            s_min.c[c] = n > 0 ? mn[it][c] : 0.f;       // still NaN: no number among the candidates
             s_max.c[c] = n > 0 ? mx[it][c] : 0.f;
             s_var.c[c] = var[it][c];
             s_std.c[c] = n > 0 ? ma_std(var[it][c]) : 0.f;
-            s_pmn.c[c] = pmn[it][c];
-            s_pmx.c[c] = pmx[it][c];
+            s_pmn.c[c] = mn[it][c] != mn[it][c] ? -1 : pmn[it][c];       // a NaN that stood in for "none" is no winner
+            s_pmx.c[c] = mx[it][c] != mx[it][c] ? -1 : pmx[it][c];
         }
         float *o = orow + out_offset<W>(p, Fg, a.A);
         auto put = [&](int kind, const VF &val) {

@@ -14,7 +14,8 @@
 //   2. entry pass (pn_fwd_kernel): a wavefront owns a target and walks its entries in tiles of 16.  h1 of the tile goes to
 //      the wavefront's LDS, z2 = h1 W2^T + b2 runs on the fp32 matrix cores (v_mfma_f32_16x16x4_f32: tile entries x 16
 //      channels per block, k in steps of 16), and the running (max, winner) of a channel is kept in registers in entry
-//      order: strict compares, so the earliest entry wins a tie (R4).  Nothing per entry is written.
+//      order: strict compares, so the earliest entry wins a tie (R4); a NaN message never wins and never blocks, and a
+//      channel whose messages are all NaN is NaN with win -1.  Nothing per entry is written.
 // Backward (out and win are the forward's)
 //   g_z2[i, o] = g_out[i, o] act2'(out[i, o]) belongs to the one entry win[i, o] names; the tile's routed g_z2 [16, H2]
 //   goes to LDS and g_h1 = g_z2 W2 runs on the matrix cores, g_pre1 = g_h1 act'(h1) with h1 formed again.
@@ -274,10 +275,12 @@ __global__ __launch_bounds__(kPnBlock) void pn_fwd_kernel(const float *__restric
             rv[cb] = 0.0f;
             rt[cb] = kPnNone;
         }
+        bool seen = false;                     // the row has an entry
         for (int base = 0; base < total; base += kPnTile) {
             const int32_t jl = pn_entry(g, i, lo, n, base + m);
             const unsigned mask = (unsigned)(__ballot(jl >= 0) & 0xffffull);
             if (mask == 0u) continue;          // a tile of empty slots: the same for the whole wavefront
+            seen = true;
             pn_wave_sync();                    // the previous tile's reads of h1s are done
             pn_fill_h1_target(A, S, bi, i, jl, g.self_loop ? n - base : -1, H1, act, h1s, lane);
             pn_wave_sync();
@@ -298,18 +301,24 @@ __global__ __launch_bounds__(kPnBlock) void pn_fwd_kernel(const float *__restric
             // acc[cb][r]: entry base + 4 q + r, channel 16 cb + m
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
-                float bv = 0.0f;
+                float bv = NAN;        // NaN: no number among this quarter's messages yet
                 int bt = kPnNone;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int e = 4 * q + r;
                     if (!((mask >> e) & 1u)) continue;
                     const float v = act2 ? pn_act(acc[cb][r], act) : acc[cb][r];
-                    if (bt == kPnNone || v > bv) {
+                    // while bv is NaN any message replaces it, so the first number is taken whatever it is (+-inf too);
+                    // once bv is a number a NaN fails the comparison: it never wins and never blocks, wherever in the
+                    // row and in whichever quarter of the wavefront it stands
+                    if (v > bv || bv != bv) {
                         bv = v;
                         bt = base + e;
                     }
                 }
+                // a NaN that stood in for "none" names no entry: a (value, entry) pair with an entry always holds a
+                // number, and the two merges below need no more
+                if (bv != bv) bt = kPnNone;
 #pragma unroll
                 for (int off = 16; off < kWave; off <<= 1) {
                     const float ov = __shfl_xor(bv, off, kWave);
@@ -329,7 +338,8 @@ __global__ __launch_bounds__(kPnBlock) void pn_fwd_kernel(const float *__restric
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
                 const int64_t at = i * H2 + cb * 16 + m;
-                out[at] = rt[cb] == kPnNone ? 0.0f : rv[cb];
+                // no entry: zeros (R3).  Entries, but no number among a channel's messages: NaN, win -1
+                out[at] = rt[cb] == kPnNone ? (seen ? NAN : 0.0f) : rv[cb];
                 win[at] = rt[cb] == kPnNone ? -1 : pn_code(g, lo, n, rt[cb]);
             }
         }

@@ -11,8 +11,8 @@
 // group walks the chunk kInFlight gathers at a time over the channels c = lane, lane + LPT of the contiguous head rows,
 // a channel sum is each lane's partial sum in ascending c followed by the xor butterfly of the group, and lane e keeps
 // the scalars of entry e (score, then expf(score - m)) which the group takes back by shuffle.  The running (m, l, acc)
-// is rescaled once per chunk that holds a valid entry; l and acc add their terms in ascending entry order, the implicit
-// self entry last.  Sums run in slot / edge / reverse-index order with no LDS, no __syncthreads and no float atomics: the
+// is rescaled once per chunk that holds a valid entry (by 0 while m is still -inf: nothing finite has been added); l and
+// acc add their terms in ascending entry order, the implicit self entry last; a score of -inf adds exactly 0.  Sums run in slot / edge / reverse-index order with no LDS, no __syncthreads and no float atomics: the
 // bits depend on LPT (the chunk length), never on the launch or the run, and a table and the edge list of the same
 // entries in the same order give the same bits.  Every loop is bounded by a row length or a reverse-list length read
 // once and clamped.
@@ -198,9 +198,13 @@ __device__ __forceinline__ void softmax_row_fwd(const RowGraph &g, const Unit &u
         }
         if (alpha != nullptr && base + lane < n) alpha[(lo + base + lane) * H + h] = sl;     // the score, until the row's (m, l) is known
         if (group_max<LPT>(jl >= 0 ? 1.f : 0.f) == 0.f) continue;      // a chunk of empty slots: the running state stays
+        // Non-finite scores follow torch.softmax of the whole row, wherever the chunks fall.  A score of -inf weighs
+        // exactly 0 and is never an operand of expf: beside m_new == -inf the difference would be NaN.  While m is -inf
+        // nothing finite has been added, so the state is rescaled by 0, not by expf(-inf - m_new): a NaN that a NaN score
+        // left in (l, acc) stays NaN through the product, zeros stay zeros.  A finite m gives the bits of expf(m - m_new).
         const float m_new = fmaxf(m, group_max<LPT>(sl));
-        const float scale = (cnt == 0) ? 0.f : expf(m - m_new);
-        const float pl = jl >= 0 ? expf(sl - m_new) : 0.f;
+        const float scale = (m == -INFINITY) ? 0.f : expf(m - m_new);
+        const float pl = (jl >= 0 && sl != -INFINITY) ? expf(sl - m_new) : 0.f;
         m = m_new;
         l *= scale;
 #pragma unroll
@@ -213,6 +217,7 @@ __device__ __forceinline__ void softmax_row_fwd(const RowGraph &g, const Unit &u
             ++cnt;
         });
     }
+    if (m == -INFINITY) l = NAN;      // every score -inf (or NaN): the row has no softmax -- NaN in out, lse and alpha
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         const int c = lane + it * LPT;

@@ -84,6 +84,11 @@ def gravnet_aggregate(h: torch.Tensor, s: torch.Tensor, table: Union[NeighborTab
     j = table.nbr[i, t] of exp(-10 d_ij) h[j], d_ij = |s[j] - s_i|^2 in fp32 (the kNN build's distance chain).  A row
     without a valid slot gives zeros.
 
+    Non-finite values: the mean half follows IEEE; the max half runs over the messages that are numbers (+-inf
+    included) wherever they stand in the row -- a NaN never wins and never blocks, and a channel whose messages are all
+    NaN is NaN and receives no gradient (upstream's amax propagates the NaN instead).  A non-finite h[j, p] changes
+    channel p of the rows that list j and nothing else, forward and backward.
+
     NeighborTable (knn_table): one node set, s_i = s[i].  BipartiteTable (knn_xy_table): h, s belong to the candidates x,
     s_dst to the queries y.  Differentiable in h, s and s_dst.  1 <= S <= 16 coordinates, 1 <= P <= 128 features,
     k <= 64; anything else is a ValueError.  bf16 inputs (fp16 under fp16 autocast) are upcast exactly and the aggregate

@@ -43,9 +43,13 @@ class _InterpolateAggregate(torch.autograd.Function):
 
 def interpolate_aggregate(x: torch.Tensor, table: Union[NeighborTable, BipartiteTable]) -> torch.Tensor:
     """[N_dst, F]: for every row i of `table`, sum over its valid slots j = table.nbr[i, t] of r_t x[j] with
-    r_t = w_t / sum_t w_t and w_t = 1 / max(table.dist[i, t], 1e-16), the table's own fp32 squared distances.  A slot is
-    valid by its id (-1 or an id outside the sources is empty, whatever its distance); a row without a valid slot gives
-    zeros.
+    r_t = w_t / sum_t w_t and w_t = 1 / clamp(table.dist[i, t], min=1e-16), the table's own fp32 squared distances.  A
+    slot is valid by its id (-1 or an id outside the sources is empty, whatever its distance); a row without a valid slot
+    gives zeros.
+
+    Non-finite values: the clamp keeps a NaN, as torch.clamp does, so a NaN distance in a valid slot makes its whole row
+    NaN (a table of knn_table / knn_xy_table never holds one there; a hand-built table may); a non-finite x[j, f] shows
+    in feature f of the rows that list j and nowhere else.
 
     BipartiteTable (knn_xy_table): x belongs to the candidates.  NeighborTable (knn_table): one node set.  Differentiable
     in x; the distances carry no gradient.  1 <= F <= 256 features, k <= 64; anything else is a ValueError.  bf16 input

@@ -115,9 +115,16 @@ def multi_aggregate(x: torch.Tensor, graph: Graph, aggrs: Sequence[str], groups:
 
     out is [Nt, A, F] for groups == 1 and [Nt, G, A, F/G] otherwise: the features split into G groups (PNA's towers)
     with the A statistics side by side inside each.  var = (1/n) sum (x_j - mean)^2, centred on the row's mean (error
-    at most (2n+8) u var + ((n+2) u mean|x|)^2, u = 2^-24); std = sqrt(max(var, 1e-5)), exactly 0 where that is
+    at most (2n+8) u var + ((n+2) u mean|x|)^2, u = 2^-24); std = sqrt(clamp(var, min=1e-5)), exactly 0 where that is
     <= sqrt(1e-5) -- PyG's StdAggregation.  min / max keep the lowest position on ties.  A row without an entry gives
     zeros and count 0.
+
+    Non-finite values: sum, mean and var follow IEEE (a non-finite x[j, f] makes feature f of the rows that list j
+    non-finite), and std is NaN where var is: the clamp keeps a NaN, as torch.clamp does.  min / max run over the
+    candidates that are numbers, +-inf included, in any order of the row: a NaN never wins and never blocks, and a
+    feature whose candidates are all NaN is NaN and receives no gradient -- upstream's amin / amax propagate the NaN
+    instead.  Every other row, every other feature and every gradient row of a source that shares no row with j keep
+    the bits of the run without the value.
 
     graph: a NeighborTable (knn_table), a BipartiteTable (knn_xy_table; x belongs to its candidates) or an EdgeList (x
     over its sources); a counted radius table is taken as its edge list (one host read).  x [Ns, F], 1 <= F <= 256,

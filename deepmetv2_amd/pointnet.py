@@ -119,6 +119,11 @@ def pointnet_aggregate(x_src: Optional[torch.Tensor], pos_src: torch.Tensor, pos
     in x_src, pos_src, pos_dst and the parameters; bf16 inputs (fp16 under fp16 autocast) are upcast exactly.  Over a
     -1-padded table: no edge list and no host sync, forward or backward.
 
+    Non-finite values: the maximum runs over the messages that are numbers (+-inf included), wherever an entry stands in
+    its row; a NaN message never wins and never blocks, and a channel whose messages are all NaN is NaN with win -1 --
+    upstream's amax propagates the NaN instead.  ReLU (v > 0 ? v : 0) turns a NaN pre-activation into 0; ELU carries it on.
+    A non-finite input of source j changes the rows that list j and nothing else, forward and backward.
+
     return_winners=True: (out, win), win[Nt, H2] int32 the winning table slot or grouped list position, -2 for the
     added self entry, -1 for a row without an entry."""
     Nt, Ns, width = _graph_sizes(graph)

@@ -517,6 +517,22 @@ int dmet_gather_sum_csr_f32(const float *P, const float *Q, const int32_t *rowpt
 int dmet_gather_sum_bwd_f32(const float *g_out, const int32_t *deg, const int32_t *rev_ptr, const int32_t *rev_idx,
                             const int32_t *tgt, int64_t N, int k, int H, int mean, float *gP, float *gQ,
                             dmet_stream_t stream);
+/* ---- Non-finite values in the fused aggregations ---------------------------------------------------------------------
+ * One contract for dmet_gravnet_*, dmet_attention_*, dmet_gat_*, dmet_interpolate_*, dmet_multi_aggr_*,
+ * dmet_weighted_sum_* and dmet_pointnet_* (the sections below name their lanes); tests/nonfinite_contract.py holds them to it.
+ *   Sum lanes follow IEEE: a non-finite term makes its channel non-finite.
+ *   Softmax lanes follow torch.softmax of the row's scores wherever in the row an entry stands and however the row falls
+ *     into chunks: -inf beside a finite score weighs exactly 0; a row holding only -inf, or any +inf or NaN, is NaN in out,
+ *     lse and all its alpha; an empty slot is told by its id.
+ *   Max / min lanes give the max / min over the candidates that are numbers; +-inf are numbers and can win; ties go to the
+ *     lowest position (R4); a NaN candidate never wins and never blocks, in any slot; a channel of a non-empty row whose
+ *     candidates are all NaN gives NaN with winner "none" (255 / -1), so the backward routes nothing for it.  The result
+ *     does not depend on the order of the row's entries except through R4.  (Gather-max, above, reports -inf there; PyG's
+ *     amax propagates a NaN.)
+ *   Clamp lanes keep a NaN, as torch.clamp does: they are written as a comparison, never as fmaxf.
+ *   Locality, forward and backward: a non-finite value in source row j changes the outputs of the rows that list j and
+ *     nothing else; every other output row, and every gradient row of a source or target that shares no row with j, has
+ *     the bits of the run without it. */
 /* ---- GravNet aggregation --------------------------------------------------------------------------------------
  * replaces the propagate step of torch_geometric.nn.GravNetConv (message x_j * exp(-10 d^2), aggr ['mean', 'max']) and
  * its autograd graph, which index_select the [E, P] messages twice and scatter them twice (csrc/gravnet.hip).
@@ -530,6 +546,8 @@ int dmet_gather_sum_bwd_f32(const float *g_out, const int32_t *deg, const int32_
  *   out[i, 0:P]  = (sum_t w h[j,:]) / cnt_i   slots added in ascending t, cnt_i = the number of valid slots (PyG's mean)
  *   out[i, P:2P] = max_t w h[j,p]             arg[Nt, P] uint8 = the winning slot, ties to the lowest slot (R4)
  *   cnt[Nt] int32 = cnt_i.  A row without a valid slot gives zeros in both halves (R3), cnt 0 and arg = 255 ("no winner").
+ *   Non-finite values: the mean half is a sum lane, the max half a max lane over the messages w h[j,p] that are numbers; a
+ *   channel whose messages are all NaN gives NaN with arg 255.
  *   Nothing per edge is written.
  * dmet_gravnet_bwd_f32, with g_msg[i,t,p] = g_out[i,p] / cnt_i + (arg[i,p] == t ? g_out[i,P+p] : 0):
  *   g_h[j,p]     = sum over the (i,t) with nbr[i,t] == j of w g_msg[i,t,p]
@@ -570,8 +588,12 @@ int dmet_gravnet_bwd_f32(const float *s_tgt, const float *s_src, const float *h,
  *   chunking, never on the launch or on the run; a table and a list that hold the same entries in the same order give
  *   the same bits.  A row with no valid entry gives out = 0 (R3) and lse = 0.
  *   alpha[E or Nt*width, H] (may be NULL): the weights, 0 in an empty slot (told by its id).  Nothing else per edge is
- *   written.  Non-finite scores follow the formulas: an entry whose score overflowed to -inf weighs 0 beside a finite
- *   m; a row whose scores are all -inf (or hold +inf or NaN) gives NaN in out, lse and alpha, as torch's softmax does.
+ *   written.  Non-finite scores: a softmax lane.  An entry whose score is -inf weighs exactly 0 beside a finite score,
+ *   wherever it stands -- a first chunk (or any run of chunks) of nothing but such entries leaves l = 0 and acc = 0, and a
+ *   state with m == -inf is rescaled by 0, never by expf(-inf - m); a NaN score makes l NaN and the product with 0 keeps
+ *   it.  A row whose scores are all -inf (or hold +inf or NaN) gives NaN in out, lse and alpha, as torch's softmax does.
+ *   The value sum is a sum lane: a weight of exactly 0 times a non-finite v[j,h,c] is NaN in that channel, as in
+ *   alpha.unsqueeze(-1) * v[src].
  * dmet_attention_bwd_f32, two launches.  By target, with delta[i,h] = sum_c g_out[i,h,c] out[i,h,c]:
  *   alpha_e = expf(score_e - lse[i,h])  (recomputed with the forward's chain),
  *   g_s_e = alpha_e (sum_c g_out[i,h,c] v[j,h,c] - delta[i,h]),   g_q[i,h,:] = (sum_e g_s_e k[j,h,:]) / sqrtf(C)
@@ -619,6 +641,8 @@ int dmet_attention_bwd_f32(const float *q, const float *k, const float *v, const
  *   order, then an xor butterfly over the lanes.  The bits depend on that chunking, never on the launch or on the run; a
  *   table and a list that hold the same entries in the same order give the same bits.  A row with no valid entry gives
  *   out = 0 (R3) and lse = 0; with self_loops a row with no other entry gives out[i,h,:] = xl[i,h,:] exactly.
+ *   Non-finite scores: a softmax lane, as in the attention section; with self_loops a row whose written entries all score
+ *   -inf gives out[i,h,:] = xl[i,h,:] exactly, the self weight 1 and lse = the self score.
  *   alpha[E or Nt*width, H] (may be NULL): the weights of the written entries, 0 in an empty slot and in a skipped
  *   written self loop; the implicit entry's weight is not returned.  Nothing else per edge is written.
  * dmet_gat_bwd_f32, two launches.  By target, with delta[i,h] = sum_c g_out[i,h,c] out[i,h,c] and the score recomputed
@@ -659,17 +683,19 @@ int dmet_gat_bwd_f32(int mode, const float *xl, const float *xr, const float *at
  *   dmet_knn_f32, periodic or not; the value in an empty slot is ignored), x[Ns, F] fp32 the source features.
  *   1 <= k <= DMET_MAX_K, 1 <= F <= 256.
  * dmet_interpolate_fwd_f32, for target i and every valid slot t, j = nbr[i,t]:
- *   w_t = 1.0f / fmaxf(dist[i,t], 1e-16f)
+ *   w_t = 1.0f / (dist[i,t] < 1e-16f ? 1e-16f : dist[i,t])     torch.clamp(min=1e-16): a NaN distance stays NaN (a clamp
+ *                                                              lane), so W_i, r and the whole row of out are NaN
  *   W_i = sum_t w_t                         valid slots in ascending t, fp32
  *   r_t = w_t / W_i
  *   out[i,f] = fmaf(r_t, x[j,f], acc)       valid slots in ascending t, acc from 0
  *   wsum[Nt] fp32: wsum[i] = W_i.  A row without a valid slot gives out[i,:] = 0 exactly (R3) and wsum[i] = 0.
  *   The weights are normalised before the sum (upstream divides the sum): nothing overflows at w = 1e16, the backward
- *   needs r anyway, and the two forms differ by rounding only.  Nothing per edge is written.
+ *   needs r anyway, and the two forms differ by rounding only.  Nothing per edge is written.  out is a sum lane: a
+ *   non-finite x[j,f] shows in feature f of the rows that list j and nowhere else.
  * dmet_interpolate_bwd_f32, by source j over the reverse index rev_ptr[Ns+1], rev_pos[] of
  *   dmet_reverse_index(nbr, Nt*k, Ns), positions p = i*k + t in ascending order:
- *   g_x[j,f] = fmaf(r_p, g_out[i,f], acc)   r_p = (1.0f / fmaxf(dist[p], 1e-16f)) / wsum[i]: the forward's expression, the
- *   same bits.  A source nobody lists gets g_x[j,:] = 0.  A long list is walked by its one owner.
+ *   g_x[j,f] = fmaf(r_p, g_out[i,f], acc)   r_p = w_p / wsum[i] with w_p the forward's expression of dist[p], clamp
+ *   included: the same bits, NaN where the forward's was.  A source nobody lists gets g_x[j,:] = 0.  A long list is walked by its one owner.
  *   There is no gradient into dist (upstream forms the weights under no_grad).
  * No float atomics: sums run in a fixed order, two runs give identical bits.  Every element of out, wsum and g_x is
  * written, not accumulated.  Rows are read and written 16 bytes at a time where F % 4 == 0 and x / out (g_out / g_x)
@@ -693,13 +719,16 @@ int dmet_interpolate_bwd_f32(const float *g_out, const float *dist, const float 
  *   5 var, 6 std; the first zero nibble ends the list; 1 <= A <= 6, each statistic at most once.
  * dmet_multi_aggr_fwd_f32, for target i with valid entries j_1..j_n in ascending position order, per feature f:
  *   sum  = ((0 + x[j_1,f]) + x[j_2,f]) + ...          mean = sum / (float)n
- *   min, max: the first strictly smaller / larger value wins, so the lowest position keeps a tie (R4)
+ *   min, max: over the candidates that are numbers; the first is taken whatever it is (+-inf too), then the first strictly
+ *          smaller / larger value wins, so the lowest position keeps a tie (R4); a NaN never wins and never blocks
  *   var  = (((0 + d_1*d_1) + d_2*d_2) + ...) / (float)n with d_e = x[j_e,f] - mean: a second walk over the row, centred
  *          on the row's own mean (error at most (2n+8) u var + ((n+2) u mean|x|)^2, u = 2^-24)
- *   std  = s = sqrtf(fmaxf(var, 1e-5f)), 0 where s <= sqrtf(1e-5f)
+ *   std  = s = sqrtf(var < 1e-5f ? 1e-5f : var), 0 where s <= sqrtf(1e-5f): the clamp keeps a NaN, so std is NaN where var
+ *          is (a clamp lane); sum, mean and var are sum lanes
  *   out[Nt, G, A, F/G]: statistic a of feature f at out[i, f / (F/G), a, f % (F/G)].  count[Nt] int32 = n.  n == 0: every
  *   statistic 0 exactly (R3).  mean[Nt, F], var[Nt, F] (required with var or std, optional else), argmin[Nt, F] int32
- *   (required with min), argmax[Nt, F] (required with max): the winner's position, -1 in an empty row.
+ *   (required with min), argmax[Nt, F] (required with max): the winner's position, -1 in an empty row.  A feature of a
+ *   non-empty row whose candidates are all NaN gives min / max = NaN with position -1.
  * dmet_multi_aggr_bwd_f32: one launch per target forms c1[i,f] = (2 g_v) / n and c0[i,f] = (g_sum + g_mean / n) -
  *   c1 mean, g_v = g_var + g_std / (2 std) where var > 1e-5 and std > 0, g_v = g_var otherwise, 0 and 0 for n == 0 (c0,
  *   c1: caller's work rows [Nt, F]; c1 only with var or std); then by source j over the positions p of the by-source
@@ -732,7 +761,8 @@ int dmet_multi_aggr_bwd_f32(const float *x, const float *g_out, const int32_t *c
  *   an empty slot is never read into a result: a NaN there changes nothing.
  * dmet_weighted_sum_fwd_f32, for target i with valid entries e_1..e_n in ascending position order, per feature f:
  *   out[i,f] = fmaf(w_e, x[j_e,f], acc) from acc = 0; with w == NULL the step is acc + x[j_e,f], the bits of w all ones.
- *   count[Nt] int32 = n (may be NULL).  n == 0: out[i,:] = 0 exactly (R3), count 0.
+ *   count[Nt] int32 = n (may be NULL).  n == 0: out[i,:] = 0 exactly (R3), count 0.  out is a sum lane: a non-finite
+ *   x[j,f] or w_e shows in the rows that hold it (feature f, or every feature) and nowhere else.
  * dmet_weighted_sum_bwd_f32 runs up to two launches:
  *   by source, when g_x != NULL: for source j over the positions p of the by-source index rev_ptr[Ns+1], rev_pos[]
  *     (dmet_reverse_index over idx) in ascending order, i = p / width or tgt[p]:
@@ -779,7 +809,10 @@ int dmet_weighted_sum_bwd_f32(const float *x, const float *w, const float *g_out
  *     difference of exactly 0
  *   z2_e[o] = b2[o] + sum_c h1_e[c] W2[o,c]   on v_mfma_f32_16x16x4_f32, c in the order 16 B + 4 q + t for B, then t = 0..3,
  *     then the matrix core's own q = 0..3;  m_e = act(z2_e) when act2 else z2_e
- *   out[i,o] = max_e m_e[o] over the row's entries in entry order, strict compares: the earliest entry wins a tie (R4)
+ *   out[i,o] = max_e m_e[o] over the row's entries in entry order, strict compares: the earliest entry wins a tie (R4).
+ *     A max lane: over the messages that are numbers, wherever in the row and in whichever quarter of the wavefront an
+ *     entry stands; a channel of a target with entries whose messages are all NaN gives NaN with win -1.  (ReLU is
+ *     v > 0 ? v : 0, so it turns a NaN pre-activation into 0; ELU carries it on.)
  *   win[Nt,H2] int32: the winning table slot t (table) or grouped list position (list), -2 for the implicit entry, -1
  *     for a target without an entry, whose out row is exactly 0 (R3).  Nothing per edge is written.
  * dmet_pointnet_bwd_f32, with g_z2[i,o] = g_out[i,o] act'(out[i,o]) (act2; else g_out[i,o]) routed to entry win[i,o]:

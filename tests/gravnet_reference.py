@@ -7,6 +7,8 @@ PyG's forward is
     return lin_out1(x_r) + lin_out2(out)
 Here the edges are the valid slots of a fixed-width table nbr[Nt, k] (-1 = empty): slot t of row i is the edge
 nbr[i, t] -> i.  Empty slots are skipped, the max breaks ties to the lowest slot, a row without a valid slot gives zeros.
+The max is taken over the messages that are numbers (nonfinite_contract.nan_skipping_max: a NaN never wins and never
+blocks); a channel of a non-empty row whose messages are all NaN is NaN with no winner.
 """
 import torch
 
@@ -26,12 +28,12 @@ def messages(h, s_src, s_tgt, nbr):
 
 
 def lowest_slot_argmax(msg, valid):
-    """arg[Nt, P] int64: the lowest valid slot holding the row's maximum; k (one past the last slot) for an empty row."""
+    """arg[Nt, P] int64: the lowest valid slot holding the row's maximum over the messages that are numbers; k (one past
+    the last slot) for an empty row and for a channel whose messages are all NaN."""
+    from nonfinite_contract import nan_skipping_max
     k = msg.shape[1]
-    masked = msg.detach().masked_fill(~valid.unsqueeze(-1), float("-inf"))
-    top = masked.amax(1, keepdim=True)
-    slot = torch.arange(k).view(1, k, 1).expand_as(masked)
-    return torch.where((masked == top) & valid.unsqueeze(-1), slot, torch.full_like(slot, k)).amin(1)
+    _top, pos = nan_skipping_max(msg.detach().transpose(1, 2), valid.unsqueeze(1).expand(-1, msg.shape[2], -1))
+    return torch.where(pos < 0, torch.full_like(pos, k), pos)
 
 
 def aggregate(h, s, nbr, s_dst=None, arg=None):
@@ -45,8 +47,10 @@ def aggregate(h, s, nbr, s_dst=None, arg=None):
     mean = msg.sum(1) / cnt.clamp(min=1).unsqueeze(-1).to(msg.dtype)
     own = lowest_slot_argmax(msg, valid)
     use = own if arg is None else arg.long()
+    none = has & (use >= msg.shape[1])                      # entries, but no number among a channel's messages
     use = torch.where(has, use, torch.zeros_like(use)).clamp(max=msg.shape[1] - 1)
     mx = torch.where(has, msg.gather(1, use.unsqueeze(1)).squeeze(1), torch.zeros_like(mean))
+    mx = torch.where(none, torch.full_like(mx, float("nan")), mx)
     with torch.no_grad():
         hinf = h.abs().amax(1) if h.shape[0] else h.new_zeros(1)      # no source: every slot is empty
         bar = torch.where(valid, hinf[nbr.long().clamp(min=0)], torch.zeros((), dtype=h.dtype)).sum(1)

@@ -41,7 +41,10 @@ def positions_of_list(src, rowptr, Ns):
 
 def stats(x, tgt, src, valid, Nt):
     """Per row, in float64 and row by row: dict of sum, mean, min, max, var, std [Nt, F], abs_sum, abs_mean [Nt, F],
-    count [Nt], argmin, argmax [Nt, F] (positions, the lowest on ties, -1 in an empty row)."""
+    count [Nt], argmin, argmax [Nt, F] (positions, the lowest on ties, -1 in an empty row).  min and max are taken over
+    the candidates that are numbers (nonfinite_contract.nan_skipping_min / _max): a NaN never wins and never blocks, a
+    feature whose candidates are all NaN is NaN with position -1."""
+    from nonfinite_contract import nan_skipping_max, nan_skipping_min
     x = x.double()
     F = x.shape[1]
     out = {k: torch.zeros(Nt, F, dtype=torch.float64) for k in KINDS + ("abs_sum", "abs_mean")}
@@ -66,10 +69,11 @@ def stats(x, tgt, src, valid, Nt):
         out["var"][i] = var
         s = var.clamp(min=VAR_FLOOR).sqrt()
         out["std"][i] = torch.where(s <= math.sqrt(VAR_FLOOR), torch.zeros_like(s), s)
-        mn, mx = xs.amin(0), xs.amax(0)
-        out["min"][i], out["max"][i] = mn, mx
-        out["argmin"][i] = ps[(xs == mn).to(torch.int8).argmax(0)]      # argmax: the first of equal values
-        out["argmax"][i] = ps[(xs == mx).to(torch.int8).argmax(0)]
+        every = torch.ones(xs.shape[1], n, dtype=torch.bool)
+        for kind, arg, pick in (("min", "argmin", nan_skipping_min), ("max", "argmax", nan_skipping_max)):
+            val, slot = pick(xs.t(), every)                              # the lowest of equal values
+            out[kind][i] = val
+            out[arg][i] = torch.where(slot >= 0, ps[slot.clamp(min=0)], torch.full_like(slot, -1))
     return out
 
 
@@ -193,7 +197,7 @@ def emulate_fwd(x, tgt, src, valid, Nt, one_pass=False):
             v = x[src[p]]
             s = s + v
             sq = sq + v * v
-            lo, hi = v < mn, v > mx
+            lo, hi = (v < mn) | ((pmn < 0) & ~np.isnan(v)), (v > mx) | ((pmx < 0) & ~np.isnan(v))
             mn, pmn = np.where(lo, v, mn), np.where(lo, p, pmn)
             mx, pmx = np.where(hi, v, mx), np.where(hi, p, pmx)
         mean = s / f32(n)
@@ -205,7 +209,8 @@ def emulate_fwd(x, tgt, src, valid, Nt, one_pass=False):
                 d = x[src[p]] - mean
                 acc = acc + d * d
             var = acc / f32(n)
-        sd = np.sqrt(np.maximum(var, f32(VAR_FLOOR)))
+        sd = np.sqrt(np.where(var < f32(VAR_FLOOR), f32(VAR_FLOOR), var))       # the clamp keeps a NaN
+        mn, mx = np.where(pmn < 0, f32(np.nan), mn), np.where(pmx < 0, f32(np.nan), mx)
         out["count"][i] = n
         out["sum"][i], out["mean"][i], out["min"][i], out["max"][i], out["var"][i] = s, mean, mn, mx, var
         out["std"][i] = np.where(sd <= np.sqrt(f32(VAR_FLOOR)), f32(0), sd)

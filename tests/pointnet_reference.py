@@ -9,7 +9,9 @@ Here local_nn = Linear(W1, b1) - act - Linear(W2, b2) [- act], act ReLU or ELU(a
 entry list (tgt, src, code, is_self) grouped by target: the valid slots of a table row in slot order, or a grouped edge
 list in position order, then -- with self loops -- one added entry i -> i (code -2, position difference exactly 0) after
 the row's own, the written entries j == i having been dropped.  `code` is what the kernels' win holds for the entry: the
-table slot or the list position.  Ties go to the earliest entry (R4).
+table slot or the list position.  Ties go to the earliest entry (R4).  The max is taken over the messages that are numbers
+(nonfinite_contract.nan_skipping_max: a NaN never wins and never blocks); a channel of a target with entries whose
+messages are all NaN is NaN with win -1.
 
 Bounds.  u = 2^-24.  A value formed by a chain of fused multiply-adds s_k = fl(s_{k-1} + t_k) from s_0 carries, to first
 order, at most u * sum_k |s_k| of rounding error: one rounding of magnitude at most u |s_k| per step.  The kernels form
@@ -92,6 +94,7 @@ class Reference:
     gradients.  All float64 CPU tensors; x may be None (F = 0); b1 / b2 may be None."""
 
     def __init__(self, x, pos_src, pos_dst, W1, b1, W2, b2, act, act2, entries, num_targets):
+        from nonfinite_contract import nan_skipping_max
         tgt, src, code, is_self = entries
         d = lambda t: None if t is None else t.detach().cpu().to(F64)
         x, pos_src, pos_dst, W1, b1, W2, b2 = map(d, (x, pos_src, pos_dst, W1, b1, W2, b2))
@@ -146,11 +149,11 @@ class Reference:
             if hi == lo:
                 continue
             mi = self.m[lo:hi]
-            top = mi.max(0).values
-            first = (mi == top).to(torch.int64).argmax(0)                      # the earliest entry holding the maximum
+            top, first = nan_skipping_max(mi.t(), torch.ones(H2, hi - lo, dtype=torch.bool))   # the earliest entry holding it
             self.out[i] = top
-            self.win_e[i] = lo + first
-            self.win[i] = code[lo + first]
+            self.win_e[i] = torch.where(first >= 0, lo + first, first)
+            self.win[i] = torch.where(first >= 0, code[lo + first.clamp(min=0)], first)
+            first = first.clamp(min=0)
             if hi - lo > 1:
                 cols = torch.arange(H2)
                 rest = mi.clone()
