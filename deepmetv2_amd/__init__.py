@@ -28,6 +28,8 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import TopKPooling, SAGPooling        # torch_geometric.nn
     from deepmetv2_amd import topk, filter_adj               # torch_geometric.nn.pool.select / .connect (filter_table: tables)
     from deepmetv2_amd import SortAggregation, global_sort_pool   # torch_geometric.nn.aggr / torch_geometric.nn
+    from deepmetv2_amd import grid_cluster                   # torch_cluster
+    from deepmetv2_amd import voxel_grid, consecutive_cluster   # torch_geometric.nn / torch_geometric.nn.pool.consecutive
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -44,8 +46,8 @@ from .scatter import (met_reduce, scatter_add, scatter_log_softmax, scatter_logs
                       scatter_min, scatter_softmax, scatter_std, scatter_sum, segment_csr, softmax)
 from .aggr import AttentionalAggregation
 from .nn import accelerate
-from .pool import (avg_pool, avg_pool_x, global_add_pool, global_max_pool, global_mean_pool, graclus, max_pool,
-                   max_pool_x, normalized_cut, normalized_cut_2d)
+from .pool import (avg_pool, avg_pool_x, consecutive_cluster, global_add_pool, global_max_pool, global_mean_pool, graclus,
+                   grid_cluster, max_pool, max_pool_x, normalized_cut, normalized_cut_2d, voxel_grid)
 from .drn import DynamicReductionNetwork
 from .gravnet import GravNetConv, gravnet_aggregate
 from .attention import TransformerConv, attention_aggregate
@@ -66,6 +68,7 @@ __all__ = [
     "u_perp_par_loss", "to_undirected", "raise_deferred_errors", "accelerate", "build_async", "GraphFuture", "Batch", "EventLoader", "DeviceLoader", "collate", "events_from_padded",
     "graclus", "normalized_cut", "normalized_cut_2d", "max_pool", "max_pool_x", "avg_pool", "avg_pool_x",
     "global_max_pool", "global_mean_pool", "global_add_pool", "DynamicReductionNetwork",
+    "grid_cluster", "voxel_grid", "consecutive_cluster",
     "GravNetConv", "gravnet_aggregate", "TransformerConv", "attention_aggregate", "fps", "nearest",
     "knn_interpolate", "interpolate_aggregate", "PointNetConv", "PointConv", "pointnet_aggregate",
     "GATConv", "GATv2Conv", "gat_aggregate", "gat_v1_aggregate",

@@ -2956,3 +2956,65 @@ def _filter_edges(edge_index: torch.Tensor, node_map: torch.Tensor) -> Tuple[tor
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
     return out, kept, nbad
+
+
+# ---- voxel clustering (csrc/voxel.hip) -----------------------------------------------------------------------------------
+VOXEL_MAX_DIM = 8           # DMET_VOXEL_MAX_DIM
+
+
+def _voxel_cells(pos: torch.Tensor, grid: torch.Tensor, ptr: torch.Tensor,
+                 batch: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(id[N] int64, cell[N] int32 holding the uint32 event-local cell ids, nvox[D + 1] int64, flags[2] int32) of
+    dmet_voxel_cells_f32 for pos[N, D] fp32 and grid[3, D] fp32 = (size, start, end) on the device.  flags[0]: the cell
+    count of an event passed 2^32 - 1 and was cut; flags[1]: batch disagrees with ptr."""
+    dev = _require_device(pos, grid, ptr, batch)
+    pos = _f32c(pos.detach(), "pos")
+    if pos.dim() != 2 or not 1 <= pos.shape[1] <= VOXEL_MAX_DIM:
+        raise ValueError(f"pos must be [N, D] with 1 <= D <= {VOXEL_MAX_DIM}, got {tuple(pos.shape)}")
+    N, D = pos.shape
+    grid = _f32c(grid, "grid")
+    if tuple(grid.shape) != (3, D):
+        raise ValueError(f"grid must be [3, {D}], got {tuple(grid.shape)}")
+    ptr = _sel_vec(ptr, "ptr", torch.int64)
+    B = ptr.numel() - 1
+    batch = _sel_vec(batch, "batch", torch.int64, N) if batch is not None else None
+    ids = torch.empty((N,), dtype=torch.int64, device=dev)
+    cell = torch.empty((N,), dtype=torch.int32, device=dev)
+    nvox = torch.empty((D + 1,), dtype=torch.int64, device=dev)
+    flags = torch.empty((2,), dtype=torch.int32, device=dev)
+    _t = timer.record('voxel_cells', dev)
+    with _on(dev):
+        _lib.check(_lib.load().dmet_voxel_cells_f32(_ptr(pos), N, D, grid.data_ptr(), ptr.data_ptr(), B, _ptr(batch),
+                                                    nvox.data_ptr(), flags.data_ptr(), _ptr(ids), _ptr(cell), _stream(dev)),
+                   "dmet_voxel_cells_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return ids, cell, nvox, flags
+
+
+def _voxel_coarsen(cell: torch.Tensor, ptr: torch.Tensor):
+    """(node_map[N] int64, order[N] int64, rowptr[N + 1] int32, batch[N] int64, ptr[B + 1] int64, record[3] int64) of
+    dmet_voxel_coarsen for the event-local cell ids of _voxel_cells, N > 0.  rowptr and batch are written up to C + 1 and
+    C entries, C = record[0] (left on the device: the caller reads the record and cuts them)."""
+    dev = _require_device(cell, ptr)
+    L = _lib.load()
+    cell = _sel_vec(cell, "cell", torch.int32)
+    ptr = _sel_vec(ptr, "ptr", torch.int64)
+    N, B = cell.numel(), ptr.numel() - 1
+    if N < 1 or B < 1:
+        raise ValueError(f"voxel_coarsen: needs nodes and events, got N={N}, B={B}")
+    node_map = torch.empty((N,), dtype=torch.int64, device=dev)
+    order = torch.empty((N,), dtype=torch.int64, device=dev)
+    rowptr = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+    out_batch = torch.empty((N,), dtype=torch.int64, device=dev)
+    out_ptr = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+    record = torch.empty((3,), dtype=torch.int64, device=dev)
+    _t = timer.record('voxel_coarsen', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_voxel_coarsen_workspace_bytes(N, B), dev)
+        _lib.check(L.dmet_voxel_coarsen(cell.data_ptr(), ptr.data_ptr(), B, N, node_map.data_ptr(), order.data_ptr(),
+                                        rowptr.data_ptr(), out_batch.data_ptr(), out_ptr.data_ptr(), record.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_voxel_coarsen")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return node_map, order, rowptr, out_batch, out_ptr, record

@@ -14,7 +14,8 @@ LIB_PATH = os.path.join(PKG_DIR, "libdmet_hip.so")
 SOURCES = ["knn.hip", "radius.hip", "edgeconv.hip", "edgemlp.hip", "misc.hip", "dense.hip", "encoder.hip", "norm.hip", "edgeconv_bwd.hip",
            "head.hip", "finalize.hip", "pool.hip",
            "edgemlp_f32.hip", "edgemlp_bf16.hip", "edgeconv_sum.hip", "gravnet.hip", "attention.hip", "fps.hip", "interpolate.hip",
-           "pointnet.hip", "gat.hip", "segment.hip", "multi_aggr.hip", "weighted_sum.hip", "event_norm.hip", "select.hip"]
+           "pointnet.hip", "gat.hip", "segment.hip", "multi_aggr.hip", "weighted_sum.hip", "event_norm.hip", "select.hip",
+           "voxel.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "bn_affine.h", "knn_common.h", "knn_filter.h", "knn_key64.h", "knn_tile_schedule.h",
                                            "nls_body.h",
                                            "edgemlp_fused.h", "row_softmax.h")] + \

@@ -17,11 +17,23 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from .graph import BatchInfo, _registry_get, _registry_put, batch_info, coalesced_tag, lookup_graph, register_batch
+from .graph import (BatchInfo, _batch_registry, _deferred, _registry_get, _registry_put, batch_info, coalesced_tag, lookup_graph,
+                    register_batch)
 from .scatter import _SegmentMaxRows, _SegmentSumRows, scatter_add
 
 # graclus output tensor -> partner[N] int32 (the pair-pooling path takes it; any other cluster vector is general)
 _graclus_registry = {}
+# voxel_grid / grid_cluster output tensor -> _VoxelRecord (same weak-reference registry, same caveat: an in-place write
+# bumps the version and drops the entry; a write through .data or from a kernel does not)
+_voxel_registry = {}
+
+VOXEL_MAX_DIM = _native.VOXEL_MAX_DIM
+VOXEL_MAX_CELLS = 2 ** 32 - 1           # cells of one event: the kernels keep the event-local cell id as a uint32
+# Largest event whose result is registered for the one-launch coarsening.  Up to _native.SELECT_LDS_NODES nodes an event
+# is ranked in LDS; above, ONE workgroup ranks it through L2 in the workspace, log2(n)^2 / 2 passes over 16 n bytes.  At
+# 2^17 nodes that is 153 passes over 2 MiB, about where a global radix sort of the whole batch catches up: larger events
+# (and N above this without a batch) take the generic branch.
+VOXEL_MAX_EVENT = 1 << 17
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -109,6 +121,168 @@ def normalized_cut_2d(edge_index: torch.Tensor, pos: torch.Tensor) -> torch.Tens
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# voxel clustering
+# ---------------------------------------------------------------------------------------------------------------
+class _VoxelRecord:
+    """What voxel_grid / grid_cluster know about the tensor they returned: the event-local cell ids, the events, and --
+    once somebody pooled it -- the coarsening (dmet_voxel_coarsen, run lazily: a caller who only wants the ids pays the
+    cells launch alone)."""
+    __slots__ = ("cell", "ptr", "B", "has_batch", "N", "result")
+
+    def __init__(self, cell, ptr, B, has_batch, N):
+        self.cell, self.ptr, self.B, self.has_batch, self.N = cell, ptr, B, has_batch, N
+        self.result = None
+
+    def coarsen(self):
+        """(node_map, order, rowptr[C + 1], pooled batch[C], pooled ptr, C, largest, smallest pooled event); the first
+        call makes the one host read (the record of three numbers)."""
+        if self.result is None:
+            node_map, order, rowptr, pb, ptr, record = _native._voxel_coarsen(self.cell, self.ptr)
+            C, mx, mn = (int(v) for v in record.tolist())
+            self.result = (node_map, order, rowptr[: C + 1], pb[:C], ptr, C, mx, mn)
+        return self.result
+
+
+def _voxel_spec(who: str, name: str, value, D: int):
+    """size / start / end as the caller gave it -> a list of D host floats, or a [D] fp32 tensor left on its device."""
+    if isinstance(value, torch.Tensor):
+        if value.dim() > 1 or value.numel() not in (1, D):
+            raise ValueError(f"{who}: {name} must be a number or hold {D} values (one per dimension of pos), got "
+                             f"{tuple(value.shape)}")
+        if value.device.type == "cpu":
+            value = value.reshape(-1).tolist()
+        else:
+            return value.detach().to(torch.float32).reshape(-1).expand(D)
+    if not hasattr(value, "__iter__"):
+        return [float(value)] * D
+    value = [float(v) for v in value]
+    if len(value) == 1 and D > 1:
+        value = value * D
+    if len(value) != D:
+        raise ValueError(f"{who}: {name} must be a number or hold {D} values (one per dimension of pos), got {len(value)}")
+    return value
+
+
+def _host_cells(size, start, end) -> int:
+    """The cell count of one event from host numbers, by the kernel's rule: fp32 throughout, trunc(q) + 1 per dimension,
+    1 for a NaN, infinite or negative q."""
+    q = (torch.tensor(end, dtype=torch.float32) - torch.tensor(start, dtype=torch.float32)) / torch.tensor(size, dtype=torch.float32)
+    cells = 1
+    for v in q.tolist():
+        cells *= int(v) + 1 if v >= 0.0 and v != float("inf") else 1
+    return cells
+
+
+def _voxel(who: str, pos: torch.Tensor, size, batch: Optional[torch.Tensor], start, end) -> torch.Tensor:
+    if not isinstance(pos, torch.Tensor) or not pos.dtype.is_floating_point or pos.dtype == torch.float64:
+        raise TypeError(f"{who}: pos must be a float32, bfloat16 or float16 tensor, got "
+                        f"{pos.dtype if isinstance(pos, torch.Tensor) else type(pos).__name__}")
+    if pos.dim() == 1:
+        pos = pos.unsqueeze(1)
+    if pos.dim() != 2 or not 1 <= pos.shape[1] <= VOXEL_MAX_DIM:
+        raise ValueError(f"{who}: pos must be [N, D] or [N] with 1 <= D <= {VOXEL_MAX_DIM}, got {tuple(pos.shape)}")
+    N, D = pos.shape
+    spec = {"size": _voxel_spec(who, "size", size, D)}
+    for name, value in (("start", start), ("end", end)):
+        spec[name] = _voxel_spec(who, name, value, D) if value is not None else None
+    if isinstance(spec["size"], list):
+        s32 = torch.tensor(spec["size"], dtype=torch.float32)
+        if not bool(((s32 > 0) & torch.isfinite(s32)).all()):
+            raise ValueError(f"{who}: size must be positive and finite in fp32, got {spec['size']}")
+    host_known = all(isinstance(v, list) for v in spec.values())
+    if host_known:
+        cells = _host_cells(spec["size"], spec["start"], spec["end"])
+        if cells > VOXEL_MAX_CELLS:
+            # B cells <= 2^63 - 1 then holds for every B <= 2^31 - 1, the largest event count the package takes
+            raise ValueError(f"{who}: the grid has {cells} cells per event, more than 2^32 - 1")
+    dev = _native._require_device(pos, batch, *[v for v in spec.values() if isinstance(v, torch.Tensor)])
+    if N == 0:
+        if batch is not None:
+            batch_info(batch, N, dev)
+        return torch.zeros(0, dtype=torch.int64, device=dev)
+    check_batch = False
+    if batch is not None:
+        check_batch = _registry_get(_batch_registry, batch) is not None      # else batch_info reads and checks it here
+        binfo = batch_info(batch, N, dev)
+    else:
+        binfo = BatchInfo(torch.arange(0, N + 1, N, dtype=torch.int64, device=dev), 1, N, N, N)      # [0, N], no copy
+    posf = pos.detach().to(torch.float32).contiguous()
+
+    def upload(rows):       # host numbers through pinned memory: a pageable copy would stall the launch thread
+        return torch.tensor(rows, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
+
+    if host_known:
+        grid = upload([spec["size"], spec["start"], spec["end"]])
+    else:
+        rows = []
+        for name, own in (("size", None), ("start", torch.amin), ("end", torch.amax)):
+            v = spec[name]
+            rows.append(own(posf, 0) if v is None else upload(v) if isinstance(v, list) else v)
+        grid = torch.stack(rows)
+    _deferred.poll()
+    ids, cell, _nvox, flags = _native._voxel_cells(posf, grid, binfo.ptr, batch if check_batch else None)
+    capturing = torch.cuda.is_current_stream_capturing()       # a captured graph cannot report: as _check_full_rows
+    if not host_known and not capturing:
+        _deferred.post(flags[0:1], f"{who}: the grid has more than 2^32 - 1 cells per event; its cell counts were cut and "
+                                   "the ids clamped to them")
+    if check_batch and not capturing:
+        _deferred.post(flags[1:2], f"{who}: batch is not the sorted vector it was registered as; the ids follow the "
+                                   "registered ptr")
+    if binfo.max_nodes is not None and binfo.max_nodes <= VOXEL_MAX_EVENT:
+        _registry_put(_voxel_registry, ids, _VoxelRecord(cell, binfo.ptr, binfo.num_events, batch is not None, N))
+    return ids
+
+
+def grid_cluster(pos: torch.Tensor, size, start=None, end=None) -> torch.Tensor:
+    """torch_cluster.grid_cluster: the voxel of every point, int64 [N].  pos [N, D] or [N], 1 <= D <= 8, fp32 (bf16 /
+    fp16 are upcast exactly; float64 is a TypeError); size / start / end a number, D numbers or a [D] tensor; start / end
+    default to pos.min(0) / pos.max(0).  In fp32, one rounding for the subtraction and one for the division:
+
+        nvox_d = trunc((end_d - start_d) / size_d) + 1,  c_d = trunc((pos_d - start_d) / size_d),
+        id = sum_d c_d * prod_{d' < d} nvox_d'
+
+    upstream's value bit for bit for finite pos inside [start, end].  Where upstream returns garbage: c_d is clamped to
+    [0, nvox_d - 1], a NaN coordinate goes to cell 0, a non-finite or negative (end - start) / size gives nvox_d = 1.
+    size <= 0 or non-finite, and more than 2^32 - 1 cells, are a ValueError when given as host numbers; a grid computed on
+    the device (a device tensor, or start / end = None) that has too many cells is cut, its ids clamped, and a deferred
+    check reports it (the next operator call or raise_deferred_errors()).  No host sync.  Not differentiable.
+    The result is registered (events of up to 2^17 nodes): pooling it takes the one-launch coarsening."""
+    return _voxel("grid_cluster", pos, size, None, start, end)
+
+
+def voxel_grid(pos: torch.Tensor, size, batch: Optional[torch.Tensor] = None, start=None, end=None) -> torch.Tensor:
+    """torch_geometric.nn.voxel_grid: grid_cluster with the batch id appended as one more coordinate of size 1, start 0
+    and end B - 1, so id = cell + event * cells: the event is the most significant digit.  B and the events come from
+    the registered batch (register_batch, a Batch, a pooled batch) without a host sync, with or without start / end; any
+    other batch vector is read once (batch_info), where an unsorted one is a ValueError.  A registered batch that is not
+    the sorted vector it was registered as is reported by a deferred check.  start / end = None are pos.min(0) /
+    pos.max(0) over the whole batch, as upstream.  Rules, refusals and registration as grid_cluster."""
+    return _voxel("voxel_grid", pos, size, batch, start, end)
+
+
+def consecutive_cluster(src: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """torch_geometric.nn.pool.consecutive.consecutive_cluster: (node_map int64 [N], perm int64 [C]).  node_map[i] is
+    the rank of src[i] among the sorted unique values; perm[c] is the HIGHEST node index of cluster c.  That is upstream's
+    CPU result; upstream's GPU result is unspecified (a scatter with duplicate indices: whichever write lands last), this
+    one is the same on every run.  A voxel_grid / grid_cluster result takes the one-launch coarsening; any other vector
+    goes through torch.unique.  One host sync (C)."""
+    _native._require_device(src)
+    if src.dim() != 1:
+        raise ValueError(f"consecutive_cluster: src must be 1-D, got {tuple(src.shape)}")
+    N = src.numel()
+    if N == 0:
+        return torch.zeros(0, dtype=torch.int64, device=src.device), torch.zeros(0, dtype=torch.int64, device=src.device)
+    vox = _registry_get(_voxel_registry, src)
+    if vox is not None and vox.N == N:
+        node_map, order, rowptr = vox.coarsen()[:3]
+        return node_map, order.index_select(0, rowptr[1:].to(torch.int64) - 1)
+    uniq, inv = torch.unique(src, sorted=True, return_inverse=True)
+    perm = torch.full((uniq.numel(),), -1, dtype=torch.int64, device=src.device).scatter_reduce_(
+        0, inv, torch.arange(N, dtype=torch.int64, device=src.device), "amax")
+    return inv, perm
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # cluster pooling
 # ---------------------------------------------------------------------------------------------------------------
 class _PairPool(torch.autograd.Function):
@@ -160,6 +334,16 @@ class _Coarsening:
             self.C, self.max_nodes, self.min_nodes = C, mx, mn
             self._pair_ptr = binfo.ptr
             self._sorted = True
+            return
+        vox = _registry_get(_voxel_registry, cluster)
+        if vox is not None and vox.N == N and N > 0 and cluster.dim() == 1 and (
+                vox.ptr is binfo.ptr if batch is not None else not vox.has_batch):
+            # voxel_grid / grid_cluster ids over these very events: one ranking per event (dmet_voxel_coarsen) instead of
+            # the global sort below; the same attributes, the same one host read
+            self.node_map, self.order, self.rowptr, pb, ptr, self.C, mx, mn = vox.coarsen()
+            self._sorted = True
+            if batch is not None:
+                self.batch, self.ptr, self.max_nodes, self.min_nodes = pb, ptr, mx, mn
             return
         # any other cluster vector: PyG's consecutive_cluster (ids ranked by sorted unique value)
         if cluster.dim() != 1 or cluster.numel() != N:

@@ -1303,6 +1303,52 @@ int dmet_filter_edges_write(const int64_t *row, const int64_t *col, int64_t E, c
                             const void *ws, size_t ws_bytes, int64_t Eout, int64_t *out_index, int64_t *kept,
                             dmet_stream_t stream);
 
+/* ---- Voxel clustering: torch_cluster's grid_cluster, PyG's voxel_grid and consecutive_cluster (csrc/voxel.hip) -----------
+ * dmet_voxel_cells_f32 replaces torch_cluster.grid_cluster(pos, size, start, end) and, with events, PyG's
+ *   voxel_grid(pos, size, batch, start, end).  pos[N,D] fp32, 1 <= D <= DMET_VOXEL_MAX_DIM.  grid[3,D] fp32 in DEVICE
+ *   memory: row 0 the cell sizes, row 1 start, row 2 end (the caller fills in pos.min(0) / pos.max(0) where upstream
+ *   would).  Event b owns the nodes ptr[b] .. ptr[b+1]-1 (non-decreasing, ptr[0] = 0, ptr[B] = N: the caller's
+ *   precondition; a node's event is found from ptr, one binary search per workgroup and a walk of at most B steps).
+ *   Two launches.  The first, one thread, writes nvox[0..D): nvox_d = trunc((end_d - start_d) / size_d) + 1 in fp32, 1 when
+ *   that quotient is NaN, infinite or negative; nvox[D] = cells = their product, and flags[0] = 1 when the product would pass
+ *   2^32 - 1: the count that passes it is cut so that cells fits (B cells <= 2^63 - 1 follows from B <= 2^31 - 1).
+ *   The second, one node per thread: c_d = trunc((pos_d - start_d) / size_d), the subtraction and the correctly rounded
+ *   division one fp32 rounding each, clamped to [0, nvox_d - 1] (NaN and -inf: 0, +inf: nvox_d - 1);
+ *   cell[i] = sum_d c_d prod_{d' < d} nvox_d' (uint32, event-local) and id[i] = cell[i] + b cells (int64): upstream's value
+ *   for every finite pos inside [start, end], the event being the most significant digit as PyG's appended batch
+ *   coordinate makes it.  batch (int64 [N], may be NULL): flags[1] = 1 when some batch[i] differs from the event ptr
+ *   gives, else 0.  N = 0: only the first launch.
+ *
+ * dmet_voxel_coarsen replaces PyG's consecutive_cluster and what the pooling operators derive from it (a global stable
+ *   sort, unique, scatter, searchsorted) for ids of the form above.  Two launches.  The first, one workgroup per event: the
+ *   event's nodes ranked ascending by the 64-bit key (cell << 32 | local index) -- distinct keys, padded with ~0 to a power
+ *   of two, so the bitonic network has one answer, the stable order -- a mark on each position whose cell differs from its
+ *   predecessor's, the marks prefix-summed by wavefront ballots.  An event of up to DMET_SELECT_LDS_NODES nodes keeps its
+ *   keys in LDS (128 KiB of keys, 144 KiB with one spare slot per eight against bank conflicts; one workgroup per CU); a
+ *   larger one keeps the same array, unpadded, in the workspace at ws[2 lo ..) and runs the same code (same bits).  Three
+ *   stages of the network run as one pass over the keys, in registers.  The second, one workgroup per event, adds up the B cluster counts (exclusive for its own offset) and writes:
+ *   node_map[N] int64, the consecutive cluster id of every node (= unique(id, sorted, return_inverse)[1]);
+ *   order[N] int64, the nodes grouped by cluster, ascending node index inside one (= sort(id, stable)[1]);
+ *   rowptr[0..C] int32, cluster c is order[rowptr[c] .. rowptr[c+1]), rowptr[C] = ptr[B]; out_batch[0..C) int64, the event
+ *   of every cluster; out_ptr[B+1] int64, the clusters of event b are out_ptr[b] .. out_ptr[b+1]-1;
+ *   record[3] int64 = (C, the largest and the smallest number of clusters in one event).  rowptr holds N + 1 entries and
+ *   out_batch N; entries beyond C + 1 and C are not written.  Nodes no event owns get node_map = order = -1.
+ *   No atomics, integer arithmetic only: bit-identical from run to run whatever the buffers held.
+ *   Limits: N <= 2^31-1, any n_b.  B == 0: returns 0 at once; N == 0 with B > 0 is refused (the caller fills the empty
+ *   result).
+ *
+ *   Both entries: -EINVAL with a dmet_last_error() message naming the argument, before any HIP call, for a bad size, a
+ *   small workspace or a NULL operand of a non-empty problem.  Asynchronous on `stream`, no allocation, no global state. */
+#define DMET_VOXEL_MAX_DIM 8            /* D of dmet_voxel_cells_f32 */
+#define DMET_VOXEL_THREADS 1024         /* workgroup of an event in dmet_voxel_coarsen */
+int dmet_voxel_cells_f32(const float *pos, int64_t N, int D, const float *grid, const int64_t *ptr, int B,
+                         const int64_t *batch, int64_t *nvox, int32_t *flags, int64_t *id, uint32_t *cell,
+                         dmet_stream_t stream);
+size_t dmet_voxel_coarsen_workspace_bytes(int64_t N, int B);
+int dmet_voxel_coarsen(const uint32_t *cell, const int64_t *ptr, int B, int64_t N, int64_t *node_map, int64_t *order,
+                       int32_t *rowptr, int64_t *out_batch, int64_t *out_ptr, int64_t *record, void *ws, size_t ws_bytes,
+                       dmet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
