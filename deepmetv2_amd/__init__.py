@@ -30,6 +30,7 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import SortAggregation, global_sort_pool   # torch_geometric.nn.aggr / torch_geometric.nn
     from deepmetv2_amd import grid_cluster                   # torch_cluster
     from deepmetv2_amd import voxel_grid, consecutive_cluster   # torch_geometric.nn / torch_geometric.nn.pool.consecutive
+    from deepmetv2_amd import EdgePooling                    # torch_geometric.nn (edge_matching: its _merge_edges)
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -60,6 +61,7 @@ from .gcn import GCNConv, GINConv, GraphConv, SAGEConv, gcn_norm
 from .event_norm import (GraphNorm, GraphSizeNorm, InstanceNorm, LayerNorm, MeanSubtractionNorm, PairNorm, event_moments,
                          event_normalize)
 from .select import SAGPooling, SortAggregation, TopKPooling, filter_adj, filter_table, global_sort_pool, topk
+from .edge_pool import EdgePooling, edge_matching
 
 __all__ = [
     "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "knn_xy_table", "radius", "radius_graph", "radius_table",
@@ -79,5 +81,6 @@ __all__ = [
     "GraphNorm", "InstanceNorm", "LayerNorm", "PairNorm", "GraphSizeNorm", "MeanSubtractionNorm", "event_moments",
     "event_normalize",
     "TopKPooling", "SAGPooling", "SortAggregation", "global_sort_pool", "topk", "filter_adj", "filter_table",
+    "EdgePooling", "edge_matching",
 ]
 __version__ = "0.1.0"

@@ -3018,3 +3018,49 @@ def _voxel_coarsen(cell: torch.Tensor, ptr: torch.Tensor):
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
     return node_map, order, rowptr, out_batch, out_ptr, record
+
+
+# ---- edge pooling (csrc/edge_match.hip) ------------------------------------------------------------------------------------
+EDGE_MATCH_LDS_NODES = 16384    # DMET_EDGE_MATCH_LDS_NODES: the largest event whose state words stay in LDS
+
+
+def _edge_match(rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, perm: Optional[torch.Tensor],
+                score: torch.Tensor, ptr: torch.Tensor, want_rounds: bool = False):
+    """(cluster[N] int64, partner[N] int32, edge[N] int64, rounds[B] int32 or None, flags[3] int32) of dmet_edge_match_f32
+    for edges grouped by target (rowptr[N + 1], src[E], tgt[E] int32), perm[E] int32 = the caller-order id of every
+    grouped position (None: the position), score[E] by grouped position.  flags: an end outside [0, N) | an edge across
+    two events | the round bound was reached."""
+    dev = _require_device(rowptr, src, tgt, perm, score, ptr)
+    L = _lib.load()
+    rowptr = _sel_vec(rowptr, "rowptr", torch.int32)
+    if rowptr.numel() < 1:
+        raise TypeError("edge_match: rowptr must hold N + 1 entries")
+    N = rowptr.numel() - 1
+    src = _sel_vec(src, "src", torch.int32)
+    E = src.numel()
+    tgt = _sel_vec(tgt, "tgt", torch.int32, E)
+    perm = _sel_vec(perm, "perm", torch.int32, E) if perm is not None else None
+    score = _sel_vec(_f32c(score.detach(), "score"), "score", torch.float32, E)
+    ptr = _sel_vec(ptr, "ptr", torch.int64)
+    if ptr.numel() < 1:
+        raise TypeError("edge_match: ptr must hold B + 1 entries")
+    B = ptr.numel() - 1
+    if B > 0 and N > 0:
+        cluster = torch.empty((N,), dtype=torch.int64, device=dev)
+        partner = torch.empty((N,), dtype=torch.int32, device=dev)
+        edge = torch.empty((N,), dtype=torch.int64, device=dev)
+    else:       # no event owns a node: the kernel is not launched
+        cluster = torch.arange(N, dtype=torch.int64, device=dev)
+        partner = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        edge = torch.full((N,), -1, dtype=torch.int64, device=dev)
+    rounds = torch.empty((B,), dtype=torch.int32, device=dev) if want_rounds else None
+    flags = torch.empty((3,), dtype=torch.int32, device=dev)
+    _t = timer.record('edge_match', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_edge_match_workspace_bytes(N, E), dev)
+        _lib.check(L.dmet_edge_match_f32(rowptr.data_ptr(), _ptr(src), _ptr(tgt), _ptr(perm), _ptr(score), E, ptr.data_ptr(), B, N,
+                                         _ptr(cluster), _ptr(partner), _ptr(edge), _ptr(rounds), flags.data_ptr(), _ptr(ws),
+                                         ws.numel(), _stream(dev)), "dmet_edge_match_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return cluster, partner, edge, rounds, flags

@@ -1,6 +1,7 @@
 // select.hip -- score-based selection pooling (torch_geometric's topk / filter_adj, TopKPooling, SAGPooling,
 // SortAggregation).  Semantics: include/dmet.h, section "Selection pooling".
 #include "common.h"
+#include "score_key.h"
 
 namespace dmet {
 namespace {
@@ -12,21 +13,7 @@ constexpr int kEdgeThreads = DMET_SELECT_EDGE_BLOCK;  // filter_edges: one edge 
 constexpr int kEdgeWaves = kEdgeThreads / kWave;
 static_assert(kEdgeWaves <= kWave, "the wave counts of an edge block are scanned by one wave");
 
-// "largest canonical score, lowest index" as one unsigned comparison.  High word: the order-preserving map of the fp32
-// bits (sign set: all bits flipped, else the sign bit set), after -0.0 became +0.0 and every NaN 0xFFFFFFFF (above +inf,
-// whose image is 0xFF800000).  Low word: ~local index.  Keys of an event are distinct and > 0, the key of a padding slot.
-__device__ __forceinline__ uint64_t select_key(float v, uint32_t i)
-{
-    uint32_t u = __float_as_uint(v);
-    uint32_t hi;
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) {
-        hi = 0xFFFFFFFFu;
-    } else {
-        if (u == 0x80000000u) u = 0u;
-        hi = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    return ((uint64_t)hi << 32) | (uint64_t)(uint32_t)~i;
-}
+// select_key (score_key.h) with the local index: keys of an event are distinct and > 0, the key of a padding slot.
 
 // Descending bitonic network over key[0 .. P), P a power of two, by the whole workgroup: P / 2 compare-exchanges per
 // stage, pair t of a stage with stride j is (i, i | j) with i = t's bits with a 0 inserted at bit log2(j); one barrier

@@ -440,13 +440,17 @@ def avg_pool_x(cluster: torch.Tensor, x: torch.Tensor, batch: Optional[torch.Ten
     return _pool_x(cluster, x, batch, size, "mean")
 
 
-def pool_edge(node_map: torch.Tensor, edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor], C: int):
+def pool_edge(node_map: torch.Tensor, edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor], C: int, *,
+              self_loops: bool = False):
     """PyG's pool_edge: map the endpoints to pooled rows, drop self loops, coalesce (edge_attr summed over duplicates).
-    Plain torch bookkeeping plus the package's deterministic scatter_add."""
+    Plain torch bookkeeping plus the package's deterministic scatter_add.  self_loops=True keeps the self loops, the
+    edges inside a cluster among them: coalesce(node_map[edge_index]), what EdgePooling returns."""
     ei = node_map[edge_index.reshape(-1)].view(2, -1)
-    keep = ei[0] != ei[1]
-    ei = ei[:, keep]
-    attr = edge_attr[keep] if edge_attr is not None else None
+    attr = edge_attr
+    if not self_loops:
+        keep = ei[0] != ei[1]
+        ei = ei[:, keep]
+        attr = edge_attr[keep] if edge_attr is not None else None
     if ei.numel() == 0:
         return ei, attr
     key, inv = torch.unique(ei[0] * C + ei[1], sorted=True, return_inverse=True)

@@ -1349,6 +1349,51 @@ int dmet_voxel_coarsen(const uint32_t *cell, const int64_t *ptr, int B, int64_t 
                        int32_t *rowptr, int64_t *out_batch, int64_t *out_ptr, int64_t *record, void *ws, size_t ws_bytes,
                        dmet_stream_t stream);
 
+/* ---- Edge pooling: the greedy edge contraction of torch_geometric.nn.pool.EdgePooling (csrc/edge_match.hip) --------------
+ * dmet_edge_match_f32 replaces torch_geometric.nn.pool.EdgePooling._merge_edges, which copies the edge index to the host
+ *   and walks the sorted edges in a Python loop.  One workgroup per event, every round in one launch.
+ *   The rule (the result is defined by this sequential form): take the candidate edges of an event in descending
+ *   canonical score, ties to the lower edge id in the CALLER's order; an edge (s, t) is taken when s and t are both still
+ *   free, and claims both.  A self loop s == t claims its one node, which becomes a one-node cluster carrying that edge (as
+ *   upstream).  Canonical score: the order of dmet_topk_f32 -- -0.0 counts as +0.0, every NaN ranks above +inf -- as the
+ *   same 64-bit key, (order-preserving map of the fp32 bits << 32) | ~edge id.  Keys are distinct: a strict total order.
+ *   The parallel form: in a round every live edge (both ends free) offers its key to both ends, an integer max per node;
+ *   a live edge that holds the largest key at both of its ends is taken; rounds repeat until no live edge is left.  For a
+ *   strict total order this takes exactly the edges of the sequential rule (the locally dominant edges of the live graph
+ *   are the ones the sequential walk reaches with both ends free, by induction over the rounds), and the largest live key
+ *   is always taken, so there are at most n_b rounds; the kernel's loop is bounded by n_b + 1 and sets flags[2] should it
+ *   ever get there.  Typical counts: 13 to 16 rounds for the events of a 64 x 4 500 batch under a k = 16 kNN graph with
+ *   the layer's softmax scores; n_b / 2 for a path with monotone scores, the worst case.
+ *   Arguments: the edges grouped by target -- rowptr[N+1] int32, src[E], tgt[E] int32 (tgt[e] == i for rowptr[i] <= e <
+ *   rowptr[i+1]) --, perm[E] int32 = the caller-order id of every grouped position (NULL = the position itself),
+ *   score[E] fp32 by grouped position, ptr[B+1] (values clamped to [0, N]).  Event b owns the nodes ptr[b] .. ptr[b+1]-1
+ *   and the positions rowptr[ptr[b]] .. rowptr[ptr[b+1]]-1.
+ *   An edge with an end outside [0, N) is no candidate and sets flags[0]; one whose ends lie in different events is no
+ *   candidate and sets flags[1].  flags[3] int32 is cleared by the call (a memset node on the stream) and written 0 / 1.
+ *   Outputs, every element written by the kernel: cluster[N] int64 = min(u, v) for a pair (u, v), u otherwise (the
+ *   convention of dmet_graclus_f32); partner[N] int32 = v, -1 for a one-node cluster (what dmet_pool_pairs_index /
+ *   dmet_pool_pairs_f32 read); edge[N] int64 = the caller-order id of the claiming edge, -1 for a node nobody claimed;
+ *   rounds[B] int32 (may be NULL) = the rounds of event b that had a live edge.  Nodes no event owns are unclaimed.
+ *   An event of up to DMET_EDGE_MATCH_LDS_NODES nodes keeps one 64-bit state word per node in LDS (128 KiB of the CU's
+ *   160); a larger one keeps the same words in the workspace, N words, at ws[ptr[b] ..), and runs the same code (same
+ *   bits).  Behind the N words the workspace holds two lists of E positions each (dmet_edge_match_workspace_bytes(N, E)
+ *   = 8 N + 8 E bytes): a round appends its live edges to one list while it walks the other, so an edge is visited
+ *   while it is live and once more, not once per round; the order inside a list depends on the run, the set does not, and
+ *   nothing reads the order (DMET_EDGE_MATCH_STATE=workspace in the environment, read on every call, sends every event
+ *   through the workspace form, for tests).  Integer atomic max only (LDS, or L2 for the workspace form), no float
+ *   atomics: the result is a function of the input alone, whatever the buffers and the workspace held.
+ *   Limits: N, E <= 2^31-1, any n_b.  Events without edges, E == 0 and N == 0 are valid; B == 0 or N == 0 returns 0 after
+ *   clearing flags and rounds and writes nothing else (no event owns a node).  -EINVAL with a dmet_last_error() message naming the
+ *   argument, before any HIP call, for a bad size, a small workspace or a NULL operand of a non-empty problem.
+ *   Asynchronous on `stream`, no allocation, no global state. */
+#define DMET_EDGE_MATCH_THREADS 1024    /* workgroup of an event */
+#define DMET_EDGE_MATCH_LDS_NODES 16384 /* events up to this size keep their 64-bit state words in LDS (128 KiB) */
+size_t dmet_edge_match_workspace_bytes(int64_t N, int64_t E);
+int dmet_edge_match_f32(const int32_t *rowptr, const int32_t *src, const int32_t *tgt, const int32_t *perm,
+                        const float *score, int64_t E, const int64_t *ptr, int B, int64_t N, int64_t *cluster,
+                        int32_t *partner, int64_t *edge, int32_t *rounds, int32_t *flags, void *ws, size_t ws_bytes,
+                        dmet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
