@@ -199,6 +199,9 @@ SIGNATURES = {
     "dmet_voxel_coarsen": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dmet_edge_match_workspace_bytes": (_sz, [_i64, _i64]),
     "dmet_edge_match_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dmet_components_workspace_bytes": (_sz, [_i64]),
+    "dmet_components_i32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i,
+                                 _vp, _sz, _vp]),
 }
 
 

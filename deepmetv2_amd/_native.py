@@ -3064,3 +3064,72 @@ def _edge_match(rowptr: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, perm
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
     return cluster, partner, edge, rounds, flags
+
+
+# ---- connected components and DBSCAN (csrc/components.hip) ---------------------------------------------------------------
+COMPONENTS_LDS_NODES = 16384    # DMET_COMPONENTS_LDS_NODES: the largest event whose parent words stay in LDS
+COMPONENTS_CC, COMPONENTS_DBSCAN = 0, 1
+
+
+def _mask_u8(t: Optional[torch.Tensor], name: str, n: int) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    if t.dtype != torch.bool or t.numel() != n:
+        raise TypeError(f"{name} must be a bool tensor of {n} values, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous().view(torch.uint8).view(-1)
+
+
+def _components(ptr: torch.Tensor, N: int, *, nbr: Optional[torch.Tensor] = None, cnt: Optional[torch.Tensor] = None,
+                rowptr: Optional[torch.Tensor] = None, src: Optional[torch.Tensor] = None,
+                tgt: Optional[torch.Tensor] = None, edge_mask: Optional[torch.Tensor] = None,
+                node_mask: Optional[torch.Tensor] = None, min_samples: Optional[int] = None, count_self: bool = False,
+                lds_nodes: int = 0):
+    """(labels[N] int64, core[N] bool or None, nclusters[B] int64 or None, flags[4] int32) of dmet_components_i32 for a
+    table (nbr[N, k] int32, cnt[N] int32 or None) or a by-target list (rowptr[N + 1], src[E], tgt[E] int32).
+    min_samples=None: connected components, labels = the smallest global id of every component (edge_mask / node_mask:
+    bool, one value per position / node); else DBSCAN mode: event-local cluster numbers, the core mask and the cluster
+    count of every event.  flags: entries with an end outside [0, N) | entries across two events | a loop bound was
+    reached | (DBSCAN, table) rows that fill every slot.  lds_nodes: the largest event kept in LDS (0: the default)."""
+    dev = _require_device(ptr, nbr, cnt, rowptr, src, tgt, edge_mask, node_mask)
+    L = _lib.load()
+    N = int(N)
+    ptr = _sel_vec(ptr, "ptr", torch.int64)
+    if ptr.numel() < 1:
+        raise TypeError("components: ptr must hold B + 1 entries")
+    B = ptr.numel() - 1
+    if (nbr is None) == (rowptr is None):
+        raise TypeError("components: pass a table (nbr) or a grouped list (rowptr, src, tgt), one of them")
+    k, E = 0, 0
+    if nbr is not None:
+        if nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != N:
+            raise TypeError(f"components: nbr must be an int32 [{N}, k] tensor, got {nbr.dtype} {tuple(nbr.shape)}")
+        nbr = nbr.contiguous()
+        k = nbr.shape[1]
+        cnt = _sel_vec(cnt, "cnt", torch.int32, N) if cnt is not None else None
+        positions = N * k
+    else:
+        rowptr = _sel_vec(rowptr, "rowptr", torch.int32, N + 1)
+        src = _sel_vec(src, "src", torch.int32)
+        E = src.numel()
+        tgt = _sel_vec(tgt, "tgt", torch.int32, E)
+        positions = E
+    dbscan = min_samples is not None
+    if dbscan and (edge_mask is not None or node_mask is not None):
+        raise TypeError("components: DBSCAN mode takes no masks")
+    edge_mask = _mask_u8(edge_mask, "edge_mask", positions)
+    node_mask = _mask_u8(node_mask, "node_mask", N)
+    labels = torch.empty((N,), dtype=torch.int64, device=dev)
+    core = torch.empty((N,), dtype=torch.bool, device=dev) if dbscan else None
+    nclusters = torch.empty((B,), dtype=torch.int64, device=dev) if dbscan else None
+    flags = torch.empty((4,), dtype=torch.int32, device=dev)
+    _t = timer.record('components', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_components_workspace_bytes(N), dev)
+        _lib.check(L.dmet_components_i32(_ptr(nbr), k, _ptr(cnt), rowptr.data_ptr() if rowptr is not None else None, _ptr(src),
+                                         _ptr(tgt), E, _ptr(edge_mask), _ptr(node_mask), ptr.data_ptr(), B, N,
+                                         COMPONENTS_DBSCAN if dbscan else COMPONENTS_CC, int(min_samples) if dbscan else 0,
+                                         1 if count_self else 0, _ptr(labels), _ptr(core), _ptr(nclusters), flags.data_ptr(),
+                                         int(lds_nodes), ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_components_i32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return labels, core, nclusters, flags

@@ -1394,6 +1394,66 @@ int dmet_edge_match_f32(const int32_t *rowptr, const int32_t *src, const int32_t
                         int32_t *partner, int64_t *edge, int32_t *rounds, int32_t *flags, void *ws, size_t ws_bytes,
                         dmet_stream_t stream);
 
+/* ---- Components and DBSCAN: connected components and density clustering of every event (csrc/components.hip) -------------
+ * dmet_components_i32 replaces scipy.sparse.csgraph.connected_components (PyG's LargestConnectedComponents runs it on the
+ *   host) and sklearn.cluster.DBSCAN over a given neighbourhood graph.  One workgroup per event, one launch for the batch.
+ *   The graph, one of two forms:
+ *     table (nbr != NULL): nbr[N, k] int32, row i lists the neighbours of node i; with cnt[N] int32 the first
+ *       min(cnt[i], k) slots of row i are read and nothing beyond them, without it all k; a slot holding -1 is empty.
+ *     list  (nbr == NULL, rowptr != NULL): rowptr[N+1], src[E], tgt[E] int32, the entries grouped by target (tgt[e] == i
+ *       for rowptr[i] <= e < rowptr[i+1]); event b owns the positions rowptr[ptr[b]] .. rowptr[ptr[b+1]] - 1.
+ *   Event b owns the nodes ptr[b] .. ptr[b+1]-1 (ptr[B+1] int64, values clamped to [0, N]).  An entry (i, j) joins i and j
+ *   whichever way round it is listed (weak connectivity); duplicates and self entries are harmless.  An entry with an end
+ *   outside [0, N) joins nothing and adds 1 to flags[0]; one whose ends lie in two events joins nothing and adds 1 to
+ *   flags[1].  flags[4] int32 is cleared by the call (a memset node on the stream); flags[2] is set should a loop of the
+ *   union-find ever reach its bound (a defect of the kernel: see below); flags[3] counts, in DBSCAN mode over a table, the
+ *   rows that fill all k slots (a radius table that may have cut a neighbourhood).
+ *
+ *   mode = DMET_COMPONENTS_CC: labels[i] int64 = the smallest global id of the component of node i: canonical, the same
+ *   for every order of the entries, every launch and every run.  node_mask[N] (uint8, may be NULL): a node with 0 gets -1
+ *   and every entry that touches it joins nothing.  edge_mask (uint8, may be NULL): one value per position -- [N k] for a
+ *   table, where the value of an empty slot (-1, or beyond cnt) is never read, [E] in grouped order for a list --, an
+ *   entry with 0 joins nothing.  core and nclusters are not touched.
+ *
+ *   mode = DMET_COMPONENTS_DBSCAN (no masks): n_i = the non-empty slots of row i (table: min(cnt[i], k), or the slots
+ *   != -1; list: rowptr[i+1] - rowptr[i]), plus 1 with count_self -- the caller's statement that rows list no self entry.
+ *   Node i is core when n_i >= min_samples (>= 1); core[i] uint8 = 1 / 0.  Core nodes joined by an entry form clusters, the
+ *   components of the core-core subgraph; the root of a cluster is its smallest core id.  A node that is not core takes
+ *   the cluster of the core node IN ITS OWN ROW whose cluster has the smallest root, and is noise, -1, with no core node
+ *   in its row: the graph is taken as symmetric, as a radius graph is (an entry (i, j) without its mirror makes j no
+ *   border node of i's cluster).  labels[i] int64 = the EVENT-LOCAL number of i's cluster, 0, 1, ... in ascending root id
+ *   (sklearn's discovery order), or -1; nclusters[b] int64 = the clusters of event b (0 for an event without nodes).  The
+ *   batch-wide number is labels + the exclusive sum of nclusters, left to the caller.  Whenever flags is all zero the
+ *   labels and the core mask are those of sklearn.cluster.DBSCAN(metric='precomputed') on the same symmetric entry set.
+ *
+ *   The kernel: one parent word (int32, event-local) per node; an event of up to lds_nodes nodes keeps the words in LDS,
+ *   a larger one in the workspace at ws[ptr[b] ..) (dmet_components_workspace_bytes(N) = 4 N bytes) through agent-scope
+ *   atomics, and runs the same code (same labels).  lds_nodes: 0 = DMET_COMPONENTS_LDS_NODES (64 KiB of the CU's 160,
+ *   two workgroups per CU), larger values are cut to it, 1 .. sends larger events through the workspace (for tests).
+ *   Union-find: an entry finds the roots of its ends, halving the paths, and hooks the larger root under the smaller with
+ *   a compare-and-swap that only a root passes: a parent is never larger than its child, so a find walks at most n_b
+ *   steps and the root of a finished component is its smallest id; a failed swap means some other hook succeeded, and an
+ *   event has fewer than n_b of those, so a hook is retried at most n_b + 1 times.  Both loops carry those bounds and set
+ *   flags[2] there; neither is reached.  After a barrier the paths are compressed in full.  DBSCAN mode runs core test,
+ *   unions over core-core entries, compression, border pass (an integer max per node) and a workgroup scan over the roots,
+ *   with barriers between them.  Integer atomics only: the result is a function of the input alone, whatever lane ran
+ *   first and whatever labels, core, nclusters and the workspace held; every output element is written exactly once.
+ *   Nodes no event owns (ptr[0] > 0, ptr[B] < N) are components of their own (CC; -1 when masked) or noise, not core.
+ *   Limits: N, E <= 2^31-1, any n_b, any k >= 0.  B == 0 with N == 0 returns 0 after clearing flags; B == 0 with N > 0 is
+ *   refused.  -EINVAL with a dmet_last_error() message naming the argument, before any HIP call, for a bad size or mode, a
+ *   small workspace, a mask in DBSCAN mode or a NULL operand of a non-empty problem.  Asynchronous on `stream`, no
+ *   allocation, no global state. */
+#define DMET_COMPONENTS_THREADS 1024    /* workgroup of an event */
+#define DMET_COMPONENTS_LDS_NODES 16384 /* events up to this size keep their int32 parent words in LDS (64 KiB) */
+#define DMET_COMPONENTS_CC 0
+#define DMET_COMPONENTS_DBSCAN 1
+size_t dmet_components_workspace_bytes(int64_t N);
+int dmet_components_i32(const int32_t *nbr, int k, const int32_t *cnt, const int32_t *rowptr, const int32_t *src,
+                        const int32_t *tgt, int64_t E, const uint8_t *edge_mask, const uint8_t *node_mask,
+                        const int64_t *ptr, int B, int64_t N, int mode, int min_samples, int count_self, int64_t *labels,
+                        uint8_t *core, int64_t *nclusters, int32_t *flags, int lds_nodes, void *ws, size_t ws_bytes,
+                        dmet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
