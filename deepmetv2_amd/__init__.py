@@ -34,6 +34,8 @@ Drop-in names (same spelling and argument meaning as the third-party operators t
     from deepmetv2_amd import connected_components, largest_connected_components   # scipy.sparse.csgraph / PyG's
                                                              # LargestConnectedComponents, per event on the device
     from deepmetv2_amd import dbscan, dbscan_graph           # sklearn.cluster.DBSCAN (dbscan_graph: over a given graph)
+    from deepmetv2_amd import condensation_cluster, condensation_points   # object-condensation inference (Kieseler 2020):
+                                                             # upstream's host loop over the condensation points
 
 All of them run hand-written HIP kernels for gfx950 through the C ABI in include/dmet.h
 (deepmetv2_amd/libdmet_hip.so, built by `python -m deepmetv2_amd.build`).  There is no CPU implementation:
@@ -66,6 +68,7 @@ from .event_norm import (GraphNorm, GraphSizeNorm, InstanceNorm, LayerNorm, Mean
 from .select import SAGPooling, SortAggregation, TopKPooling, filter_adj, filter_table, global_sort_pool, topk
 from .edge_pool import EdgePooling, edge_matching
 from .components import connected_components, dbscan, dbscan_graph, largest_connected_components
+from .condense import condensation_cluster, condensation_points
 
 __all__ = [
     "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph", "knn_table", "knn_xy_table", "radius", "radius_graph", "radius_table",
@@ -87,5 +90,6 @@ __all__ = [
     "TopKPooling", "SAGPooling", "SortAggregation", "global_sort_pool", "topk", "filter_adj", "filter_table",
     "EdgePooling", "edge_matching",
     "connected_components", "largest_connected_components", "dbscan_graph", "dbscan",
+    "condensation_cluster", "condensation_points",
 ]
 __version__ = "0.1.0"

@@ -202,6 +202,8 @@ SIGNATURES = {
     "dmet_components_workspace_bytes": (_sz, [_i64]),
     "dmet_components_i32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _i,
                                  _vp, _sz, _vp]),
+    "dmet_condense_workspace_bytes": (_sz, [_i64]),
+    "dmet_condense_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _f, _f, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
 }
 
 

@@ -3133,3 +3133,44 @@ def _components(ptr: torch.Tensor, N: int, *, nbr: Optional[torch.Tensor] = None
     if _t is not None:
         _t.record(torch.cuda.current_stream(dev))
     return labels, core, nclusters, flags
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Condensation clustering (csrc/condense.hip)
+# ---------------------------------------------------------------------------------------------------------------
+CONDENSE_LDS_NODES = 16384      # DMET_CONDENSE_LDS_NODES: the largest event whose state words stay in LDS
+CONDENSE_WINDOW = 64            # DMET_CONDENSE_WINDOW
+CONDENSE_MAX_DIM = 8            # DMET_CONDENSE_MAX_DIM
+
+
+def _condense(beta: torch.Tensor, x: torch.Tensor, order: torch.Tensor, ptr: torch.Tensor, t_beta: float, t_d: float,
+              lds_nodes: int = 0):
+    """(local[N] int64, assoc[N] int64, nclusters[B] int64, flags[2] int32) of dmet_condense_f32 for beta[N], x[N, D] fp32
+    and the ranking order[N] int64 (`_topk` over the score with non-candidates at -inf, out_ptr = ptr, M = N).  local: the
+    event-local number of a node's condensation point, assoc: its global id, -1 both for noise.  flags: ranking entries
+    outside their event | the walk reached its bound.  lds_nodes: the largest event kept in LDS (0: the default)."""
+    dev = _require_device(beta, x, order, ptr)
+    L = _lib.load()
+    beta = _f32c(beta.detach(), "beta")
+    x = _f32c(x.detach(), "x")
+    if beta.dim() != 1 or x.dim() != 2 or x.shape[0] != beta.numel():
+        raise ValueError(f"condense: beta must be [N] and x [N, D], got {tuple(beta.shape)} and {tuple(x.shape)}")
+    N, D = x.shape
+    order = _sel_vec(order, "order", torch.int64, N)
+    ptr = _sel_vec(ptr, "ptr", torch.int64)
+    if ptr.numel() < 1:
+        raise TypeError("condense: ptr must hold B + 1 entries")
+    B = ptr.numel() - 1
+    local = torch.empty((N,), dtype=torch.int64, device=dev)
+    assoc = torch.empty((N,), dtype=torch.int64, device=dev)
+    nclusters = torch.empty((B,), dtype=torch.int64, device=dev)
+    flags = torch.empty((2,), dtype=torch.int32, device=dev)
+    _t = timer.record('condense', dev)
+    with _on(dev):
+        ws = _ws(L.dmet_condense_workspace_bytes(N), dev)
+        _lib.check(L.dmet_condense_f32(_ptr(beta), _ptr(x), _ptr(order), ptr.data_ptr(), B, N, int(D), float(t_beta),
+                                       float(t_d), _ptr(local), _ptr(assoc), _ptr(nclusters), flags.data_ptr(),
+                                       int(lds_nodes), ws.data_ptr(), ws.numel(), _stream(dev)), "dmet_condense_f32")
+    if _t is not None:
+        _t.record(torch.cuda.current_stream(dev))
+    return local, assoc, nclusters, flags

@@ -15,7 +15,7 @@ SOURCES = ["knn.hip", "radius.hip", "edgeconv.hip", "edgemlp.hip", "misc.hip", "
            "head.hip", "finalize.hip", "pool.hip",
            "edgemlp_f32.hip", "edgemlp_bf16.hip", "edgeconv_sum.hip", "gravnet.hip", "attention.hip", "fps.hip", "interpolate.hip",
            "pointnet.hip", "gat.hip", "segment.hip", "multi_aggr.hip", "weighted_sum.hip", "event_norm.hip", "select.hip",
-           "voxel.hip", "edge_match.hip", "components.hip"]
+           "voxel.hip", "edge_match.hip", "components.hip", "condense.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "bn_affine.h", "knn_common.h", "knn_filter.h", "knn_key64.h", "knn_tile_schedule.h",
                                            "nls_body.h",
                                            "edgemlp_fused.h", "row_softmax.h", "score_key.h")] + \

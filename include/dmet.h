@@ -1454,6 +1454,62 @@ int dmet_components_i32(const int32_t *nbr, int k, const int32_t *cnt, const int
                         uint8_t *core, int64_t *nclusters, int32_t *flags, int lds_nodes, void *ws, size_t ws_bytes,
                         dmet_stream_t stream);
 
+/* ---- Condensation clustering: object-condensation inference of every event (csrc/condense.hip) ---------------------------
+ * dmet_condense_f32 collects the nodes of every event around its condensation points (Kieseler 2020), the step upstream
+ *   runs as a host loop with one device read per point.  One workgroup per event, one launch for the batch.
+ *   Arguments: beta[N] fp32, the condensation weights; x[N, D] fp32 row-major, the cluster coordinates, 1 <= D <=
+ *   DMET_CONDENSE_MAX_DIM; event b owns the nodes ptr[b] .. ptr[b+1]-1 (ptr[B+1] int64, non-decreasing, values clamped to
+ *   [0, N]); order[N] int64, the ranking: order[ptr[b] .. ptr[b+1]) lists GLOBAL node ids of event b, best first, as
+ *   dmet_topk_f32 writes perm for out_ptr = ptr, M = N over the score (beta > t_beta ? beta : -inf); t_beta finite;
+ *   t_d finite and > 0.
+ *   The rule, per event:
+ *     1. Candidates are the nodes with beta[i] > t_beta, compared in fp32 and strictly: a NaN is never one, +inf is.
+ *     2. They are walked in the order of `order`: descending canonical beta (-0.0 = +0.0), ties to the lower index.  The
+ *        walk reads order from the event's first slot and ends at the first entry that fails beta > t_beta.
+ *     3. A candidate that is still unassigned becomes the event's next condensation point c, numbered 0, 1, ... in the
+ *        order found, and takes its own number.
+ *     4. Every still-unassigned node j of the event, candidate or not, with d2(j, c) < t_d2 takes that number.
+ *        d2 is the fp32 chain of rule R1 over the D coordinates in order: a = x[j,c] - x[p,c]; acc = fmaf(a, a, acc) from
+ *        0 (d2(a, b) and d2(b, a) are the same bits); t_d2 = t_d * t_d, one fp32 rounding, as dmet_radius_f32 forms r2;
+ *        the comparison is strict, as there.  A NaN distance is below nothing: a candidate with a NaN coordinate becomes
+ *        a condensation point of itself alone.
+ *     5. Nodes left unassigned are noise.
+ *   So a candidate is a condensation point iff no condensation point of a higher rank lies within t_d of it, and a node's
+ *   point is the highest-ranked condensation point within t_d of it.
+ *   Outputs, every element written exactly once: local[N] int64 = the EVENT-LOCAL number of the node's condensation
+ *   point, -1 for noise; assoc[N] int64 = the GLOBAL id of that point (a point holds itself), -1 for noise; nclusters[B]
+ *   int64 = the points of event b (0 for an event without nodes).  The batch-wide number is local + the exclusive sum of
+ *   nclusters, left to the caller.  Nodes no event owns (ptr[0] > 0, ptr[B] < N) are noise.  Unwritten regions: none.
+ *   flags[2] int32 is cleared by the call (a memset node on the stream).  flags[0] counts the entries of `order` the walk
+ *   met that lie outside their event: such an entry is compared against the event's range BEFORE anything is read
+ *   through it, and skipped.  flags[1] is set should the walk reach its bound of n_b + 1 windows (a defect of the kernel:
+ *   every window holds a condensation point, so there are at most n_b).  A ranking that lists a node twice or leaves one
+ *   out is the caller's error beyond that: no access leaves the buffers, the labels are then not the rule's.
+ *
+ *   The kernel: one state word (int32: the node's number, or -1) per node; an event of up to lds_nodes nodes keeps the
+ *   words in LDS, a larger one in the workspace at ws[ptr[b] ..) (ws_bytes, the size of ws, at least
+ *   dmet_condense_workspace_bytes(N) = 4 N bytes) through agent-scope accesses, and runs the same code (same outputs).
+ *   lds_nodes: 0 = DMET_CONDENSE_LDS_NODES, larger values
+ *   are cut to it, 1 .. sends larger events through the workspace (for tests).  The walk is windowed: wavefront 0
+ *   compacts the next DMET_CONDENSE_WINDOW still-unassigned candidates from its cursor in `order`, resolves them among
+ *   themselves in rank order (entry s, if still alive, is a point and the alive entries behind it within t_d take its
+ *   number: a dead entry suppresses nobody), and after a workgroup barrier every thread holds its own unassigned nodes
+ *   against the window's points in rank order and takes the first within t_d.  A node within t_d of a point of an earlier
+ *   window was assigned there and is never collected, so the windows give exactly the sequential rule.  No float
+ *   atomics; the result is a function of the inputs alone, whatever local, assoc, nclusters and the workspace held.
+ *   Limits: N <= 2^31-1, any n_b.  B == 0 with N == 0 returns 0 after clearing flags; B == 0 with N > 0 is refused.
+ *   -EINVAL with a dmet_last_error() message naming the argument, before any HIP call, for N < 0, B < 0, D outside
+ *   1..DMET_CONDENSE_MAX_DIM, a t_beta that is not finite, a t_d that is not finite and > 0, lds_nodes < 0, a small
+ *   workspace or a NULL operand of a non-empty problem.  Asynchronous on `stream`, no allocation, no global state. */
+#define DMET_CONDENSE_THREADS 1024      /* workgroup of an event */
+#define DMET_CONDENSE_LDS_NODES 16384   /* events up to this size keep their int32 state words in LDS (64 KiB) */
+#define DMET_CONDENSE_WINDOW 64         /* candidates resolved per window: one wavefront */
+#define DMET_CONDENSE_MAX_DIM 8
+size_t dmet_condense_workspace_bytes(int64_t N);
+int dmet_condense_f32(const float *beta, const float *x, const int64_t *order, const int64_t *ptr, int B, int64_t N, int D,
+                      float t_beta, float t_d, int64_t *local, int64_t *assoc, int64_t *nclusters, int32_t *flags,
+                      int lds_nodes, void *ws, size_t ws_bytes, dmet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
