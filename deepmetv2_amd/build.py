@@ -18,7 +18,7 @@ SOURCES = ["knn.hip", "radius.hip", "edgeconv.hip", "edgemlp.hip", "misc.hip", "
            "voxel.hip", "edge_match.hip", "components.hip", "condense.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "bn_affine.h", "knn_common.h", "knn_filter.h", "knn_key64.h", "knn_tile_schedule.h",
                                            "nls_body.h",
-                                           "edgemlp_fused.h", "row_softmax.h", "score_key.h")] + \
+                                           "edgemlp_fused.h", "row_softmax.h", "score_key.h", "event_wg.h")] + \
           [os.path.join(PKG_DIR, "..", "include", "dmet.h")]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=off", "-Wall",

@@ -44,6 +44,7 @@ static inline bool env_is(const char *name, const char *value)
 }
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }   // the parts of a workspace start 16-byte aligned
 
 // Event that owns node i: the b with ptr[b] <= i < ptr[b+1] (empty events are skipped naturally).
 __device__ __forceinline__ int find_event(const int64_t *__restrict__ ptr, int B, int64_t i)

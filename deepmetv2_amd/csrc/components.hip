@@ -1,6 +1,6 @@
 // components.hip -- connected components and DBSCAN of every event of a batch as one union-find launch.
 // Semantics: include/dmet.h, section "Components and DBSCAN".
-#include "common.h"
+#include "event_wg.h"
 
 namespace dmet {
 namespace {
@@ -16,42 +16,7 @@ constexpr int32_t kNoise = INT32_MIN;
 
 enum { kFlagRange = 0, kFlagCross = 1, kFlagBound = 2, kFlagFull = 3, kNumFlags = 4 };
 
-// The words in LDS are plain ds accesses.  In the workspace they go to L2 (agent scope): the hooks are formed there by
-// the atomics, and a load served by the CU's L1 could return the word as it was before them (cf. edge_match.hip).
-template <bool kGlobal>
-__device__ __forceinline__ int32_t pw_load(const int32_t *p)
-{
-    if (kGlobal) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-template <bool kGlobal>
-__device__ __forceinline__ void pw_store(int32_t *p, int32_t v)
-{
-    if (kGlobal) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// true: *p was `expect` and is now `v`
-template <bool kGlobal>
-__device__ __forceinline__ bool pw_cas(int32_t *p, int32_t expect, int32_t v)
-{
-    if (kGlobal)
-        return __hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
-    return __hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-template <bool kGlobal>
-__device__ __forceinline__ void pw_max(int32_t *p, int32_t v)
-{
-    if (kGlobal) __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-template <bool kGlobal>
-__device__ __forceinline__ void pw_add(int32_t *p, int32_t v)
-{
-    if (kGlobal) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
+// The parent words are the state words of event_wg.h: the hooks are formed by its compare-and-swap.
 
 // The root of x, halving the path on the way.  A parent is smaller than its child, so x falls with every step and the n
 // steps of the bound are never used up; should they be, `bound` is set and the caller stops.  The halving store writes
@@ -61,10 +26,10 @@ template <bool kGlobal, bool kHalve = true>
 __device__ __forceinline__ int32_t uf_find(int32_t *p, int32_t x, int64_t n, bool &bound)
 {
     for (int64_t step = 0; step < n; ++step) {
-        const int32_t px = pw_load<kGlobal>(p + x);
+        const int32_t px = state_load<kGlobal>(p + x);
         if (px == x) return x;
-        const int32_t gp = pw_load<kGlobal>(p + px);
-        if (kHalve && gp != px) pw_store<kGlobal>(p + x, gp);
+        const int32_t gp = state_load<kGlobal>(p + px);
+        if (kHalve && gp != px) state_store<kGlobal>(p + x, gp);
         x = gp;
     }
     bound = true;
@@ -82,7 +47,7 @@ __device__ __forceinline__ void uf_union(int32_t *p, int32_t a, int32_t b, int64
         b = uf_find<kGlobal>(p, b, n, bound);
         if (bound || a == b) return;
         const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        if (pw_cas<kGlobal>(p + hi, hi, lo)) return;
+        if (state_cas<kGlobal>(p + hi, hi, lo)) return;
         a = hi;
         b = lo;
     }
@@ -146,11 +111,11 @@ struct DbscanArgs {
 };
 
 template <bool kGlobal, bool kTable, bool kDbscan>
-__device__ __forceinline__ void components_event(int32_t *p, unsigned *wsum, const Graph &g, const uint8_t *edge_mask,
+__device__ __forceinline__ void components_event(int32_t *p, int *wsum, const Graph &g, const uint8_t *edge_mask,
                                                  const uint8_t *node_mask, const DbscanArgs &da, int64_t lo, int64_t n,
                                                  int64_t N, const Outputs &out, int b)
 {
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int tid = threadIdx.x;
     int range = 0, cross = 0, full = 0;
     bool bound = false;
 
@@ -158,14 +123,14 @@ __device__ __forceinline__ void components_event(int32_t *p, unsigned *wsum, con
     if (kDbscan) {
         const bool walk = kTable && !g.cnt;         // a -1-padded table: the count of a row is found by walking it
         if (walk) {
-            for (int64_t i = tid; i < n; i += kCompThreads) pw_store<kGlobal>(p + i, 0);
+            for (int64_t i = tid; i < n; i += kCompThreads) state_store<kGlobal>(p + i, 0);
             __syncthreads();
-            for_each_entry<kTable>(g, lo, n, [&](int64_t tg, int64_t, int64_t) { pw_add<kGlobal>(p + (tg - lo), 1); });
+            for_each_entry<kTable>(g, lo, n, [&](int64_t tg, int64_t, int64_t) { state_add<kGlobal>(p + (tg - lo), 1); });
             __syncthreads();
         }
         for (int64_t i = tid; i < n; i += kCompThreads) {
             int64_t c;
-            if (walk) c = pw_load<kGlobal>(p + i);
+            if (walk) c = state_load<kGlobal>(p + i);
             else if (kTable) {
                 c = g.cnt[lo + i];
                 c = c < 0 ? 0 : (c > g.k ? g.k : c);
@@ -175,11 +140,11 @@ __device__ __forceinline__ void components_event(int32_t *p, unsigned *wsum, con
             }
             if (kTable && c >= g.k) ++full;
             const bool is_core = c + (da.count_self ? 1 : 0) >= (int64_t)da.min_samples;
-            pw_store<kGlobal>(p + i, is_core ? (int32_t)i : kNoise);
+            state_store<kGlobal>(p + i, is_core ? (int32_t)i : kNoise);
             out.core[lo + i] = is_core ? 1 : 0;
         }
     } else {
-        for (int64_t i = tid; i < n; i += kCompThreads) pw_store<kGlobal>(p + i, (int32_t)i);
+        for (int64_t i = tid; i < n; i += kCompThreads) state_store<kGlobal>(p + i, (int32_t)i);
     }
     __syncthreads();
 
@@ -192,7 +157,7 @@ __device__ __forceinline__ void components_event(int32_t *p, unsigned *wsum, con
         const int32_t t = (int32_t)(tg - lo), s = (int32_t)(sg - lo);
         if (t == s) return;
         if (kDbscan) {
-            if (pw_load<kGlobal>(p + t) < 0 || pw_load<kGlobal>(p + s) < 0) return;    // core-core entries only
+            if (state_load<kGlobal>(p + t) < 0 || state_load<kGlobal>(p + s) < 0) return;    // core-core entries only
         } else {
             if (edge_mask && !edge_mask[pos]) return;
             if (node_mask && !(node_mask[tg] && node_mask[sg])) return;
@@ -205,19 +170,19 @@ __device__ __forceinline__ void components_event(int32_t *p, unsigned *wsum, con
     // more; in the second only the owner of a word writes it (a halving store of another lane could land after the
     // owner's and leave an ancestor that is no root): after the barrier every word >= 0 is the root of its node -----------
     for (int64_t i = tid; i < n; i += kCompThreads)
-        if (!kDbscan || pw_load<kGlobal>(p + i) >= 0) uf_find<kGlobal>(p, (int32_t)i, n, bound);
+        if (!kDbscan || state_load<kGlobal>(p + i) >= 0) uf_find<kGlobal>(p, (int32_t)i, n, bound);
     __syncthreads();
     for (int64_t i = tid; i < n; i += kCompThreads) {
-        if (kDbscan && pw_load<kGlobal>(p + i) < 0) continue;
+        if (kDbscan && state_load<kGlobal>(p + i) < 0) continue;
         const int32_t r = uf_find<kGlobal, false>(p, (int32_t)i, n, bound);
-        if (r != (int32_t)i) pw_store<kGlobal>(p + i, r);
+        if (r != (int32_t)i) state_store<kGlobal>(p + i, r);
     }
     __syncthreads();
 
     if (!kDbscan) {
         for (int64_t i = tid; i < n; i += kCompThreads) {
             const bool in = !node_mask || node_mask[lo + i];
-            out.labels[lo + i] = in ? lo + (int64_t)pw_load<kGlobal>(p + i) : -1;
+            out.labels[lo + i] = in ? lo + (int64_t)state_load<kGlobal>(p + i) : -1;
         }
     } else {
         // ---- phase 4: the border pass.  A node that is not core takes, over the core nodes of its own row, the smallest
@@ -225,37 +190,27 @@ __device__ __forceinline__ void components_event(int32_t *p, unsigned *wsum, con
         for_each_entry<kTable>(g, lo, n, [&](int64_t tg, int64_t sg, int64_t) {
             const int64_t t = tg - lo, s = sg - lo;
             if (t < 0 || t >= n || s < 0 || s >= n) return;
-            if (pw_load<kGlobal>(p + t) >= 0) return;
-            const int32_t rs = pw_load<kGlobal>(p + s);
-            if (rs >= 0) pw_max<kGlobal>(p + t, -1 - rs);
+            if (state_load<kGlobal>(p + t) >= 0) return;
+            const int32_t rs = state_load<kGlobal>(p + s);
+            if (rs >= 0) state_max<kGlobal>(p + t, -1 - rs);
         });
         __syncthreads();
 
         // ---- phase 5: the roots numbered in ascending id by a workgroup scan; a root's number is parked in its own label,
         // which the other nodes of its cluster read after the barrier (both sides through L2, as the workspace words) ------
         int64_t running = 0;
-        for (int64_t i0 = 0; i0 < n; i0 += kCompThreads) {          // uniform over the workgroup: ballot and barriers
+        for (int64_t i0 = 0; i0 < n; i0 += kCompThreads) {          // uniform over the workgroup: wg_rank and a barrier
             const int64_t i = i0 + tid;
-            const bool root = i < n && pw_load<kGlobal>(p + i) == (int32_t)i;
-            const uint64_t mask = __ballot(root);
-            if (lane == 0) wsum[wave] = (unsigned)__popcll(mask);
-            __syncthreads();
-            unsigned before = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < kCompWaves; ++w) {
-                const unsigned c = wsum[w];
-                before += w < wave ? c : 0u;
-                total += c;
-            }
-            if (root)
-                __hip_atomic_store(out.labels + lo + i, running + before + __popcll(mask & ((1ull << lane) - 1ull)),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool root = i < n && state_load<kGlobal>(p + i) == (int32_t)i;
+            int before, total;
+            wg_rank<kCompWaves>(root, wsum, before, total);
+            if (root) __hip_atomic_store(out.labels + lo + i, running + before, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             running += total;
             __syncthreads();
         }
         if (tid == 0) out.nclusters[b] = running;
         for (int64_t i = tid; i < n; i += kCompThreads) {
-            const int32_t v = pw_load<kGlobal>(p + i);
+            const int32_t v = state_load<kGlobal>(p + i);
             if (v == (int32_t)i) continue;                          // a root: written above
             if (v == kNoise) {
                 out.labels[lo + i] = -1;
@@ -271,8 +226,9 @@ __device__ __forceinline__ void components_event(int32_t *p, unsigned *wsum, con
     if (bound) atomicOr(&out.flags[kFlagBound], 1);
 }
 
-// One workgroup per event.  An event of up to lds_nodes <= DMET_COMPONENTS_LDS_NODES nodes keeps its parent words in LDS
-// (64 KiB); a larger one keeps them in the caller's workspace at ws[lo ..): the events' ranges are disjoint.
+// An event of up to lds_nodes <= DMET_COMPONENTS_LDS_NODES nodes keeps its parent words in LDS (64 KiB); a larger one
+// keeps them in the caller's workspace at ws[lo ..): the events' ranges are disjoint.  Nodes no event owns are components
+// of their own; DBSCAN: noise, not core.
 template <bool kTable, bool kDbscan>
 __global__ __launch_bounds__(kCompThreads) void components_kernel(
     const int32_t *__restrict__ nbr, int k, int lanes, const int32_t *__restrict__ cnt, const int32_t *__restrict__ rowptr,
@@ -282,37 +238,24 @@ __global__ __launch_bounds__(kCompThreads) void components_kernel(
     int32_t *__restrict__ flags, int32_t *ws, int lds_nodes)
 {
     __shared__ int32_t lds[DMET_COMPONENTS_LDS_NODES];
-    __shared__ unsigned wsum[kCompWaves];
+    __shared__ int wsum[kCompWaves];
     const int b = blockIdx.x;
-    int64_t lo = ptr[b], hi = ptr[b + 1];
-    lo = lo < 0 ? 0 : (lo > N ? N : lo);
-    hi = hi < lo ? lo : (hi > N ? N : hi);
-    // nodes no event owns (ptr[0] > 0, ptr[B] < N): components of their own; DBSCAN: noise, not core
-    auto unowned = [&](int64_t from, int64_t to) {
-        for (int64_t i = from + threadIdx.x; i < to; i += kCompThreads) {
-            if (kDbscan) {
-                labels[i] = -1;
-                core[i] = 0;
-            } else {
-                labels[i] = !node_mask || node_mask[i] ? i : -1;
-            }
+    const EventRange ev = event_range(ptr, b, N);
+    for_unowned<kCompThreads>(ev, b, B, N, [&](int64_t i) {
+        if (kDbscan) {
+            labels[i] = -1;
+            core[i] = 0;
+        } else {
+            labels[i] = !node_mask || node_mask[i] ? i : -1;
         }
-    };
-    if (b == 0) unowned(0, lo);
-    if (b == B - 1) unowned(hi, N);
-    const int64_t n = hi - lo;
+    });
+    const int64_t lo = ev.lo, n = ev.n;
     if (n <= 0) {                                           // uniform over the workgroup
         if (kDbscan && threadIdx.x == 0) nclusters[b] = 0;
         return;
     }
     Graph g{nbr, cnt, k, lanes, src, tgt, 0, 0};
-    if (!kTable) {
-        int64_t e0 = rowptr[lo], e1 = rowptr[hi];
-        e0 = e0 < 0 ? 0 : (e0 > E ? E : e0);
-        e1 = e1 < e0 ? e0 : (e1 > E ? E : e1);
-        g.e0 = e0;
-        g.e1 = e1;
-    }
+    if (!kTable) edge_range(rowptr, ev, E, g.e0, g.e1);
     const DbscanArgs da{min_samples, count_self, rowptr};
     const Outputs out{labels, core, nclusters, flags};
     if (n <= lds_nodes)
@@ -366,7 +309,7 @@ extern "C" int dmet_components_i32(const int32_t *nbr, int k, const int32_t *cnt
                  "dmet_components_i32: ws_bytes=%zu, dmet_components_workspace_bytes asks for %zu", ws_bytes,
                  dmet_components_workspace_bytes(N));
     DMET_REQUIRE(ws || N == 0, "dmet_components_i32: ws is NULL");
-    const int limit = lds_nodes == 0 || lds_nodes > DMET_COMPONENTS_LDS_NODES ? DMET_COMPONENTS_LDS_NODES : lds_nodes;
+    const int limit = lds_limit(lds_nodes, DMET_COMPONENTS_LDS_NODES);
     // lanes of a table row: the next power of two from the width, 64 at the most; a counted table's rows are taken as
     // shallow (a radius table is mostly padding) and get 16
     int lanes = 1;

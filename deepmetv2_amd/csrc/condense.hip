@@ -1,6 +1,6 @@
 // condense.hip -- object-condensation inference of every event of a batch as one windowed walk per workgroup.
 // Semantics: include/dmet.h, section "Condensation clustering".
-#include "common.h"
+#include "event_wg.h"
 
 namespace dmet {
 namespace {
@@ -14,32 +14,7 @@ constexpr int32_t kFree = -1;               // a state word: the node's event-lo
 
 enum { kFlagRange = 0, kFlagBound = 1, kNumFlags = 2 };
 
-// The words in LDS are plain ds accesses.  In the workspace both sides go to L2 (agent scope): a word written by
-// wavefront 0 is read by the thread that owns the node, and a load served by the CU's L1 could return the word as it
-// was before (cf. components.hip).
-template <bool kGlobal>
-__device__ __forceinline__ int32_t sw_load(const int32_t *p)
-{
-    if (kGlobal) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-template <bool kGlobal>
-__device__ __forceinline__ void sw_store(int32_t *p, int32_t v)
-{
-    if (kGlobal) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// LDS written by some lanes of a wavefront and read by others of the same one: the ds queue of a wavefront is in order,
-// the fences keep the compiler from moving the accesses across.
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
+// The state words (event_wg.h): a word written by wavefront 0 is read by the thread that owns the node.
 
 // The window of one event: what wavefront 0 leaves for the workgroup.
 struct Window {
@@ -95,7 +70,7 @@ __device__ __forceinline__ int collect(const int32_t *st, Window &w, Walk &wk, c
             const uint64_t failed = __ballot(lane < have && in && !(bt[u] > t_beta));
             const int stop = failed ? __builtin_ctzll(failed) : have;       // entries before `stop` are candidates
             const bool live = lane < stop;
-            const bool take = live && in && sw_load<kGlobal>(st + id[u]) == kFree;
+            const bool take = live && in && state_load<kGlobal>(st + id[u]) == kFree;
             const uint64_t tm = __ballot(take);
             const int slot = cnt + __popcll(tm & lanes_below(lane));
             const bool put = take && slot < kWin;
@@ -119,7 +94,7 @@ __device__ __forceinline__ void condense_event(int32_t *st, Window &w, const flo
                                                float t_beta, float td2, int64_t lo, int64_t n, const Outputs &out, int b)
 {
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    for (int64_t i = tid; i < n; i += kCondThreads) sw_store<kGlobal>(st + i, kFree);
+    for (int64_t i = tid; i < n; i += kCondThreads) state_store<kGlobal>(st + i, kFree);
     __syncthreads();
 
     Walk wk{0, false, 0};
@@ -169,7 +144,7 @@ __device__ __forceinline__ void condense_event(int32_t *st, Window &w, const flo
                 for (int c = 0; c < D; ++c) w.px[c * kWin + q] = xs[c];
             }
             if (have) {
-                sw_store<kGlobal>(st + me, mynum);
+                state_store<kGlobal>(st + me, mynum);
                 out.local[lo + me] = mynum;
                 out.assoc[lo + me] = lo + mypt;
             }
@@ -183,7 +158,7 @@ __device__ __forceinline__ void condense_event(int32_t *st, Window &w, const flo
         if (w.ncand == 0) break;            // uniform: no candidate is left
         // ---- every thread: its own unassigned nodes against the window's points, in rank order ----------------------------
         for (int64_t j = tid; j < n; j += kCondThreads) {
-            if (sw_load<kGlobal>(st + j) != kFree) continue;
+            if (state_load<kGlobal>(st + j) != kFree) continue;
             float xj[D];
 #pragma unroll
             for (int c = 0; c < D; ++c) xj[c] = x[(lo + j) * D + c];
@@ -196,7 +171,7 @@ __device__ __forceinline__ void condense_event(int32_t *st, Window &w, const flo
                 }
                 if (acc < td2) {
                     const int32_t num = (int32_t)nfound + q;
-                    sw_store<kGlobal>(st + j, num);
+                    state_store<kGlobal>(st + j, num);
                     out.local[lo + j] = num;
                     out.assoc[lo + j] = lo + w.pid[q];
                     break;
@@ -208,7 +183,7 @@ __device__ __forceinline__ void condense_event(int32_t *st, Window &w, const flo
     }
 
     for (int64_t j = tid; j < n; j += kCondThreads) {
-        if (sw_load<kGlobal>(st + j) != kFree) continue;
+        if (state_load<kGlobal>(st + j) != kFree) continue;
         out.local[lo + j] = -1;
         out.assoc[lo + j] = -1;
     }
@@ -219,8 +194,8 @@ __device__ __forceinline__ void condense_event(int32_t *st, Window &w, const flo
     }
 }
 
-// One workgroup per event.  An event of up to lds_nodes <= DMET_CONDENSE_LDS_NODES nodes keeps its state words in LDS
-// (64 KiB); a larger one keeps them in the caller's workspace at ws[lo ..): the events' ranges are disjoint.
+// An event of up to lds_nodes <= DMET_CONDENSE_LDS_NODES nodes keeps its state words in LDS (64 KiB); a larger one keeps
+// them in the caller's workspace at ws[lo ..): the events' ranges are disjoint.  Nodes no event owns are noise.
 template <int D>
 __global__ __launch_bounds__(kCondThreads) void condense_kernel(
     const float *__restrict__ beta, const float *__restrict__ x, const int64_t *__restrict__ order,
@@ -230,19 +205,12 @@ __global__ __launch_bounds__(kCondThreads) void condense_kernel(
     __shared__ int32_t lds[DMET_CONDENSE_LDS_NODES];
     __shared__ Window w;
     const int b = blockIdx.x;
-    int64_t lo = ptr[b], hi = ptr[b + 1];
-    lo = lo < 0 ? 0 : (lo > N ? N : lo);
-    hi = hi < lo ? lo : (hi > N ? N : hi);
-    // nodes no event owns (ptr[0] > 0, ptr[B] < N): noise
-    auto unowned = [&](int64_t from, int64_t to) {
-        for (int64_t i = from + threadIdx.x; i < to; i += kCondThreads) {
-            local[i] = -1;
-            assoc[i] = -1;
-        }
-    };
-    if (b == 0) unowned(0, lo);
-    if (b == B - 1) unowned(hi, N);
-    const int64_t n = hi - lo;
+    const EventRange ev = event_range(ptr, b, N);
+    for_unowned<kCondThreads>(ev, b, B, N, [&](int64_t i) {
+        local[i] = -1;
+        assoc[i] = -1;
+    });
+    const int64_t lo = ev.lo, n = ev.n;
     if (n <= 0) {                                           // uniform over the workgroup
         if (threadIdx.x == 0) nclusters[b] = 0;
         return;
@@ -286,7 +254,7 @@ extern "C" int dmet_condense_f32(const float *beta, const float *x, const int64_
                  "dmet_condense_f32: ws_bytes=%zu, dmet_condense_workspace_bytes asks for %zu", ws_bytes,
                  dmet_condense_workspace_bytes(N));
     DMET_REQUIRE(ws || N == 0, "dmet_condense_f32: ws is NULL");
-    const int limit = lds_nodes == 0 || lds_nodes > DMET_CONDENSE_LDS_NODES ? DMET_CONDENSE_LDS_NODES : lds_nodes;
+    const int limit = lds_limit(lds_nodes, DMET_CONDENSE_LDS_NODES);
     const float td2 = t_d * t_d;
     with_int<1, 2, 3, 4, 5, 6, 7, 8>(D, [&](auto d) {
         hipLaunchKernelGGL(condense_kernel<decltype(d)::value>, dim3((unsigned)B), dim3(kCondThreads), 0, as_stream(stream),

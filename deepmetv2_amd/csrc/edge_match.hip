@@ -1,6 +1,6 @@
 // edge_match.hip -- greedy edge contraction as a matching of locally dominant edges (torch_geometric's
 // EdgePooling._merge_edges).  Semantics: include/dmet.h, section "Edge pooling".
-#include "common.h"
+#include "event_wg.h"
 #include "score_key.h"
 
 namespace dmet {
@@ -104,7 +104,7 @@ __device__ __forceinline__ void match_event(uint64_t *best, unsigned *cnt, int32
                 unsigned off = 0;
                 if (lane == leader) off = atomicAdd(&cnt[cur], (unsigned)__popcll(mask));
                 off = __shfl(off, leader, kWave);
-                if (live) list_store(next + off + __popcll(mask & ((1ull << lane) - 1ull)), (int32_t)e);
+                if (live) list_store(next + off + __popcll(mask & lanes_below(lane)), (int32_t)e);
             }
         }
         __syncthreads();
@@ -151,9 +151,10 @@ __device__ __forceinline__ void match_event(uint64_t *best, unsigned *cnt, int32
     }
 }
 
-// One workgroup per event.  An event of up to lds_nodes <= DMET_EDGE_MATCH_LDS_NODES nodes keeps its state words in LDS
-// (128 KiB); a larger one keeps them in the caller's workspace at ws[lo ..): the events' ranges are disjoint.  The two lists
-// of live edges follow the N state words in the workspace, E entries each, an event's at its own positions e0 .. e1.
+// An event of up to lds_nodes <= DMET_EDGE_MATCH_LDS_NODES nodes keeps its state words in LDS (128 KiB); a larger one
+// keeps them in the caller's workspace at ws[lo ..): the events' ranges are disjoint.  The two lists of live edges follow
+// the N state words in the workspace, E entries each, an event's at its own positions e0 .. e1.  Nodes no event owns are
+// clusters of their own, unclaimed.
 __global__ __launch_bounds__(kMatchThreads) void edge_match_kernel(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ src, const int32_t *__restrict__ tgt,
     const int32_t *__restrict__ perm, const float *__restrict__ score, const int64_t *__restrict__ ptr, int B, int64_t N,
@@ -163,32 +164,19 @@ __global__ __launch_bounds__(kMatchThreads) void edge_match_kernel(
     __shared__ uint64_t lds[DMET_EDGE_MATCH_LDS_NODES];
     __shared__ unsigned cnt[2];
     const int b = blockIdx.x;
-    int64_t lo = ptr[b], hi = ptr[b + 1];
-    lo = lo < 0 ? 0 : (lo > N ? N : lo);
-    hi = hi < lo ? lo : (hi > N ? N : hi);
-    // nodes no event owns (ptr[0] > 0, ptr[B] < N) are clusters of their own, unclaimed
-    if (b == 0) {
-        for (int64_t i = threadIdx.x; i < lo; i += kMatchThreads) {
-            cluster[i] = i;
-            partner[i] = -1;
-            edge[i] = -1;
-        }
-    }
-    if (b == B - 1) {
-        for (int64_t i = hi + threadIdx.x; i < N; i += kMatchThreads) {
-            cluster[i] = i;
-            partner[i] = -1;
-            edge[i] = -1;
-        }
-    }
-    const int64_t n = hi - lo;
+    const EventRange ev = event_range(ptr, b, N);
+    for_unowned<kMatchThreads>(ev, b, B, N, [&](int64_t i) {
+        cluster[i] = i;
+        partner[i] = -1;
+        edge[i] = -1;
+    });
+    const int64_t lo = ev.lo, n = ev.n;
     if (n <= 0) {                                           // uniform over the workgroup
         if (rounds && threadIdx.x == 0) rounds[b] = 0;
         return;
     }
-    int64_t e0 = rowptr[lo], e1 = rowptr[hi];
-    e0 = e0 < 0 ? 0 : (e0 > E ? E : e0);
-    e1 = e1 < e0 ? e0 : (e1 > E ? E : e1);
+    int64_t e0, e1;
+    edge_range(rowptr, ev, E, e0, e1);
     int32_t *list_a = (int32_t *)(ws + N) + e0, *list_b = (int32_t *)(ws + N) + E + e0;
     if (n <= lds_nodes)
         match_event<false>(lds, cnt, list_a, list_b, src, tgt, perm, score, e0, e1, lo, n, N, cluster, partner, edge, rounds,

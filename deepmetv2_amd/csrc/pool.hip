@@ -1,6 +1,6 @@
 // pool.hip -- graclus matching, normalized-cut edge weights and pair pooling (the DynamicReductionNetwork's coarsening,
 // model/dynamic_reduction_network.py:89-92,97-99).  Semantics: include/dmet.h, section "Graph coarsening".
-#include "common.h"
+#include "event_wg.h"
 
 namespace dmet {
 namespace {
@@ -192,20 +192,16 @@ __global__ __launch_bounds__(kPoolThreads) void leader_rank_kernel(const int32_t
                                                                   int32_t *__restrict__ rank, int32_t *__restrict__ cnt)
 {
     __shared__ int wsum[kPoolThreads / kWave];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int64_t lo = ptr[b], hi = ptr[b + 1];
     int base = 0;
     for (int64_t c0 = lo; c0 < hi; c0 += kPoolThreads) {
         const int64_t u = c0 + tid;
         const bool lead = u < hi && leader_of(partner, u, N) == u;
-        const uint64_t m = __ballot(lead);
-        const int below = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wv] = __popcll(m);
-        __syncthreads();
-        int off = base;
-        for (int k = 0; k < wv; ++k) off += wsum[k];
-        if (lead) rank[u] = off + below;
-        for (int k = 0; k < kPoolThreads / kWave; ++k) base += wsum[k];
+        int before, total;
+        wg_rank<kPoolThreads / kWave>(lead, wsum, before, total);
+        if (lead) rank[u] = base + before;
+        base += total;
         __syncthreads();
     }
     if (tid == 0) cnt[b] = base;

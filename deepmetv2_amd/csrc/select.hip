@@ -1,6 +1,6 @@
 // select.hip -- score-based selection pooling (torch_geometric's topk / filter_adj, TopKPooling, SAGPooling,
 // SortAggregation).  Semantics: include/dmet.h, section "Selection pooling".
-#include "common.h"
+#include "event_wg.h"
 #include "score_key.h"
 
 namespace dmet {
@@ -60,8 +60,9 @@ __device__ __forceinline__ void topk_event(uint64_t *key, const float *__restric
     for (int64_t p = m + threadIdx.x; p < r && o0 + p < M; p += kSelThreads) perm[o0 + p] = -1;
 }
 
-// One workgroup per event.  An event of up to DMET_SELECT_LDS_NODES nodes keeps its keys in LDS (128 KiB); a larger one
-// keeps them in the caller's workspace at ws[2 lo ..): the power of two above n is < 2 n, so the events' ranges are disjoint.
+// An event of up to DMET_SELECT_LDS_NODES nodes keeps its keys in LDS (128 KiB); a larger one keeps them in the caller's
+// workspace at ws[2 lo ..): the power of two above n is < 2 n, so the events' ranges are disjoint.  Nodes no event owns are
+// not picked either.
 __global__ __launch_bounds__(kSelThreads) void topk_kernel(const float *__restrict__ score, const int64_t *__restrict__ ptr,
                                                            const int64_t *__restrict__ out_ptr, int B, int64_t N, int64_t M,
                                                            int64_t *__restrict__ perm, int32_t *__restrict__ node_map,
@@ -69,15 +70,9 @@ __global__ __launch_bounds__(kSelThreads) void topk_kernel(const float *__restri
 {
     __shared__ uint64_t lds[DMET_SELECT_LDS_NODES];
     const int b = blockIdx.x;
-    int64_t lo = ptr[b], hi = ptr[b + 1];
-    lo = lo < 0 ? 0 : (lo > N ? N : lo);
-    hi = hi < lo ? lo : (hi > N ? N : hi);
-    // nodes no event owns (ptr[0] > 0, ptr[B] < N) are not picked either
-    if (b == 0)
-        for (int64_t i = threadIdx.x; i < lo; i += kSelThreads) node_map[i] = -1;
-    if (b == B - 1)
-        for (int64_t i = hi + threadIdx.x; i < N; i += kSelThreads) node_map[i] = -1;
-    const int64_t n = hi - lo;
+    const EventRange ev = event_range(ptr, b, N);
+    for_unowned<kSelThreads>(ev, b, B, N, [&](int64_t i) { node_map[i] = -1; });
+    const int64_t lo = ev.lo, n = ev.n;
     int64_t o0 = out_ptr[b], r = out_ptr[b + 1] - o0;
     if (o0 < 0 || o0 > M) r = 0;
     if (r > M - o0) r = M - o0;
@@ -166,7 +161,7 @@ __global__ __launch_bounds__(kRowThreads) void filter_table_kernel(const int32_t
         }
         const bool keep = v >= 0;
         const uint64_t mask = __ballot(keep);
-        const int below = __popcll(mask & ((1ull << lane) - 1ull));
+        const int below = __popcll(mask & lanes_below(lane));
         if (keep) orow[base + below] = v;
         base += __popcll(mask);
     }
@@ -270,7 +265,7 @@ __global__ __launch_bounds__(kEdgeThreads) void filter_edges_write_kernel(const 
     const uint64_t mask = __ballot(keep);
     if (lane == 0) wk[wave] = __popcll(mask);
     __syncthreads();
-    int before = __popcll(mask & ((1ull << lane) - 1ull));
+    int before = __popcll(mask & lanes_below(lane));
     for (int w = 0; w < wave; ++w) before += wk[w];
     const int64_t o = offs[blockIdx.x] + before;
     if (keep && o >= 0 && o < Eout) {
@@ -281,7 +276,6 @@ __global__ __launch_bounds__(kEdgeThreads) void filter_edges_write_kernel(const 
 }
 
 inline int64_t edge_blocks(int64_t E) { return (E + kEdgeThreads - 1) / kEdgeThreads; }
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 }  // namespace dmet

@@ -1,7 +1,7 @@
 // voxel.hip -- voxel clustering (torch_cluster's grid_cluster, PyG's voxel_grid) and the coarsening of its result
 // (PyG's consecutive_cluster plus what the pooling operators derive from it).  Semantics: include/dmet.h, section
 // "Voxel clustering".
-#include "common.h"
+#include "event_wg.h"
 
 namespace dmet {
 namespace {
@@ -152,7 +152,6 @@ __device__ __forceinline__ int64_t coarsen_event(uint64_t *key, int *wsum, const
         key[slot<PAD>(i)] = (int64_t)i < n ? ((uint64_t)cell[lo + i] << 32) | (uint64_t)(uint32_t)i : ~0ull;
     __syncthreads();
     bitonic_asc<idx_t, PAD>(key, P);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     int64_t run = 0;                                        // clusters that start before this round (uniform)
     for (int64_t base = 0; base < n; base += kVoxThreads) {
         const int64_t p = base + threadIdx.x;
@@ -162,15 +161,8 @@ __device__ __forceinline__ int64_t coarsen_event(uint64_t *key, int *wsum, const
             k = key[slot<PAD>((idx_t)p)];
             head = p == 0 || (uint32_t)(key[slot<PAD>((idx_t)(p - 1))] >> 32) != (uint32_t)(k >> 32);
         }
-        const uint64_t mask = __ballot(head);
-        if (lane == 0) wsum[wave] = __popcll(mask);
-        __syncthreads();
-        int before = __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
-        for (int w = 0; w < kVoxWaves; ++w) {
-            const int v = wsum[w];
-            before += w < wave ? v : 0;
-            total += v;
-        }
+        int before, total;
+        wg_rank<kVoxWaves>(head, wsum, before, total);
         if (p < n) {
             const int64_t r = run + before + (head ? 1 : 0) - 1;
             const int64_t i = (int64_t)(uint32_t)k;         // < n: the n real keys lead the padding
@@ -184,8 +176,9 @@ __device__ __forceinline__ int64_t coarsen_event(uint64_t *key, int *wsum, const
     return run;
 }
 
-// One workgroup per event.  An event of up to DMET_SELECT_LDS_NODES nodes keeps its keys in LDS (144 KiB padded); a larger one
-// keeps them in the caller's workspace at ws[2 lo ..): the power of two above n is < 2 n, so the events' ranges are disjoint.
+// An event of up to DMET_SELECT_LDS_NODES nodes keeps its keys in LDS (144 KiB padded); a larger one keeps them in the
+// caller's workspace at ws[2 lo ..): the power of two above n is < 2 n, so the events' ranges are disjoint.  Nodes no event
+// owns belong to no cluster.
 __global__ __launch_bounds__(kVoxThreads) void voxel_coarsen_kernel(const uint32_t *__restrict__ cell,
                                                                     const int64_t *__restrict__ ptr, int B, int64_t N,
                                                                     int64_t *__restrict__ node_map, int64_t *__restrict__ order,
@@ -195,15 +188,13 @@ __global__ __launch_bounds__(kVoxThreads) void voxel_coarsen_kernel(const uint32
     __shared__ uint64_t lds[DMET_SELECT_LDS_NODES + DMET_SELECT_LDS_NODES / 8];        // 144 KiB: padded, see slot()
     __shared__ int wsum[kVoxWaves];
     const int b = blockIdx.x;
-    int64_t lo = ptr[b], hi = ptr[b + 1];
-    lo = lo < 0 ? 0 : (lo > N ? N : lo);
-    hi = hi < lo ? lo : (hi > N ? N : hi);
-    // nodes no event owns (ptr[0] > 0, ptr[B] < N) belong to no cluster
+    const EventRange ev = event_range(ptr, b, N);
+    const int64_t lo = ev.lo, hi = ev.hi, n = ev.n;
+    // the nodes no event owns (ptr[0] > 0, ptr[B] < N), as for_unowned walks them
     if (b == 0)
         for (int64_t i = threadIdx.x; i < lo; i += kVoxThreads) node_map[i] = order[i] = -1;
     if (b == B - 1)
         for (int64_t i = hi + threadIdx.x; i < N; i += kVoxThreads) node_map[i] = order[i] = -1;
-    const int64_t n = hi - lo;
     int64_t c = 0;
     if (n > 0) {                                            // uniform over the workgroup
         if (n <= DMET_SELECT_LDS_NODES) c = coarsen_event<int, true>(lds, wsum, cell, lo, n, node_map, order, first);
@@ -243,10 +234,8 @@ __global__ __launch_bounds__(kOutThreads) void voxel_write_kernel(const int64_t 
         __syncthreads();
     }
     before = part[0][0], total = part[1][0];
-    int64_t lo = ptr[b], hi = ptr[b + 1];
-    lo = lo < 0 ? 0 : (lo > N ? N : lo);
-    hi = hi < lo ? lo : (hi > N ? N : hi);
-    const int64_t n = hi - lo;
+    const EventRange ev = event_range(ptr, b, N);
+    const int64_t lo = ev.lo, hi = ev.hi, n = ev.n;
     int64_t c = count[b];
     c = c < 0 ? 0 : (c > n ? n : c);
     for (int64_t i = tid; i < n; i += kOutThreads) node_map[lo + i] += before;
@@ -264,7 +253,6 @@ __global__ __launch_bounds__(kOutThreads) void voxel_write_kernel(const int64_t 
     }
 }
 
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline size_t keys_bytes(int64_t N) { return align16((size_t)N * 2 * sizeof(uint64_t)); }
 inline size_t first_bytes(int64_t N) { return align16((size_t)N * sizeof(int32_t)); }
 
